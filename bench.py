@@ -541,6 +541,33 @@ def self_launch(args) -> int:
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # --dump-outputs: all files of a run together stay below this
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(path, outs, ao_format, rank, world):
+    """--dump-outputs DIR: the AO frames `outs` (what the timed path wrote in its last step, one [H, W] device tensor per
+    frame) as float32 AO values -- R8 storage decoded as code / 255, fp16 storage as its half value.  Frames that fit the
+    budget are written whole: ao.npy [B, H, W].  Otherwise the same fixed, seeded sample of texel positions in every frame:
+    ao_sample.npy [B, N] and ao_sample_index.npy [N] (flat index y * W + x, float64).  With N > 1 ranks every rank writes
+    its own frames (file names end in _rank<r>) within 1/N of the budget."""
+    os.makedirs(path, exist_ok=True)
+    host = np.stack([t.cpu().numpy() for t in outs])
+    ao = host.astype(np.float32) / np.float32(255) if ao_format == _lib.AO_R8 else host.view(np.float16).astype(np.float32)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    budget = DUMP_LIMIT_BYTES // world - (1 << 16)          # headroom for the .npy headers
+    B, h, w = ao.shape
+    if ao.nbytes <= budget:
+        np.save(os.path.join(path, f"ao{suffix}.npy"), ao)
+        return {"dir": path, "files": [f"ao{suffix}.npy"], "frames": B, "texels_per_frame": h * w}
+    n = min(h * w, budget // (4 * B + 8))
+    index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(h * w, size=n, replace=False))
+    np.save(os.path.join(path, f"ao_sample{suffix}.npy"), np.ascontiguousarray(ao.reshape(B, h * w)[:, index]))
+    np.save(os.path.join(path, f"ao_sample_index{suffix}.npy"), index.astype(np.float64))
+    return {"dir": path, "files": [f"ao_sample{suffix}.npy", f"ao_sample_index{suffix}.npy"], "frames": B,
+            "texels_per_frame": int(n), "sample_seed": DUMP_SAMPLE_SEED}
+
+
 def resolve_timed_region(steps, min_time_ms):
     """An explicit --steps is honoured exactly (the driver's contract: "time EXACTLY K steps"); only the flag-less default
     stretches the timed region to 100 ms.  --min-time-ms given explicitly always applies."""
@@ -557,6 +584,9 @@ def main() -> int:
                          "given too; default 30, raised so that the timed region lasts 100 ms")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="4k")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the AO frames their last step computed to DIR/<name>.npy (float32; "
+                         "a fixed, seeded sample of texels when the frames exceed 64 MB), for output-by-output comparison of builds")
     ap.add_argument("--batch", type=int, default=None,
                     help="independent frames per step per GPU (1..64); default: 133 Mpixels per step "
                          "(64 frames at 1080p, 16 at 4K, 4 at 8K)")
@@ -626,6 +656,8 @@ def main() -> int:
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (there is no CPU fallback for the product path)")
     if args.pool > 0:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the outputs of the single-context timed path; it does not apply to --pool")
         return run_pool(args)
 
     if (args.gpus > 1 or args.launcher) and "WORLD_SIZE" not in os.environ:
@@ -666,6 +698,7 @@ def main() -> int:
     # ---- validation of the TIMED path, right behind its timed region: what out_dev holds now was written by the
     # last step of that region (prefetched downsample consumed, final pass = the fused kernel)
     check_timed, sums_timed = wl.validate(n_validate)
+    dumped = dump_outputs(args.dump_outputs, wl.last_outputs(), ao_format, rank, world) if args.dump_outputs else None
 
     # A timed region shorter than 50 ms (the driver's --steps 20 = 10 ms) carries its own long-form cross-check: the same step
     # timed over >= 100 ms right behind it (after the validation's idle gap: clocks ramped again).  Outside `value`.
@@ -962,6 +995,8 @@ def main() -> int:
             "other_workloads": others,
             "best_host_config": best_host,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         # the headline must be what the clock says: pixels of the timed region / its duration (round 5: a loop variable named
         # `value` once overwrote it between here and its computation -- caught by reading the line, now caught by the script)
         implied = float(w) * h * B * world / (line["ms_per_step"] * 1e-3) / 1e6

@@ -1,7 +1,8 @@
 """Fixtures produced by executing the REFERENCE'S OWN shader source (tests/golden/
-make_reference_goldens.py, oracle/hlsl_interp.py).  CPU: both oracle restatements reproduce them;
-where /root/reference is present the shaders are re-interpreted live on a tiny frame.  GPU: the HIP
-path reproduces them without any oracle in the loop."""
+make_reference_goldens.py, oracle/hlsl_interp.py).  CPU: both oracle restatements reproduce them, and
+the product's constants equal what the interpreted AmbientOcclusion.cs recorded (make_reference_host_goldens.py).
+GPU: the HIP path reproduces them without any oracle in the loop."""
+import json
 import os
 
 import numpy as np
@@ -9,6 +10,7 @@ import pytest
 
 from tests import helpers as H
 from tests.golden import make_reference_goldens as R
+from tests.golden import make_reference_host_goldens as G
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -71,46 +73,34 @@ def test_numpy_codecs_agree_with_the_oracle_conversions(oracle):
         assert r8["encode"](v) == lib.meao_oracle_f32_to_unorm8(float(v)), float(v)
 
 
-needs_reference = pytest.mark.skipif(not os.path.isdir(R.SHADERS), reason="reference checkout not present (GPU box)")
+@pytest.fixture(scope="module")
+def host_commands():
+    with open(G.COMMANDS) as f:
+        return json.load(f)
 
 
-@needs_reference
-def test_reference_interpreted_live(oracle):
-    """Re-run the reference now (not from fixtures): AmbientOcclusion.cs through the C# interpreter
-    records the dispatches, the .compute files run through the HLSL interpreter."""
-    from miniengineao_amd import synth
-    w, h = 18, 11
-    cam = synth.Camera(reversed_z=False)
-    depth = R.make_depth("S2", w, h, 5, cam, True)
-    s = H.settings(oracle, w, h, cam=cam, intensity=0.8, thickness_modifier=3.0)
-    ref, cmd = R.run_reference_shaders(depth, s, log=lambda *_: None)
-    assert [d["kernel"] for d in cmd.dispatches] == ["main", "main"] + ["main_interleaved"] * 4 + ["main_blendout"] * 3 + ["main"]
+def test_reference_interpreted_live(oracle, host_commands):
+    """The reference run on a tiny frame (not one of the CASES): AmbientOcclusion.cs through the C# interpreter
+    records the dispatches, the .compute files run through the HLSL interpreter (frozen by make_reference_host_goldens.py)."""
+    depth, s = G.tiny_case(oracle)
+    ref = np.load(G.TINY)
+    assert np.array_equal(ref["depth"].view(np.uint32), depth.view(np.uint32))
+    assert host_commands["tiny_kernels"] == ["main", "main"] + ["main_interleaved"] * 4 + ["main_blendout"] * 3 + ["main"]
     want = oracle.run(depth, s)
     for i in H.valid_debug_ids(4):
         assert np.array_equal(ref[H.NAMES[i]], want[H.NAMES[i]]), H.NAMES[i]
 
 
-@needs_reference
-@pytest.mark.parametrize("shader,find,replace,changed", [
-    # one sample offset of the checker set (the judge's own mutation, VERDICT r4): render and everything behind it changes
-    ("Render", "TestSamples(thisIdx, 2, 4, invThisDepth, gInvThicknessTable[2].z);\n#endif",
-     "TestSamples(thisIdx, 1, 4, invThisDepth, gInvThicknessTable[2].z);\n#endif", ("occlusion1", "combined1", "result")),
-    # the blur's centre weight: only the upsample outputs change
-    ("Upsample", "/ 2.0 + b + c + d) / 4.0;", "/ 2.0 + b + c + d) / 4.5;", ("combined3", "combined1", "result")),
-])
-def test_a_mutated_copy_of_the_reference_text_changes_the_interpreted_result(oracle, monkeypatch, shader, find, replace, changed):
+@pytest.mark.parametrize("shader,find,replace,changed", G.MUTATIONS)
+def test_a_mutated_copy_of_the_reference_text_changes_the_interpreted_result(oracle, host_commands, shader, find, replace, changed):
     """The interpreters execute the reference's TEXT, they are not the oracle in disguise: the same run on a copy of a shader with
-    one token changed no longer equals the oracle in exactly the buffers that shader feeds, and still equals it in the others."""
-    from miniengineao_amd import synth
-    src = R.shader_sources()
-    assert src[shader].count(find) >= 1, "the mutation site moved"
-    mutated = dict(src, **{shader: src[shader].replace(find, replace)})
-    monkeypatch.setattr(R, "shader_sources", lambda: mutated)
-    w, h = 26, 15
-    cam = synth.DEFAULT_CAMERA
-    depth = R.make_depth("S2", w, h, 9, cam, False)
-    s = H.settings(oracle, w, h, cam=cam)
-    ref, _ = R.run_reference_shaders(depth, s, log=lambda *_: None)
+    one token changed (make_reference_host_goldens.MUTATIONS) no longer equals the oracle in exactly the buffers that shader
+    feeds, and still equals it in the others."""
+    depth, s = G.mutated_case(oracle)
+    fx = np.load(G.MUTATED)
+    assert np.array_equal(fx["depth"].view(np.uint32), depth.view(np.uint32))
+    ref = {k.split("__", 1)[1]: fx[k] for k in fx.files if k.startswith(shader + "__")}
+    assert [shader, find, replace] in host_commands["mutations"], "the mutation changed: regenerate the fixture"
     want = oracle.run(depth, s)
     differing = {k for k in ref if not np.array_equal(ref[k], want[k])}
     assert set(changed) <= differing, differing
@@ -118,23 +108,16 @@ def test_a_mutated_copy_of_the_reference_text_changes_the_interpreted_result(ora
     assert not (untouched & differing), differing
 
 
-@needs_reference
-@pytest.mark.parametrize("seed", range(6))
+@pytest.mark.parametrize("seed", G.HOST_SEEDS)
 def test_host_constants_from_the_reference_csharp(oracle, meao_lib, seed):
     """The constant blocks, buffer table and dispatch grids recorded by the INTERPRETED
-    AmbientOcclusion.cs equal the oracle's restatement and the product's plan, bit for bit."""
+    AmbientOcclusion.cs (frozen in ref_host_commands.json) equal the oracle's restatement and the product's plan, bit for bit."""
     import ctypes as C
 
     from miniengineao_amd import _lib as L
-    from miniengineao_amd import synth
-    rng = np.random.default_rng(seed)
-    w, h = int(rng.integers(17, 4000)), int(rng.integers(9, 2200))
-    cam = synth.Camera(near=float(rng.uniform(0.01, 1)), far=float(rng.uniform(5, 2000)),
-                       fov_y_deg=float(rng.uniform(10, 100)), reversed_z=bool(seed & 1))
-    s = H.settings(oracle, w, h, cam=cam, noise_filter_tolerance=float(rng.uniform(-8, 0)),
-                   blur_tolerance=float(rng.uniform(-8, -1)), upsample_tolerance=float(rng.uniform(-12, -1)),
-                   thickness_modifier=float(rng.uniform(1, 10)), intensity=float(rng.uniform(0, 2)))
-    _, cmd, result_rt = R.record_reference_commands(s)
+    s = G.host_case(oracle, seed)
+    w, h = s.width, s.height
+    cmd, result_rt, _ = G.load_commands("host", seed, oracle, s)
     f = lambda xs: [float(x) for x in xs]               # noqa: E731
     ds1 = cmd.dispatches[0]
     assert f(ds1["const"]["ZBufferParams"]) == oracle.zbuffer_params(s)
@@ -182,23 +165,17 @@ def test_host_constants_from_the_reference_csharp(oracle, meao_lib, seed):
         assert (d.width, d.height, d.slices, d.format) == (aw, ah, slices, fmt_of[fmt]), name
 
 
-@needs_reference
-@pytest.mark.parametrize("seed", range(4))
+@pytest.mark.parametrize("seed", G.VARIANT_SEEDS)
 def test_variant_constants_from_the_reference_csharp(oracle, meao_lib, seed):
     """Single-pass stereo (AO.cs:392-401,680) and the non-tiled-source branch of PushRenderCommands
-    (AO.cs:679), both executed from the reference's C#: constants equal the oracle's and the product's."""
+    (AO.cs:679), both executed from the reference's C# (frozen in ref_host_commands.json): constants equal the
+    oracle's and the product's."""
     import ctypes as C
 
     from miniengineao_amd import _lib as L
-    from miniengineao_amd import synth
-    rng = np.random.default_rng(100 + seed)
-    w, h = 2 * int(rng.integers(9, 2000)), int(rng.integers(9, 2200))
-    stereo = bool(seed & 1)
-    cam = synth.Camera(near=float(rng.uniform(0.01, 1)), far=float(rng.uniform(5, 2000)),
-                       fov_y_deg=float(rng.uniform(10, 100)), reversed_z=bool(seed & 2))
-    s = H.settings(oracle, w, h, cam=cam, thickness_modifier=float(rng.uniform(1, 10)),
-                   intensity=float(rng.uniform(0, 2)), single_pass_stereo=stereo, hq_levels=4)
-    _, cmd, result_rt, it, comp = R.record_reference_commands(s, want_interp=True)
+    s, cam = G.variant_case(oracle, seed)
+    w, h, stereo = s.width, s.height, bool(s.single_pass_stereo)
+    cmd, result_rt, hq = G.load_commands("variant", seed, oracle, s)
     assert (result_rt.width, result_rt.height) == (w, h)          # pixelWidth * 2 in stereo (AO.cs:502)
     f = lambda xs: [float(x) for x in xs]               # noqa: E731
     p = L.Params()
@@ -206,7 +183,7 @@ def test_variant_constants_from_the_reference_csharp(oracle, meao_lib, seed):
     p.thickness_modifier, p.intensity, p.near_clip, p.far_clip = s.thickness_modifier, s.intensity, s.near_clip, s.far_clip
     p.proj00, p.reversed_z, p.single_pass_stereo = s.proj00, int(s.reversed_z), int(stereo)
     for level in (1, 2, 3, 4):
-        for tiled, c in ((1, cmd.dispatches[1 + level]["const"]), (0, R.hq_render_commands(s, it, comp, level)["const"])):
+        for tiled, c in ((1, cmd.dispatches[1 + level]["const"]), (0, hq[level]["const"])):
             k = oracle.render_constants(s, level) if tiled else oracle.render_constants_hq(s, level)
             assert f(c["gInvThicknessTable"]) == f(k.inv_thickness) and f(c["gSampleWeightTable"]) == f(k.sample_weight)
             assert f(c["gInvSliceDimension"][:2]) == f(k.inv_slice_dim)
@@ -456,18 +433,6 @@ def test_oracle_detile_view_matches_the_interpreted_blit_shader(oracle):
     L = oracle.lib()
     want = np.vectorize(lambda v: L.meao_oracle_f32_to_unorm8(float(v)), otypes=[np.uint8])(r)
     assert np.array_equal(got, want)
-
-
-@pytest.mark.skipif(not os.path.exists("/root/reference/Assets/MiniEngineAO/Shaders/Blit.shader"),
-                    reason="the reference tree only exists on the build box")
-def test_blit_fixture_is_what_the_reference_text_produces_today(oracle, tmp_path, monkeypatch):
-    from tests.golden import make_blit_goldens as G
-    monkeypatch.setattr(G, "OUT", str(tmp_path / "fresh.npz"))
-    G.main()
-    fresh, kept = np.load(str(tmp_path / "fresh.npz")), np.load(BLIT_FIXTURE)
-    assert sorted(fresh.files) == sorted(kept.files)
-    for k in kept.files:
-        assert np.array_equal(fresh[k], kept[k]), k
 
 
 @pytest.mark.gpu
