@@ -125,6 +125,8 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_execute(IntPtr ctx, IntPtr depth, int depth_loc, IntPtr ao_out, int out_loc, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_execute_batch(IntPtr ctx, int n, IntPtr[] depth, int depth_loc, IntPtr[] ao_out, int out_loc, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_prefetch_batch(IntPtr ctx, int n, IntPtr[] depth);
+        [DllImport(Lib)] public static extern int meao_execute_batch_params(IntPtr ctx, int n, IntPtr[] depth, int depth_loc, IntPtr[] ao_out, int out_loc, [In] MeaoParams[] prm, IntPtr stream);
+        [DllImport(Lib)] public static extern int meao_prefetch_batch_params(IntPtr ctx, int n, IntPtr[] depth, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_synchronize(IntPtr ctx, IntPtr stream);
 
         [DllImport(Lib)] public static extern int meao_get_intermediate(IntPtr ctx, int frame, int debug_id, IntPtr dst, ulong dst_capacity, int dst_loc, out MeaoDesc desc);
@@ -146,6 +148,8 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_pool_set_params(IntPtr pool, ref MeaoParams p);
         [DllImport(Lib)] public static extern int meao_pool_execute_batch(IntPtr pool, int n, IntPtr[] depth, int depth_loc, IntPtr[] ao_out, int out_loc);
         [DllImport(Lib)] public static extern int meao_pool_prefetch_batch(IntPtr pool, int n, IntPtr[] depth);
+        [DllImport(Lib)] public static extern int meao_pool_execute_batch_params(IntPtr pool, int n, IntPtr[] depth, int depth_loc, IntPtr[] ao_out, int out_loc, [In] MeaoParams[] prm);
+        [DllImport(Lib)] public static extern int meao_pool_prefetch_batch_params(IntPtr pool, int n, IntPtr[] depth, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue(IntPtr pool, int mode, int n, IntPtr[] ao, IntPtr[] color_rgba16f, IntPtr[] gbuffer0_rgba8);
         [DllImport(Lib)] public static extern int meao_pool_composite_flush(IntPtr pool);
         [DllImport(Lib)] public static extern int meao_pool_composite_pending(IntPtr pool, out int out_frames);

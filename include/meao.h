@@ -32,7 +32,7 @@ extern "C" {
 #define MEAO_API
 #endif
 
-#define MEAO_ABI_VERSION 6
+#define MEAO_ABI_VERSION 7
 #define MEAO_MAX_BATCH 64      /* frames per batched launch */
 #define MEAO_NUM_PASSES 7      /* downsample, render, upsample x4, render_hq (see meao_pass) */
 
@@ -256,6 +256,21 @@ MEAO_API int32_t meao_execute_batch(meao_ctx *ctx, int32_t n, const void *const 
  * re-allocates the context's intermediates with a second set of downsample buffers (one device
  * synchronisation; on allocation failure the context is left unchanged and usable). */
 MEAO_API int32_t meao_prefetch_batch(meao_ctx *ctx, int32_t n, const void *const *depth);
+/* Per-frame parameters (several cameras in one batch).  meao_execute_batch where frame f uses params[f] instead of the context's
+ * parameters.  The context's own parameters (meao_set_params) are neither read nor changed.  Every params[f] is validated like
+ * meao_set_params; if any is invalid, nothing is launched and MEAO_ERR_INVALID_ARGUMENT names the frame.  Same launch structure,
+ * same contracts (no allocation and no host synchronisation for DEVICE/DEVICE, asynchronous on `stream`); each kernel reads
+ * its frame's constants from a context-owned table filled by one copy on `stream`.  The tables form a ring of 8 slots
+ * (meao_create allocates it: 8 x max_batch x ~6 KB of device memory and as much pinned host memory): a per-frame call made
+ * while the per-frame call 8 calls before it has not yet completed on the device waits for that call first (back-pressure;
+ * a host that stays fewer than 8 per-frame calls ahead of the device never waits). */
+MEAO_API int32_t meao_execute_batch_params(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc,
+                                           void *const *ao_out, int32_t out_loc, const meao_params *params,
+                                           meao_stream stream);
+/* meao_prefetch_batch whose frames' downsample pass uses params[f].  A prefetched downsample is reused only if the consuming
+ * execute gets the same pointers AND each frame has the same near_clip, far_clip and reversed_z it was computed with
+ * (whichever entry point announced or consumes it); otherwise the pass is re-run. */
+MEAO_API int32_t meao_prefetch_batch_params(meao_ctx *ctx, int32_t n, const void *const *depth, const meao_params *params);
 /* Waits for `stream`; NULL = the stream of the last meao_execute* of this context.  meao_composite /
  * meao_composite_flush do not change what NULL means: a composite issued on another stream is waited for
  * by naming that stream here (or by synchronising it directly). */
@@ -371,6 +386,10 @@ MEAO_API int32_t meao_pool_execute_batch(meao_pool *pool, int32_t n, const void 
  * member's next execute carries its share of the next batch's downsample pass.  Create the pool with
  * cfg.pipelined = 1 to keep this call free of allocation. */
 MEAO_API int32_t meao_pool_prefetch_batch(meao_pool *pool, int32_t n, const void *const *depth);
+/* The per-frame forms for the pool: params[f] goes with frame f to member f mod G. */
+MEAO_API int32_t meao_pool_execute_batch_params(meao_pool *pool, int32_t n, const void *const *depth, int32_t depth_loc,
+                                                void *const *ao_out, int32_t out_loc, const meao_params *params);
+MEAO_API int32_t meao_pool_prefetch_batch_params(meao_pool *pool, int32_t n, const void *const *depth, const meao_params *params);
 /* meao_composite_enqueue / meao_composite_flush for the pool, frames dealt f -> member f mod G: the composite
  * of frame f rides inside the next execute of the member that owns (and produced) it. */
 MEAO_API int32_t meao_pool_composite_enqueue(meao_pool *pool, int32_t mode, int32_t n, const void *const *ao,

@@ -110,6 +110,21 @@ public:
         check(meao_prefetch_batch(ctx_, static_cast<int32_t>(nextDeviceDepth.size()), nextDeviceDepth.data()));
     }
 
+    // Several cameras in one batch: frame f uses params[f] (meao_execute_batch_params); the instance's own parameters are neither
+    // read nor changed.  PrefetchBatchParams announces the next batch with its frames' parameters (meao_prefetch_batch_params).
+    void RenderBatchParams(const std::vector<const void *> &deviceDepth, const std::vector<void *> &deviceAo,
+                           const std::vector<meao_params> &params, meao_stream stream = nullptr)
+    {
+        if (params.size() != deviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        check(meao_execute_batch_params(ctx_, static_cast<int32_t>(deviceDepth.size()), deviceDepth.data(), MEAO_MEM_DEVICE,
+                                        deviceAo.data(), MEAO_MEM_DEVICE, params.data(), stream));
+    }
+    void PrefetchBatchParams(const std::vector<const void *> &nextDeviceDepth, const std::vector<meao_params> &params)
+    {
+        if (params.size() != nextDeviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        check(meao_prefetch_batch_params(ctx_, static_cast<int32_t>(nextDeviceDepth.size()), nextDeviceDepth.data(), params.data()));
+    }
+
     void Synchronize(meao_stream stream = nullptr) { check(meao_synchronize(ctx_, stream)); }
 
     // PushCompositeCommands (AO.cs:822-839).  Composite(): now, on `stream`.  CompositeWithNextFrame(): the
@@ -233,6 +248,20 @@ public:
     void PrefetchBatch(const std::vector<const void *> &nextDeviceDepth)
     {
         check(meao_pool_prefetch_batch(pool_, static_cast<int32_t>(nextDeviceDepth.size()), nextDeviceDepth.data()));
+    }
+    // per-frame parameters: params[f] goes with frame f to member f mod G
+    void RenderDeviceBatchParams(const std::vector<const void *> &deviceDepth, const std::vector<void *> &deviceAo,
+                                 const std::vector<meao_params> &params)
+    {
+        if (params.size() != deviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        check(meao_pool_execute_batch_params(pool_, static_cast<int32_t>(deviceDepth.size()), deviceDepth.data(), MEAO_MEM_DEVICE,
+                                             deviceAo.data(), MEAO_MEM_DEVICE, params.data()));
+    }
+    void PrefetchBatchParams(const std::vector<const void *> &nextDeviceDepth, const std::vector<meao_params> &params)
+    {
+        if (params.size() != nextDeviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        check(meao_pool_prefetch_batch_params(pool_, static_cast<int32_t>(nextDeviceDepth.size()), nextDeviceDepth.data(),
+                                              params.data()));
     }
     void GatherToDevice(const std::vector<const void *> &deviceAo, const std::vector<void *> &dst, int32_t dstDevice)
     {

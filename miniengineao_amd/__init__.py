@@ -8,8 +8,9 @@ using the hot path without the built library raises ImportError (no CPU fallback
 """
 from . import synth  # noqa: F401
 from .sharding import frames_for_rank  # noqa: F401
+from .frame_params import FrameParams  # noqa: F401
 
-__all__ = ["AmbientOcclusion", "AmbientOcclusionPool", "synth", "frames_for_rank"]
+__all__ = ["AmbientOcclusion", "AmbientOcclusionPool", "FrameParams", "synth", "frames_for_rank"]
 
 
 def __getattr__(name):

@@ -22,7 +22,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # MEAO_LIB_PATH: an alternative build of the same library (A/B of kernel variants, tools/run_gpu_variants_ab.sh)
 LIB_PATH = os.environ.get("MEAO_LIB_PATH") or os.path.join(_PKG, "lib", "libmeao_hip.so")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 MAX_BATCH = 64
 NUM_PASSES = 7
 PASS_NAMES = ("downsample", "render", "upsample_L4_to_L3", "upsample_L3_to_L2",
@@ -107,6 +107,9 @@ SIGNATURES = {
     "meao_execute_batch": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
                                        C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
     "meao_prefetch_batch": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "meao_execute_batch_params": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
+                                              C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Params), C.c_void_p]),
+    "meao_prefetch_batch_params": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(Params)]),
     "meao_synchronize": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "meao_get_intermediate": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64,
                                           C.c_int32, C.POINTER(Desc)]),
@@ -130,6 +133,9 @@ SIGNATURES = {
     "meao_pool_gather_to_device": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32]),
     "meao_pool_synchronize": (C.c_int32, [C.c_void_p]),
     "meao_pool_prefetch_batch": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "meao_pool_execute_batch_params": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
+                                                   C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Params)]),
+    "meao_pool_prefetch_batch_params": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(Params)]),
     "meao_pool_composite_enqueue": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_void_p)]),
     "meao_pool_composite_flush": (C.c_int32, [C.c_void_p]),

@@ -15,6 +15,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib as L
+from .frame_params import FrameParams, params_array
 
 _NP_OF_FMT = {L.FMT_F32: np.float32, L.FMT_F16: np.uint16, L.FMT_UNORM8: np.uint8}
 
@@ -125,9 +126,11 @@ class AmbientOcclusion:
         default; uint16 / uint32 codes for UNORM16 / UNORM24 / F16 bits) -> AO (H, W) uint8 / f16 bits."""
         return self.render_batch([depth])[0]
 
-    def render_batch(self, depths: Sequence[np.ndarray]) -> list:
+    def render_batch(self, depths: Sequence[np.ndarray], params: Optional[Sequence[Optional[FrameParams]]] = None) -> list:
+        """params: one FrameParams per frame (meao_execute_batch_params; unset fields = this instance's values), or None."""
         n = len(depths)
         self._sync_params()
+        prm = None if params is None else params_array(params, n, self._prm)
         dt = {L.DEPTH_F32: np.float32, L.DEPTH_UNORM16: np.uint16, L.DEPTH_UNORM24: np.uint32,
               L.DEPTH_F16: np.uint16}[self._cfg.depth_format]
         ins = [np.ascontiguousarray(d, dtype=dt) for d in depths]
@@ -137,25 +140,37 @@ class AmbientOcclusion:
         outs = [np.empty((self.height, self.width), self.ao_dtype) for _ in range(n)]
         pin = (C.c_void_p * n)(*[d.ctypes.data for d in ins])
         pout = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        L.check(self._lib.meao_execute_batch(self._ctx, n, pin, L.MEM_HOST, pout, L.MEM_HOST, None), self._ctx)
+        if prm is None:
+            L.check(self._lib.meao_execute_batch(self._ctx, n, pin, L.MEM_HOST, pout, L.MEM_HOST, None), self._ctx)
+        else:
+            L.check(self._lib.meao_execute_batch_params(self._ctx, n, pin, L.MEM_HOST, pout, L.MEM_HOST, prm, None), self._ctx)
         return outs
 
-    def execute_device(self, depth_ptrs: Sequence[int], out_ptrs: Sequence[int], stream: int = 0) -> None:
-        """Device-resident frames (raw device addresses, e.g. torch ``data_ptr()``); asynchronous."""
+    def execute_device(self, depth_ptrs: Sequence[int], out_ptrs: Sequence[int], stream: int = 0,
+                       params: Optional[Sequence[Optional[FrameParams]]] = None) -> None:
+        """Device-resident frames (raw device addresses, e.g. torch ``data_ptr()``); asynchronous.  params: as in render_batch."""
         n = len(depth_ptrs)
         self._sync_params()
         pin = (C.c_void_p * n)(*depth_ptrs)
         pout = (C.c_void_p * n)(*out_ptrs)
-        L.check(self._lib.meao_execute_batch(self._ctx, n, pin, L.MEM_DEVICE, pout, L.MEM_DEVICE,
-                                             C.c_void_p(stream) if stream else None), self._ctx)
+        s = C.c_void_p(stream) if stream else None
+        if params is None:
+            L.check(self._lib.meao_execute_batch(self._ctx, n, pin, L.MEM_DEVICE, pout, L.MEM_DEVICE, s), self._ctx)
+        else:
+            prm = params_array(params, n, self._prm)
+            L.check(self._lib.meao_execute_batch_params(self._ctx, n, pin, L.MEM_DEVICE, pout, L.MEM_DEVICE, prm, s), self._ctx)
 
-    def prefetch_device(self, depth_ptrs: Sequence[int]) -> None:
+    def prefetch_device(self, depth_ptrs: Sequence[int], params: Optional[Sequence[Optional[FrameParams]]] = None) -> None:
         """Announce the device depth frames of the call after next (meao_prefetch_batch): the next
-        execute_device() carries their downsample pass inside its last upsample kernel."""
+        execute_device() carries their downsample pass inside its last upsample kernel.  params: the frames' own
+        parameters (meao_prefetch_batch_params), as they will be given to the consuming execute_device()."""
         n = len(depth_ptrs)
         self._sync_params()     # pending property changes first: meao_set_params would drop the announcement
         pin = (C.c_void_p * n)(*depth_ptrs)
-        L.check(self._lib.meao_prefetch_batch(self._ctx, n, pin), self._ctx)
+        if params is None:
+            L.check(self._lib.meao_prefetch_batch(self._ctx, n, pin), self._ctx)
+        else:
+            L.check(self._lib.meao_prefetch_batch_params(self._ctx, n, pin, params_array(params, n, self._prm)), self._ctx)
 
     def synchronize(self, stream: int = 0) -> None:
         L.check(self._lib.meao_synchronize(self._ctx, C.c_void_p(stream) if stream else None), self._ctx)
@@ -308,6 +323,7 @@ class AmbientOcclusionPool:
         prm.near_clip, prm.far_clip, prm.reversed_z, prm.intensity = near_clip, far_clip, 1 if reversed_z else 0, intensity
         if projection00 is not None:
             prm.proj00 = projection00
+        self._prm = prm           # what unset FrameParams fields take
         try:
             self._check(self._lib.meao_pool_set_params(self._pool, C.byref(prm)))
         except Exception:
@@ -323,27 +339,40 @@ class AmbientOcclusionPool:
     def device_of_frame(self, frame: int) -> int:
         return self._lib.meao_pool_device_of_frame(self._pool, frame)
 
-    def render_batch(self, depths: Sequence[np.ndarray]) -> list:
-        """Host arrays in and out."""
+    def render_batch(self, depths: Sequence[np.ndarray], params: Optional[Sequence[Optional[FrameParams]]] = None) -> list:
+        """Host arrays in and out.  params: one FrameParams per frame (it goes with the frame to its member), or None."""
         n = len(depths)
         ins = [np.ascontiguousarray(d, dtype=np.float32) for d in depths]
         dt = np.uint8 if self._cfg.ao_format == L.AO_R8 else np.uint16
         outs = [np.empty((self._cfg.height, self._cfg.width), dt) for _ in range(n)]
         pin = (C.c_void_p * n)(*[d.ctypes.data for d in ins])
         pout = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        self._check(self._lib.meao_pool_execute_batch(self._pool, n, pin, L.MEM_HOST, pout, L.MEM_HOST))
+        if params is None:
+            self._check(self._lib.meao_pool_execute_batch(self._pool, n, pin, L.MEM_HOST, pout, L.MEM_HOST))
+        else:
+            self._check(self._lib.meao_pool_execute_batch_params(self._pool, n, pin, L.MEM_HOST, pout, L.MEM_HOST,
+                                                                 params_array(params, n, self._prm)))
         return outs
 
-    def execute_device(self, depth_ptrs: Sequence[int], out_ptrs: Sequence[int]) -> None:
+    def execute_device(self, depth_ptrs: Sequence[int], out_ptrs: Sequence[int],
+                       params: Optional[Sequence[Optional[FrameParams]]] = None) -> None:
         """Frame f resident on device_of_frame(f); asynchronous (synchronize())."""
         n = len(depth_ptrs)
         pin, pout = (C.c_void_p * n)(*depth_ptrs), (C.c_void_p * n)(*out_ptrs)
-        self._check(self._lib.meao_pool_execute_batch(self._pool, n, pin, L.MEM_DEVICE, pout, L.MEM_DEVICE))
+        if params is None:
+            self._check(self._lib.meao_pool_execute_batch(self._pool, n, pin, L.MEM_DEVICE, pout, L.MEM_DEVICE))
+        else:
+            self._check(self._lib.meao_pool_execute_batch_params(self._pool, n, pin, L.MEM_DEVICE, pout, L.MEM_DEVICE,
+                                                                 params_array(params, n, self._prm)))
 
-    def prefetch_device(self, depth_ptrs: Sequence[int]) -> None:
+    def prefetch_device(self, depth_ptrs: Sequence[int], params: Optional[Sequence[Optional[FrameParams]]] = None) -> None:
         """meao_pool_prefetch_batch: the frames of the call after next, dealt like execute_device deals them."""
         n = len(depth_ptrs)
-        self._check(self._lib.meao_pool_prefetch_batch(self._pool, n, (C.c_void_p * n)(*depth_ptrs)))
+        if params is None:
+            self._check(self._lib.meao_pool_prefetch_batch(self._pool, n, (C.c_void_p * n)(*depth_ptrs)))
+        else:
+            self._check(self._lib.meao_pool_prefetch_batch_params(self._pool, n, (C.c_void_p * n)(*depth_ptrs),
+                                                                  params_array(params, n, self._prm)))
 
     def composite_enqueue_device(self, mode: int, ao_ptrs: Sequence[int], color_ptrs: Sequence[int],
                                  gbuffer0_ptrs: Optional[Sequence[int]] = None) -> None:

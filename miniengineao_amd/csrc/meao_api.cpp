@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -96,7 +97,28 @@ struct meao_ctx {
     int debug_fail_allocs = 0;         // meao_test_fail_next_allocs: arena allocations still to fail (testhooks variant only)
 #endif
 
+    // Per-frame parameters (meao_execute_batch_params / meao_prefetch_batch_params).  A call with per-frame constants fills one
+    // slot of a ring of FrameArgs tables (max_batch entries each): built in pinned host memory, copied to the device slot on the
+    // call's stream, both reused once the event recorded behind that call's last launch has completed.  Allocated by meao_create.
+    static constexpr int kFrameRing = 8;
+    FrameArgs *frame_table = nullptr, *frame_stage = nullptr;
+    hipEvent_t frame_ev[kFrameRing] = {};
+    bool frame_ev_pending[kFrameRing] = {};
+    int frame_ring_pos = 0;
+    std::vector<Plan> frame_plan, next_plan;     // MEAO_MAX_BATCH each: the plans of this call's frames / of the announced batch's
+    bool next_per_frame = false;                 // the announced batch came with its own parameters (next_prm)
+    meao_params next_prm[MEAO_MAX_BATCH] = {};
+    // ZBufferParams inputs (near, far, reversed_z) each frame of a ready prefetched set was downsampled with, and whether that
+    // pass stamped the hostile flags (exact division): the consuming call must match both
+    struct ZbInputs { float near_clip, far_clip; int32_t reversed_z; };
+    ZbInputs ready_zb[MEAO_MAX_BATCH] = {};
+    bool ready_exact = false;
+
     const void *last_out[MEAO_MAX_BATCH] = {};   // device address of the last results (debug id 17)
+    // the last call's parameters per frame, for the debug buffers built on demand (ids 1, 6-9)
+    float last_zp[MEAO_MAX_BATCH][2] = {};
+    int32_t last_reversed_z[MEAO_MAX_BATCH] = {};
+    float last_pad[MEAO_MAX_BATCH][4] = {};
     const void *last_depth[MEAO_MAX_BATCH] = {}; // device address of the last call's raw depth frames (debug id 1 is built from them)
     int last_frames = 0;
 
@@ -209,7 +231,7 @@ bool exact_rcp_div_applicable(const meao_config &c, const meao_params &p, const 
     return true;
 }
 
-void drop_prefetch(meao_ctx *ctx) { ctx->next_n = 0; ctx->ready_n = 0; ctx->ready_stream = nullptr; }
+void drop_prefetch(meao_ctx *ctx) { ctx->next_n = 0; ctx->next_per_frame = false; ctx->ready_n = 0; ctx->ready_stream = nullptr; }
 
 void update_plan(meao_ctx *ctx)
 {
@@ -391,8 +413,11 @@ struct ArgBuilder {
     void *const *out_dev;
     const uint32_t *hostile;      // flags and generation of the downsample set this call reads
     uint32_t generation;
+    const Plan *plan;             // the constants: the context's, or one frame's (meao_execute_batch_params)
+    const meao_params *prm;
+    int exact_rcp_div;            // of the call (over all its frames)
 
-    const Plan &p() const { return ctx->plan; }
+    const Plan &p() const { return *plan; }
     const meao_config &c() const { return ctx->cfg; }
     int rtne() const { return ctx->cfg.f16_rounding == MEAO_F16_RTNE; }
     // 4-texel vector loads / stores need 16-byte (f32, UNORM24), 8-byte (16-bit) aligned depth rows and 4- (R8) / 8-byte (F16)
@@ -419,9 +444,9 @@ struct ArgBuilder {
         for (int k = 0; k < 5; ++k) { ds.w[k] = p().mip[k].w; ds.h[k] = p().mip[k].h; }
         ds.zp0 = p().zbuffer_params[0];
         ds.zp1 = p().zbuffer_params[1];
-        ds.reversed_z = ctx->prm.reversed_z != 0;
+        ds.reversed_z = prm->reversed_z != 0;
         ds.f16_rtne = rtne();
-        ds.exact_rcp_div = ctx->exact_rcp_div;
+        ds.exact_rcp_div = exact_rcp_div;
         if (lean) {
             ds.rows_per_lane = 1;
             ds.tiles_x = (ds.w[1] + kLeanMipW - 1) / kLeanMipW;
@@ -480,7 +505,7 @@ struct ArgBuilder {
         rn.num_levels = count;
         rn.blocks_per_frame = blocks;
         rn.f16_rtne = rtne();
-        rn.exact_rcp_div = ctx->exact_rcp_div;
+        rn.exact_rcp_div = exact_rcp_div;
         rn.exhaustive = c().sample_set == MEAO_SAMPLES_EXHAUSTIVE;
         rn.hostile = hostile;
         rn.generation = generation;
@@ -516,7 +541,7 @@ struct ArgBuilder {
         up.blur_tolerance = k.blur_tolerance;
         up.upsample_tolerance = k.upsample_tolerance;
         up.f16_rtne = rtne();
-        up.exact_rcp_div = ctx->exact_rcp_div;
+        up.exact_rcp_div = exact_rcp_div;
         up.hostile = hostile;
         up.generation = generation;
         bool vec_ok = (up.hw & 3) == 0;
@@ -542,7 +567,7 @@ struct ArgBuilder {
         HiDepthArgs hd{};
         for (int f = 0; f < n; ++f) hd.raw[f] = depth_dev[f];
         hd.depth_format = c().depth_format;
-        hd.reversed_z = ctx->prm.reversed_z != 0;
+        hd.reversed_z = prm->reversed_z != 0;
         hd.zp0 = p().zbuffer_params[0];
         hd.zp1 = p().zbuffer_params[1];
         return hd;
@@ -551,12 +576,85 @@ struct ArgBuilder {
 
 uint32_t next_generation(meao_ctx *ctx) { if (++ctx->gen_counter == 0) ++ctx->gen_counter; return ctx->gen_counter; }   // never 0
 
-// The launch sequence of one batch.
-int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *out_dev, hipStream_t stream)
+// The argument blocks of every launch of one call, built by one ArgBuilder: the context's constants (a shared call; the kernarg
+// copies), or one frame's (an entry of the FrameArgs table of a per-frame call).  `nb` builds the announced batch's pass.
+struct CallShape {
+    BatchShape b;
+    bool three_level;     // the launch list has Step::BlendThreeLevel
+};
+
+void build_call_args(const ArgBuilder &args, const ArgBuilder &nb, const CallShape &cs, int other, FrameArgs *out)
+{
+    meao_ctx *ctx = args.ctx;
+    const meao_config &c = ctx->cfg;
+    const int n = args.n;
+    if (!cs.b.prefetched) out->ds = args.downsample(n, args.depth_dev, ctx->ds_cur, ctx->set_gen[ctx->ds_cur], false, true);
+    out->render = args.render(1, c.num_levels, false, !cs.b.carry_composite);
+    if (c.hq_levels > 0) out->render_hq = args.render(1, c.num_levels, true, false);
+    for (int hi = 1; hi < c.num_levels; ++hi) out->up[hi] = args.upsample(hi);
+    if (cs.three_level && out->up[1].tile_h != ups_tile_h(false)) {      // the nested launch tiles L2 -> L1 with 64 x 32
+        out->up[1].tile_h = ups_tile_h(false);
+        out->up[1].tiles_y = (out->up[1].hh + out->up[1].tile_h - 1) / out->up[1].tile_h;
+    }
+    out->up[0] = args.upsample(0, cs.b.next == 1);
+    out->hi = args.hi_depth();
+    if (cs.b.next != 0)
+        out->next_ds = nb.downsample(ctx->next_n, ctx->next_depth, other, ctx->set_gen[other], cs.b.next == 1, cs.b.next == 2);
+}
+
+bool same_zb(const meao_ctx::ZbInputs &z, const meao_params &p)
+{
+    return std::memcmp(&z.near_clip, &p.near_clip, sizeof(float)) == 0 && std::memcmp(&z.far_clip, &p.far_clip, sizeof(float)) == 0 &&
+           (z.reversed_z != 0) == (p.reversed_z != 0);
+}
+
+// A ring slot of per-frame constants (meao_execute_batch_params) in use by one call.  From the moment its copy is queued,
+// whatever the call does next -- all its launches, or an early return on a failed one -- the slot is handed back guarded:
+// an event recorded behind the call's work on its stream (reuse waits for it), or, if even that fails, a synchronised stream.
+struct RingSlotGuard {
+    meao_ctx *ctx;
+    int slot;
+    hipStream_t stream;
+    bool armed = false;
+    ~RingSlotGuard()
+    {
+        if (!armed) return;
+        if (hipEventRecord(ctx->frame_ev[slot], stream) == hipSuccess) {
+            ctx->frame_ev_pending[slot] = true;
+        } else {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(stream);
+        }
+    }
+};
+
+// The launch sequence of one batch.  fp: per-frame parameters (meao_execute_batch_params), nullptr = the context's.
+int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *out_dev, hipStream_t stream,
+              const meao_params *fp = nullptr)
 {
     const meao_config &c = ctx->cfg;
     hipEvent_t *ev = nullptr;
     uint32_t ran = 0;
+
+    // Constants of this call's frames: the context's plan, or each frame's own (the same plan code, so the per-frame values are
+    // those a shared call with that frame's parameters would use).  Exact division is chosen for the call: AND over its frames.
+    const Plan *plan_of[MEAO_MAX_BATCH];
+    const meao_params *prm_of[MEAO_MAX_BATCH];
+    int exact = ctx->exact_rcp_div;
+    if (fp) {
+        exact = 1;
+        for (int f = 0; f < n; ++f) {
+            build_plan(c.width, c.height, c.num_levels, c.sample_set, fp[f], &ctx->frame_plan[f]);
+            plan_of[f] = &ctx->frame_plan[f];
+            prm_of[f] = &fp[f];
+            if (!exact_rcp_div_applicable(c, fp[f], ctx->frame_plan[f])) exact = 0;
+        }
+    } else {
+        for (int f = 0; f < n; ++f) { plan_of[f] = &ctx->plan; prm_of[f] = &ctx->prm; }
+    }
+    const bool next_per_frame = ctx->next_n > 0 && ctx->next_per_frame;
+    const bool per_frame = fp != nullptr || next_per_frame;
+
     if (ctx->profiling) {
         if (ctx->profile_phase == 0) {
             if (ctx->ring_fill == kProfileRing) fold_profile(ctx);
@@ -567,42 +665,72 @@ int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *o
 
     // A previous call may already have downsampled exactly these frames (meao_prefetch_batch).  The
     // prefetched set is only valid on the stream of the execute that carried it: stream order is what
-    // orders that kernel before this call's readers.
+    // orders that kernel before this call's readers.  It must also have been computed with each frame's ZBufferParams inputs, and
+    // have stamped the hostile flags if this call reads them (exact division).
     BatchShape shape{};
     shape.frames = n;
-    shape.prefetched = ctx->ready_n == n && ctx->ready_stream == stream && std::memcmp(ctx->ready_depth, depth_dev, sizeof(void *) * n) == 0;
+    shape.prefetched = ctx->ready_n == n && ctx->ready_stream == stream && std::memcmp(ctx->ready_depth, depth_dev, sizeof(void *) * n) == 0 &&
+                       (ctx->ready_exact || !exact);
+    for (int f = 0; shape.prefetched && f < n; ++f) shape.prefetched = same_zb(ctx->ready_zb[f], *prm_of[f]);
     ctx->ds_cur = shape.prefetched ? ctx->ready_set : 0;
     ctx->ready_n = 0;
     if (!shape.prefetched) ctx->set_gen[ctx->ds_cur] = next_generation(ctx);      // direct launches take a fresh generation per pass: no flag clearing
-    if (ctx->pending_comp.frames > 0 && c.sample_set == MEAO_SAMPLES_EXHAUSTIVE) {
-        const int rc = flush_pending_composite(ctx, stream);     // the 68-sample render kernel carries nothing
+    if (ctx->pending_comp.frames > 0 && (c.sample_set == MEAO_SAMPLES_EXHAUSTIVE || per_frame)) {
+        // the 68-sample render kernel carries nothing, and the per-frame render kernels neither
+        const int rc = flush_pending_composite(ctx, stream);
         if (rc != MEAO_OK) return rc;
     }
     shape.carry_composite = ctx->pending_comp.frames > 0;
 
-    const ArgBuilder args{ctx, n, depth_dev, out_dev, ctx->hostile_of(ctx->ds_cur), ctx->set_gen[ctx->ds_cur]};
+    const ArgBuilder args{ctx, n, depth_dev, out_dev, ctx->hostile_of(ctx->ds_cur), ctx->set_gen[ctx->ds_cur], &ctx->plan, &ctx->prm, exact};
     // The announced next batch: its pass rides in this call's last kernel where the fused form applies (f32 depth, 16-byte
     // loads, a workgroup per carried tile), else it runs as a launch of its own behind it.  Either way the next call finds it done.
     // (Inside the render launch instead -- CarriedMips in the texel loop, round 6 -- it costs the same 56-60 us per 16 4K frames:
     // profiles/r06_ab_next_downsample_in_render_vs_final_vs_own_launch.jsonl, r06_scripts/r06_downsample_in_render.patch.)
     const int other = 1 - ctx->ds_cur;
-    DownsampleArgs next_ds{};
-    UpsampleArgs final_up = args.upsample(0);
-    const HiDepthArgs hi_depth = args.hi_depth();
     if (ctx->next_n > 0) {
         ctx->set_gen[other] = next_generation(ctx);
-        next_ds = args.downsample(ctx->next_n, ctx->next_depth, other, ctx->set_gen[other], true, false);
-        const UpsampleArgs carrying = args.upsample(0, true);
-        if (!ctx->next_ds_own_launch && fused_downsample_applicable(carrying, hi_depth, next_ds, n)) {
-            shape.next = 1;
-            final_up = carrying;
-        } else {
-            shape.next = 2;
-            next_ds = args.downsample(ctx->next_n, ctx->next_depth, other, ctx->set_gen[other], false, true);
-        }
+        const DownsampleArgs lean = args.downsample(ctx->next_n, ctx->next_depth, other, ctx->set_gen[other], true, false);
+        shape.next = !ctx->next_ds_own_launch && fused_downsample_applicable(args.upsample(0, true), args.hi_depth(), lean, n) ? 1 : 2;
     }
 
     const LaunchList list = plan_launches(ctx, shape);
+    CallShape cs{shape, false};
+    for (int i = 0; i < list.n; ++i) cs.three_level = cs.three_level || list.v[i].step == Step::BlendThreeLevel;
+    FrameArgs shared{};
+    build_call_args(args, args, cs, other, &shared);
+
+    // Per-frame constants: frame f's blocks (and the announced batch's frame f for the carried pass) into a ring slot, one copy.
+    const FrameArgs *pf = nullptr;
+    int ring_slot = -1;
+    RingSlotGuard slot_guard{ctx, 0, stream};
+    if (per_frame) {
+        ring_slot = ctx->frame_ring_pos;
+        ctx->frame_ring_pos = (ctx->frame_ring_pos + 1) % meao_ctx::kFrameRing;
+        // back-pressure only: the slot's call is kFrameRing calls old (meao.h: the host waits only when it runs that far ahead)
+        if (ctx->frame_ev_pending[ring_slot]) {
+            MEAO_HIP(ctx, hipEventSynchronize(ctx->frame_ev[ring_slot]));
+            ctx->frame_ev_pending[ring_slot] = false;
+        }
+        FrameArgs *stage = ctx->frame_stage + static_cast<size_t>(ring_slot) * c.max_batch;
+        const int count = std::max(n, shape.next != 0 ? ctx->next_n : 0);
+        for (int f = 0; f < count; ++f) {
+            const ArgBuilder fa{ctx, n, depth_dev, out_dev, args.hostile, args.generation, f < n ? plan_of[f] : &ctx->plan,
+                                f < n ? prm_of[f] : &ctx->prm, exact};
+            const bool own_next = next_per_frame && f < ctx->next_n;
+            const ArgBuilder fb{ctx, n, depth_dev, out_dev, args.hostile, args.generation, own_next ? &ctx->next_plan[f] : &ctx->plan,
+                                own_next ? &ctx->next_prm[f] : &ctx->prm, exact};
+            build_call_args(fa, fb, cs, other, &stage[f]);
+        }
+        FrameArgs *dev = ctx->frame_table + static_cast<size_t>(ring_slot) * c.max_batch;
+        slot_guard.slot = ring_slot;
+        slot_guard.armed = true;      // from here on every exit of this call hands the slot back guarded
+        MEAO_HIP(ctx, hipMemcpyAsync(dev, stage, sizeof(FrameArgs) * count, hipMemcpyHostToDevice, stream));
+        pf = dev;
+    }
+    auto P = [&](auto member) { return pf ? &(pf->*member) : nullptr; };
+    auto PU = [&](int hi) { return pf ? &pf->up[hi] : nullptr; };
+
     for (int i = 0; i < list.n; ++i) {
         const Launch &L = list.v[i];
         TraceRange tr(ctx, L.range);
@@ -611,42 +739,37 @@ int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *o
         if (timed && ev) MEAO_HIP(ctx, hipEventRecord(ev[L.slot * 2], stream));
         switch (L.step) {
         case Step::Downsample:
-            MEAO_HIP(ctx, launch_downsample(args.downsample(n, depth_dev, ctx->ds_cur, ctx->set_gen[ctx->ds_cur], false, true), n, stream));
+            MEAO_HIP(ctx, launch_downsample(shared.ds, n, stream, P(&FrameArgs::ds)));
             break;
         case Step::Render:
-            MEAO_HIP(ctx, launch_render(args.render(1, c.num_levels, false, true), c.ao_format, n, stream));
+            MEAO_HIP(ctx, launch_render(shared.render, c.ao_format, n, stream, P(&FrameArgs::render)));
             break;
         case Step::RenderWithComposite:
             // the composite of frames an earlier call produced streams under this (VALU-bound) kernel
-            MEAO_HIP(ctx, launch_render_with_composite(args.render(1, c.num_levels, false, false), ctx->pending_comp, c.ao_format, n, stream));
+            MEAO_HIP(ctx, launch_render_with_composite(shared.render, ctx->pending_comp, c.ao_format, n, stream));
             ctx->pending_comp.frames = 0;
             break;
         case Step::RenderHq:
-            MEAO_HIP(ctx, launch_render_wide(args.render(1, c.num_levels, true, false), c.ao_format, n, stream));
+            MEAO_HIP(ctx, launch_render_wide(shared.render_hq, c.ao_format, n, stream, P(&FrameArgs::render_hq)));
             break;
         case Step::Blend:
-            MEAO_HIP(ctx, launch_upsample(args.upsample(L.hi), nullptr, c.ao_format, n, stream));
+            MEAO_HIP(ctx, launch_upsample(shared.up[L.hi], nullptr, c.ao_format, n, stream, PU(L.hi)));
             break;
         case Step::BlendTwoLevel:
-            MEAO_HIP(ctx, launch_upsample_two_level(args.upsample(2), args.upsample(3), c.ao_format, n, stream));
+            MEAO_HIP(ctx, launch_upsample_two_level(shared.up[2], shared.up[3], c.ao_format, n, stream, PU(2), PU(3)));
             break;
-        case Step::BlendThreeLevel: {
-            UpsampleArgs outer = args.upsample(1);
-            if (outer.tile_h != ups_tile_h(false)) {        // the nested launch tiles L2 -> L1 with 64 x 32
-                outer.tile_h = ups_tile_h(false);
-                outer.tiles_y = (outer.hh + outer.tile_h - 1) / outer.tile_h;
-            }
-            MEAO_HIP(ctx, launch_upsample_three_level(outer, args.upsample(2), args.upsample(3), c.ao_format, n, stream));
+        case Step::BlendThreeLevel:
+            MEAO_HIP(ctx, launch_upsample_three_level(shared.up[1], shared.up[2], shared.up[3], c.ao_format, n, stream, PU(1), PU(2), PU(3)));
             break;
-        }
         case Step::Final:
-            MEAO_HIP(ctx, launch_upsample(final_up, &hi_depth, c.ao_format, n, stream));
+            MEAO_HIP(ctx, launch_upsample(shared.up[0], &shared.hi, c.ao_format, n, stream, PU(0), P(&FrameArgs::hi)));
             break;
         case Step::FinalWithNextDownsample:
-            MEAO_HIP(ctx, launch_upsample_final_with_downsample(final_up, hi_depth, next_ds, c.ao_format, n, stream));
+            MEAO_HIP(ctx, launch_upsample_final_with_downsample(shared.up[0], shared.hi, shared.next_ds, c.ao_format, n, stream, PU(0),
+                                                                P(&FrameArgs::hi), P(&FrameArgs::next_ds)));
             break;
         case Step::DownsampleNext:
-            MEAO_HIP(ctx, launch_downsample(next_ds, ctx->next_n, stream));
+            MEAO_HIP(ctx, launch_downsample(shared.next_ds, ctx->next_n, stream, P(&FrameArgs::next_ds)));
             break;
         }
         if (timed) {
@@ -658,11 +781,25 @@ int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *o
         ctx->ready_n = ctx->next_n;
         ctx->ready_set = other;
         ctx->ready_stream = stream;
+        ctx->ready_exact = exact != 0;
         std::memcpy(ctx->ready_depth, ctx->next_depth, sizeof ctx->ready_depth);
+        for (int f = 0; f < ctx->next_n; ++f) {
+            const meao_params &q = next_per_frame ? ctx->next_prm[f] : ctx->prm;
+            ctx->ready_zb[f] = meao_ctx::ZbInputs{q.near_clip, q.far_clip, q.reversed_z != 0};
+        }
         ctx->next_n = 0;
+        ctx->next_per_frame = false;
     }
     if (ev) ctx->ran_mask[ctx->ring_fill++] = ran;
-    for (int f = 0; f < n; ++f) { ctx->last_out[f] = out_dev[f]; ctx->last_depth[f] = depth_dev[f]; }
+    for (int f = 0; f < n; ++f) {
+        ctx->last_out[f] = out_dev[f];
+        ctx->last_depth[f] = depth_dev[f];
+        // the parameters the buffers built on demand need (debug ids 1, 6-9), as this call used them
+        ctx->last_zp[f][0] = plan_of[f]->zbuffer_params[0];
+        ctx->last_zp[f][1] = plan_of[f]->zbuffer_params[1];
+        ctx->last_reversed_z[f] = prm_of[f]->reversed_z != 0;
+        for (int k = 0; k < 4; ++k) ctx->last_pad[f][k] = plan_of[f]->render[k].pad_value;
+    }
     ctx->last_frames = n;
     ctx->last_stream = stream;
     return MEAO_OK;
@@ -821,6 +958,16 @@ int32_t meao_create(const meao_config *cfg, meao_ctx **out_ctx)
         if (e == hipSuccess) e = hipMemset(ctx->hostile, 0, bytes);
         if (e != hipSuccess) rc = fail_hip(ctx, e, "hipMalloc (hostile flags)");
     }
+    if (rc == MEAO_OK) {
+        // per-frame constants (meao_execute_batch_params): a ring of FrameArgs tables, device + pinned staging, and their events
+        ctx->frame_plan.resize(MEAO_MAX_BATCH);
+        ctx->next_plan.resize(MEAO_MAX_BATCH);
+        const size_t bytes = sizeof(FrameArgs) * meao_ctx::kFrameRing * cfg->max_batch;
+        e = hipMalloc(reinterpret_cast<void **>(&ctx->frame_table), bytes);
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&ctx->frame_stage), bytes, hipHostMallocDefault);
+        for (int i = 0; e == hipSuccess && i < meao_ctx::kFrameRing; ++i) e = hipEventCreateWithFlags(&ctx->frame_ev[i], hipEventDisableTiming);
+        if (e != hipSuccess) rc = fail_hip(ctx, e, "per-frame constant tables");
+    }
     // cfg.pipelined: the second downsample set exists from the start, so meao_prefetch_batch never re-allocates
     if (rc == MEAO_OK) rc = reallocate(ctx, *cfg, cfg->pipelined != 0);
     if (rc != MEAO_OK) {
@@ -846,6 +993,10 @@ int32_t meao_destroy(meao_ctx *ctx)
     release_buffers(ctx);
     if (ctx->counter) (void)hipFree(ctx->counter);
     if (ctx->hostile) (void)hipFree(ctx->hostile);
+    if (ctx->frame_table) (void)hipFree(ctx->frame_table);
+    if (ctx->frame_stage) (void)hipHostFree(ctx->frame_stage);
+    for (hipEvent_t e : ctx->frame_ev)
+        if (e) (void)hipEventDestroy(e);
     if (ctx->roctx_lib) (void)dlclose(ctx->roctx_lib);
     for (hipEvent_t ev : ctx->events) (void)hipEventDestroy(ev);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -903,8 +1054,21 @@ const char *meao_last_error(const meao_ctx *ctx) { return ctx ? ctx->err.c_str()
 
 // meao_execute_batch; wait_for_host = false (pool members only) leaves the staged copies of a HOST call in
 // flight on `stream_` -- the caller synchronises the stream before it touches the host buffers.
+// Every params[f] valid (as meao_set_params checks it); else the status, with the frame named in the context's error.
+static int validate_frame_params(meao_ctx *ctx, int32_t n, const meao_params *params, const char *what)
+{
+    for (int f = 0; f < n; ++f) {
+        if (params[f].struct_size != sizeof(meao_params))
+            return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(what) + ": params[" + std::to_string(f) + "]: struct_size mismatch (ABI)");
+        if (!params_valid(params[f]))
+            return fail(ctx, MEAO_ERR_INVALID_ARGUMENT,
+                        std::string(what) + ": params[" + std::to_string(f) + "]: non-finite or degenerate parameter");
+    }
+    return MEAO_OK;
+}
+
 int meao::execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
-                                 int32_t out_loc, meao_stream stream_, bool wait_for_host)
+                                 int32_t out_loc, meao_stream stream_, bool wait_for_host, const meao_params *params)
 {
     if (!ctx || !depth || !ao_out) return MEAO_ERR_INVALID_ARGUMENT;
     if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_execute_batch: n must be 1..max_batch");
@@ -913,6 +1077,10 @@ int meao::execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *de
     for (int f = 0; f < n; ++f)
         if (!depth[f] || !ao_out[f]) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_execute_batch: null frame pointer");
     if (!ctx->arena) return fail(ctx, MEAO_ERR_OUT_OF_MEMORY, "meao_execute_batch: the context has no intermediates");
+    if (params) {
+        const int vr = validate_frame_params(ctx, n, params, "meao_execute_batch_params");
+        if (vr != MEAO_OK) return vr;
+    }
     int rc = use_device(ctx);
     if (rc != MEAO_OK) return rc;
     hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->own_stream;
@@ -944,7 +1112,7 @@ int meao::execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *de
         for (int f = 0; f < n; ++f) out_dev[f] = ao_out[f];
     }
 
-    rc = run_batch(ctx, n, depth_dev, out_dev, stream);
+    rc = run_batch(ctx, n, depth_dev, out_dev, stream, params);
     if (rc != MEAO_OK) return rc;
 
     if (out_loc == MEAO_MEM_HOST)
@@ -962,7 +1130,14 @@ int32_t meao_execute_batch(meao_ctx *ctx, int32_t n, const void *const *depth, i
     return meao::execute_batch_internal(ctx, n, depth, depth_loc, ao_out, out_loc, stream_, true);
 }
 
-int32_t meao_prefetch_batch(meao_ctx *ctx, int32_t n, const void *const *depth)
+int32_t meao_execute_batch_params(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
+                                  int32_t out_loc, const meao_params *params, meao_stream stream_)
+{
+    if (!params) return ctx ? fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_execute_batch_params: params is null") : MEAO_ERR_INVALID_ARGUMENT;
+    return meao::execute_batch_internal(ctx, n, depth, depth_loc, ao_out, out_loc, stream_, true, params);
+}
+
+static int prefetch_batch(meao_ctx *ctx, int32_t n, const void *const *depth, const meao_params *params)
 {
     if (!ctx || !depth) return MEAO_ERR_INVALID_ARGUMENT;
     if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_prefetch_batch: n must be 1..max_batch");
@@ -979,7 +1154,25 @@ int32_t meao_prefetch_batch(meao_ctx *ctx, int32_t n, const void *const *depth)
     }
     ctx->next_n = n;
     for (int f = 0; f < n; ++f) ctx->next_depth[f] = depth[f];
+    ctx->next_per_frame = params != nullptr;
+    if (params)
+        for (int f = 0; f < n; ++f) {
+            ctx->next_prm[f] = params[f];
+            build_plan(ctx->cfg.width, ctx->cfg.height, ctx->cfg.num_levels, ctx->cfg.sample_set, params[f], &ctx->next_plan[f]);
+        }
     return MEAO_OK;
+}
+
+int32_t meao_prefetch_batch(meao_ctx *ctx, int32_t n, const void *const *depth) { return prefetch_batch(ctx, n, depth, nullptr); }
+
+int32_t meao_prefetch_batch_params(meao_ctx *ctx, int32_t n, const void *const *depth, const meao_params *params)
+{
+    if (!ctx || !params) return MEAO_ERR_INVALID_ARGUMENT;
+    if (n >= 1 && n <= ctx->cfg.max_batch) {
+        const int rc = validate_frame_params(ctx, n, params, "meao_prefetch_batch_params");
+        if (rc != MEAO_OK) return rc;
+    }
+    return prefetch_batch(ctx, n, depth, params);
 }
 
 int32_t meao_execute(meao_ctx *ctx, const void *depth, int32_t depth_loc, void *ao_out, int32_t out_loc,
@@ -1027,10 +1220,10 @@ static int locate_debug_buffer(meao_ctx *ctx, int32_t frame, int32_t debug_id, c
         la.dst = reinterpret_cast<uint16_t *>(ctx->atlas_scratch);
         la.pixels = static_cast<int64_t>(d.width) * d.height;
         la.depth_format = ctx->cfg.depth_format;
-        la.reversed_z = ctx->prm.reversed_z != 0;
+        la.reversed_z = ctx->last_reversed_z[frame];          // the parameters the last call used for this frame
         la.f16_rtne = ctx->cfg.f16_rounding == MEAO_F16_RTNE;
-        la.zp0 = ctx->plan.zbuffer_params[0];
-        la.zp1 = ctx->plan.zbuffer_params[1];
+        la.zp0 = ctx->last_zp[frame][0];
+        la.zp1 = ctx->last_zp[frame][1];
         MEAO_HIP(ctx, launch_linear_depth(la, s));
         *out_src = ctx->atlas_scratch;
     } else if (debug_id <= 5) *out_src = slot + ctx->off_low_of(ctx->ds_cur, debug_id - 2);
@@ -1045,7 +1238,7 @@ static int locate_debug_buffer(meao_ctx *ctx, int32_t frame, int32_t debug_id, c
         ta.dst = reinterpret_cast<uint16_t *>(ctx->atlas_scratch);
         ta.lw = ctx->plan.mip[level].w; ta.lh = ctx->plan.mip[level].h;
         ta.sw = d.width; ta.sh = d.height;
-        ta.pad_value = ctx->plan.render[level - 1].pad_value;
+        ta.pad_value = ctx->last_pad[frame][level - 1];
         ta.f16_rtne = ctx->cfg.f16_rounding == MEAO_F16_RTNE;
         MEAO_HIP(ctx, launch_tile_atlas(ta, s));
         *out_src = ctx->atlas_scratch;

@@ -305,6 +305,17 @@ __device__ __forceinline__ int xcd_contiguous(int id, int n)
     return xcd * q + min(xcd, r) + (id >> 3);
 }
 
+// Frame `frame`'s copy of an argument block of a per-frame call: `first` is the block's address in frame 0's FrameArgs.
+// Read through the constant address space, as the kernarg copy of a shared launch is: the table is written by a copy
+// ordered before the launch and never during it, so every field is a workgroup-uniform scalar load.
+template <typename T>
+__device__ __forceinline__ const T &frame_block(const T *first, int frame)
+{
+    typedef const __attribute__((address_space(4))) char *const_bytes;
+    const const_bytes p = (const_bytes)first + sizeof(FrameArgs) * static_cast<uint32_t>(frame);
+    return *(const T *)p;
+}
+
 // True when the downsample pass that produced this frame's depth mips saw a texel outside the
 // verified operand range of the exact v_rcp_f32 sequences (see nice_denominator).
 __device__ __forceinline__ bool frame_is_hostile(const uint32_t *hostile, uint32_t generation, int frame)

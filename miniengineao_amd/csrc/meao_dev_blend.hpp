@@ -168,5 +168,50 @@ __device__ __forceinline__ void blend_window_into_lds(const UpsampleArgs &in, fl
 }
 
 
+// ---- the nested blend launches (meao_k_upsample_nested.hip and its per-frame form)
+// Upsample.main_blendout L4 -> L3 evaluated inside the L3 -> L2 pass: the smallest pass of the chain
+// (one wave of workgroups, three barriers, two memory round trips: latency-bound, and a launch of its
+// own) disappears; each L3 -> L2 tile computes the 38 x 22 window of Combined3 it needs itself
+// (1.6x the texels of that pass, which is 1/16 of the last pass's work).
+template <int AOFMT, bool RTNE, int DIV>
+__device__ __forceinline__ void upsample_two_level_tile(const UpsampleArgs &outer, const UpsampleArgs &inner, float *smem, int tile,
+                                                        int frame)
+{
+    typedef UpsTile<ups_tile_h(false)> T;
+    typedef UpsLds<false> Lds;
+    static_assert(kNestScratch <= Lds::kInvN + Lds::kHbN + Lds::kDepN, "the nested pass's scratch precedes s_ao");
+    float *const s_ao = smem + Lds::kInvN + Lds::kHbN + Lds::kDepN;
+    const int tile_x = tile % outer.tiles_x, tile_y = tile / outer.tiles_x;
+    const int LX0 = (tile_x * kUpsTileW) >> 1, LY0 = (tile_y * ups_tile_h(false)) >> 1;
+    blend_window_into_lds<AOFMT, RTNE, DIV>(inner, s_ao, T::kRawPitch, LX0 - 3, LY0 - 3, T::kRawW, T::kRawH, smem, frame,
+                                            LX0, LY0, T::kLowW, T::kLowH);
+    upsample_tile<AOFMT, RTNE, false, DIV, true>(outer, smem, tile, frame);
+}
+
+// ---- one frame per call: L4 -> L3 and L3 -> L2 inside the L2 -> L1 launch ---------------------------------
+// With one or two frames per call the three blend passes are three launches of a few hundred workgroups that
+// each wait out a memory round trip and three barriers; their arithmetic is nothing.  Here every L2 -> L1 tile
+// evaluates the window of Combined2 it reads (as in the two-level launch), and for that the window of
+// Combined3 those taps come from: inner -> the raw-tap array of mid -> the raw-tap array of the outer tile.
+// ~2.6x the arithmetic of the two small passes, one launch and one latency chain instead of three; both
+// intermediate buffers are still written (each tile its own 16 x 8 of Combined3 and 32 x 16 of Combined2).
+template <int AOFMT, bool RTNE, int DIV>
+__device__ __forceinline__ void upsample_three_level_tile(const UpsampleArgs &outer, const UpsampleArgs &mid, const UpsampleArgs &inner,
+                                                          float *smem, int tile, int frame)
+{
+    typedef UpsTile<ups_tile_h(false)> T;
+    typedef UpsLds<false> Lds;
+    float *const s_ao = smem + Lds::kInvN + Lds::kHbN + Lds::kDepN;      // raw taps of the outer tile
+    float *const inner_scratch = smem + Lds::kFloats;
+    const int tile_x = tile % outer.tiles_x, tile_y = tile / outer.tiles_x;
+    const int LX0 = (tile_x * kUpsTileW) >> 1, LY0 = (tile_y * ups_tile_h(false)) >> 1;      // L2 coordinates
+    const NestExtent mid_ext(mid, LX0 - 3, LY0 - 3, T::kRawW, T::kRawH);                   // what mid reads of Combined3
+    blend_window_into_lds<AOFMT, RTNE, DIV>(inner, smem, kNestRawW, mid_ext.rx0, mid_ext.ry0, mid_ext.rw, mid_ext.rh,
+                                            inner_scratch, frame, LX0 >> 1, LY0 >> 1, T::kLowW / 2, T::kLowH / 2);
+    blend_window_into_lds<AOFMT, RTNE, DIV, true>(mid, s_ao, T::kRawPitch, LX0 - 3, LY0 - 3, T::kRawW, T::kRawH, smem, frame,
+                                                  LX0, LY0, T::kLowW, T::kLowH);
+    upsample_tile<AOFMT, RTNE, false, DIV, true>(outer, smem, tile, frame);
+}
+
 }  // namespace
 }  // namespace meao

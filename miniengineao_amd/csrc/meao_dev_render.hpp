@@ -344,5 +344,62 @@ __device__ __forceinline__ void render_tile(const RenderArgs &a, float *tile, in
 }
 
 
+// ------------------------------------------------------------------------------------------
+// Render.main (WIDE_SAMPLING, REN:22,27-29,46-50): the same estimator on the NON-tiled f32
+// LowDepth<level>, sampling every other texel (offsets doubled, REN:79-82) out to 8 texels, one
+// output texel per source texel (REN:174).  The reference's host never dispatches it; it is
+// the "high quality" pass of the MiniEngine original and feeds Upsample.main_premin*.
+// Tile 64 x 32 outputs, LDS window (64+16) x (32+16) of raw f32 depth with clamp addressing
+// (REN:116,121 Gather on the 2D texture); no f16 round trip, no padding texels.
+template <int AOFMT, bool RTNE, int DIV, bool EXH>
+__device__ __forceinline__ void render_wide_tile(const RenderArgs &a, float *tile, int frame, int block)
+{
+    typedef AoTexel<AOFMT> AO;
+
+    int b = block, lv = 0;
+#pragma unroll
+    for (int k = 1; k < 4; ++k)
+        if (k < a.num_levels && b >= a.level[k].block_begin) lv = k;
+    const RenderLevelArgs &L = a.level[lv];
+    b -= L.block_begin;
+    const int X0 = (b % L.tiles_x) * kWideTileW, Y0 = (b / L.tiles_x) * kRenTileH;
+    const int lw = L.lw, lh = L.lh;
+    const float *__restrict__ src = frame_ptr(L.src, a.frame_stride, frame);
+
+    for (int i = threadIdx.x; i < kWideLdsW * kWideLdsH; i += kThreads) {
+        const int c = i % kWideLdsW, r = i / kWideLdsW;
+        const int x = clampi(X0 - kWideApron + c, 0, lw - 1), y = clampi(Y0 - kWideApron + r, 0, lh - 1);
+        tile[i] = src[static_cast<size_t>(y) * lw + x];
+    }
+    __syncthreads();
+
+    const int txl = threadIdx.x & 31, tyl = threadIdx.x >> 5;
+    const int X = X0 + 2 * txl;
+    if (X >= lw) return;
+    typename AO::type *__restrict__ dst = frame_ptr(static_cast<typename AO::type *>(L.dst), a.frame_stride, frame);
+    const bool pair_store = ((lw & 1) == 0);
+    const TermConstants<EXH> terms(L);
+
+#pragma unroll 1
+    for (int k = 0; k < kRenTileH / 8; ++k) {
+        const int ly = tyl + 8 * k, Y = Y0 + ly;
+        if (Y >= lh) break;
+        const float *centre = &tile[(ly + kWideApron) * kWideLdsW + 2 * txl + kWideApron];
+        const float2v c = *reinterpret_cast<const float2v *>(centre);
+        const float2v inv_depth = float2v{rcp_strict<DIV>(c.x), rcp_strict<DIV>(c.y)};   // REN:140
+        const float2v out = accumulate_terms<EXH, 2 * kWideLdsW, 2>(terms, centre, inv_depth);
+
+        typename AO::type *p = dst + static_cast<size_t>(Y) * lw + X;
+        const typename AO::type e0 = AO::template encode<RTNE>(out.x), e1 = AO::template encode<RTNE>(out.y);
+        if (pair_store) {
+            typename AO::type2 pr; pr.x = e0; pr.y = e1;
+            *reinterpret_cast<typename AO::type2 *>(p) = pr;
+        } else {
+            p[0] = e0;
+            if (X + 1 < lw) p[1] = e1;
+        }
+    }
+}
+
 }  // namespace
 }  // namespace meao

@@ -24,8 +24,9 @@ void launch_downsample_t(const DownsampleArgs &a, dim3 grid, hipStream_t s)
 // ------------------------------------------------------------------------------------------
 // launchers
 
-hipError_t launch_downsample(const DownsampleArgs &a, int frames, hipStream_t s)
+hipError_t launch_downsample(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf)
 {
+    if (pf) return launch_downsample_frames(a, frames, s, pf);
     if (a.rows_per_lane != 1 && a.rows_per_lane != kMipRowsPerLane) return hipErrorInvalidValue;
     const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
     // exact_rcp_div is only ever set together with RTZ depth storage; the pass itself stores f32 (no f16 conversion here)

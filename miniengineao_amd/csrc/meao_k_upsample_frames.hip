@@ -1,0 +1,82 @@
+// meao_k_upsample_frames.hip -- the upsample kernels with per-frame constants (meao_execute_batch_params): frame blockIdx.z's
+// UpsampleArgs (and HiDepthArgs) from the FrameArgs table, then the same tiles as upsample_kernel / upsample_final_kernel /
+// upsample_final_small_kernel / upsample_blend_tall_kernel.
+#include "meao_dev_upsample.hpp"
+
+namespace meao {
+namespace {
+
+template <int AOFMT, bool RTNE, int DIV>
+__global__ __launch_bounds__(kThreads, 1) void upsample_frames_kernel(const UpsampleArgs *t)
+{
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<false>::kFloats];
+    upsample_tile_checked<AOFMT, RTNE, false, DIV>(frame_block(t, blockIdx.z), smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z);
+}
+
+template <int AOFMT, bool RTNE, int DIV, bool RAW_F32>
+__global__ __launch_bounds__(kThreads, RAW_F32 ? 7 : 6) void upsample_final_frames_kernel(const UpsampleArgs *t, const HiDepthArgs *th)
+{
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true>::kFloats];
+    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, ups_tile_h(true), RAW_F32>(frame_block(t, blockIdx.z), smem,
+                                                                                  xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z,
+                                                                                  NoHook(), &frame_block(th, blockIdx.z));
+}
+
+template <int AOFMT, bool RTNE, int DIV, bool RAW_F32>
+__global__ __launch_bounds__(kThreads) void upsample_final_small_frames_kernel(const UpsampleArgs *t, const HiDepthArgs *th)
+{
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true, kUpsTileHSmall>::kFloats];
+    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, kUpsTileHSmall, RAW_F32>(frame_block(t, blockIdx.z), smem,
+                                                                                xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z,
+                                                                                NoHook(), &frame_block(th, blockIdx.z));
+}
+
+template <int AOFMT, bool RTNE, int DIV>
+__global__ __launch_bounds__(kThreads, 6) void upsample_blend_tall_frames_kernel(const UpsampleArgs *t)
+{
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<false, kUpsTileHTall>::kFloats];
+    upsample_tile_checked<AOFMT, RTNE, false, DIV, NoHook, kUpsTileHTall>(frame_block(t, blockIdx.z), smem,
+                                                                          xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z);
+}
+
+template <int AOFMT, bool RTNE, int DIV>
+void launch_ups_frames_t(const UpsampleArgs &a, const HiDepthArgs *hi, const UpsampleArgs *pf, const HiDepthArgs *pf_hi, dim3 grid, hipStream_t s)
+{
+    const dim3 block(kThreads);
+    if (hi) {
+        const bool f32 = hi->depth_format == MEAO_DEPTH_F32;
+        if (a.tile_h == kUpsTileHSmall) {
+            if (f32) upsample_final_small_frames_kernel<AOFMT, RTNE, DIV, true><<<grid, block, 0, s>>>(pf, pf_hi);
+            else upsample_final_small_frames_kernel<AOFMT, RTNE, DIV, false><<<grid, block, 0, s>>>(pf, pf_hi);
+        } else {
+            if (f32) upsample_final_frames_kernel<AOFMT, RTNE, DIV, true><<<grid, block, 0, s>>>(pf, pf_hi);
+            else upsample_final_frames_kernel<AOFMT, RTNE, DIV, false><<<grid, block, 0, s>>>(pf, pf_hi);
+        }
+    } else if (a.tile_h == kUpsTileHTall) {
+        upsample_blend_tall_frames_kernel<AOFMT, RTNE, DIV><<<grid, block, 0, s>>>(pf);
+    } else {
+        upsample_frames_kernel<AOFMT, RTNE, DIV><<<grid, block, 0, s>>>(pf);
+    }
+}
+
+}  // namespace
+
+// hi: the shared HiDepthArgs of a final pass (selects the raw-format kernel), nullptr = a blend pass; pf_hi: the frames' blocks
+hipError_t launch_upsample_frames(const UpsampleArgs &a, const HiDepthArgs *hi, int ao_format, int frames, hipStream_t s,
+                                  const UpsampleArgs *pf, const HiDepthArgs *pf_hi)
+{
+    if (hi && !pf_hi) return hipErrorInvalidValue;
+    const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
+    if (ao_format == MEAO_AO_R8) {
+        if (a.f16_rtne) launch_ups_frames_t<MEAO_AO_R8, true, DIV_IEEE>(a, hi, pf, pf_hi, grid, s);
+        else if (a.exact_rcp_div) launch_ups_frames_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(a, hi, pf, pf_hi, grid, s);
+        else launch_ups_frames_t<MEAO_AO_R8, false, DIV_IEEE>(a, hi, pf, pf_hi, grid, s);
+    } else {
+        if (a.f16_rtne) launch_ups_frames_t<MEAO_AO_F16, true, DIV_IEEE>(a, hi, pf, pf_hi, grid, s);
+        else if (a.exact_rcp_div) launch_ups_frames_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(a, hi, pf, pf_hi, grid, s);
+        else launch_ups_frames_t<MEAO_AO_F16, false, DIV_IEEE>(a, hi, pf, pf_hi, grid, s);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace meao

@@ -1,34 +1,8 @@
 // meao_k_upsample_fused.hip -- the full-resolution upsample kernel that carries the next batch's downsample pass (meao_prefetch_batch).
-#include "meao_dev_upsample.hpp"
-#include "meao_dev_downsample.hpp"
+#include "meao_dev_fused.hpp"
 
 namespace meao {
 namespace {
-
-// Hook of the fused last kernel: puts the two 16-byte depth loads of the carried (lean) downsample tile in flight inside the
-// upsample tile, before its bilateral phase -- after the tile's own hoisted operands have landed, so that nothing in the
-// bilateral phase waits behind them (vmcnt retires in order) -- to be consumed after it (A/B against "tile first" and "after
-// the prefetch": profiles/r02_ab_v15p..v17p_split_ds*.jsonl).
-struct IssueCarriedLoadsLean {
-    static constexpr bool kBeforeBilateral = true;
-    // Forms of the bilateral texel (A/B with the whole-tile copy of the phase, profiles/r04_ab_fused_bilateral_forms.jsonl; before that
-    // copy existed both lost here): exact sequences 272 us, UNORM8 estimate 257, grouped reciprocals 264, both 256 us per 16 frames.
-    static constexpr bool kGroupReciprocals = true;
-    static constexpr bool kEstimateR8 = true;
-    static constexpr bool kReuseEstimate = false;        // (round 6, with registers to spare: 240.1 vs 240.3 us -- the exact path is rare; left off)
-    static constexpr bool kPairReciprocals = MEAO_X_BIL_PAIR_RCP != 0;
-    const DownsampleArgs &d;
-    float4v (&q)[2];
-    bool mine, full;
-    int tile, frame;
-    __device__ __forceinline__ void after_prefetch() const {}
-    __device__ __forceinline__ void before_bilateral() const
-    {
-        if (!mine) return;
-        if (full) downsample_lean_load<true>(d, tile, frame, q);
-        else downsample_lean_load<false>(d, tile, frame, q);
-    }
-};
 
 // Upsample.main of this batch carrying the downsample pass of the NEXT batch (meao_prefetch_batch).  The carried pass is pure
 // streaming with ~2 VALU instructions per byte; inside this kernel its traffic overlaps the arithmetic of the other resident
@@ -76,9 +50,11 @@ static void launch_upsample_fused_t(const UpsampleArgs &a, const HiDepthArgs &hi
 }
 
 hipError_t launch_upsample_final_with_downsample(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, int ao_format,
-                                                 int frames, hipStream_t s)
+                                                 int frames, hipStream_t s, const UpsampleArgs *pf, const HiDepthArgs *pf_hi,
+                                                 const DownsampleArgs *pf_d)
 {
     if (!fused_downsample_applicable(a, hi, d, frames)) return hipErrorInvalidValue;      // the caller asks first
+    if (pf || pf_hi || pf_d) return launch_upsample_final_with_downsample_frames(a, ao_format, frames, s, pf, pf_hi, pf_d);
     const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
     if (ao_format == MEAO_AO_R8) {
         if (a.f16_rtne) launch_upsample_fused_t<MEAO_AO_R8, true, DIV_IEEE>(a, hi, d, grid, s);

@@ -60,3 +60,8 @@
 #include "meao_k_upsample_nested.hip"
 #include "meao_k_upsample_fused.hip"
 #include "meao_k_misc.hip"
+#include "meao_k_downsample_frames.hip"
+#include "meao_k_render_frames.hip"
+#include "meao_k_upsample_frames.hip"
+#include "meao_k_upsample_nested_frames.hip"
+#include "meao_k_upsample_fused_frames.hip"

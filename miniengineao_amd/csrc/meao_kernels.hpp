@@ -132,23 +132,56 @@ struct TileAtlasArgs {
     int32_t f16_rtne;
 };
 
-hipError_t launch_downsample(const DownsampleArgs &a, int frames, hipStream_t s);
-hipError_t launch_render(const RenderArgs &a, int ao_format, int frames, hipStream_t s);
-hipError_t launch_render_wide(const RenderArgs &a, int ao_format, int frames, hipStream_t s);
+// ---------------------------------------------------------------------------------------
+// Per-frame constants (meao_execute_batch_params): the argument blocks of every pass of one call, once per frame, in a
+// context-owned device table that the call fills with one copy on its stream.  Frame f's block is built from frame f's
+// parameters exactly as the kernarg block of a shared call is built from the context's; launch shapes (tiling, template
+// choice) are the same in every frame.  The per-frame kernels (*_frames_kernel) read `table[frame].<pass>` through the
+// constant address space -- workgroup-uniform scalar loads, like the kernarg copy -- and run the same device functions.
+struct FrameArgs {
+    DownsampleArgs ds;          // this call's downsample pass
+    DownsampleArgs next_ds;     // the announced next batch's pass (frame f of THAT batch)
+    RenderArgs render, render_hq;
+    UpsampleArgs up[4];         // the pass writing level hi (up[0]: the final pass)
+    HiDepthArgs hi;
+};
+
+// The launchers below take, for each argument block, an optional per-frame source: nullptr = the shared block (the kernarg
+// copy of `a`, the kernels of the shared calls), else the block's address in frame 0's FrameArgs of a device table
+// (`a` still selects the kernel and the grid).
+hipError_t launch_downsample(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf = nullptr);
+hipError_t launch_render(const RenderArgs &a, int ao_format, int frames, hipStream_t s, const RenderArgs *pf = nullptr);
+hipError_t launch_render_wide(const RenderArgs &a, int ao_format, int frames, hipStream_t s, const RenderArgs *pf = nullptr);
 // hi: the raw depth frames of the final pass (Upsample.main), nullptr = a blend pass (main_blendout)
-hipError_t launch_upsample(const UpsampleArgs &a, const HiDepthArgs *hi, int ao_format, int frames, hipStream_t s);
+hipError_t launch_upsample(const UpsampleArgs &a, const HiDepthArgs *hi, int ao_format, int frames, hipStream_t s,
+                           const UpsampleArgs *pf = nullptr, const HiDepthArgs *pf_hi = nullptr);
 // Two blend passes in one launch: `inner` (e.g. L4 -> L3) is evaluated per tile of `outer` (L3 -> L2) for the
 // window of its output that the tile reads; inner's target is still written (each tile stores its own part).
 hipError_t launch_upsample_two_level(const UpsampleArgs &outer, const UpsampleArgs &inner, int ao_format, int frames,
-                                     hipStream_t s);
+                                     hipStream_t s, const UpsampleArgs *pf_outer = nullptr, const UpsampleArgs *pf_inner = nullptr);
 // one or two frames per call: L4->L3 and L3->L2 inside the L2->L1 launch (outer = L2->L1, mid = L3->L2, inner = L4->L3)
 hipError_t launch_upsample_three_level(const UpsampleArgs &outer, const UpsampleArgs &mid, const UpsampleArgs &inner, int ao_format,
-                                       int frames, hipStream_t s);
+                                       int frames, hipStream_t s, const UpsampleArgs *pf_outer = nullptr,
+                                       const UpsampleArgs *pf_mid = nullptr, const UpsampleArgs *pf_inner = nullptr);
 // Upsample.main of this batch + the downsample pass of the next one in a single kernel (f32 depth, d.vec_ok, one carried
-// tile per upsample tile: fused_downsample_applicable).
+// tile per upsample tile: fused_downsample_applicable).  Per-frame form: frame f's table entry holds this batch's frame f
+// and the next batch's frame f.
 bool fused_downsample_applicable(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, int frames);
 hipError_t launch_upsample_final_with_downsample(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, int ao_format,
-                                                 int frames, hipStream_t s);
+                                                 int frames, hipStream_t s, const UpsampleArgs *pf = nullptr,
+                                                 const HiDepthArgs *pf_hi = nullptr, const DownsampleArgs *pf_d = nullptr);
+// The per-frame forms (meao_k_*_frames.hip: units of their own, so that the shared kernels compile exactly as they would
+// without them).  `a` / `outer` select the kernel and the grid; every argument block comes from the table.
+hipError_t launch_downsample_frames(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf);
+hipError_t launch_render_frames(const RenderArgs &a, int ao_format, int frames, hipStream_t s, const RenderArgs *pf, bool wide);
+hipError_t launch_upsample_frames(const UpsampleArgs &a, const HiDepthArgs *hi, int ao_format, int frames, hipStream_t s,
+                                  const UpsampleArgs *pf, const HiDepthArgs *pf_hi);
+hipError_t launch_upsample_two_level_frames(const UpsampleArgs &outer, int ao_format, int frames, hipStream_t s,
+                                            const UpsampleArgs *pf_outer, const UpsampleArgs *pf_inner);
+hipError_t launch_upsample_three_level_frames(const UpsampleArgs &outer, int ao_format, int frames, hipStream_t s,
+                                              const UpsampleArgs *pf_outer, const UpsampleArgs *pf_mid, const UpsampleArgs *pf_inner);
+hipError_t launch_upsample_final_with_downsample_frames(const UpsampleArgs &a, int ao_format, int frames, hipStream_t s,
+                                                        const UpsampleArgs *pf, const HiDepthArgs *pf_hi, const DownsampleArgs *pf_d);
 hipError_t launch_tile_atlas(const TileAtlasArgs &a, hipStream_t s);
 // LinearDepth (debug id 1) on demand: dst[i] = f16(Linearize(depth[i])) for one frame (DS1:37-48).
 struct LinearDepthArgs {
@@ -192,7 +225,8 @@ hipError_t launch_render_with_composite(const RenderArgs &a, const CompositeBatc
 hipError_t launch_selftest(int which, unsigned long long *count, hipStream_t s);
 
 // meao_api.cpp, for meao_pool.cpp: meao_execute_batch that can leave the staged copies of a HOST call in flight
+// (params: meao_execute_batch_params, one entry per frame; nullptr = the context's parameters)
 int execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
-                           int32_t out_loc, meao_stream stream, bool wait_for_host);
+                           int32_t out_loc, meao_stream stream, bool wait_for_host, const meao_params *params = nullptr);
 
 }  // namespace meao

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "meao_kernels.hpp"
+#include "meao_plan.hpp"
 
 #ifndef MEAO_TESTING
 #define MEAO_TESTING 0      // 1: the `testhooks` variant library (meao_test_* entry points), never the product
@@ -389,8 +390,18 @@ int32_t meao_pool_set_params(meao_pool *p, const meao_params *prm)
     return MEAO_OK;
 }
 
-int32_t meao_pool_execute_batch(meao_pool *p, int32_t n, const void *const *depth, int32_t depth_loc,
-                                void *const *ao_out, int32_t out_loc)
+// every params[f] valid before any member is given work: an invalid entry launches nothing anywhere
+static int32_t pool_check_params(meao_pool *p, int32_t n, const meao_params *params, const char *what)
+{
+    for (int32_t f = 0; f < n; ++f)
+        if (params[f].struct_size != sizeof(meao_params) || !meao::params_valid(params[f]))
+            return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, std::string(what) + ": params[" + std::to_string(f) + "] is invalid");
+    return MEAO_OK;
+}
+
+// params: per-frame parameters (meao_pool_execute_batch_params), dealt with the frames; nullptr = the members' own
+static int32_t pool_execute_batch(meao_pool *p, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
+                                  int32_t out_loc, const meao_params *params)
 {
     if (!p || !depth || !ao_out) return MEAO_ERR_INVALID_ARGUMENT;
     const int32_t G = static_cast<int32_t>(p->ctx.size());
@@ -410,7 +421,10 @@ int32_t meao_pool_execute_batch(meao_pool *p, int32_t n, const void *const *dept
         const int32_t k = share_of(m, G, n, depth, d);
         share_of(m, G, n, ao_out, o);
         if (k == 0) return MEAO_OK;
-        return meao::execute_batch_internal(p->ctx[m], k, d, depth_loc, o, out_loc, p->stream[m], false);
+        meao_params prm[MEAO_MAX_BATCH];
+        if (params)
+            for (int32_t f = m, i = 0; f < n; f += G) prm[i++] = params[f];
+        return meao::execute_batch_internal(p->ctx[m], k, d, depth_loc, o, out_loc, p->stream[m], false, params ? prm : nullptr);
     }, !host, &failed);
     if (status != MEAO_OK)
         status = pool_fail(p, status, std::string("meao_pool_execute_batch: member ") + std::to_string(failed) + ": " +
@@ -426,7 +440,24 @@ int32_t meao_pool_execute_batch(meao_pool *p, int32_t n, const void *const *dept
     return status;
 }
 
-int32_t meao_pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *depth)
+int32_t meao_pool_execute_batch(meao_pool *p, int32_t n, const void *const *depth, int32_t depth_loc,
+                                void *const *ao_out, int32_t out_loc)
+{
+    return pool_execute_batch(p, n, depth, depth_loc, ao_out, out_loc, nullptr);
+}
+
+int32_t meao_pool_execute_batch_params(meao_pool *p, int32_t n, const void *const *depth, int32_t depth_loc,
+                                       void *const *ao_out, int32_t out_loc, const meao_params *params)
+{
+    if (!p || !params) return MEAO_ERR_INVALID_ARGUMENT;
+    if (n >= 1 && n <= p->max_batch * static_cast<int32_t>(p->ctx.size())) {
+        const int32_t rc = pool_check_params(p, n, params, "meao_pool_execute_batch_params");
+        if (rc != MEAO_OK) return rc;
+    }
+    return pool_execute_batch(p, n, depth, depth_loc, ao_out, out_loc, params);
+}
+
+static int32_t pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *depth, const meao_params *params)
 {
     if (!p || !depth) return MEAO_ERR_INVALID_ARGUMENT;
     const int32_t G = static_cast<int32_t>(p->ctx.size());
@@ -442,13 +473,28 @@ int32_t meao_pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *dep
         const int32_t k = share_of(m, G, n, depth, d);
         if (k == 0) return MEAO_OK;
         if (hipSetDevice(p->device[m]) != hipSuccess) { (void)hipGetLastError(); set_device_failed = true; return MEAO_ERR_HIP; }
-        return meao_prefetch_batch(p->ctx[m], k, d);
+        if (!params) return meao_prefetch_batch(p->ctx[m], k, d);
+        meao_params prm[MEAO_MAX_BATCH];
+        for (int32_t f = m, i = 0; f < n; f += G) prm[i++] = params[f];
+        return meao_prefetch_batch_params(p->ctx[m], k, d, prm);
     }, false, &failed);
     if (status != MEAO_OK)       // (a failed hipSetDevice never reached the context: its last error would name an older failure)
         return pool_fail(p, status, std::string("meao_pool_prefetch_batch: member ") + std::to_string(failed) + ": " +
                                         (set_device_failed ? "hipSetDevice(" + std::to_string(p->device[failed]) + ") failed"
                                                            : std::string(meao_last_error(p->ctx[failed]))));
     return MEAO_OK;
+}
+
+int32_t meao_pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *depth) { return pool_prefetch_batch(p, n, depth, nullptr); }
+
+int32_t meao_pool_prefetch_batch_params(meao_pool *p, int32_t n, const void *const *depth, const meao_params *params)
+{
+    if (!p || !params) return MEAO_ERR_INVALID_ARGUMENT;
+    if (n >= 1 && n <= p->max_batch * static_cast<int32_t>(p->ctx.size())) {
+        const int32_t rc = pool_check_params(p, n, params, "meao_pool_prefetch_batch_params");
+        if (rc != MEAO_OK) return rc;
+    }
+    return pool_prefetch_batch(p, n, depth, params);
 }
 
 int32_t meao_pool_composite_enqueue(meao_pool *p, int32_t mode, int32_t n, const void *const *ao, void *const *color_rgba16f,
