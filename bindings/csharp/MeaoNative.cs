@@ -127,6 +127,9 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_prefetch_batch(IntPtr ctx, int n, IntPtr[] depth);
         [DllImport(Lib)] public static extern int meao_execute_batch_params(IntPtr ctx, int n, IntPtr[] depth, int depth_loc, IntPtr[] ao_out, int out_loc, [In] MeaoParams[] prm, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_prefetch_batch_params(IntPtr ctx, int n, IntPtr[] depth, [In] MeaoParams[] prm);
+        // row-pitched surfaces: pitches in bytes, 0 = tightly packed; prm = null for the context's parameters
+        [DllImport(Lib)] public static extern int meao_execute_batch_pitched(IntPtr ctx, int n, IntPtr[] depth, ulong depth_pitch, int depth_loc, IntPtr[] ao_out, ulong ao_pitch, int out_loc, [In] MeaoParams[] prm, IntPtr stream);
+        [DllImport(Lib)] public static extern int meao_prefetch_batch_pitched(IntPtr ctx, int n, IntPtr[] depth, ulong depth_pitch, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_synchronize(IntPtr ctx, IntPtr stream);
 
         [DllImport(Lib)] public static extern int meao_get_intermediate(IntPtr ctx, int frame, int debug_id, IntPtr dst, ulong dst_capacity, int dst_loc, out MeaoDesc desc);
@@ -150,6 +153,8 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_pool_prefetch_batch(IntPtr pool, int n, IntPtr[] depth);
         [DllImport(Lib)] public static extern int meao_pool_execute_batch_params(IntPtr pool, int n, IntPtr[] depth, int depth_loc, IntPtr[] ao_out, int out_loc, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_pool_prefetch_batch_params(IntPtr pool, int n, IntPtr[] depth, [In] MeaoParams[] prm);
+        [DllImport(Lib)] public static extern int meao_pool_execute_batch_pitched(IntPtr pool, int n, IntPtr[] depth, ulong depth_pitch, int depth_loc, IntPtr[] ao_out, ulong ao_pitch, int out_loc, [In] MeaoParams[] prm);
+        [DllImport(Lib)] public static extern int meao_pool_prefetch_batch_pitched(IntPtr pool, int n, IntPtr[] depth, ulong depth_pitch, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue(IntPtr pool, int mode, int n, IntPtr[] ao, IntPtr[] color_rgba16f, IntPtr[] gbuffer0_rgba8);
         [DllImport(Lib)] public static extern int meao_pool_composite_flush(IntPtr pool);
         [DllImport(Lib)] public static extern int meao_pool_composite_pending(IntPtr pool, out int out_frames);

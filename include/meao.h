@@ -217,7 +217,7 @@ MEAO_API const char *meao_last_error(const meao_ctx *ctx);
 
 /* ---- the hot path (replaces the recorded "SSAO" CommandBuffer, AO.cs:496-531) ----------- */
 /* depth: width*height raw device depth texels in cfg.depth_format (default float32), row-major,
- *        tightly packed
+ *        tightly packed (row-pitched surfaces: meao_execute_batch_pitched)
  *        (_CameraDepthTexture / ResolvedDepth, AO.cs:608-641).
  * ao_out: width*height AO texels in cfg.ao_format (the "AmbientOcclusion" RT, AO.cs:475).
  * Alignment of DEVICE pointers: none required.  When width % 4 == 0 and every depth pointer is
@@ -271,6 +271,30 @@ MEAO_API int32_t meao_execute_batch_params(meao_ctx *ctx, int32_t n, const void 
  * execute gets the same pointers AND each frame has the same near_clip, far_clip and reversed_z it was computed with
  * (whichever entry point announced or consumes it); otherwise the pass is re-run. */
 MEAO_API int32_t meao_prefetch_batch_params(meao_ctx *ctx, int32_t n, const void *const *depth, const meao_params *params);
+/* Row-pitched surfaces (linear textures with a row pitch, a viewport inside a larger target, a cropped tensor).
+ * depth_pitch / ao_pitch: bytes between the starts of consecutive rows; 0 = tightly packed.  One pitch per surface kind per call;
+ * the per-frame pointers already give every frame its own origin.  params: NULL = the context's parameters (meao_execute_batch),
+ * else one per frame (meao_execute_batch_params).  Otherwise the contracts of meao_execute_batch / meao_execute_batch_params hold
+ * unchanged: no allocation and no host synchronisation for DEVICE/DEVICE, asynchronous on `stream`, the per-frame table ring.
+ * Validation, before anything is enqueued (nothing is launched on failure; meao_last_error names the argument):
+ *   MEAO_ERR_INVALID_ARGUMENT  a non-zero pitch smaller than width x element size, or not a multiple of the element size
+ *                              (depth: 4 F32 / 2 UNORM16 / 4 UNORM24 / 2 F16 bytes; AO: 1 R8 / 2 F16 bytes);
+ *   MEAO_ERR_UNSUPPORTED       pitch / element size >= 2^24, or (height - 1) x pitch + width x element size > 2^32 - 1
+ *                              (offsets into caller memory are 32-bit byte offsets).
+ * DEVICE frames are read and written in place -- no copy, no pack kernel -- by the pitched forms of the kernels that address
+ * caller memory (the downsample pass and the full-resolution upsample); pitches of 0 or of the packed row launch exactly the
+ * kernels of meao_execute_batch.  The 4-texel vector forms need, beyond the alignment rules of meao_execute_batch, a pitch that
+ * is a multiple of 4 texels; otherwise the scalar forms run (same results).  HOST frames are staged packed (hipMemcpy2DAsync), the
+ * results copied back into the pitched rows; bytes of a surface outside its width x height texels are never read or written.
+ * Pipelining: a prefetched downsample is reused only by a call with the same pointers, the same depth pitch (0 and the packed
+ * row count as the same) and the near / far / reversed_z rule of meao_prefetch_batch_params.  Debug ids 1 and 17
+ * (meao_get_intermediate, meao_debug_view) honour the last call's pitches.  meao_composite* and meao_pool_gather_to_device take
+ * tightly packed surfaces only. */
+MEAO_API int32_t meao_execute_batch_pitched(meao_ctx *ctx, int32_t n, const void *const *depth, uint64_t depth_pitch, int32_t depth_loc,
+                                            void *const *ao_out, uint64_t ao_pitch, int32_t out_loc, const meao_params *params,
+                                            meao_stream stream);
+MEAO_API int32_t meao_prefetch_batch_pitched(meao_ctx *ctx, int32_t n, const void *const *depth, uint64_t depth_pitch,
+                                             const meao_params *params);
 /* Waits for `stream`; NULL = the stream of the last meao_execute* of this context.  meao_composite /
  * meao_composite_flush do not change what NULL means: a composite issued on another stream is waited for
  * by naming that stream here (or by synchronising it directly). */
@@ -390,6 +414,13 @@ MEAO_API int32_t meao_pool_prefetch_batch(meao_pool *pool, int32_t n, const void
 MEAO_API int32_t meao_pool_execute_batch_params(meao_pool *pool, int32_t n, const void *const *depth, int32_t depth_loc,
                                                 void *const *ao_out, int32_t out_loc, const meao_params *params);
 MEAO_API int32_t meao_pool_prefetch_batch_params(meao_pool *pool, int32_t n, const void *const *depth, const meao_params *params);
+/* The pitched forms for the pool (meao_execute_batch_pitched): the pitches go to every member, frame f (and params[f], if given) to
+ * member f mod G. */
+MEAO_API int32_t meao_pool_execute_batch_pitched(meao_pool *pool, int32_t n, const void *const *depth, uint64_t depth_pitch,
+                                                 int32_t depth_loc, void *const *ao_out, uint64_t ao_pitch, int32_t out_loc,
+                                                 const meao_params *params);
+MEAO_API int32_t meao_pool_prefetch_batch_pitched(meao_pool *pool, int32_t n, const void *const *depth, uint64_t depth_pitch,
+                                                  const meao_params *params);
 /* meao_composite_enqueue / meao_composite_flush for the pool, frames dealt f -> member f mod G: the composite
  * of frame f rides inside the next execute of the member that owns (and produced) it. */
 MEAO_API int32_t meao_pool_composite_enqueue(meao_pool *pool, int32_t mode, int32_t n, const void *const *ao,

@@ -125,6 +125,24 @@ public:
         check(meao_prefetch_batch_params(ctx_, static_cast<int32_t>(nextDeviceDepth.size()), nextDeviceDepth.data(), params.data()));
     }
 
+    // Row-pitched device surfaces (meao_execute_batch_pitched): pitches in bytes, 0 = tightly packed; params empty = the instance's
+    // parameters, else one per frame.
+    void RenderBatchPitched(const std::vector<const void *> &deviceDepth, uint64_t depthPitch, const std::vector<void *> &deviceAo,
+                            uint64_t aoPitch, const std::vector<meao_params> &params = {}, meao_stream stream = nullptr)
+    {
+        if (!params.empty() && params.size() != deviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        check(meao_execute_batch_pitched(ctx_, static_cast<int32_t>(deviceDepth.size()), deviceDepth.data(), depthPitch, MEAO_MEM_DEVICE,
+                                         deviceAo.data(), aoPitch, MEAO_MEM_DEVICE, params.empty() ? nullptr : params.data(), stream));
+    }
+    void PrefetchBatchPitched(const std::vector<const void *> &nextDeviceDepth, uint64_t depthPitch,
+                              const std::vector<meao_params> &params = {})
+    {
+        if (!params.empty() && params.size() != nextDeviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        sync();
+        check(meao_prefetch_batch_pitched(ctx_, static_cast<int32_t>(nextDeviceDepth.size()), nextDeviceDepth.data(), depthPitch,
+                                          params.empty() ? nullptr : params.data()));
+    }
+
     void Synchronize(meao_stream stream = nullptr) { check(meao_synchronize(ctx_, stream)); }
 
     // PushCompositeCommands (AO.cs:822-839).  Composite(): now, on `stream`.  CompositeWithNextFrame(): the
@@ -262,6 +280,22 @@ public:
         if (params.size() != nextDeviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
         check(meao_pool_prefetch_batch_params(pool_, static_cast<int32_t>(nextDeviceDepth.size()), nextDeviceDepth.data(),
                                               params.data()));
+    }
+    // row-pitched device surfaces (meao_pool_execute_batch_pitched); params empty = the members' own parameters
+    void RenderDeviceBatchPitched(const std::vector<const void *> &deviceDepth, uint64_t depthPitch, const std::vector<void *> &deviceAo,
+                                  uint64_t aoPitch, const std::vector<meao_params> &params = {})
+    {
+        if (!params.empty() && params.size() != deviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        check(meao_pool_execute_batch_pitched(pool_, static_cast<int32_t>(deviceDepth.size()), deviceDepth.data(), depthPitch,
+                                              MEAO_MEM_DEVICE, deviceAo.data(), aoPitch, MEAO_MEM_DEVICE,
+                                              params.empty() ? nullptr : params.data()));
+    }
+    void PrefetchBatchPitched(const std::vector<const void *> &nextDeviceDepth, uint64_t depthPitch,
+                              const std::vector<meao_params> &params = {})
+    {
+        if (!params.empty() && params.size() != nextDeviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        check(meao_pool_prefetch_batch_pitched(pool_, static_cast<int32_t>(nextDeviceDepth.size()), nextDeviceDepth.data(), depthPitch,
+                                               params.empty() ? nullptr : params.data()));
     }
     void GatherToDevice(const std::vector<const void *> &deviceAo, const std::vector<void *> &dst, int32_t dstDevice)
     {

@@ -110,6 +110,9 @@ SIGNATURES = {
     "meao_execute_batch_params": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
                                               C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Params), C.c_void_p]),
     "meao_prefetch_batch_params": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(Params)]),
+    "meao_execute_batch_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.c_int32,
+                                               C.POINTER(C.c_void_p), C.c_uint64, C.c_int32, C.POINTER(Params), C.c_void_p]),
+    "meao_prefetch_batch_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(Params)]),
     "meao_synchronize": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "meao_get_intermediate": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64,
                                           C.c_int32, C.POINTER(Desc)]),
@@ -136,6 +139,9 @@ SIGNATURES = {
     "meao_pool_execute_batch_params": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
                                                    C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Params)]),
     "meao_pool_prefetch_batch_params": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(Params)]),
+    "meao_pool_execute_batch_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.c_int32,
+                                                    C.POINTER(C.c_void_p), C.c_uint64, C.c_int32, C.POINTER(Params)]),
+    "meao_pool_prefetch_batch_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(Params)]),
     "meao_pool_composite_enqueue": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_void_p)]),
     "meao_pool_composite_flush": (C.c_int32, [C.c_void_p]),

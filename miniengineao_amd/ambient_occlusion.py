@@ -147,30 +147,68 @@ class AmbientOcclusion:
         return outs
 
     def execute_device(self, depth_ptrs: Sequence[int], out_ptrs: Sequence[int], stream: int = 0,
-                       params: Optional[Sequence[Optional[FrameParams]]] = None) -> None:
-        """Device-resident frames (raw device addresses, e.g. torch ``data_ptr()``); asynchronous.  params: as in render_batch."""
+                       params: Optional[Sequence[Optional[FrameParams]]] = None, *, depth_pitch: int = 0, out_pitch: int = 0) -> None:
+        """Device-resident frames (raw device addresses, e.g. torch ``data_ptr()``); asynchronous.  params: as in render_batch.
+        depth_pitch / out_pitch: bytes between consecutive rows of the surfaces (meao_execute_batch_pitched); 0 = tightly packed."""
         n = len(depth_ptrs)
         self._sync_params()
         pin = (C.c_void_p * n)(*depth_ptrs)
         pout = (C.c_void_p * n)(*out_ptrs)
         s = C.c_void_p(stream) if stream else None
-        if params is None:
+        if depth_pitch or out_pitch:
+            prm = None if params is None else params_array(params, n, self._prm)
+            L.check(self._lib.meao_execute_batch_pitched(self._ctx, n, pin, depth_pitch, L.MEM_DEVICE, pout, out_pitch, L.MEM_DEVICE,
+                                                         prm, s), self._ctx)
+        elif params is None:
             L.check(self._lib.meao_execute_batch(self._ctx, n, pin, L.MEM_DEVICE, pout, L.MEM_DEVICE, s), self._ctx)
         else:
             prm = params_array(params, n, self._prm)
             L.check(self._lib.meao_execute_batch_params(self._ctx, n, pin, L.MEM_DEVICE, pout, L.MEM_DEVICE, prm, s), self._ctx)
 
-    def prefetch_device(self, depth_ptrs: Sequence[int], params: Optional[Sequence[Optional[FrameParams]]] = None) -> None:
+    def prefetch_device(self, depth_ptrs: Sequence[int], params: Optional[Sequence[Optional[FrameParams]]] = None, *,
+                        depth_pitch: int = 0) -> None:
         """Announce the device depth frames of the call after next (meao_prefetch_batch): the next
         execute_device() carries their downsample pass inside its last upsample kernel.  params: the frames' own
-        parameters (meao_prefetch_batch_params), as they will be given to the consuming execute_device()."""
+        parameters (meao_prefetch_batch_params), as they will be given to the consuming execute_device().  depth_pitch: their row
+        pitch in bytes (meao_prefetch_batch_pitched; 0 = tightly packed), as it will be given to the consuming call."""
         n = len(depth_ptrs)
         self._sync_params()     # pending property changes first: meao_set_params would drop the announcement
         pin = (C.c_void_p * n)(*depth_ptrs)
-        if params is None:
+        if depth_pitch:
+            prm = None if params is None else params_array(params, n, self._prm)
+            L.check(self._lib.meao_prefetch_batch_pitched(self._ctx, n, pin, depth_pitch, prm), self._ctx)
+        elif params is None:
             L.check(self._lib.meao_prefetch_batch(self._ctx, n, pin), self._ctx)
         else:
             L.check(self._lib.meao_prefetch_batch_params(self._ctx, n, pin, params_array(params, n, self._prm)), self._ctx)
+
+    def execute_tensors(self, depth, out=None, params: Optional[Sequence[Optional[FrameParams]]] = None):
+        """Torch tensors on this context's device, used in place (meao_execute_batch_pitched), on torch.cuda.current_stream().
+        depth: an (N, H, W) tensor or a list of (H, W) tensors in the dtype of depth_format (float32, float16, uint16 for UNORM16,
+        int32 for UNORM24) -- e.g. a crop ``surface[:, y0:y0 + H, x0:x0 + W]`` of larger targets.  Rows must be contiguous and all
+        frames must share one row stride, which becomes the pitch; any other layout raises ValueError (nothing is copied).
+        out: the same for the AO (uint8 for R8, float16 for F16 storage), or None: allocated packed.  Returns out."""
+        import torch
+        from .surfaces import frame_pointers, packed_pitch
+        depth_dt = {L.DEPTH_F32: torch.float32, L.DEPTH_UNORM16: torch.uint16, L.DEPTH_UNORM24: torch.int32,
+                    L.DEPTH_F16: torch.float16}[self._cfg.depth_format]
+        ao_dt = torch.uint8 if self._cfg.ao_format == L.AO_R8 else torch.float16
+        dev = torch.device("cuda", self._cfg.device)        # every frame of depth and out must be on the context's device
+        frames = list(depth) if not hasattr(depth, "dim") else depth
+        d_ptrs, d_pitch = frame_pointers(frames, self.height, self.width, depth_dt, "depth", device=dev)
+        n = len(d_ptrs)
+        first = frames[0]
+        if out is None:
+            out = torch.empty((n, self.height, self.width), dtype=ao_dt, device=dev)
+        o_frames = list(out) if not hasattr(out, "dim") else out
+        o_ptrs, o_pitch = frame_pointers(o_frames, self.height, self.width, ao_dt, "out", device=dev)
+        if len(o_ptrs) != n:
+            raise ValueError(f"out has {len(o_ptrs)} frames, depth {n}")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self.execute_device(d_ptrs, o_ptrs, stream=stream, params=params,
+                            depth_pitch=packed_pitch(d_pitch, self.width, first.element_size()),
+                            out_pitch=packed_pitch(o_pitch, self.width, o_frames[0].element_size()))
+        return out
 
     def synchronize(self, stream: int = 0) -> None:
         L.check(self._lib.meao_synchronize(self._ctx, C.c_void_p(stream) if stream else None), self._ctx)
@@ -355,20 +393,30 @@ class AmbientOcclusionPool:
         return outs
 
     def execute_device(self, depth_ptrs: Sequence[int], out_ptrs: Sequence[int],
-                       params: Optional[Sequence[Optional[FrameParams]]] = None) -> None:
-        """Frame f resident on device_of_frame(f); asynchronous (synchronize())."""
+                       params: Optional[Sequence[Optional[FrameParams]]] = None, *, depth_pitch: int = 0, out_pitch: int = 0) -> None:
+        """Frame f resident on device_of_frame(f); asynchronous (synchronize()).  depth_pitch / out_pitch: row pitches in bytes of
+        every frame's surfaces (meao_pool_execute_batch_pitched); 0 = tightly packed."""
         n = len(depth_ptrs)
         pin, pout = (C.c_void_p * n)(*depth_ptrs), (C.c_void_p * n)(*out_ptrs)
-        if params is None:
+        if depth_pitch or out_pitch:
+            prm = None if params is None else params_array(params, n, self._prm)
+            self._check(self._lib.meao_pool_execute_batch_pitched(self._pool, n, pin, depth_pitch, L.MEM_DEVICE, pout, out_pitch,
+                                                                  L.MEM_DEVICE, prm))
+        elif params is None:
             self._check(self._lib.meao_pool_execute_batch(self._pool, n, pin, L.MEM_DEVICE, pout, L.MEM_DEVICE))
         else:
             self._check(self._lib.meao_pool_execute_batch_params(self._pool, n, pin, L.MEM_DEVICE, pout, L.MEM_DEVICE,
                                                                  params_array(params, n, self._prm)))
 
-    def prefetch_device(self, depth_ptrs: Sequence[int], params: Optional[Sequence[Optional[FrameParams]]] = None) -> None:
-        """meao_pool_prefetch_batch: the frames of the call after next, dealt like execute_device deals them."""
+    def prefetch_device(self, depth_ptrs: Sequence[int], params: Optional[Sequence[Optional[FrameParams]]] = None, *,
+                        depth_pitch: int = 0) -> None:
+        """meao_pool_prefetch_batch: the frames of the call after next, dealt like execute_device deals them.  depth_pitch: their
+        row pitch in bytes (meao_pool_prefetch_batch_pitched; 0 = tightly packed)."""
         n = len(depth_ptrs)
-        if params is None:
+        if depth_pitch:
+            prm = None if params is None else params_array(params, n, self._prm)
+            self._check(self._lib.meao_pool_prefetch_batch_pitched(self._pool, n, (C.c_void_p * n)(*depth_ptrs), depth_pitch, prm))
+        elif params is None:
             self._check(self._lib.meao_pool_prefetch_batch(self._pool, n, (C.c_void_p * n)(*depth_ptrs)))
         else:
             self._check(self._lib.meao_pool_prefetch_batch_params(self._pool, n, (C.c_void_p * n)(*depth_ptrs),

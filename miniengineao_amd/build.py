@@ -25,7 +25,9 @@ KERNEL_UNITS = ["meao_k_downsample.hip", "meao_k_render.hip", "meao_k_upsample.h
                 "meao_k_upsample_nested.hip", "meao_k_upsample_fused.hip", "meao_k_misc.hip",
                 # the per-frame forms (meao_execute_batch_params) in units of their own: the shared kernels' units are unchanged
                 "meao_k_downsample_frames.hip", "meao_k_render_frames.hip", "meao_k_upsample_frames.hip",
-                "meao_k_upsample_nested_frames.hip", "meao_k_upsample_fused_frames.hip"]
+                "meao_k_upsample_nested_frames.hip", "meao_k_upsample_fused_frames.hip",
+                # the row-pitched forms of the kernels that address caller memory (meao_execute_batch_pitched), likewise
+                "meao_k_pitched.hip", "meao_k_pitched_frames.hip", "meao_k_pitched_fused.hip"]
 HOST_UNITS = ["meao_plan.cpp", "meao_api.cpp", "meao_pool.cpp"]
 SOURCES = HOST_UNITS + KERNEL_UNITS
 HEADERS = ["meao_plan.hpp", "meao_kernels.hpp", "meao_dev.hpp", "meao_dev_downsample.hpp", "meao_dev_render.hpp",

@@ -121,6 +121,13 @@ struct meao_ctx {
     float last_pad[MEAO_MAX_BATCH][4] = {};
     const void *last_depth[MEAO_MAX_BATCH] = {}; // device address of the last call's raw depth frames (debug id 1 is built from them)
     int last_frames = 0;
+    // Row pitches (meao_execute_batch_pitched) in texels, cfg.width when tightly packed: of the announced batch and of the frames a
+    // ready prefetched set was downsampled from (the consuming call must match).  In bytes, 0 = packed: of the last call's device
+    // frames (last_depth, last_out), which debug ids 1 and 17 pack into pack_scratch first.
+    int32_t next_depth_pitch = 0, ready_depth_pitch = 0;
+    uint64_t last_depth_pitch = 0, last_out_pitch = 0;
+    char *pack_scratch = nullptr;
+    uint64_t pack_scratch_bytes = 0;
 
     // profiling: a ring of per-execute event sets (one start/end pair per launch slot); each entry
     // remembers which slots it used
@@ -246,8 +253,9 @@ void release_staging(meao_ctx *ctx)
     if (ctx->stage_out) (void)hipFree(ctx->stage_out);
     if (ctx->stage_view) (void)hipFree(ctx->stage_view);
     if (ctx->atlas_scratch) (void)hipFree(ctx->atlas_scratch);
-    ctx->stage_depth = ctx->stage_out = ctx->stage_view = ctx->atlas_scratch = nullptr;
-    ctx->atlas_scratch_bytes = 0;
+    if (ctx->pack_scratch) (void)hipFree(ctx->pack_scratch);
+    ctx->stage_depth = ctx->stage_out = ctx->stage_view = ctx->atlas_scratch = ctx->pack_scratch = nullptr;
+    ctx->atlas_scratch_bytes = ctx->pack_scratch_bytes = 0;
 }
 
 void release_buffers(meao_ctx *ctx)
@@ -416,6 +424,7 @@ struct ArgBuilder {
     const Plan *plan;             // the constants: the context's, or one frame's (meao_execute_batch_params)
     const meao_params *prm;
     int exact_rcp_div;            // of the call (over all its frames)
+    int32_t depth_pitch, out_pitch;   // row strides of the call's depth / result frames in texels (cfg.width = packed)
 
     const Plan &p() const { return *plan; }
     const meao_config &c() const { return ctx->cfg; }
@@ -428,10 +437,11 @@ struct ArgBuilder {
 
     // ---- PushDownsampleCommands (AO.cs:604-658).  lean: tiled for the tile the final kernel carries (kLeanMipW x kLeanMipRows),
     // else for the stand-alone pass (small_ok: calls with few tiles use the one-row-per-lane tile)
-    DownsampleArgs downsample(int frames, const void *const *depth, int set, uint32_t gen, bool lean, bool small_ok) const
+    DownsampleArgs downsample(int frames, const void *const *depth, int32_t pitch, int set, uint32_t gen, bool lean, bool small_ok) const
     {
         DownsampleArgs ds{};
-        bool aligned = (p().mip[0].w & 7) == 0;
+        bool aligned = (p().mip[0].w & 7) == 0 && (pitch & 3) == 0;     // (a packed row: W % 8 == 0 says it all)
+        ds.depth_pitch = pitch;
         for (int f = 0; f < frames; ++f) {
             ds.depth[f] = depth[f];
             aligned = aligned && aligned_to(depth[f], depth_align());
@@ -550,8 +560,10 @@ struct ArgBuilder {
             up.hi_ao = slot_ptr<void>(ctx, ctx->off_occ[hi - 1]);
             up.dst[0] = slot_ptr<void>(ctx, ctx->off_comb[hi - 1]);
         } else {        // main: HiResDB from the raw depth frames (hi_depth()), no HiResAO, write the result
-            up.hi_depth = nullptr;
             up.hi_ao = nullptr;
+            up.pitch.depth = depth_pitch;      // (in place of hi_depth, which the final pass does not read)
+            up.pitch.dst = out_pitch;
+            vec_ok = vec_ok && (depth_pitch & 3) == 0 && (out_pitch & 3) == 0;     // (packed rows: hw % 4 == 0 says it all)
             for (int f = 0; f < n; ++f) {
                 up.dst[f] = out_dev[f];
                 vec_ok = vec_ok && aligned_to(out_dev[f], out_align()) && aligned_to(depth_dev[f], depth_align());
@@ -588,7 +600,7 @@ void build_call_args(const ArgBuilder &args, const ArgBuilder &nb, const CallSha
     meao_ctx *ctx = args.ctx;
     const meao_config &c = ctx->cfg;
     const int n = args.n;
-    if (!cs.b.prefetched) out->ds = args.downsample(n, args.depth_dev, ctx->ds_cur, ctx->set_gen[ctx->ds_cur], false, true);
+    if (!cs.b.prefetched) out->ds = args.downsample(n, args.depth_dev, args.depth_pitch, ctx->ds_cur, ctx->set_gen[ctx->ds_cur], false, true);
     out->render = args.render(1, c.num_levels, false, !cs.b.carry_composite);
     if (c.hq_levels > 0) out->render_hq = args.render(1, c.num_levels, true, false);
     for (int hi = 1; hi < c.num_levels; ++hi) out->up[hi] = args.upsample(hi);
@@ -599,7 +611,8 @@ void build_call_args(const ArgBuilder &args, const ArgBuilder &nb, const CallSha
     out->up[0] = args.upsample(0, cs.b.next == 1);
     out->hi = args.hi_depth();
     if (cs.b.next != 0)
-        out->next_ds = nb.downsample(ctx->next_n, ctx->next_depth, other, ctx->set_gen[other], cs.b.next == 1, cs.b.next == 2);
+        out->next_ds = nb.downsample(ctx->next_n, ctx->next_depth, ctx->next_depth_pitch, other, ctx->set_gen[other], cs.b.next == 1,
+                                     cs.b.next == 2);
 }
 
 bool same_zb(const meao_ctx::ZbInputs &z, const meao_params &p)
@@ -629,8 +642,9 @@ struct RingSlotGuard {
 };
 
 // The launch sequence of one batch.  fp: per-frame parameters (meao_execute_batch_params), nullptr = the context's.
+// depth_pitch / out_pitch: row strides of the device frames in texels (cfg.width = tightly packed).
 int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *out_dev, hipStream_t stream,
-              const meao_params *fp = nullptr)
+              const meao_params *fp, int32_t depth_pitch, int32_t out_pitch)
 {
     const meao_config &c = ctx->cfg;
     hipEvent_t *ev = nullptr;
@@ -670,7 +684,7 @@ int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *o
     BatchShape shape{};
     shape.frames = n;
     shape.prefetched = ctx->ready_n == n && ctx->ready_stream == stream && std::memcmp(ctx->ready_depth, depth_dev, sizeof(void *) * n) == 0 &&
-                       (ctx->ready_exact || !exact);
+                       (ctx->ready_exact || !exact) && ctx->ready_depth_pitch == depth_pitch;
     for (int f = 0; shape.prefetched && f < n; ++f) shape.prefetched = same_zb(ctx->ready_zb[f], *prm_of[f]);
     ctx->ds_cur = shape.prefetched ? ctx->ready_set : 0;
     ctx->ready_n = 0;
@@ -682,7 +696,8 @@ int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *o
     }
     shape.carry_composite = ctx->pending_comp.frames > 0;
 
-    const ArgBuilder args{ctx, n, depth_dev, out_dev, ctx->hostile_of(ctx->ds_cur), ctx->set_gen[ctx->ds_cur], &ctx->plan, &ctx->prm, exact};
+    const ArgBuilder args{ctx, n, depth_dev, out_dev, ctx->hostile_of(ctx->ds_cur), ctx->set_gen[ctx->ds_cur], &ctx->plan, &ctx->prm, exact,
+                          depth_pitch, out_pitch};
     // The announced next batch: its pass rides in this call's last kernel where the fused form applies (f32 depth, 16-byte
     // loads, a workgroup per carried tile), else it runs as a launch of its own behind it.  Either way the next call finds it done.
     // (Inside the render launch instead -- CarriedMips in the texel loop, round 6 -- it costs the same 56-60 us per 16 4K frames:
@@ -690,7 +705,7 @@ int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *o
     const int other = 1 - ctx->ds_cur;
     if (ctx->next_n > 0) {
         ctx->set_gen[other] = next_generation(ctx);
-        const DownsampleArgs lean = args.downsample(ctx->next_n, ctx->next_depth, other, ctx->set_gen[other], true, false);
+        const DownsampleArgs lean = args.downsample(ctx->next_n, ctx->next_depth, ctx->next_depth_pitch, other, ctx->set_gen[other], true, false);
         shape.next = !ctx->next_ds_own_launch && fused_downsample_applicable(args.upsample(0, true), args.hi_depth(), lean, n) ? 1 : 2;
     }
 
@@ -716,10 +731,10 @@ int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *o
         const int count = std::max(n, shape.next != 0 ? ctx->next_n : 0);
         for (int f = 0; f < count; ++f) {
             const ArgBuilder fa{ctx, n, depth_dev, out_dev, args.hostile, args.generation, f < n ? plan_of[f] : &ctx->plan,
-                                f < n ? prm_of[f] : &ctx->prm, exact};
+                                f < n ? prm_of[f] : &ctx->prm, exact, depth_pitch, out_pitch};
             const bool own_next = next_per_frame && f < ctx->next_n;
             const ArgBuilder fb{ctx, n, depth_dev, out_dev, args.hostile, args.generation, own_next ? &ctx->next_plan[f] : &ctx->plan,
-                                own_next ? &ctx->next_prm[f] : &ctx->prm, exact};
+                                own_next ? &ctx->next_prm[f] : &ctx->prm, exact, depth_pitch, out_pitch};
             build_call_args(fa, fb, cs, other, &stage[f]);
         }
         FrameArgs *dev = ctx->frame_table + static_cast<size_t>(ring_slot) * c.max_batch;
@@ -782,6 +797,7 @@ int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *o
         ctx->ready_set = other;
         ctx->ready_stream = stream;
         ctx->ready_exact = exact != 0;
+        ctx->ready_depth_pitch = ctx->next_depth_pitch;
         std::memcpy(ctx->ready_depth, ctx->next_depth, sizeof ctx->ready_depth);
         for (int f = 0; f < ctx->next_n; ++f) {
             const meao_params &q = next_per_frame ? ctx->next_prm[f] : ctx->prm;
@@ -801,6 +817,8 @@ int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *o
         for (int k = 0; k < 4; ++k) ctx->last_pad[f][k] = plan_of[f]->render[k].pad_value;
     }
     ctx->last_frames = n;
+    ctx->last_depth_pitch = depth_pitch == c.width ? 0 : static_cast<uint64_t>(depth_pitch) * depth_elem(c.depth_format);
+    ctx->last_out_pitch = out_pitch == c.width ? 0 : static_cast<uint64_t>(out_pitch) * ao_elem(c);
     ctx->last_stream = stream;
     return MEAO_OK;
 }
@@ -1067,8 +1085,25 @@ static int validate_frame_params(meao_ctx *ctx, int32_t n, const meao_params *pa
     return MEAO_OK;
 }
 
+// A row pitch of meao_execute_batch_pitched / meao_prefetch_batch_pitched (bytes, 0 = tightly packed) -> the row stride in texels.
+// The final pass forms row offsets with __umul24 (stride < 2^24 texels) and every offset into caller memory is a 32-bit byte
+// offset (the frame's last texel ends at most 2^32 - 1 bytes after its origin).
+static int pitch_texels(meao_ctx *ctx, uint64_t pitch, uint64_t elem, const char *what, int32_t *out)
+{
+    const uint64_t w = static_cast<uint64_t>(ctx->cfg.width), h = static_cast<uint64_t>(ctx->cfg.height);
+    if (pitch == 0) { *out = ctx->cfg.width; return MEAO_OK; }
+    if (pitch < w * elem) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(what) + ": smaller than a row (width x element size)");
+    if (pitch % elem != 0) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(what) + ": not a multiple of the element size");
+    if (pitch / elem >= (1ull << 24)) return fail(ctx, MEAO_ERR_UNSUPPORTED, std::string(what) + ": 2^24 texels or more");
+    if ((h - 1) * pitch + w * elem > 0xffffffffull)
+        return fail(ctx, MEAO_ERR_UNSUPPORTED, std::string(what) + ": a frame spans more than 2^32 - 1 bytes");
+    *out = static_cast<int32_t>(pitch / elem);
+    return MEAO_OK;
+}
+
 int meao::execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
-                                 int32_t out_loc, meao_stream stream_, bool wait_for_host, const meao_params *params)
+                                 int32_t out_loc, meao_stream stream_, bool wait_for_host, const meao_params *params,
+                                 uint64_t depth_pitch, uint64_t ao_pitch)
 {
     if (!ctx || !depth || !ao_out) return MEAO_ERR_INVALID_ARGUMENT;
     if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_execute_batch: n must be 1..max_batch");
@@ -1081,12 +1116,21 @@ int meao::execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *de
         const int vr = validate_frame_params(ctx, n, params, "meao_execute_batch_params");
         if (vr != MEAO_OK) return vr;
     }
+    int32_t depth_rows = 0, out_rows = 0;     // row strides in texels
+    {
+        int vr = pitch_texels(ctx, depth_pitch, depth_elem(ctx->cfg.depth_format), "meao_execute_batch_pitched: depth_pitch", &depth_rows);
+        if (vr == MEAO_OK) vr = pitch_texels(ctx, ao_pitch, ao_elem(ctx->cfg), "meao_execute_batch_pitched: ao_pitch", &out_rows);
+        if (vr != MEAO_OK) return vr;
+    }
     int rc = use_device(ctx);
     if (rc != MEAO_OK) return rc;
     hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->own_stream;
 
     const uint64_t px = static_cast<uint64_t>(ctx->cfg.width) * ctx->cfg.height;
     const uint64_t depth_bytes = px * depth_elem(ctx->cfg.depth_format), out_bytes = px * ao_elem(ctx->cfg);
+    const uint64_t depth_row = static_cast<uint64_t>(ctx->cfg.width) * depth_elem(ctx->cfg.depth_format);
+    const uint64_t out_row = static_cast<uint64_t>(ctx->cfg.width) * ao_elem(ctx->cfg);
+    const bool depth_packed = depth_rows == ctx->cfg.width, out_packed = out_rows == ctx->cfg.width;
     const void *depth_dev[MEAO_MAX_BATCH];
     void *out_dev[MEAO_MAX_BATCH];
     if (depth_loc == MEAO_MEM_HOST) {
@@ -1096,9 +1140,11 @@ int meao::execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *de
         }
         for (int f = 0; f < n; ++f) {
             char *d = ctx->stage_depth + ctx->stage_depth_frame * f;
-            MEAO_HIP(ctx, hipMemcpyAsync(d, depth[f], depth_bytes, hipMemcpyHostToDevice, stream));
+            if (depth_packed) MEAO_HIP(ctx, hipMemcpyAsync(d, depth[f], depth_bytes, hipMemcpyHostToDevice, stream));
+            else MEAO_HIP(ctx, hipMemcpy2DAsync(d, depth_row, depth[f], depth_pitch, depth_row, ctx->cfg.height, hipMemcpyHostToDevice, stream));
             depth_dev[f] = d;
         }
+        depth_rows = ctx->cfg.width;          // staged packed
     } else {
         for (int f = 0; f < n; ++f) depth_dev[f] = depth[f];
     }
@@ -1108,16 +1154,19 @@ int meao::execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *de
             MEAO_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->stage_out), ctx->stage_out_frame * ctx->cfg.max_batch));
         }
         for (int f = 0; f < n; ++f) out_dev[f] = ctx->stage_out + ctx->stage_out_frame * f;
+        out_rows = ctx->cfg.width;
     } else {
         for (int f = 0; f < n; ++f) out_dev[f] = ao_out[f];
     }
 
-    rc = run_batch(ctx, n, depth_dev, out_dev, stream, params);
+    rc = run_batch(ctx, n, depth_dev, out_dev, stream, params, depth_rows, out_rows);
     if (rc != MEAO_OK) return rc;
 
     if (out_loc == MEAO_MEM_HOST)
-        for (int f = 0; f < n; ++f)
-            MEAO_HIP(ctx, hipMemcpyAsync(ao_out[f], out_dev[f], out_bytes, hipMemcpyDeviceToHost, stream));
+        for (int f = 0; f < n; ++f) {
+            if (out_packed) MEAO_HIP(ctx, hipMemcpyAsync(ao_out[f], out_dev[f], out_bytes, hipMemcpyDeviceToHost, stream));
+            else MEAO_HIP(ctx, hipMemcpy2DAsync(ao_out[f], ao_pitch, out_dev[f], out_row, out_row, ctx->cfg.height, hipMemcpyDeviceToHost, stream));
+        }
     if (wait_for_host && (out_loc == MEAO_MEM_HOST || depth_loc == MEAO_MEM_HOST)) MEAO_HIP(ctx, hipStreamSynchronize(stream));
     return MEAO_OK;
 }
@@ -1137,13 +1186,16 @@ int32_t meao_execute_batch_params(meao_ctx *ctx, int32_t n, const void *const *d
     return meao::execute_batch_internal(ctx, n, depth, depth_loc, ao_out, out_loc, stream_, true, params);
 }
 
-static int prefetch_batch(meao_ctx *ctx, int32_t n, const void *const *depth, const meao_params *params)
+static int prefetch_batch(meao_ctx *ctx, int32_t n, const void *const *depth, const meao_params *params, uint64_t depth_pitch = 0)
 {
     if (!ctx || !depth) return MEAO_ERR_INVALID_ARGUMENT;
     if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_prefetch_batch: n must be 1..max_batch");
     for (int f = 0; f < n; ++f)
         if (!depth[f]) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_prefetch_batch: null frame pointer");
-    int rc = use_device(ctx);
+    int32_t rows = 0;
+    int rc = pitch_texels(ctx, depth_pitch, depth_elem(ctx->cfg.depth_format), "meao_prefetch_batch_pitched: depth_pitch", &rows);
+    if (rc != MEAO_OK) return rc;
+    rc = use_device(ctx);
     if (rc != MEAO_OK) return rc;
     if (!ctx->two_ds_sets) {
         // Created without cfg.pipelined: the first announcement re-lays the slots out with a second
@@ -1153,6 +1205,7 @@ static int prefetch_batch(meao_ctx *ctx, int32_t n, const void *const *depth, co
         if (rc != MEAO_OK) return rc;
     }
     ctx->next_n = n;
+    ctx->next_depth_pitch = rows;
     for (int f = 0; f < n; ++f) ctx->next_depth[f] = depth[f];
     ctx->next_per_frame = params != nullptr;
     if (params)
@@ -1173,6 +1226,22 @@ int32_t meao_prefetch_batch_params(meao_ctx *ctx, int32_t n, const void *const *
         if (rc != MEAO_OK) return rc;
     }
     return prefetch_batch(ctx, n, depth, params);
+}
+
+int32_t meao_execute_batch_pitched(meao_ctx *ctx, int32_t n, const void *const *depth, uint64_t depth_pitch, int32_t depth_loc,
+                                   void *const *ao_out, uint64_t ao_pitch, int32_t out_loc, const meao_params *params, meao_stream stream_)
+{
+    return meao::execute_batch_internal(ctx, n, depth, depth_loc, ao_out, out_loc, stream_, true, params, depth_pitch, ao_pitch);
+}
+
+int32_t meao_prefetch_batch_pitched(meao_ctx *ctx, int32_t n, const void *const *depth, uint64_t depth_pitch, const meao_params *params)
+{
+    if (!ctx || !depth) return MEAO_ERR_INVALID_ARGUMENT;
+    if (params && n >= 1 && n <= ctx->cfg.max_batch) {
+        const int rc = validate_frame_params(ctx, n, params, "meao_prefetch_batch_pitched");
+        if (rc != MEAO_OK) return rc;
+    }
+    return prefetch_batch(ctx, n, depth, params, depth_pitch);
 }
 
 int32_t meao_execute(meao_ctx *ctx, const void *depth, int32_t depth_loc, void *ao_out, int32_t out_loc,
@@ -1204,6 +1273,18 @@ static int reserve_scratch(meao_ctx *ctx, uint64_t bytes)
     return MEAO_OK;
 }
 
+// Packed copies of the last call's pitched frames (debug ids 1 and 17): at least `bytes`.
+static int reserve_pack_scratch(meao_ctx *ctx, uint64_t bytes)
+{
+    if (ctx->pack_scratch_bytes >= bytes) return MEAO_OK;
+    if (ctx->pack_scratch) (void)hipFree(ctx->pack_scratch);
+    ctx->pack_scratch = nullptr;
+    ctx->pack_scratch_bytes = 0;
+    MEAO_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->pack_scratch), bytes));
+    ctx->pack_scratch_bytes = bytes;
+    return MEAO_OK;
+}
+
 // Device address of debug buffer `debug_id` of batch slot `frame` (LinearDepth and TiledDepth are built on demand).
 static int locate_debug_buffer(meao_ctx *ctx, int32_t frame, int32_t debug_id, const meao_desc &d, hipStream_t s,
                                const void **out_src)
@@ -1213,10 +1294,18 @@ static int locate_debug_buffer(meao_ctx *ctx, int32_t frame, int32_t debug_id, c
     if (debug_id == 1) {
         // LinearDepth: materialised on demand from the raw depth frame of the last call (its one consumer on the hot path,
         // the full-resolution upsample, evaluates Linearize itself).  The caller's depth frame must still be alive.
-        const int rc = reserve_scratch(ctx, d.bytes);
+        int rc = reserve_scratch(ctx, d.bytes);
         if (rc != MEAO_OK) return rc;
         LinearDepthArgs la{};
         la.depth = ctx->last_depth[frame];
+        if (ctx->last_depth_pitch != 0) {     // a pitched frame: packed into the context's scratch first (not a hot path)
+            const uint64_t row = static_cast<uint64_t>(ctx->cfg.width) * depth_elem(ctx->cfg.depth_format);
+            rc = reserve_pack_scratch(ctx, row * ctx->cfg.height);
+            if (rc != MEAO_OK) return rc;
+            MEAO_HIP(ctx, hipMemcpy2DAsync(ctx->pack_scratch, row, la.depth, ctx->last_depth_pitch, row, ctx->cfg.height,
+                                           hipMemcpyDeviceToDevice, s));
+            la.depth = ctx->pack_scratch;
+        }
         la.dst = reinterpret_cast<uint16_t *>(ctx->atlas_scratch);
         la.pixels = static_cast<int64_t>(d.width) * d.height;
         la.depth_format = ctx->cfg.depth_format;
@@ -1250,6 +1339,14 @@ static int locate_debug_buffer(meao_ctx *ctx, int32_t frame, int32_t debug_id, c
         *out_src = slot + ctx->off_comb[debug_id - 14];
     } else if (debug_id == 17) {
         *out_src = ctx->last_out[frame];
+        if (ctx->last_out_pitch != 0) {       // pitched results: packed into the context's scratch first
+            const uint64_t row = static_cast<uint64_t>(ctx->cfg.width) * ao_elem(ctx->cfg);
+            const int rc = reserve_pack_scratch(ctx, row * ctx->cfg.height);
+            if (rc != MEAO_OK) return rc;
+            MEAO_HIP(ctx, hipMemcpy2DAsync(ctx->pack_scratch, row, *out_src, ctx->last_out_pitch, row, ctx->cfg.height,
+                                           hipMemcpyDeviceToDevice, s));
+            *out_src = ctx->pack_scratch;
+        }
     } else {
         const int level = debug_id - MEAO_DEBUG_OCCLUSION_HQ1 + 1;
         if (!level_has_hq(nl, ctx->cfg.hq_levels, level))

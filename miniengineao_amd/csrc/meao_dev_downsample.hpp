@@ -83,15 +83,16 @@ __device__ __forceinline__ void raw_depth_quad(const void *depth, int format, si
 // The generic tile (stand-alone pass; every depth format, any width): kMipTileW x (8 * ROWS) texels of LowDepth1.  A lane takes
 // 4 consecutive LowDepth1 texels -- raw texels 2j, 2j+2, 2j+4, 2j+6 of raw row 2i -- in each of its ROWS rows (i, i + 8, ...):
 // with 16-byte loads two per row, all of them in flight before the first is used.
-// VEC: W % 8 == 0 and every frame aligned to 4 texels.
-template <bool VEC, int DIV, int ROWS>
+// VEC: W % 8 == 0 and every frame aligned to 4 texels.  PITCHED: the depth rows are a.depth_pitch texels apart instead of W
+// (and, with VEC, that stride is a multiple of 4 texels).
+template <bool VEC, int DIV, int ROWS, bool PITCHED = false>
 __device__ __forceinline__ void downsample_tile(const DownsampleArgs &a, int tile, int frame)
 {
     const unsigned tid = threadIdx.x;
     const int tile_x = tile % a.tiles_x, tile_y = tile / a.tiles_x;
     const int j0 = tile_x * kMipTileW + static_cast<int>(tid % kMipLanesPerRow) * 4;     // LowDepth1 column of the lane's first texel
     const int ib = tile_y * (kMipRowsPerPass * ROWS) + static_cast<int>(tid / kMipLanesPerRow);
-    const int W = a.w[0], w1 = a.w[1], h1 = a.h[1];
+    const int W = PITCHED ? a.depth_pitch : a.w[0], w1 = a.w[1], h1 = a.h[1];
     if (j0 >= w1) return;
     const void *__restrict__ depth = a.depth[frame];
     const int format = a.depth_format;
@@ -185,12 +186,13 @@ struct LeanMipLane {
     }
 };
 
-// FULL: every row of the tile is inside the level (otherwise rows past it re-read its last row and are never used)
-template <bool FULL>
+// FULL: every row of the tile is inside the level (otherwise rows past it re-read its last row and are never used).
+// PITCHED: depth rows a.depth_pitch texels apart (a multiple of 4; the byte offset of the frame's last texel is < 2^32).
+template <bool FULL, bool PITCHED = false>
 __device__ __forceinline__ void downsample_lean_load(const DownsampleArgs &a, int tile, int frame, float4v (&q)[2])
 {
     const LeanMipLane L(a, tile);
-    const uint32_t W = static_cast<uint32_t>(a.w[0]);
+    const uint32_t W = static_cast<uint32_t>(PITCHED ? a.depth_pitch : a.w[0]);
     if (L.j0 >= static_cast<uint32_t>(a.w[1])) return;
     const float *__restrict__ depth = static_cast<const float *>(a.depth[frame]);
     const int i = FULL ? L.i : min(L.i, a.h[1] - 1);

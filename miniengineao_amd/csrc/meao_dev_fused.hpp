@@ -12,7 +12,9 @@ namespace {
 // upsample tile, before its bilateral phase -- after the tile's own hoisted operands have landed, so that nothing in the
 // bilateral phase waits behind them (vmcnt retires in order) -- to be consumed after it (A/B against "tile first" and "after
 // the prefetch": profiles/r02_ab_v15p..v17p_split_ds*.jsonl).
-struct IssueCarriedLoadsLean {
+// PITCHED: the carried frames' depth rows are d.depth_pitch texels apart (meao_k_pitched_fused*.hip).
+template <bool PITCHED>
+struct IssueCarriedLoadsLeanT {
     static constexpr bool kBeforeBilateral = true;
     // Forms of the bilateral texel (A/B with the whole-tile copy of the phase, profiles/r04_ab_fused_bilateral_forms.jsonl; before that
     // copy existed both lost here): exact sequences 272 us, UNORM8 estimate 257, grouped reciprocals 264, both 256 us per 16 frames.
@@ -28,10 +30,11 @@ struct IssueCarriedLoadsLean {
     __device__ __forceinline__ void before_bilateral() const
     {
         if (!mine) return;
-        if (full) downsample_lean_load<true>(d, tile, frame, q);
-        else downsample_lean_load<false>(d, tile, frame, q);
+        if (full) downsample_lean_load<true, PITCHED>(d, tile, frame, q);
+        else downsample_lean_load<false, PITCHED>(d, tile, frame, q);
     }
 };
+typedef IssueCarriedLoadsLeanT<false> IssueCarriedLoadsLean;
 
 }  // namespace
 }  // namespace meao

@@ -458,8 +458,9 @@ __device__ __forceinline__ bool ups_tile_is_interior(const UpsampleArgs &a, int 
 }
 
 // Hi-res operands.  CLAMPED: every lane loads (out-of-frame lanes re-read the frame's last row / quad and never use it),
-// so that the code is branch-free and the compiler's s_waitcnt counts stay exact.
-template <int AOFMT, bool FINAL, int TILE_H, bool CLAMPED, bool RAW_F32>
+// so that the code is branch-free and the compiler's s_waitcnt counts stay exact.  PITCHED (final pass): raw depth rows are
+// a.pitch.depth texels apart.
+template <int AOFMT, bool FINAL, int TILE_H, bool CLAMPED, bool RAW_F32, bool PITCHED = false>
 __device__ __forceinline__ void ups_issue_hoisted(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, FINAL, TILE_H> &L)
 {
     const int tid = thread_index_opaque();
@@ -478,7 +479,8 @@ __device__ __forceinline__ void ups_issue_hoisted(const UpsampleArgs &a, const H
             if constexpr (FINAL && !CLAMPED) L.hraw[pass][f] = uint4v{0x3f000000u, 0x3f000000u, 0x3f000000u, 0x3f000000u};   // texels past the frame: a clean depth, never used
             if (CLAMPED || (hhx0 < hw && hy < hh)) {
                 // texel index in the level (< 2^27): 32-bit byte offsets from the frame's uniform bases (saddr addressing)
-                const uint32_t hrow = static_cast<uint32_t>(hy * hw + hhx0);
+                const uint32_t hrow = PITCHED ? static_cast<uint32_t>(hy) * static_cast<uint32_t>(a.pitch.depth) + static_cast<uint32_t>(hhx0)
+                                              : static_cast<uint32_t>(hy * hw + hhx0);
                 if constexpr (FINAL) {
                     L.hraw[pass][f] = load_raw_quad<RAW_F32>(hi->raw[frame], hi->depth_format, hrow);
                 } else {
@@ -492,14 +494,14 @@ __device__ __forceinline__ void ups_issue_hoisted(const UpsampleArgs &a, const H
 }
 
 // The same for a tile that lies inside the frame: no clamps, one 24-bit multiply -- the rows of a lane are its first one plus
-// multiples of the level's width that are uniform (scalar).
-template <int AOFMT, bool FINAL, int TILE_H, bool RAW_F32>
+// multiples of the level's width that are uniform (scalar).  PITCHED (final pass): of the raw depth's row stride instead.
+template <int AOFMT, bool FINAL, int TILE_H, bool RAW_F32, bool PITCHED = false>
 __device__ __forceinline__ void ups_issue_hoisted_inside(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, FINAL, TILE_H> &L)
 {
     const int tid = thread_index_opaque();
     typedef typename AoTexel<AOFMT>::type ao_t;
     const int HX0 = (tile % a.tiles_x) * kUpsTileW, HY0 = (tile / a.tiles_x) * TILE_H;
-    const uint32_t hw = static_cast<uint32_t>(a.hw);
+    const uint32_t hw = static_cast<uint32_t>((FINAL && PITCHED) ? a.pitch.depth : a.hw);      // row stride of the loads (pitch < 2^24)
     const uint32_t first = __umul24(static_cast<uint32_t>(HY0 + 2 * (tid >> 4)), hw) + static_cast<uint32_t>(HX0 + 4 * (tid & 15));    // rows, widths < 2^24
 #pragma unroll
     for (int pass = 0; pass < TILE_H / 32; ++pass)
@@ -520,7 +522,7 @@ __device__ __forceinline__ void ups_issue_hoisted_inside(const UpsampleArgs &a, 
 // All loads of an interior tile: window first, hi-res operands behind them.  The window comes from L2 (written by the
 // previous pass), the hi-res operands of the final pass from HBM; vmcnt retires loads in issue order, so with the hi-res
 // loads in front the window wait would last an HBM latency.
-template <int AOFMT, bool FINAL, int TILE_H, bool RAW_F32>
+template <int AOFMT, bool FINAL, int TILE_H, bool RAW_F32, bool PITCHED = false>
 __device__ __forceinline__ void ups_issue_interior_loads(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, FINAL, TILE_H> &L,
                                                          bool inside)
 {
@@ -542,8 +544,8 @@ __device__ __forceinline__ void ups_issue_interior_loads(const UpsampleArgs &a, 
         L.wa[round] = *reinterpret_cast<const typename AO::type4 *>(at_byte_offset(lo_ao, idx * static_cast<uint32_t>(sizeof(ao_t))));
     }
     __builtin_amdgcn_sched_barrier(0);          // keep the issue order: window, then hi-res
-    if (inside) ups_issue_hoisted_inside<AOFMT, FINAL, TILE_H, RAW_F32>(a, hi, tile, frame, L);      // (wave-uniform; the same loads either way)
-    else ups_issue_hoisted<AOFMT, FINAL, TILE_H, true, RAW_F32>(a, hi, tile, frame, L);
+    if (inside) ups_issue_hoisted_inside<AOFMT, FINAL, TILE_H, RAW_F32, PITCHED>(a, hi, tile, frame, L);      // (wave-uniform; the same loads either way)
+    else ups_issue_hoisted<AOFMT, FINAL, TILE_H, true, RAW_F32, PITCHED>(a, hi, tile, frame, L);
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -579,7 +581,7 @@ __device__ __forceinline__ bool ups_tile_from_raw(const UpsampleArgs &a, int til
 
 // Loads of a from-raw tile: the AO window (L2: the previous pass wrote it), the apron's raw texels (lines of the neighbouring
 // tiles' hi-res operands), the tile's own hi-res operands (HBM) -- in that order, vmcnt retires in issue order.
-template <int AOFMT, int TILE_H, bool RAW_F32>
+template <int AOFMT, int TILE_H, bool RAW_F32, bool PITCHED = false>
 __device__ __forceinline__ void ups_issue_from_raw_loads(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, true, TILE_H> &L,
                                                          int apron_r, int apron_k)
 {
@@ -601,12 +603,13 @@ __device__ __forceinline__ void ups_issue_from_raw_loads(const UpsampleArgs &a, 
     }
     {   // every lane loads (lanes past the last item repeat it), so that the code is branch-free
         const int cy = clampi(LY0 - 3 + apron_r, 0, lh - 1);
-        const uint32_t at = static_cast<uint32_t>(2 * cy * a.hw + (HX0 - 8 + 8 * apron_k));      // raw texel (2X, 2Y) of LowDepth1 texel (X, Y)
+        const uint32_t at = PITCHED ? static_cast<uint32_t>(2 * cy) * static_cast<uint32_t>(a.pitch.depth) + static_cast<uint32_t>(HX0 - 8 + 8 * apron_k)
+                                    : static_cast<uint32_t>(2 * cy * a.hw + (HX0 - 8 + 8 * apron_k));      // raw texel (2X, 2Y) of LowDepth1 texel (X, Y)
         L.araw[0] = load_raw_quad<RAW_F32, false>(hi->raw[frame], hi->depth_format, at);
         L.araw[1] = load_raw_quad<RAW_F32, false>(hi->raw[frame], hi->depth_format, at + 4u);
     }
     __builtin_amdgcn_sched_barrier(0);          // keep the issue order: window, apron, hi-res
-    ups_issue_hoisted_inside<AOFMT, true, TILE_H, RAW_F32>(a, hi, tile, frame, L);      // a from-raw tile lies inside the frame
+    ups_issue_hoisted_inside<AOFMT, true, TILE_H, RAW_F32, PITCHED>(a, hi, tile, frame, L);      // a from-raw tile lies inside the frame
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -626,7 +629,10 @@ struct NoHook {
 };
 
 // RAW_F32 (FINAL): the caller's depth frames are f32 -- no format switch in the code (the other formats take the generic instance)
-template <int AOFMT, bool RTNE, bool FINAL, int DIV, bool NESTED = false, typename Hook = NoHook, int TILE_H = ups_tile_h(FINAL), bool RAW_F32 = true>
+// PITCHED (FINAL): the caller's surfaces are row-pitched -- raw depth rows a.pitch.depth and dst rows a.pitch.dst texels apart
+// (meao_execute_batch_pitched).  Only the addresses of caller memory change; context-owned buffers keep hw.
+template <int AOFMT, bool RTNE, bool FINAL, int DIV, bool NESTED = false, typename Hook = NoHook, int TILE_H = ups_tile_h(FINAL), bool RAW_F32 = true,
+          bool PITCHED = false>
 __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem, int tile, int frame, Hook hook = Hook(),
                                               const HiDepthArgs *hi = nullptr)
 {
@@ -678,6 +684,8 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
     const float zp0 = FINAL ? hi->zp0 : 0.0f, zp1 = FINAL ? hi->zp1 : 0.0f;
     const float sky_depth = (FINAL && hi->reversed_z == 0) ? 1.0f : 0.0f;
     const int raw_format = (FINAL && !RAW_F32) ? hi->depth_format : MEAO_DEPTH_F32;
+    static_assert(!PITCHED || (FINAL && !NESTED), "only the full-resolution pass addresses caller memory");
+    const int raw_pitch = PITCHED ? a.pitch.depth : hw, dst_pitch = PITCHED ? a.pitch.dst : hw;     // row strides of caller memory
 
     PhaseClock clk(FINAL ? 0 : 8);
     __builtin_amdgcn_s_setprio(3);
@@ -694,7 +702,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
     // full-resolution pass, tile inside the frame: no LowDepth1 read at all (ups_issue_from_raw_loads)
     const bool from_raw = !NESTED && ups_tile_from_raw<FINAL, TILE_H>(a, tile);
     const bool window_first = !NESTED && !from_raw && (MEAO_X_HOT_PATH_ONLY || ups_tile_is_interior<FINAL, TILE_H>(a, tile));
-    if (hoist_ok && !window_first && !from_raw) ups_issue_hoisted<AOFMT, FINAL, TILE_H, false, RAW_F32>(a, hi, tile, frame, L);
+    if (hoist_ok && !window_first && !from_raw) ups_issue_hoisted<AOFMT, FINAL, TILE_H, false, RAW_F32, PITCHED>(a, hi, tile, frame, L);
 
     // ---- PrefetchData (UPS:54-72): raw window = virtual low-res texels
     // [LX0-3, LX0+34] x [LY0-3, LY0+kLowH+2], clamp addressing per texel.
@@ -706,7 +714,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
             int apron_r, apron_k;      // the lane's apron item, computed once: pinned, or the compiler derives it again where it is converted
             UpsApron<TILE_H>::item(min(tid, UpsApron<TILE_H>::kItems - 1), apron_r, apron_k);
             asm volatile("" : "+v"(apron_r), "+v"(apron_k));
-            ups_issue_from_raw_loads<AOFMT, TILE_H, RAW_F32>(a, hi, tile, frame, L, apron_r, apron_k);
+            ups_issue_from_raw_loads<AOFMT, TILE_H, RAW_F32, PITCHED>(a, hi, tile, frame, L, apron_r, apron_k);
             auto &wa = L.wa;
 #pragma unroll
             for (int round = 0; round < kRounds; ++round) {
@@ -745,7 +753,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
         }
     } else if (window_first) {
         constexpr int kItems = Loads::kItems, kRounds = Loads::kRounds;
-        if constexpr (!NESTED) ups_issue_interior_loads<AOFMT, FINAL, TILE_H, RAW_F32>(a, hi, tile, frame, L,
+        if constexpr (!NESTED) ups_issue_interior_loads<AOFMT, FINAL, TILE_H, RAW_F32, PITCHED>(a, hi, tile, frame, L,
                                                                                        MEAO_X_HOT_PATH_ONLY || (HX0 + kUpsTileW <= hw && HY0 + kTileH <= hh));
         auto &wd = L.wd;
         auto &wa = L.wa;
@@ -979,6 +987,9 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                 const int hy = hy0 + f;
                 if (!WHOLE && hy >= hh) break;
                 const size_t hrow = static_cast<size_t>(hy) * hw + hx0;
+                // (pitched: the raw depth and the result rows have strides of their own)
+                const size_t hrow_raw = PITCHED ? static_cast<size_t>(hy) * raw_pitch + hx0 : hrow;
+                const size_t hrow_dst = PITCHED ? static_cast<size_t>(hy) * dst_pitch + hx0 : hrow;
                 float hd[4], ha[4] = {1.0f, 1.0f, 1.0f, 1.0f};                  // HiSSAOs = 1 in "main" (UPS:222)
                 if constexpr (FINAL) {
                     // HiResDB = f16(Linearize(raw depth)), evaluated here (hi_depth_quad); LinearDepth is not a buffer
@@ -989,7 +1000,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                     } else {
                         float rawd[4];
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) rawd[e] = (hx0 + e < hw) ? raw_depth_texel(hi->raw[frame], raw_format, hrow + e) : 0.5f;
+                        for (int e = 0; e < 4; ++e) rawd[e] = (hx0 + e < hw) ? raw_depth_texel(hi->raw[frame], raw_format, hrow_raw + e) : 0.5f;
                         redo |= !hi_depth_quad<RTNE, DIV>(rawd, zp0, zp1, sky_depth, hd);
                     }
                 } else {
@@ -1068,7 +1079,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                         bilateral_k);
                     res[e] = AO::template encode<RTNE>(v);
                 }
-                ao_t *o = dst + hrow;
+                ao_t *o = dst + hrow_dst;
                 if (vec_ok) {
                     typename AO::type4 r4; r4.x = res[0]; r4.y = res[1]; r4.z = res[2]; r4.w = res[3];
                     // the blend passes' outputs are re-read by the next pass from L2; the result leaves the path, but a tile row of it is half a
@@ -1095,7 +1106,9 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                     const int hy = HY0 + 2 * ty + f, hx = hx0 + e;
                     if (hx >= hw || hy >= hh) continue;
                     const size_t at = static_cast<size_t>(hy) * hw + hx;
-                    const float rawv = raw_depth_texel(hi->raw[frame], raw_format, at);
+                    const size_t at_raw = PITCHED ? static_cast<size_t>(hy) * raw_pitch + hx : at;
+                    const size_t at_dst = PITCHED ? static_cast<size_t>(hy) * dst_pitch + hx : at;
+                    const float rawv = raw_depth_texel(hi->raw[frame], raw_format, at_raw);
                     const float hdv = through_f16<RTNE>(linearize<DIV_IEEE>(rawv, zp0, zp1, sky_depth));
                     const int cc = ((e + 1) >> 1) + 1, rr = f + 1;                        // as above
                     const int comp = (e & 1) ? (f ? 3 : 0) : (f ? 2 : 1);
@@ -1107,7 +1120,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                         gd[i] = dep_at(r + 2, c + 2);
                         ga[i] = s_vb[r * T::kBlurPitch + c];
                     }
-                    dst[at] = AO::template encode<RTNE>(bilateral_upsample<DIV_IEEE>(hdv, 1.0f, gd[0], gd[1], gd[2], gd[3],
+                    dst[at_dst] = AO::template encode<RTNE>(bilateral_upsample<DIV_IEEE>(hdv, 1.0f, gd[0], gd[1], gd[2], gd[3],
                                                                                       ga[0], ga[1], ga[2], ga[3], bilateral_k));
                 }
             }
@@ -1122,17 +1135,18 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
 }
 
 // The (rare) hostile-frame variant of a tile: the same code with IEEE division.
-template <int AOFMT, bool RTNE, bool FINAL, int DIV, typename Hook = NoHook, int TILE_H = ups_tile_h(FINAL), bool RAW_F32 = true>
+template <int AOFMT, bool RTNE, bool FINAL, int DIV, typename Hook = NoHook, int TILE_H = ups_tile_h(FINAL), bool RAW_F32 = true,
+          bool PITCHED = false>
 __device__ __forceinline__ void upsample_tile_checked(const UpsampleArgs &a, float *smem, int tile, int frame, Hook hook = Hook(),
                                                       const HiDepthArgs *hi = nullptr)
 {
     if constexpr (DIV == DIV_EXACT_RCP) {
         if (frame_is_hostile(a.hostile, a.generation, frame)) {       // wave-uniform, decided per frame
-            upsample_tile<AOFMT, RTNE, FINAL, DIV_IEEE, false, Hook, TILE_H, RAW_F32>(a, smem, tile, frame, hook, hi);
+            upsample_tile<AOFMT, RTNE, FINAL, DIV_IEEE, false, Hook, TILE_H, RAW_F32, PITCHED>(a, smem, tile, frame, hook, hi);
             return;
         }
     }
-    upsample_tile<AOFMT, RTNE, FINAL, DIV, false, Hook, TILE_H, RAW_F32>(a, smem, tile, frame, hook, hi);
+    upsample_tile<AOFMT, RTNE, FINAL, DIV, false, Hook, TILE_H, RAW_F32, PITCHED>(a, smem, tile, frame, hook, hi);
 }
 
 

@@ -54,6 +54,8 @@ hipError_t launch_upsample_final_with_downsample(const UpsampleArgs &a, const Hi
                                                  const DownsampleArgs *pf_d)
 {
     if (!fused_downsample_applicable(a, hi, d, frames)) return hipErrorInvalidValue;      // the caller asks first
+    if (final_pitched(a) || downsample_pitched(d))
+        return launch_upsample_final_with_downsample_pitched(a, hi, d, ao_format, frames, s, pf, pf_hi, pf_d);
     if (pf || pf_hi || pf_d) return launch_upsample_final_with_downsample_frames(a, ao_format, frames, s, pf, pf_hi, pf_d);
     const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
     if (ao_format == MEAO_AO_R8) {

@@ -65,3 +65,6 @@
 #include "meao_k_upsample_frames.hip"
 #include "meao_k_upsample_nested_frames.hip"
 #include "meao_k_upsample_fused_frames.hip"
+#include "meao_k_pitched.hip"
+#include "meao_k_pitched_frames.hip"
+#include "meao_k_pitched_fused.hip"

@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/meao.h"
@@ -16,6 +17,9 @@ namespace meao {
 struct DownsampleArgs {
     const void *depth[MEAO_MAX_BATCH];   // caller-owned raw depth (depth_format), one pointer per frame
     int32_t depth_format;                // meao_depth_format
+    // row stride of the depth frames in texels (= w[0] for tightly packed frames; meao_execute_batch_pitched).  Read only by the
+    // pitched kernels (meao_k_pitched*.hip); it sits in what was alignment padding, so the block's layout is unchanged.
+    int32_t depth_pitch;
     float *low[4];                       // LowDepth1..4 f32, frame 0
     uint64_t frame_stride;               // bytes between consecutive frames' intermediates
     int32_t w[5], h[5];                  // mip 0..4 dims
@@ -96,7 +100,13 @@ struct UpsampleArgs {
     const float *lo_depth;     // LoResDB  f32
     const void *lo_ao;         // LoResAO1
     const void *lo_ao2;        // LoResAO2 of main_premin* (min-combined in PrefetchData), or nullptr
-    const void *hi_depth;      // HiResDB  f32 (blend passes); unused in the final pass, which linearizes the raw depth itself (HiDepthArgs)
+    union {
+        const void *hi_depth;  // HiResDB  f32 (blend passes); unused in the final pass, which linearizes the raw depth itself (HiDepthArgs)
+        // Final pass: row strides in texels of the raw depth frames (HiDepthArgs::raw) and of dst (= hw when tightly packed;
+        // meao_execute_batch_pitched).  Read only by the pitched kernels; they share the final pass's unused hi_depth, so the
+        // layouts of UpsampleArgs and FrameArgs are unchanged (HiDepthArgs has no padding to put them in).
+        struct { int32_t depth, dst; } pitch;
+    };
     const void *hi_ao;         // HiResAO, nullptr in the final pass
     void *dst[MEAO_MAX_BATCH]; // per-frame destination (caller-owned in the final pass)
     uint64_t frame_stride;     // applies to lo_*, hi_* (context-owned intermediates)
@@ -107,9 +117,21 @@ struct UpsampleArgs {
     int32_t f16_rtne;
     int32_t exact_rcp_div;     // operands proven inside the exact range of the v_rcp_f32 sequences
     int32_t vec_ok;            // hw % 4 == 0 and, in the final pass, every dst and raw depth pointer aligned for 4-texel accesses
+                               // (and, pitched, both row strides multiples of 4 texels)
     const uint32_t *hostile;   // as in RenderArgs
     uint32_t generation;
 };
+
+static_assert(sizeof(DownsampleArgs) == 656 && offsetof(DownsampleArgs, low) == 520, "pitch field in former padding");
+static_assert(sizeof(UpsampleArgs) == 632 && offsetof(UpsampleArgs, hi_ao) == 32, "pitch fields in the final pass's unused hi_depth");
+
+// Pitched surfaces (meao_execute_batch_pitched): a pass whose caller-memory row strides differ from the packed ones runs the
+// pitched instance of its kernel (meao_k_pitched*.hip); a stride of 0 or of the packed row means packed.
+inline bool downsample_pitched(const DownsampleArgs &d) { return d.depth_pitch != 0 && d.depth_pitch != d.w[0]; }
+inline bool final_pitched(const UpsampleArgs &a)
+{
+    return (a.pitch.depth != 0 && a.pitch.depth != a.hw) || (a.pitch.dst != 0 && a.pitch.dst != a.hw);
+}
 
 // Final pass (Upsample.main): HiResDB = LinearZ = f16(Linearize(depth)) (DS1:37-48, UPS:217-223) is evaluated from the caller's raw
 // depth frame inside the bilateral phase -- same reciprocal sequence, same f16 round trip, hostile texels divided with IEEE '/'
@@ -182,6 +204,18 @@ hipError_t launch_upsample_three_level_frames(const UpsampleArgs &outer, int ao_
                                               const UpsampleArgs *pf_outer, const UpsampleArgs *pf_mid, const UpsampleArgs *pf_inner);
 hipError_t launch_upsample_final_with_downsample_frames(const UpsampleArgs &a, int ao_format, int frames, hipStream_t s,
                                                         const UpsampleArgs *pf, const HiDepthArgs *pf_hi, const DownsampleArgs *pf_d);
+// The pitched forms (meao_k_pitched*.hip): the launchers above hand a pass over to them when downsample_pitched / final_pitched
+// says its caller-memory strides are not the packed ones; pf != nullptr selects the per-frame kernels.  Every stride of the blocks
+// must then be set (a packed side carries its packed row).
+hipError_t launch_downsample_pitched(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf);
+hipError_t launch_downsample_pitched_frames(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf);
+hipError_t launch_upsample_final_pitched(const UpsampleArgs &a, const HiDepthArgs &hi, int ao_format, int frames, hipStream_t s,
+                                         const UpsampleArgs *pf, const HiDepthArgs *pf_hi);
+hipError_t launch_upsample_final_pitched_frames(const UpsampleArgs &a, const HiDepthArgs &hi, int ao_format, int frames, hipStream_t s,
+                                                const UpsampleArgs *pf, const HiDepthArgs *pf_hi);
+hipError_t launch_upsample_final_with_downsample_pitched(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, int ao_format,
+                                                         int frames, hipStream_t s, const UpsampleArgs *pf, const HiDepthArgs *pf_hi,
+                                                         const DownsampleArgs *pf_d);
 hipError_t launch_tile_atlas(const TileAtlasArgs &a, hipStream_t s);
 // LinearDepth (debug id 1) on demand: dst[i] = f16(Linearize(depth[i])) for one frame (DS1:37-48).
 struct LinearDepthArgs {
@@ -226,7 +260,9 @@ hipError_t launch_selftest(int which, unsigned long long *count, hipStream_t s);
 
 // meao_api.cpp, for meao_pool.cpp: meao_execute_batch that can leave the staged copies of a HOST call in flight
 // (params: meao_execute_batch_params, one entry per frame; nullptr = the context's parameters)
+// (depth_pitch / ao_pitch: meao_execute_batch_pitched, bytes, 0 = tightly packed)
 int execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
-                           int32_t out_loc, meao_stream stream, bool wait_for_host, const meao_params *params = nullptr);
+                           int32_t out_loc, meao_stream stream, bool wait_for_host, const meao_params *params = nullptr,
+                           uint64_t depth_pitch = 0, uint64_t ao_pitch = 0);
 
 }  // namespace meao

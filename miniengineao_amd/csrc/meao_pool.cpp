@@ -399,9 +399,11 @@ static int32_t pool_check_params(meao_pool *p, int32_t n, const meao_params *par
     return MEAO_OK;
 }
 
-// params: per-frame parameters (meao_pool_execute_batch_params), dealt with the frames; nullptr = the members' own
+// params: per-frame parameters (meao_pool_execute_batch_params), dealt with the frames; nullptr = the members' own.
+// depth_pitch / ao_pitch: meao_pool_execute_batch_pitched, passed to every member (they share the geometry, so an invalid pitch
+// fails in every member before anything is enqueued).
 static int32_t pool_execute_batch(meao_pool *p, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
-                                  int32_t out_loc, const meao_params *params)
+                                  int32_t out_loc, const meao_params *params, uint64_t depth_pitch = 0, uint64_t ao_pitch = 0)
 {
     if (!p || !depth || !ao_out) return MEAO_ERR_INVALID_ARGUMENT;
     const int32_t G = static_cast<int32_t>(p->ctx.size());
@@ -424,7 +426,8 @@ static int32_t pool_execute_batch(meao_pool *p, int32_t n, const void *const *de
         meao_params prm[MEAO_MAX_BATCH];
         if (params)
             for (int32_t f = m, i = 0; f < n; f += G) prm[i++] = params[f];
-        return meao::execute_batch_internal(p->ctx[m], k, d, depth_loc, o, out_loc, p->stream[m], false, params ? prm : nullptr);
+        return meao::execute_batch_internal(p->ctx[m], k, d, depth_loc, o, out_loc, p->stream[m], false, params ? prm : nullptr,
+                                            depth_pitch, ao_pitch);
     }, !host, &failed);
     if (status != MEAO_OK)
         status = pool_fail(p, status, std::string("meao_pool_execute_batch: member ") + std::to_string(failed) + ": " +
@@ -457,7 +460,7 @@ int32_t meao_pool_execute_batch_params(meao_pool *p, int32_t n, const void *cons
     return pool_execute_batch(p, n, depth, depth_loc, ao_out, out_loc, params);
 }
 
-static int32_t pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *depth, const meao_params *params)
+static int32_t pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *depth, const meao_params *params, uint64_t depth_pitch = 0)
 {
     if (!p || !depth) return MEAO_ERR_INVALID_ARGUMENT;
     const int32_t G = static_cast<int32_t>(p->ctx.size());
@@ -473,6 +476,12 @@ static int32_t pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *d
         const int32_t k = share_of(m, G, n, depth, d);
         if (k == 0) return MEAO_OK;
         if (hipSetDevice(p->device[m]) != hipSuccess) { (void)hipGetLastError(); set_device_failed = true; return MEAO_ERR_HIP; }
+        if (depth_pitch != 0) {
+            meao_params prm[MEAO_MAX_BATCH];
+            if (params)
+                for (int32_t f = m, i = 0; f < n; f += G) prm[i++] = params[f];
+            return meao_prefetch_batch_pitched(p->ctx[m], k, d, depth_pitch, params ? prm : nullptr);
+        }
         if (!params) return meao_prefetch_batch(p->ctx[m], k, d);
         meao_params prm[MEAO_MAX_BATCH];
         for (int32_t f = m, i = 0; f < n; f += G) prm[i++] = params[f];
@@ -495,6 +504,27 @@ int32_t meao_pool_prefetch_batch_params(meao_pool *p, int32_t n, const void *con
         if (rc != MEAO_OK) return rc;
     }
     return pool_prefetch_batch(p, n, depth, params);
+}
+
+int32_t meao_pool_execute_batch_pitched(meao_pool *p, int32_t n, const void *const *depth, uint64_t depth_pitch, int32_t depth_loc,
+                                        void *const *ao_out, uint64_t ao_pitch, int32_t out_loc, const meao_params *params)
+{
+    if (!p || !depth || !ao_out) return MEAO_ERR_INVALID_ARGUMENT;
+    if (params && n >= 1 && n <= p->max_batch * static_cast<int32_t>(p->ctx.size())) {
+        const int32_t rc = pool_check_params(p, n, params, "meao_pool_execute_batch_pitched");
+        if (rc != MEAO_OK) return rc;
+    }
+    return pool_execute_batch(p, n, depth, depth_loc, ao_out, out_loc, params, depth_pitch, ao_pitch);
+}
+
+int32_t meao_pool_prefetch_batch_pitched(meao_pool *p, int32_t n, const void *const *depth, uint64_t depth_pitch, const meao_params *params)
+{
+    if (!p || !depth) return MEAO_ERR_INVALID_ARGUMENT;
+    if (params && n >= 1 && n <= p->max_batch * static_cast<int32_t>(p->ctx.size())) {
+        const int32_t rc = pool_check_params(p, n, params, "meao_pool_prefetch_batch_pitched");
+        if (rc != MEAO_OK) return rc;
+    }
+    return pool_prefetch_batch(p, n, depth, params, depth_pitch);
 }
 
 int32_t meao_pool_composite_enqueue(meao_pool *p, int32_t mode, int32_t n, const void *const *ao, void *const *color_rgba16f,

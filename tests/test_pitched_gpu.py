@@ -1,0 +1,471 @@
+"""Row-pitched depth and AO surfaces (meao_execute_batch_pitched, its prefetch and pool forms) on the GPU.
+
+Every frame lives inside a larger allocation: the depth surface's padding holds NaN (all-ones words for the UNORM formats) and the AO
+surface is pre-filled with 0xA5.  The viewport's AO must be bit-equal to the oracle run on the packed viewport depth, and no byte
+of the AO surface outside the viewport may change -- in every launch structure a packed call can reach.
+"""
+import ctypes as C
+import dataclasses
+
+import numpy as np
+import pytest
+import torch
+
+from miniengineao_amd import FrameParams
+from miniengineao_amd import _lib as L
+from miniengineao_amd import synth
+from miniengineao_amd.frame_params import params_array
+from tests import helpers as H
+
+pytestmark = pytest.mark.gpu
+
+DEPTH_ELEM = {L.DEPTH_F32: 4, L.DEPTH_UNORM16: 2, L.DEPTH_UNORM24: 4, L.DEPTH_F16: 2}
+DEPTH_NP = {L.DEPTH_F32: np.float32, L.DEPTH_UNORM16: np.uint16, L.DEPTH_UNORM24: np.uint32, L.DEPTH_F16: np.uint16}
+PAD_WORD = {L.DEPTH_F32: 0x7fc00000, L.DEPTH_UNORM16: 0xffff, L.DEPTH_UNORM24: 0xffffffff, L.DEPTH_F16: 0x7e00}
+PASS_DOWNSAMPLE = 0
+
+
+def encode_depth(d, fmt):
+    if fmt == L.DEPTH_F32:
+        return d.astype(np.float32)
+    if fmt == L.DEPTH_UNORM16:
+        return np.round(np.clip(d, 0, 1) * 65535).astype(np.uint16)
+    if fmt == L.DEPTH_UNORM24:
+        return np.round(np.clip(d, 0, 1).astype(np.float64) * 16777215).astype(np.uint32)
+    return d.astype(np.float16).view(np.uint16)
+
+
+def pitch_texels(kind, w, x0, elem):
+    """Row length in texels of a surface whose viewport starts at column x0."""
+    if kind == "packed":
+        return w
+    if kind == "+1":
+        return x0 + w + 1
+    if kind == "+3":
+        return x0 + w + 3
+    if kind == "256":
+        return -(-(x0 + w) * elem // 256) * 256 // elem
+    return 2 * w + x0                                   # "2w"
+
+
+class Surfaces:
+    """n frames of (h + 2) x pitch texels each, viewport at (x0, 1); depth and AO surfaces in one torch allocation each."""
+
+    def __init__(self, w, h, n, fmt, ao_format, depth_kind, out_kind, x0, seed, device="cuda"):
+        self.w, self.h, self.n, self.x0, self.y0 = w, h, n, x0, 1
+        de, ae = DEPTH_ELEM[fmt], (1 if ao_format == L.AO_R8 else 2)
+        self.de, self.ae = de, ae
+        self.dp = pitch_texels(depth_kind, w, x0 if depth_kind != "packed" else 0, de)
+        self.op = pitch_texels(out_kind, w, x0 if out_kind != "packed" else 0, ae)
+        self.dx0 = 0 if depth_kind == "packed" else x0
+        self.ox0 = 0 if out_kind == "packed" else x0
+        self.dy0 = 0 if depth_kind == "packed" else 1
+        self.oy0 = 0 if out_kind == "packed" else 1
+        rows_d, rows_o = h + 2 * self.dy0, h + 2 * self.oy0
+        self.views = [encode_depth(synth.occluder_field(w, h, seed + f), fmt) for f in range(n)]
+        host = np.full((n, rows_d, self.dp), PAD_WORD[fmt], dtype=np.uint32 if de == 4 else np.uint16).view(DEPTH_NP[fmt])
+        for f in range(n):
+            host[f, self.dy0:self.dy0 + h, self.dx0:self.dx0 + w] = self.views[f]
+        self.depth_host = host
+        self.depth = torch.from_numpy(host.view(np.uint8).copy()).to(device)
+        self.out = torch.full((n, rows_o, self.op * ae), 0xA5, dtype=torch.uint8, device=device)
+        self.out_rows = rows_o
+
+    def depth_ptrs(self):
+        b, fs = self.depth.data_ptr(), self.depth[0].numel()
+        return [b + f * fs + self.dy0 * self.dp * self.de + self.dx0 * self.de for f in range(self.n)]
+
+    def out_ptrs(self):
+        b, fs = self.out.data_ptr(), self.out[0].numel()
+        return [b + f * fs + self.oy0 * self.op * self.ae + self.ox0 * self.ae for f in range(self.n)]
+
+    def result(self, f):
+        """(viewport AO in the oracle's dtype, whether every byte outside it is still 0xA5)"""
+        o = self.out[f].cpu().numpy()
+        x0b, wb = self.ox0 * self.ae, self.w * self.ae
+        view = np.ascontiguousarray(o[self.oy0:self.oy0 + self.h, x0b:x0b + wb])
+        mask = np.ones(o.shape, bool)
+        mask[self.oy0:self.oy0 + self.h, x0b:x0b + wb] = False
+        return (view if self.ae == 1 else view.view(np.uint16)), bool((o[mask] == 0xA5).all())
+
+
+def pitched_call(ao, n, dptrs, dpitch, optrs, opitch, params=None, stream=None, prefetch=False):
+    """The C entry points themselves (pitches passed as given, a packed one included)."""
+    ao._sync_params()         # property changes made through the Python object reach the context first
+    pin = (C.c_void_p * n)(*dptrs)
+    prm = None if params is None else params_array(params, n, ao._prm)
+    if prefetch:
+        return ao._lib.meao_prefetch_batch_pitched(ao._ctx, n, pin, dpitch, prm)
+    pout = (C.c_void_p * n)(*optrs)
+    s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+    return ao._lib.meao_execute_batch_pitched(ao._ctx, n, pin, dpitch, L.MEM_DEVICE, pout, opitch, L.MEM_DEVICE, prm, s)
+
+
+def check(ao, oracle, s, surf, ids=None):
+    """s: the oracle Settings of every frame, or a list of one per frame."""
+    torch.cuda.synchronize()
+    for f in range(surf.n):
+        want = oracle.run(surf.views[f], s[f] if isinstance(s, list) else s, result_only=not ids)
+        got, untouched = surf.result(f)
+        assert untouched, f"frame {f}: bytes outside the viewport changed"
+        ok, _ = H.nan_aware_equal(got, want["result"])
+        assert ok, (f, H.diff_report("result", got, want["result"]))
+        for i in ids or ():
+            g = ao.debug_buffer(i, frame=f)
+            ok, _ = H.nan_aware_equal(g, want[H.NAMES[i]])
+            assert ok, (f, i, H.diff_report(H.NAMES[i], g, want[H.NAMES[i]]))
+
+
+def run_case(oracle, w, h, n, fmt=L.DEPTH_F32, ao_format=L.AO_R8, rtne=0, depth_kind="256", out_kind="256", x0=0,
+             debug=None, max_batch=None, ids=None, seed=7):
+    s = H.settings(oracle, w, h, ao_format=ao_format, f16_rounding=rtne, depth_format=fmt)
+    ao = H.component(s, max_batch=max_batch or n, debug=debug, depth_format=fmt)
+    try:
+        surf = Surfaces(w, h, n, fmt, ao_format, depth_kind, out_kind, x0, seed)
+        torch.cuda.synchronize()
+        rc = pitched_call(ao, n, surf.depth_ptrs(), surf.dp * surf.de, surf.out_ptrs(), surf.op * surf.ae)
+        assert rc == 0, ao._lib.meao_last_error(ao._ctx)
+        check(ao, oracle, s, surf, ids)
+    finally:
+        ao.close()
+
+
+# pitch kinds x origins, one frame (the small final tile and the three-level blend launch)
+@pytest.mark.parametrize("kind,x0", [("packed", 0), ("+1", 0), ("+1", 1), ("+3", 1), ("256", 0), ("256", 1), ("2w", 0)])
+def test_pitch_kinds_one_frame(oracle, kind, x0):
+    run_case(oracle, 260, 36, 1, depth_kind=kind, out_kind=kind, x0=x0, ids=[1, 2, 10, 17])
+
+
+@pytest.mark.parametrize("w,h", [(132, 40), (192, 108), (644, 364)])
+def test_odd_sizes_mixed_pitches(oracle, w, h):
+    run_case(oracle, w, h, 2, depth_kind="+3", out_kind="256", x0=1)
+    run_case(oracle, w, h, 2, depth_kind="256", out_kind="+1", x0=0)
+
+
+@pytest.mark.parametrize("fmt,ao_format,rtne", [(L.DEPTH_UNORM16, L.AO_R8, 0), (L.DEPTH_UNORM24, L.AO_F16, 0),
+                                                (L.DEPTH_F16, L.AO_F16, 1), (L.DEPTH_F32, L.AO_F16, 1)])
+def test_formats(oracle, fmt, ao_format, rtne):
+    run_case(oracle, 644, 364, 2, fmt=fmt, ao_format=ao_format, rtne=rtne, depth_kind="256", out_kind="256", x0=0, ids=[1, 17])
+    run_case(oracle, 192, 108, 1, fmt=fmt, ao_format=ao_format, rtne=rtne, depth_kind="+1", out_kind="+3", x0=1)
+
+
+def test_six_frames_tall_blend(oracle):
+    run_case(oracle, 644, 364, 6, depth_kind="256", out_kind="+3", x0=0,
+             debug={L.DEBUG_BLEND_TALL_MIN_TILES: 1}, ids=[1, 2, 10, 17])
+
+
+def test_large_frames(oracle):
+    run_case(oracle, 1920, 1080, 1, depth_kind="256", out_kind="256", x0=0)
+    run_case(oracle, 3840, 2160, 1, depth_kind="256", out_kind="+1", x0=1)
+
+
+def test_max_batch_64(oracle):
+    run_case(oracle, 132, 40, 64, depth_kind="256", out_kind="256", x0=0, max_batch=64)
+
+
+def frame_settings(base, fp):
+    return dataclasses.replace(base, intensity=np.float32(fp.intensity), near_clip=np.float32(fp.nearClipPlane))
+
+
+def per_frame_params(n, seed=0):
+    return [FrameParams(intensity=0.5 + 0.5 * ((f + seed) % 3), nearClipPlane=0.1 * (1 + (f + seed) % 4)) for f in range(n)]
+
+
+# W % 8 != 0 with scalar pitches (scalar forms), and W % 8 == 0 with pitches of a multiple of 4 texels (vector forms)
+@pytest.mark.parametrize("w,h,depth_kind,out_kind,x0", [(644, 364, "256", "+3", 1), (640, 360, "2w", "256", 0)])
+def test_per_frame_params(oracle, w, h, depth_kind, out_kind, x0):
+    n = 3
+    base = H.settings(oracle, w, h)
+    fps = per_frame_params(n)
+    ao = H.component(base, max_batch=n)
+    try:
+        surf = Surfaces(w, h, n, L.DEPTH_F32, L.AO_R8, depth_kind, out_kind, x0, 40)
+        torch.cuda.synchronize()
+        assert pitched_call(ao, n, surf.depth_ptrs(), surf.dp * 4, surf.out_ptrs(), surf.op, params=fps) == 0
+        check(ao, oracle, [frame_settings(base, fp) for fp in fps], surf)
+    finally:
+        ao.close()
+
+
+def run_stream(oracle, kinds, own_launch, per_frame=False, w=640, h=360, n=2):
+    """Three pipelined steps; step k's surfaces have the pitch kinds kinds[k] ("packed": the packed entry points, pitch 0).  Step k
+    announces step k + 1 (prefetch_device(..., depth_pitch=)), so step 1 consumes what step 0 carried and carries step 2's pass:
+    in the fused last kernel when the next frames take its 16-byte loads (f32, W % 8 == 0, a pitch of a multiple of 4 texels)
+    and DEBUG_NEXT_DOWNSAMPLE_OWN_LAUNCH is off, else as a launch of its own -- which the DOWNSAMPLE slot of the profile shows."""
+    base = H.settings(oracle, w, h)
+    ao = H.component(base, max_batch=n, debug={L.DEBUG_NEXT_DOWNSAMPLE_OWN_LAUNCH: own_launch}, pipelined=True)
+    try:
+        steps = [Surfaces(w, h, n, L.DEPTH_F32, L.AO_R8, dk, ok, 0, 100 + 10 * k) for k, (dk, ok) in enumerate(kinds)]
+        fps = [per_frame_params(n, seed=k) if per_frame else None for k in range(3)]
+        dpitch = [0 if dk == "packed" else st.dp * 4 for (dk, _), st in zip(kinds, steps)]
+        opitch = [0 if ok == "packed" else st.op for (_, ok), st in zip(kinds, steps)]
+        torch.cuda.synchronize()
+        stream = torch.cuda.current_stream().cuda_stream
+        for k in range(3):
+            if k == 1:
+                ao.set_profiling(True)
+            if k + 1 < 3:
+                ao.prefetch_device(steps[k + 1].depth_ptrs(), fps[k + 1], depth_pitch=dpitch[k + 1])
+            ao.execute_device(steps[k].depth_ptrs(), steps[k].out_ptrs(), stream=stream, params=fps[k],
+                              depth_pitch=dpitch[k], out_pitch=opitch[k])
+        ms, samples = ao.pass_times_ms()
+        fused = not own_launch and (steps[2].dp * 4) % 16 == 0 and w % 8 == 0
+        assert samples == 2 and (ms[PASS_DOWNSAMPLE] == 0) == fused, (ms, fused)
+        for k in range(3):
+            sets = base if fps[k] is None else [frame_settings(base, fp) for fp in fps[k]]
+            check(ao, oracle, sets, steps[k], ids=[2, 17] if k == 2 else None)
+    finally:
+        ao.close()
+
+
+@pytest.mark.parametrize("own_launch", [0, 1])
+def test_pipelined_stream(oracle, own_launch):
+    run_stream(oracle, [("2w", "256")] * 3, own_launch)
+
+
+def test_pipelined_stream_scalar_pitch(oracle):
+    run_stream(oracle, [("+1", "+3")] * 3, 0, w=644, h=364)           # not vector-eligible: the carried pass runs on its own
+
+
+def test_pipelined_stream_mixing_packed_and_pitched(oracle):
+    # step 0 (packed) carries pitched frames, step 1 (pitched) carries packed ones: the pitched fused kernel with either side packed
+    run_stream(oracle, [("packed", "packed"), ("2w", "256"), ("packed", "packed")], 0)
+
+
+def test_pipelined_stream_per_frame_params(oracle):
+    run_stream(oracle, [("2w", "256")] * 3, 0, per_frame=True)
+
+
+def test_prefetch_with_another_pitch_reruns_the_pass(oracle):
+    w, h = 644, 364
+    s = H.settings(oracle, w, h)
+    ao = H.component(s, max_batch=1, pipelined=True)
+    try:
+        a = Surfaces(w, h, 1, L.DEPTH_F32, L.AO_R8, "256", "256", 0, 5)
+        b = Surfaces(w, h, 1, L.DEPTH_F32, L.AO_R8, "2w", "256", 0, 6)       # same pointer announced with another pitch
+        torch.cuda.synchronize()
+        stream = torch.cuda.current_stream().cuda_stream
+        assert pitched_call(ao, 1, b.depth_ptrs(), a.dp * 4, None, 0, prefetch=True) == 0     # announce pitch P
+        assert pitched_call(ao, 1, a.depth_ptrs(), a.dp * 4, a.out_ptrs(), a.op, stream=stream) == 0
+        ao.set_profiling(True)
+        assert pitched_call(ao, 1, b.depth_ptrs(), b.dp * 4, b.out_ptrs(), b.op, stream=stream) == 0   # consume with P' != P
+        ms, samples = ao.pass_times_ms()
+        assert samples >= 1 and ms[PASS_DOWNSAMPLE] > 0, ms
+        check(ao, oracle, s, a)
+        check(ao, oracle, s, b, ids=[2, 17])
+    finally:
+        ao.close()
+
+
+def test_pool_two_members(oracle):
+    from miniengineao_amd import AmbientOcclusionPool
+    w, h, n = 260, 36, 4
+    s = H.settings(oracle, w, h)
+    pool = AmbientOcclusionPool(w, h, [0, 0], max_batch=2, near_clip=s.near_clip, far_clip=s.far_clip,
+                                projection00=s.proj00, reversed_z=s.reversed_z)
+    try:
+        surf = Surfaces(w, h, n, L.DEPTH_F32, L.AO_R8, "+3", "256", 1, 60)
+        torch.cuda.synchronize()
+        pool.execute_device(surf.depth_ptrs(), surf.out_ptrs(), depth_pitch=surf.dp * 4, out_pitch=surf.op)
+        pool.synchronize()
+        for f in range(n):
+            want = oracle.run(surf.views[f], s, result_only=True)["result"]
+            got, untouched = surf.result(f)
+            assert untouched and np.array_equal(got, want), (f, H.diff_report("result", got, want))
+    finally:
+        pool.close()
+
+
+def test_host_strided_views(oracle):
+    w, h = 192, 108
+    s = H.settings(oracle, w, h)
+    ao = H.component(s, max_batch=2)
+    try:
+        views = [synth.occluder_field(w, h, 90 + f) for f in range(2)]
+        dsurf = np.full((2, h + 2, 300), np.nan, np.float32)
+        osurf = np.full((2, h + 2, 211), 0xA5, np.uint8)
+        for f in range(2):
+            dsurf[f, 1:1 + h, 3:3 + w] = views[f]
+        pin = (C.c_void_p * 2)(*[dsurf[f, 1:, 3:].ctypes.data for f in range(2)])
+        pout = (C.c_void_p * 2)(*[osurf[f, 1:, 5:].ctypes.data for f in range(2)])
+        ao._sync_params()
+        rc = ao._lib.meao_execute_batch_pitched(ao._ctx, 2, pin, 300 * 4, L.MEM_HOST, pout, 211, L.MEM_HOST, None, None)
+        assert rc == 0
+        for f in range(2):
+            want = oracle.run(views[f], s, result_only=True)["result"]
+            assert np.array_equal(osurf[f, 1:1 + h, 5:5 + w], want)
+            mask = np.ones(osurf[f].shape, bool)
+            mask[1:1 + h, 5:5 + w] = False
+            assert (osurf[f][mask] == 0xA5).all()
+    finally:
+        ao.close()
+
+
+def test_execute_tensors_crop_and_side_stream(oracle):
+    w, h = 644, 364
+    s = H.settings(oracle, w, h)
+    ao = H.component(s, max_batch=3)
+    try:
+        big = torch.from_numpy(np.stack([synth.occluder_field(700, 400, 20 + f) for f in range(3)])).cuda()
+        crop = big[:, 17:17 + h, 9:9 + w]
+        assert not crop.is_contiguous()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            big2 = big.clone()                        # work queued on the side stream that the call must be ordered behind
+            out = ao.execute_tensors(big2[:, 17:17 + h, 9:9 + w])
+        side.synchronize()
+        ref_in = crop.contiguous()
+        packed = torch.empty((3, h, w), dtype=torch.uint8, device="cuda")
+        ao.execute_device([ref_in[f].data_ptr() for f in range(3)], [packed[f].data_ptr() for f in range(3)],
+                          stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert torch.equal(out, packed)
+        out2 = torch.full((3, h + 4, w + 12), 0xA5, dtype=torch.uint8, device="cuda")
+        ao.execute_tensors(crop, out=out2[:, 2:2 + h, 6:6 + w])
+        torch.cuda.synchronize()
+        assert torch.equal(out2[:, 2:2 + h, 6:6 + w], packed)
+        out2[:, 2:2 + h, 6:6 + w] = 0xA5
+        assert bool((out2 == 0xA5).all())
+        want = oracle.run(crop[0].cpu().numpy(), s, result_only=True)["result"]
+        assert np.array_equal(out[0].cpu().numpy(), want)
+    finally:
+        ao.close()
+
+
+def test_execute_tensors_checks_every_frame_device(oracle):
+    w, h = 132, 40
+    ao = H.component(H.settings(oracle, w, h), max_batch=2)
+    try:
+        on_gpu = torch.zeros((h, w), dtype=torch.float32, device="cuda")
+        with pytest.raises(ValueError, match=r"depth\[1\]"):
+            ao.execute_tensors([on_gpu, torch.zeros((h, w), dtype=torch.float32)])
+        with pytest.raises(ValueError, match=r"out\[1\]"):
+            ao.execute_tensors([on_gpu, on_gpu], out=[torch.empty((h, w), dtype=torch.uint8, device="cuda"),
+                                                      torch.empty((h, w), dtype=torch.uint8)])
+    finally:
+        ao.close()
+
+
+def test_invalid_pitches_launch_nothing(oracle):
+    w, h = 260, 100
+    s = H.settings(oracle, w, h, ao_format=L.AO_F16)
+    ao = H.component(s, max_batch=1)
+    try:
+        surf = Surfaces(w, h, 1, L.DEPTH_F32, L.AO_F16, "256", "256", 0, 3)
+        torch.cuda.synchronize()
+        d, o = surf.depth_ptrs(), surf.out_ptrs()
+        before = surf.out.clone()
+        cases = [((w - 1) * 4, 0, L.ERR_INVALID_ARGUMENT), (w * 4 + 2, 0, L.ERR_INVALID_ARGUMENT),
+                 (0, w * 2 - 2, L.ERR_INVALID_ARGUMENT), (0, w * 2 + 1, L.ERR_INVALID_ARGUMENT),
+                 ((1 << 24) * 4, 0, L.ERR_UNSUPPORTED), (((1 << 24) - 4) * 4, 0, L.ERR_UNSUPPORTED)]     # 2^24 texels; > 2^32 bytes
+        for dp, op, status in cases:
+            assert pitched_call(ao, 1, d, dp, o, op) == status, (dp, op)
+            msg = ao._lib.meao_last_error(ao._ctx).decode()
+            assert ("depth_pitch" if dp else "ao_pitch") in msg, msg
+        assert pitched_call(ao, 1, d, (w - 1) * 4, None, 0, prefetch=True) == L.ERR_INVALID_ARGUMENT
+        torch.cuda.synchronize()
+        assert torch.equal(surf.out, before)
+    finally:
+        ao.close()
+
+
+TRACE = r"""
+import ctypes as C, sys, torch
+from miniengineao_amd import AmbientOcclusion, _lib as L
+mode = MODE
+w, h = 640, 360                  # W % 8 == 0: the pitched fused last kernel applies
+ao = AmbientOcclusion(w, h, max_batch=2, pipelined=True)
+surf = torch.zeros((2, h, 768), dtype=torch.float32, device="cuda") + 0.5
+out = torch.zeros((2, h, 768), dtype=torch.uint8, device="cuda")
+packed_d = torch.zeros((2, h, w), dtype=torch.float32, device="cuda") + 0.5
+packed_o = torch.zeros((2, h, w), dtype=torch.uint8, device="cuda")
+torch.cuda.synchronize()
+s = torch.cuda.current_stream().cuda_stream
+dp = [surf[f].data_ptr() for f in range(2)]
+op = [out[f].data_ptr() for f in range(2)]
+if mode == "pitched":
+    ao.execute_device(dp, op, stream=s, depth_pitch=768 * 4, out_pitch=768)                        # small final tiles
+    ao.debug_set(L.DEBUG_FINAL_SMALL_MAX_TILES, 0)
+    ao.prefetch_device(dp, depth_pitch=768 * 4)
+    ao.execute_device(dp, op, stream=s, depth_pitch=768 * 4, out_pitch=768)      # carries the next pass (fused last kernel)
+    ao.execute_device(dp, op, stream=s, depth_pitch=768 * 4, out_pitch=768)      # consumes it: 64 x 64 final tiles only
+    ao.debug_set(L.DEBUG_NEXT_DOWNSAMPLE_OWN_LAUNCH, 1)
+    ao.prefetch_device(dp, depth_pitch=768 * 4)
+    ao.execute_device(dp, op, stream=s, depth_pitch=768 * 4, out_pitch=768)      # the next pass as its own launch
+elif mode == "frames":
+    ao.execute_device(dp, op, stream=s, depth_pitch=768 * 4, out_pitch=768, params=[None, None])
+    ao.debug_set(L.DEBUG_FINAL_SMALL_MAX_TILES, 0)
+    ao.prefetch_device(dp, [None, None], depth_pitch=768 * 4)
+    ao.execute_device(dp, op, stream=s, depth_pitch=768 * 4, out_pitch=768, params=[None, None])
+    ao.execute_device(dp, op, stream=s, depth_pitch=768 * 4, out_pitch=768, params=[None, None])
+else:
+    P = (C.c_void_p * 2)
+    ao._sync_params()
+    for pitch in ((0, 0), (w * 4, w)):
+        assert ao._lib.meao_execute_batch_pitched(ao._ctx, 2, P(*[packed_d[f].data_ptr() for f in range(2)]), pitch[0], L.MEM_DEVICE,
+                                                  P(*[packed_o[f].data_ptr() for f in range(2)]), pitch[1], L.MEM_DEVICE, None,
+                                                  C.c_void_p(s)) == 0
+torch.cuda.synchronize()
+ao.close()
+"""
+
+
+def kernel_trace(tmp_path, mode):
+    """Kernel names of the child's launches in start order (rocprofv3 --kernel-trace), from its first meao kernel on: what the
+    context creation and the tensors' setup launched before that is left out."""
+    import csv
+    import glob
+    import os
+    import shutil
+    import subprocess
+    import sys
+    prof = shutil.which("rocprofv3") or ("/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else None)
+    if prof is None:
+        pytest.skip("rocprofv3 is not installed")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = tmp_path / "child.py"
+    src.write_text(TRACE.replace("MODE", repr(mode)))
+    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([prof, "--kernel-trace", "--output-format", "csv", "-d", str(tmp_path / "kt"), "-o", "kt", "--",
+                        sys.executable, str(src)], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    files = glob.glob(str(tmp_path / "kt" / "**" / "*kernel_trace.csv"), recursive=True)
+    assert files, r.stdout[-2000:]
+    rows = []
+    for f in files:
+        with open(f) as fh:
+            rows += [(int(row.get("Start_Timestamp") or 0), row["Kernel_Name"]) for row in csv.DictReader(fh)]
+    names = [n for _, n in sorted(rows, key=lambda t: t[0])]
+    first = next(i for i, n in enumerate(names) if "meao::" in n or "4meao" in n)
+    return names[first:]
+
+
+def launches(names, kernel):
+    return sum(1 for k in names if "::%s<" % kernel in k or "%d%sI" % (len(kernel), kernel) in k)
+
+
+def test_kernel_trace_pitched_calls(tmp_path):
+    names = kernel_trace(tmp_path, "pitched")
+    for kernel in ("downsample_pitched_kernel", "upsample_final_pitched_kernel", "upsample_final_small_pitched_kernel",
+                   "upsample_final_with_next_downsample_pitched_kernel"):
+        assert launches(names, kernel) > 0, (kernel, names)
+    assert launches(names, "downsample_pitched_kernel") == 4, names       # calls 1, 2 and 4; the own launch of call 4
+    for packed in ("downsample_kernel", "upsample_final_kernel", "upsample_final_small_kernel",
+                   "upsample_final_with_next_downsample_kernel"):
+        assert launches(names, packed) == 0, (packed, names)
+    assert not [n for n in names if "rocclr" in n or "copy" in n.lower()], names      # read and written in place
+
+
+def test_kernel_trace_per_frame_pitched_calls(tmp_path):
+    names = kernel_trace(tmp_path, "frames")
+    for kernel in ("downsample_pitched_frames_kernel", "upsample_final_small_pitched_frames_kernel",
+                   "upsample_final_pitched_frames_kernel", "upsample_final_with_next_downsample_pitched_frames_kernel"):
+        assert launches(names, kernel) > 0, (kernel, names)
+    assert not [n for n in names if "pitched" not in n and ("final" in n or "downsample" in n)], names
+
+
+def test_kernel_trace_packed_pitches_launch_the_shared_kernels(tmp_path):
+    names = kernel_trace(tmp_path, "packed")
+    assert launches(names, "downsample_kernel") == 2 and launches(names, "upsample_final_small_kernel") == 2, names
+    assert not [n for n in names if "pitched" in n], names
