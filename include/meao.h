@@ -68,9 +68,24 @@ typedef enum meao_mem { MEAO_MEM_HOST = 0, MEAO_MEM_DEVICE = 1 } meao_mem;
  * resolved depth is available; here the downsample kernel decodes the format on load, so that
  * pass does not exist.  UNORM formats decode to v / (2^n - 1), correctly rounded (what
  * SAMPLE_DEPTH_TEXTURE returns): UNORM16 = D16, UNORM24 = the low 24 bits of a 32-bit word
- * (D24S8 / D24X8; the high byte is ignored).  F16 decodes exactly. */
+ * (D24S8 / D24X8; the high byte is ignored).  F16 decodes exactly.
+ *
+ * LINEAR_F32 / LINEAR_F16: linear view-space depth instead of a hardware depth buffer.  A texel is z along the camera axis in
+ * the units of near_clip / far_clip (Unity's LinearEyeDepth; with far_clip = 1 it is Linear01Depth); f16 texels widen to f32
+ * exactly.  Linear01 depth is dist = z * s, one f32 multiply rounded to nearest even, with s the f32 nearest to 1 / far_clip
+ * (per call, or per frame under meao_execute_batch_params): when far_clip is a power of two, dist == z / far_clip exactly.
+ * dist >= 1 (the far plane and beyond, +inf included) becomes 1e5f, the value the hardware formats give their far-plane
+ * texel; every other value passes through unchanged (NaN, negatives, +-0, denormals take the IEEE-division bodies, and
+ * meao_hostile_frames reports a frame whose level texels hold a non-sky dist that is NaN or outside [2^-24, 2^20]).  The
+ * texels are decoded with far_clip alone; near_clip and reversed_z set only the padding of the level 1-2 atlases, as for every
+ * format (Linearize of an out-of-range load: near_clip / far_clip with conventional Z, 1e5 with reversed Z), so a host passes
+ * its camera's real values.  A prefetched downsample pass is reused when each frame's s matches.  meao_params validation is
+ * unchanged.  So a linear frame equal to the Linearize of a hardware frame gives the hardware frame's results bit for bit.  Every entry point accepts them; HOST frames and pitches
+ * use their element size (4 / 2 bytes).  They arrived without an ABI version change: libraries built before them reject
+ * depth_format 4 and 5 at meao_create with MEAO_ERR_INVALID_ARGUMENT, which is how a host probes for support. */
 typedef enum meao_depth_format {
-    MEAO_DEPTH_F32 = 0, MEAO_DEPTH_UNORM16 = 1, MEAO_DEPTH_UNORM24 = 2, MEAO_DEPTH_F16 = 3
+    MEAO_DEPTH_F32 = 0, MEAO_DEPTH_UNORM16 = 1, MEAO_DEPTH_UNORM24 = 2, MEAO_DEPTH_F16 = 3,
+    MEAO_DEPTH_LINEAR_F32 = 4, MEAO_DEPTH_LINEAR_F16 = 5
 } meao_depth_format;
 
 typedef enum meao_format { MEAO_FMT_F32 = 0, MEAO_FMT_F16 = 1, MEAO_FMT_UNORM8 = 2 } meao_format;

@@ -47,7 +47,7 @@ public:
     AmbientOcclusion(int32_t pixelWidth, int32_t pixelHeight, int32_t device = 0,
                      meao_ao_format aoFormat = MEAO_AO_R8, int32_t maxBatch = 1, int32_t numLevels = 4,
                      meao_f16_rounding f16Rounding = MEAO_F16_RTZ_CLAMP,
-                     meao_depth_format depthFormat = MEAO_DEPTH_F32, int32_t hqLevels = 0,
+                     meao_depth_format depthFormat = MEAO_DEPTH_F32, int32_t hqLevels = 0,   // MEAO_DEPTH_LINEAR_*: view-space z (meao.h)
                      meao_sample_set sampleSet = MEAO_SAMPLES_CHECKER)
     {
         meao_default_config(&cfg_);

@@ -36,6 +36,7 @@ AO_R8, AO_F16 = 0, 1
 F16_RTZ_CLAMP, F16_RTNE = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
 DEPTH_F32, DEPTH_UNORM16, DEPTH_UNORM24, DEPTH_F16 = 0, 1, 2, 3
+DEPTH_LINEAR_F32, DEPTH_LINEAR_F16 = 4, 5      # linear view-space depth z (meao.h: Linear01 = z * RN(1 / far_clip))
 COMPOSITE_MULTIPLY, COMPOSITE_AMBIENT_ONLY, COMPOSITE_DEBUG = 0, 1, 2
 FMT_F32, FMT_F16, FMT_UNORM8 = 0, 1, 2
 SAMPLES_CHECKER, SAMPLES_EXHAUSTIVE = 0, 1

@@ -18,6 +18,11 @@ from . import _lib as L
 from .frame_params import FrameParams, params_array
 
 _NP_OF_FMT = {L.FMT_F32: np.float32, L.FMT_F16: np.uint16, L.FMT_UNORM8: np.uint8}
+# element type of the depth frames per meao_depth_format: numpy host arrays, torch tensors (by name: torch is imported lazily)
+DEPTH_NUMPY = {L.DEPTH_F32: np.float32, L.DEPTH_UNORM16: np.uint16, L.DEPTH_UNORM24: np.uint32, L.DEPTH_F16: np.uint16,
+               L.DEPTH_LINEAR_F32: np.float32, L.DEPTH_LINEAR_F16: np.float16}
+DEPTH_TORCH = {L.DEPTH_F32: "float32", L.DEPTH_UNORM16: "uint16", L.DEPTH_UNORM24: "int32", L.DEPTH_F16: "float16",
+               L.DEPTH_LINEAR_F32: "float32", L.DEPTH_LINEAR_F16: "float16"}
 
 # _debug values (AO.cs:789-808)
 DEBUG_BUFFER_NAMES = {
@@ -123,7 +128,7 @@ class AmbientOcclusion:
     # ---- the hot path ------------------------------------------------------------------
     def render(self, depth: np.ndarray) -> np.ndarray:
         """One frame, host arrays: (H, W) raw depth in the configured depth_format (float32 by
-        default; uint16 / uint32 codes for UNORM16 / UNORM24 / F16 bits) -> AO (H, W) uint8 / f16 bits."""
+        default; uint16 / uint32 codes for UNORM16 / UNORM24 / F16 bits; float32 / float16 view-space z for LINEAR_F32 / _F16) -> AO (H, W) uint8 / f16 bits."""
         return self.render_batch([depth])[0]
 
     def render_batch(self, depths: Sequence[np.ndarray], params: Optional[Sequence[Optional[FrameParams]]] = None) -> list:
@@ -131,8 +136,7 @@ class AmbientOcclusion:
         n = len(depths)
         self._sync_params()
         prm = None if params is None else params_array(params, n, self._prm)
-        dt = {L.DEPTH_F32: np.float32, L.DEPTH_UNORM16: np.uint16, L.DEPTH_UNORM24: np.uint32,
-              L.DEPTH_F16: np.uint16}[self._cfg.depth_format]
+        dt = DEPTH_NUMPY[self._cfg.depth_format]
         ins = [np.ascontiguousarray(d, dtype=dt) for d in depths]
         for d in ins:
             if d.shape != (self.height, self.width):
@@ -185,13 +189,12 @@ class AmbientOcclusion:
     def execute_tensors(self, depth, out=None, params: Optional[Sequence[Optional[FrameParams]]] = None):
         """Torch tensors on this context's device, used in place (meao_execute_batch_pitched), on torch.cuda.current_stream().
         depth: an (N, H, W) tensor or a list of (H, W) tensors in the dtype of depth_format (float32, float16, uint16 for UNORM16,
-        int32 for UNORM24) -- e.g. a crop ``surface[:, y0:y0 + H, x0:x0 + W]`` of larger targets.  Rows must be contiguous and all
+        int32 for UNORM24; float32 / float16 for LINEAR_F32 / LINEAR_F16) -- e.g. a crop ``surface[:, y0:y0 + H, x0:x0 + W]`` of larger targets.  Rows must be contiguous and all
         frames must share one row stride, which becomes the pitch; any other layout raises ValueError (nothing is copied).
         out: the same for the AO (uint8 for R8, float16 for F16 storage), or None: allocated packed.  Returns out."""
         import torch
         from .surfaces import frame_pointers, packed_pitch
-        depth_dt = {L.DEPTH_F32: torch.float32, L.DEPTH_UNORM16: torch.uint16, L.DEPTH_UNORM24: torch.int32,
-                    L.DEPTH_F16: torch.float16}[self._cfg.depth_format]
+        depth_dt = getattr(torch, DEPTH_TORCH[self._cfg.depth_format])
         ao_dt = torch.uint8 if self._cfg.ao_format == L.AO_R8 else torch.float16
         dev = torch.device("cuda", self._cfg.device)        # every frame of depth and out must be on the context's device
         frames = list(depth) if not hasattr(depth, "dim") else depth
@@ -343,11 +346,12 @@ class AmbientOcclusionPool:
     def __init__(self, width: int, height: int, devices: Sequence[int], *, max_batch: int = 1,
                  ao_format: int = L.AO_R8, near_clip: float = 0.3, far_clip: float = 1000.0,
                  projection00: Optional[float] = None, reversed_z: bool = True, intensity: float = 1.0,
-                 pipelined: bool = False):
+                 pipelined: bool = False, depth_format: int = L.DEPTH_F32):
         self._lib = L.load()
         cfg = L.Config()
         self._lib.meao_default_config(C.byref(cfg))
         cfg.width, cfg.height, cfg.max_batch, cfg.ao_format = width, height, max_batch, ao_format
+        cfg.depth_format = depth_format     # DEPTH_F32, or linear view-space z: DEPTH_LINEAR_F32 / DEPTH_LINEAR_F16 (float16 arrays)
         cfg.pipelined = 1 if pipelined else 0
         self._cfg = cfg
         self.devices = list(devices)
@@ -380,7 +384,7 @@ class AmbientOcclusionPool:
     def render_batch(self, depths: Sequence[np.ndarray], params: Optional[Sequence[Optional[FrameParams]]] = None) -> list:
         """Host arrays in and out.  params: one FrameParams per frame (it goes with the frame to its member), or None."""
         n = len(depths)
-        ins = [np.ascontiguousarray(d, dtype=np.float32) for d in depths]
+        ins = [np.ascontiguousarray(d, dtype=DEPTH_NUMPY[self._cfg.depth_format]) for d in depths]
         dt = np.uint8 if self._cfg.ao_format == L.AO_R8 else np.uint16
         outs = [np.empty((self._cfg.height, self._cfg.width), dt) for _ in range(n)]
         pin = (C.c_void_p * n)(*[d.ctypes.data for d in ins])

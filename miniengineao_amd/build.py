@@ -27,7 +27,9 @@ KERNEL_UNITS = ["meao_k_downsample.hip", "meao_k_render.hip", "meao_k_upsample.h
                 "meao_k_downsample_frames.hip", "meao_k_render_frames.hip", "meao_k_upsample_frames.hip",
                 "meao_k_upsample_nested_frames.hip", "meao_k_upsample_fused_frames.hip",
                 # the row-pitched forms of the kernels that address caller memory (meao_execute_batch_pitched), likewise
-                "meao_k_pitched.hip", "meao_k_pitched_frames.hip", "meao_k_pitched_fused.hip"]
+                "meao_k_pitched.hip", "meao_k_pitched_frames.hip", "meao_k_pitched_fused.hip",
+                # the kernels that read linear view-space depth (MEAO_DEPTH_LINEAR_*), likewise
+                "meao_k_linear.hip", "meao_k_linear_frames.hip", "meao_k_linear_fused.hip"]
 HOST_UNITS = ["meao_plan.cpp", "meao_api.cpp", "meao_pool.cpp"]
 SOURCES = HOST_UNITS + KERNEL_UNITS
 HEADERS = ["meao_plan.hpp", "meao_kernels.hpp", "meao_dev.hpp", "meao_dev_downsample.hpp", "meao_dev_render.hpp",

@@ -180,7 +180,7 @@ bool config_valid(const meao_config &c, std::string *why)
     if (c.ao_format != MEAO_AO_R8 && c.ao_format != MEAO_AO_F16) { *why = "unknown ao_format"; return false; }
     if (c.f16_rounding != MEAO_F16_RTZ_CLAMP && c.f16_rounding != MEAO_F16_RTNE) { *why = "unknown f16_rounding"; return false; }
     if (c.max_batch < 1 || c.max_batch > MEAO_MAX_BATCH) { *why = "max_batch must be 1..MEAO_MAX_BATCH"; return false; }
-    if (c.depth_format < MEAO_DEPTH_F32 || c.depth_format > MEAO_DEPTH_F16) { *why = "unknown depth_format"; return false; }
+    if (c.depth_format < MEAO_DEPTH_F32 || c.depth_format > MEAO_DEPTH_LINEAR_F16) { *why = "unknown depth_format"; return false; }
     if (c.hq_levels < 0 || c.hq_levels > c.num_levels) { *why = "hq_levels must be 0..num_levels"; return false; }
     if (c.sample_set != MEAO_SAMPLES_CHECKER && c.sample_set != MEAO_SAMPLES_EXHAUSTIVE) { *why = "unknown sample_set"; return false; }
     if (c.pipelined != 0 && c.pipelined != 1) { *why = "pipelined must be 0 or 1"; return false; }
@@ -452,8 +452,10 @@ struct ArgBuilder {
         for (int k = 0; k < 4; ++k) ds.low[k] = slot_ptr<float>(ctx, ctx->off_low_of(set, k));
         ds.frame_stride = ctx->slot_bytes;
         for (int k = 0; k < 5; ++k) { ds.w[k] = p().mip[k].w; ds.h[k] = p().mip[k].h; }
-        ds.zp0 = p().zbuffer_params[0];
-        ds.zp1 = p().zbuffer_params[1];
+        float zc[2];
+        depth_decode_constants(c().depth_format, p().zbuffer_params, *prm, zc);
+        ds.zp0 = zc[0];
+        ds.zp1 = zc[1];
         ds.reversed_z = prm->reversed_z != 0;
         ds.f16_rtne = rtne();
         ds.exact_rcp_div = exact_rcp_div;
@@ -580,8 +582,10 @@ struct ArgBuilder {
         for (int f = 0; f < n; ++f) hd.raw[f] = depth_dev[f];
         hd.depth_format = c().depth_format;
         hd.reversed_z = prm->reversed_z != 0;
-        hd.zp0 = p().zbuffer_params[0];
-        hd.zp1 = p().zbuffer_params[1];
+        float zc[2];
+        depth_decode_constants(c().depth_format, p().zbuffer_params, *prm, zc);
+        hd.zp0 = zc[0];
+        hd.zp1 = zc[1];
         return hd;
     }
 };
@@ -615,8 +619,12 @@ void build_call_args(const ArgBuilder &args, const ArgBuilder &nb, const CallSha
                                      cs.b.next == 2);
 }
 
-bool same_zb(const meao_ctx::ZbInputs &z, const meao_params &p)
+bool same_zb(const meao_ctx::ZbInputs &z, const meao_params &p, int depth_format)
 {
+    if (linear_depth(depth_format)) {      // linear view-space depth reads s = RN(1 / far_clip) only
+        const float s0 = 1.0f / z.far_clip, s1 = 1.0f / p.far_clip;
+        return std::memcmp(&s0, &s1, sizeof(float)) == 0;
+    }
     return std::memcmp(&z.near_clip, &p.near_clip, sizeof(float)) == 0 && std::memcmp(&z.far_clip, &p.far_clip, sizeof(float)) == 0 &&
            (z.reversed_z != 0) == (p.reversed_z != 0);
 }
@@ -685,7 +693,7 @@ int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *o
     shape.frames = n;
     shape.prefetched = ctx->ready_n == n && ctx->ready_stream == stream && std::memcmp(ctx->ready_depth, depth_dev, sizeof(void *) * n) == 0 &&
                        (ctx->ready_exact || !exact) && ctx->ready_depth_pitch == depth_pitch;
-    for (int f = 0; shape.prefetched && f < n; ++f) shape.prefetched = same_zb(ctx->ready_zb[f], *prm_of[f]);
+    for (int f = 0; shape.prefetched && f < n; ++f) shape.prefetched = same_zb(ctx->ready_zb[f], *prm_of[f], c.depth_format);
     ctx->ds_cur = shape.prefetched ? ctx->ready_set : 0;
     ctx->ready_n = 0;
     if (!shape.prefetched) ctx->set_gen[ctx->ds_cur] = next_generation(ctx);      // direct launches take a fresh generation per pass: no flag clearing
@@ -811,8 +819,7 @@ int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *o
         ctx->last_out[f] = out_dev[f];
         ctx->last_depth[f] = depth_dev[f];
         // the parameters the buffers built on demand need (debug ids 1, 6-9), as this call used them
-        ctx->last_zp[f][0] = plan_of[f]->zbuffer_params[0];
-        ctx->last_zp[f][1] = plan_of[f]->zbuffer_params[1];
+        depth_decode_constants(c.depth_format, plan_of[f]->zbuffer_params, *prm_of[f], ctx->last_zp[f]);
         ctx->last_reversed_z[f] = prm_of[f]->reversed_z != 0;
         for (int k = 0; k < 4; ++k) ctx->last_pad[f][k] = plan_of[f]->render[k].pad_value;
     }

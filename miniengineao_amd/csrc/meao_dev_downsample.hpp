@@ -49,6 +49,39 @@ __device__ __forceinline__ bool nice_denominators(float d0, float d1, float d2, 
     return lo >= 0x35800000u && hi <= 0x4B800000u;
 }
 
+// Linear view-space depth (MEAO_DEPTH_LINEAR_*, the LINEAR instances of meao_k_linear*.hip): Linear01 = z * s with s = RN(1 / far_clip),
+// carried in the zp0 field of the argument blocks.  dist >= 1 -- the far plane and beyond, +inf included -- becomes the 1e5 of the
+// raw path's far-plane texel (DS1:41-45); every other value (NaN, negatives, +-0, denormals) passes through.
+__device__ __forceinline__ float linearize_view(float z, float s)
+{
+    const float dist = z * s;
+    return dist >= 1.0f ? 1e5f : dist;
+}
+
+// The range test of linear texels, on the Linear01 values themselves: normal numbers in [2^-24, 2^20] -- the range a nice
+// denominator gives raw depth (the far-plane 1e5 is inside it) -- as one unsigned min / max chain (NaN, negatives fail).
+__device__ __forceinline__ bool nice_linear(float l0, float l1, float l2, float l3)
+{
+    const uint32_t b0 = __builtin_bit_cast(uint32_t, l0), b1 = __builtin_bit_cast(uint32_t, l1);
+    const uint32_t b2 = __builtin_bit_cast(uint32_t, l2), b3 = __builtin_bit_cast(uint32_t, l3);
+    const uint32_t lo = min(min(min(b0, b1), b2), b3), hi = max(max(max(b0, b1), b2), b3);
+    return lo >= 0x33800000u && hi <= 0x49800000u;
+}
+
+// Linear01 of one texel: Linearize of raw depth (DS1:37-48) or, LINEAR, of linear view-space depth (zp0 = s)
+template <bool LINEAR, int DIV>
+__device__ __forceinline__ float linear01(float v, float zp0, float zp1, float sky_depth)
+{
+    if constexpr (LINEAR) return linearize_view(v, zp0);
+    else return linearize<DIV>(v, zp0, zp1, sky_depth);
+}
+
+// The storage format a LINEAR kernel decodes its texels with (f16 texels widen exactly, like MEAO_DEPTH_F16)
+__device__ __forceinline__ int linear_texel_format(int depth_format)
+{
+    return depth_format == MEAO_DEPTH_LINEAR_F16 ? MEAO_DEPTH_F16 : MEAO_DEPTH_F32;
+}
+
 // One raw depth texel of any meao_depth_format (the depth-copy blit of the reference, Blit.shader pass 0, folded into the load).
 __device__ __forceinline__ float raw_depth_texel(const void *depth, int format, size_t at)
 {
@@ -84,8 +117,8 @@ __device__ __forceinline__ void raw_depth_quad(const void *depth, int format, si
 // 4 consecutive LowDepth1 texels -- raw texels 2j, 2j+2, 2j+4, 2j+6 of raw row 2i -- in each of its ROWS rows (i, i + 8, ...):
 // with 16-byte loads two per row, all of them in flight before the first is used.
 // VEC: W % 8 == 0 and every frame aligned to 4 texels.  PITCHED: the depth rows are a.depth_pitch texels apart instead of W
-// (and, with VEC, that stride is a multiple of 4 texels).
-template <bool VEC, int DIV, int ROWS, bool PITCHED = false>
+// (and, with VEC, that stride is a multiple of 4 texels).  LINEAR: linear view-space depth (linearize_view; zp0 = s).
+template <bool VEC, int DIV, int ROWS, bool PITCHED = false, bool LINEAR = false>
 __device__ __forceinline__ void downsample_tile(const DownsampleArgs &a, int tile, int frame)
 {
     const unsigned tid = threadIdx.x;
@@ -95,12 +128,14 @@ __device__ __forceinline__ void downsample_tile(const DownsampleArgs &a, int til
     const int W = PITCHED ? a.depth_pitch : a.w[0], w1 = a.w[1], h1 = a.h[1];
     if (j0 >= w1) return;
     const void *__restrict__ depth = a.depth[frame];
-    const int format = a.depth_format;
+    const int format = LINEAR ? linear_texel_format(a.depth_format) : a.depth_format;
+    // (texels past the level: a clean depth, never stored; linear: +inf, the far plane)
+    constexpr float kUnused = LINEAR ? __builtin_huge_valf() : 0.5f;
     float v[ROWS][4];
 #pragma unroll
     for (int k = 0; k < ROWS; ++k) {
         const int i = ib + kMipRowsPerPass * k;
-        v[k][0] = v[k][1] = v[k][2] = v[k][3] = 0.5f;
+        v[k][0] = v[k][1] = v[k][2] = v[k][3] = kUnused;
         if (i < h1) {
             const size_t at = static_cast<size_t>(2 * i) * W + 2 * j0;
             if constexpr (VEC) {
@@ -126,7 +161,12 @@ __device__ __forceinline__ void downsample_tile(const DownsampleArgs &a, int til
         const int i = ib + kMipRowsPerPass * k;
         if (i >= h1) continue;
         float lin[4];
-        if constexpr (DIV == DIV_EXACT_RCP) {
+        if constexpr (LINEAR) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) lin[e] = linearize_view(v[k][e], zp0);
+            if (DIV == DIV_EXACT_RCP && !__builtin_expect(nice_linear(lin[0], lin[1], lin[2], lin[3]), 1))
+                a.hostile[frame] = a.generation;     // racing stores of the same value
+        } else if constexpr (DIV == DIV_EXACT_RCP) {
             // the exact reciprocal sequence is only valid for a "nice" denominator; anything else
             // (hostile input) is divided with IEEE '/' and marks the frame for the later kernels
             if (__builtin_expect(nice_denominators(mad(zp0, v[k][0], zp1), mad(zp0, v[k][1], zp1), mad(zp0, v[k][2], zp1), mad(zp0, v[k][3], zp1)), 1)) {
@@ -201,7 +241,8 @@ __device__ __forceinline__ void downsample_lean_load(const DownsampleArgs &a, in
     q[1] = __builtin_nontemporal_load(reinterpret_cast<const float4v *>(at_byte_offset(depth, t * 4u + 16u)));
 }
 
-template <int DIV, bool FULL>
+// LINEAR: linear view-space f32 depth (linearize_view; zp0 = s).
+template <int DIV, bool FULL, bool LINEAR = false>
 __device__ __forceinline__ void downsample_lean_finish(const DownsampleArgs &a, int tile, int frame, const float4v (&q)[2])
 {
     const LeanMipLane L(a, tile);
@@ -217,7 +258,12 @@ __device__ __forceinline__ void downsample_lean_finish(const DownsampleArgs &a, 
     const float sky_depth = a.reversed_z != 0 ? 0.0f : 1.0f;
     const float v[4] = {q[0].x, q[0].z, q[1].x, q[1].z};
     float lin[4];
-    if constexpr (DIV == DIV_EXACT_RCP) {
+    if constexpr (LINEAR) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) lin[e] = linearize_view(v[e], zp0);
+        if (DIV == DIV_EXACT_RCP && !__builtin_expect(nice_linear(lin[0], lin[1], lin[2], lin[3]), 1))
+            a.hostile[frame] = a.generation;         // racing stores of the same value
+    } else if constexpr (DIV == DIV_EXACT_RCP) {
         float den[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) den[e] = mad(zp0, v[e], zp1);

@@ -266,12 +266,17 @@ __device__ __forceinline__ uint32_t bilateral_upsample_r8(float hi_depth, float 
 // Returns false when a denominator is outside the range the exact reciprocal (and everything downstream of it in the bilateral
 // step) is verified for: the caller then redoes its texels with IEEE '/' (final_lane_redo_ieee), which is what the reference
 // divides with everywhere.  hd[] of such a quad is not used.
-template <bool RTNE, int DIV>
+// LINEAR: linear view-space depth (linearize_view, zp0 = s); false = a HiResDB word the exact sequences downstream are not
+// verified for (the test of hi_depth_words: negative, -0, inf, NaN).
+template <bool RTNE, int DIV, bool LINEAR = false>
 __device__ __forceinline__ bool hi_depth_quad(const float (&d)[4], float zp0, float zp1, float sky_depth, float (&hd)[4])
 {
     float lin[4];
     bool nice = true;
-    if constexpr (DIV == DIV_EXACT_RCP) {
+    if constexpr (LINEAR) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) lin[e] = linearize_view(d[e], zp0);
+    } else if constexpr (DIV == DIV_EXACT_RCP) {
         float den[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) den[e] = mad(zp0, d[e], zp1);
@@ -293,6 +298,10 @@ __device__ __forceinline__ bool hi_depth_quad(const float (&d)[4], float zp0, fl
     }
     const float2v lo = through_f16_pair<RTNE>(lin[0], lin[1]), hi = through_f16_pair<RTNE>(lin[2], lin[3]);
     hd[0] = lo.x; hd[1] = lo.y; hd[2] = hi.x; hd[3] = hi.y;
+    if constexpr (LINEAR) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) nice = nice && __builtin_bit_cast(uint32_t, hd[e]) < 0x7f800000u;
+    }
     return nice;
 }
 
@@ -315,6 +324,15 @@ __device__ __forceinline__ void decode_raw_quad(const uint4v &q, int format, flo
         d[0] = f16_bits_to_f32(static_cast<uint16_t>(q.x & 0xffffu)); d[1] = f16_bits_to_f32(static_cast<uint16_t>(q.x >> 16));
         d[2] = f16_bits_to_f32(static_cast<uint16_t>(q.y & 0xffffu)); d[3] = f16_bits_to_f32(static_cast<uint16_t>(q.y >> 16));
     }
+}
+
+// The storage format the final pass loads its depth texels with: the caller's format, or, LINEAR, the storage of linear depth
+// (meao_depth_format values: LINEAR_F32 loads and decodes as F32, LINEAR_F16 as F16)
+template <bool LINEAR>
+__device__ __forceinline__ int stored_format(const HiDepthArgs *hi)
+{
+    if constexpr (LINEAR) return linear_texel_format(hi->depth_format);
+    else return hi->depth_format;
 }
 
 // STREAMED: the frame is read once -- past the caches' LRU (the hi-res operands); the apron texels of a from-raw window are lines
@@ -345,14 +363,34 @@ __device__ __forceinline__ uint4v load_raw_quad(const void *frame_base, int form
 // nice level texel).  So: one packed unsigned max over the words, one compare per lane.  Returns false = redo the lane (IEEE).
 // even[q][j]: Linearize of texels 0 and 2 of quad q BEFORE the f16 store -- for a quad of an even row these are the LowDepth1
 // texels under it (DS2x[st >> 1], DS1:64-70); the from-raw window of the full-resolution pass takes its interior from them.
-template <bool RTNE, int DIV, bool RAW_F32, int QUADS>
+// LINEAR: linear view-space depth (format: its storage, MEAO_DEPTH_F32 / _F16; zp0 = s) -- one packed multiply per texel pair and the
+// far-plane select instead of the reciprocals, the same f16 words, `even` and lane test.
+template <bool RTNE, int DIV, bool RAW_F32, int QUADS, bool LINEAR = false>
 __device__ __forceinline__ bool hi_depth_words(const uint4v (&raw)[QUADS], int format, float zp0, float zp1, float sky_depth,
                                                uint32_t (&words)[QUADS][2], float (&even)[QUADS][2])
 {
     float d[QUADS][4];
 #pragma unroll
     for (int q = 0; q < QUADS; ++q) decode_raw_quad<RAW_F32>(raw[q], format, d[q]);
-    if constexpr (DIV == DIV_EXACT_RCP) {
+    if constexpr (LINEAR) {
+        ushort2v top = {0, 0};
+#pragma unroll
+        for (int q = 0; q < QUADS; ++q)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                float2v lin = float2v{d[q][2 * h], d[q][2 * h + 1]} * splat(zp0);                                            // z * s
+                lin.x = lin.x >= 1.0f ? 1e5f : lin.x;
+                lin.y = lin.y >= 1.0f ? 1e5f : lin.y;
+                if constexpr (RTNE) {
+                    words[q][h] = f32_to_f16_bits<true>(lin.x) | (static_cast<uint32_t>(f32_to_f16_bits<true>(lin.y)) << 16);
+                } else {
+                    words[q][h] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(lin.x, lin.y));                     // AO.cs:454
+                }
+                even[q][h] = lin.x;
+                top = __builtin_elementwise_max(top, __builtin_bit_cast(ushort2v, words[q][h]));
+            }
+        return DIV != DIV_EXACT_RCP || (top.x < 0x7c00u && top.y < 0x7c00u);
+    } else if constexpr (DIV == DIV_EXACT_RCP) {
         static_assert(!RTNE, "exact divisions only ever run with round-toward-zero depth storage");
         float2v den[QUADS][2], r[QUADS][2], lin[QUADS][2];
 #pragma unroll
@@ -460,7 +498,7 @@ __device__ __forceinline__ bool ups_tile_is_interior(const UpsampleArgs &a, int 
 // Hi-res operands.  CLAMPED: every lane loads (out-of-frame lanes re-read the frame's last row / quad and never use it),
 // so that the code is branch-free and the compiler's s_waitcnt counts stay exact.  PITCHED (final pass): raw depth rows are
 // a.pitch.depth texels apart.
-template <int AOFMT, bool FINAL, int TILE_H, bool CLAMPED, bool RAW_F32, bool PITCHED = false>
+template <int AOFMT, bool FINAL, int TILE_H, bool CLAMPED, bool RAW_F32, bool PITCHED = false, bool LINEAR = false>
 __device__ __forceinline__ void ups_issue_hoisted(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, FINAL, TILE_H> &L)
 {
     const int tid = thread_index_opaque();
@@ -482,7 +520,7 @@ __device__ __forceinline__ void ups_issue_hoisted(const UpsampleArgs &a, const H
                 const uint32_t hrow = PITCHED ? static_cast<uint32_t>(hy) * static_cast<uint32_t>(a.pitch.depth) + static_cast<uint32_t>(hhx0)
                                               : static_cast<uint32_t>(hy * hw + hhx0);
                 if constexpr (FINAL) {
-                    L.hraw[pass][f] = load_raw_quad<RAW_F32>(hi->raw[frame], hi->depth_format, hrow);
+                    L.hraw[pass][f] = load_raw_quad<RAW_F32>(hi->raw[frame], stored_format<LINEAR>(hi), hrow);
                 } else {
                     L.hd32[pass][f] = *reinterpret_cast<const float4v *>(at_byte_offset(
                         frame_ptr(static_cast<const float *>(a.hi_depth), a.frame_stride, frame), hrow * 4u));
@@ -495,7 +533,7 @@ __device__ __forceinline__ void ups_issue_hoisted(const UpsampleArgs &a, const H
 
 // The same for a tile that lies inside the frame: no clamps, one 24-bit multiply -- the rows of a lane are its first one plus
 // multiples of the level's width that are uniform (scalar).  PITCHED (final pass): of the raw depth's row stride instead.
-template <int AOFMT, bool FINAL, int TILE_H, bool RAW_F32, bool PITCHED = false>
+template <int AOFMT, bool FINAL, int TILE_H, bool RAW_F32, bool PITCHED = false, bool LINEAR = false>
 __device__ __forceinline__ void ups_issue_hoisted_inside(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, FINAL, TILE_H> &L)
 {
     const int tid = thread_index_opaque();
@@ -509,7 +547,7 @@ __device__ __forceinline__ void ups_issue_hoisted_inside(const UpsampleArgs &a, 
         for (int f = 0; f < 2; ++f) {
             const uint32_t hrow = first + static_cast<uint32_t>(32 * pass + f) * hw;
             if constexpr (FINAL) {
-                L.hraw[pass][f] = load_raw_quad<RAW_F32>(hi->raw[frame], hi->depth_format, hrow);
+                L.hraw[pass][f] = load_raw_quad<RAW_F32>(hi->raw[frame], stored_format<LINEAR>(hi), hrow);
             } else {
                 L.hd32[pass][f] = *reinterpret_cast<const float4v *>(at_byte_offset(
                     frame_ptr(static_cast<const float *>(a.hi_depth), a.frame_stride, frame), hrow * 4u));
@@ -522,7 +560,7 @@ __device__ __forceinline__ void ups_issue_hoisted_inside(const UpsampleArgs &a, 
 // All loads of an interior tile: window first, hi-res operands behind them.  The window comes from L2 (written by the
 // previous pass), the hi-res operands of the final pass from HBM; vmcnt retires loads in issue order, so with the hi-res
 // loads in front the window wait would last an HBM latency.
-template <int AOFMT, bool FINAL, int TILE_H, bool RAW_F32, bool PITCHED = false>
+template <int AOFMT, bool FINAL, int TILE_H, bool RAW_F32, bool PITCHED = false, bool LINEAR = false>
 __device__ __forceinline__ void ups_issue_interior_loads(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, FINAL, TILE_H> &L,
                                                          bool inside)
 {
@@ -544,8 +582,8 @@ __device__ __forceinline__ void ups_issue_interior_loads(const UpsampleArgs &a, 
         L.wa[round] = *reinterpret_cast<const typename AO::type4 *>(at_byte_offset(lo_ao, idx * static_cast<uint32_t>(sizeof(ao_t))));
     }
     __builtin_amdgcn_sched_barrier(0);          // keep the issue order: window, then hi-res
-    if (inside) ups_issue_hoisted_inside<AOFMT, FINAL, TILE_H, RAW_F32, PITCHED>(a, hi, tile, frame, L);      // (wave-uniform; the same loads either way)
-    else ups_issue_hoisted<AOFMT, FINAL, TILE_H, true, RAW_F32, PITCHED>(a, hi, tile, frame, L);
+    if (inside) ups_issue_hoisted_inside<AOFMT, FINAL, TILE_H, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L);      // (wave-uniform; the same loads either way)
+    else ups_issue_hoisted<AOFMT, FINAL, TILE_H, true, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L);
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -581,7 +619,7 @@ __device__ __forceinline__ bool ups_tile_from_raw(const UpsampleArgs &a, int til
 
 // Loads of a from-raw tile: the AO window (L2: the previous pass wrote it), the apron's raw texels (lines of the neighbouring
 // tiles' hi-res operands), the tile's own hi-res operands (HBM) -- in that order, vmcnt retires in issue order.
-template <int AOFMT, int TILE_H, bool RAW_F32, bool PITCHED = false>
+template <int AOFMT, int TILE_H, bool RAW_F32, bool PITCHED = false, bool LINEAR = false>
 __device__ __forceinline__ void ups_issue_from_raw_loads(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, true, TILE_H> &L,
                                                          int apron_r, int apron_k)
 {
@@ -605,11 +643,11 @@ __device__ __forceinline__ void ups_issue_from_raw_loads(const UpsampleArgs &a, 
         const int cy = clampi(LY0 - 3 + apron_r, 0, lh - 1);
         const uint32_t at = PITCHED ? static_cast<uint32_t>(2 * cy) * static_cast<uint32_t>(a.pitch.depth) + static_cast<uint32_t>(HX0 - 8 + 8 * apron_k)
                                     : static_cast<uint32_t>(2 * cy * a.hw + (HX0 - 8 + 8 * apron_k));      // raw texel (2X, 2Y) of LowDepth1 texel (X, Y)
-        L.araw[0] = load_raw_quad<RAW_F32, false>(hi->raw[frame], hi->depth_format, at);
-        L.araw[1] = load_raw_quad<RAW_F32, false>(hi->raw[frame], hi->depth_format, at + 4u);
+        L.araw[0] = load_raw_quad<RAW_F32, false>(hi->raw[frame], stored_format<LINEAR>(hi), at);
+        L.araw[1] = load_raw_quad<RAW_F32, false>(hi->raw[frame], stored_format<LINEAR>(hi), at + 4u);
     }
     __builtin_amdgcn_sched_barrier(0);          // keep the issue order: window, apron, hi-res
-    ups_issue_hoisted_inside<AOFMT, true, TILE_H, RAW_F32, PITCHED>(a, hi, tile, frame, L);      // a from-raw tile lies inside the frame
+    ups_issue_hoisted_inside<AOFMT, true, TILE_H, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L);      // a from-raw tile lies inside the frame
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -631,8 +669,10 @@ struct NoHook {
 // RAW_F32 (FINAL): the caller's depth frames are f32 -- no format switch in the code (the other formats take the generic instance)
 // PITCHED (FINAL): the caller's surfaces are row-pitched -- raw depth rows a.pitch.depth and dst rows a.pitch.dst texels apart
 // (meao_execute_batch_pitched).  Only the addresses of caller memory change; context-owned buffers keep hw.
+// LINEAR (FINAL): the caller's depth frames are linear view-space depth (MEAO_DEPTH_LINEAR_*): f32 with RAW_F32, else f16;
+// HiResDB and the from-raw window are linearize_view of them (hi->zp0 = s).
 template <int AOFMT, bool RTNE, bool FINAL, int DIV, bool NESTED = false, typename Hook = NoHook, int TILE_H = ups_tile_h(FINAL), bool RAW_F32 = true,
-          bool PITCHED = false>
+          bool PITCHED = false, bool LINEAR = false>
 __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem, int tile, int frame, Hook hook = Hook(),
                                               const HiDepthArgs *hi = nullptr)
 {
@@ -683,7 +723,8 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
     // Linearize constants of the final pass's HiResDB (fetched here for the same reason)
     const float zp0 = FINAL ? hi->zp0 : 0.0f, zp1 = FINAL ? hi->zp1 : 0.0f;
     const float sky_depth = (FINAL && hi->reversed_z == 0) ? 1.0f : 0.0f;
-    const int raw_format = (FINAL && !RAW_F32) ? hi->depth_format : MEAO_DEPTH_F32;
+    const int raw_format = LINEAR ? (RAW_F32 ? MEAO_DEPTH_F32 : MEAO_DEPTH_F16) : (FINAL && !RAW_F32) ? hi->depth_format : MEAO_DEPTH_F32;
+    static_assert(!LINEAR || (FINAL && !NESTED), "only the full-resolution pass reads the depth frames");
     static_assert(!PITCHED || (FINAL && !NESTED), "only the full-resolution pass addresses caller memory");
     const int raw_pitch = PITCHED ? a.pitch.depth : hw, dst_pitch = PITCHED ? a.pitch.dst : hw;     // row strides of caller memory
 
@@ -702,7 +743,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
     // full-resolution pass, tile inside the frame: no LowDepth1 read at all (ups_issue_from_raw_loads)
     const bool from_raw = !NESTED && ups_tile_from_raw<FINAL, TILE_H>(a, tile);
     const bool window_first = !NESTED && !from_raw && (MEAO_X_HOT_PATH_ONLY || ups_tile_is_interior<FINAL, TILE_H>(a, tile));
-    if (hoist_ok && !window_first && !from_raw) ups_issue_hoisted<AOFMT, FINAL, TILE_H, false, RAW_F32, PITCHED>(a, hi, tile, frame, L);
+    if (hoist_ok && !window_first && !from_raw) ups_issue_hoisted<AOFMT, FINAL, TILE_H, false, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L);
 
     // ---- PrefetchData (UPS:54-72): raw window = virtual low-res texels
     // [LX0-3, LX0+34] x [LY0-3, LY0+kLowH+2], clamp addressing per texel.
@@ -714,7 +755,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
             int apron_r, apron_k;      // the lane's apron item, computed once: pinned, or the compiler derives it again where it is converted
             UpsApron<TILE_H>::item(min(tid, UpsApron<TILE_H>::kItems - 1), apron_r, apron_k);
             asm volatile("" : "+v"(apron_r), "+v"(apron_k));
-            ups_issue_from_raw_loads<AOFMT, TILE_H, RAW_F32, PITCHED>(a, hi, tile, frame, L, apron_r, apron_k);
+            ups_issue_from_raw_loads<AOFMT, TILE_H, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L, apron_r, apron_k);
             auto &wa = L.wa;
 #pragma unroll
             for (int round = 0; round < kRounds; ++round) {
@@ -744,7 +785,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                 for (int e = 0; e < 4; ++e) {
                     const int c = 4 * k + e - 1;
                     if (c >= 0 && c < T::kRawW) {
-                        const float d = linearize<DIV>(rawv[e], zp0, zp1, sky_depth);        // DS1:40-45, 64-70
+                        const float d = linear01<LINEAR, DIV>(rawv[e], zp0, zp1, sky_depth);   // DS1:40-45, 64-70
                         if (dep_kept(r, c)) dep_at(r, c) = d;
                         s_inv[r * T::kRawPitch + c] = rcp_strict<DIV>(d);                   // UPS:67
                     }
@@ -753,7 +794,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
         }
     } else if (window_first) {
         constexpr int kItems = Loads::kItems, kRounds = Loads::kRounds;
-        if constexpr (!NESTED) ups_issue_interior_loads<AOFMT, FINAL, TILE_H, RAW_F32, PITCHED>(a, hi, tile, frame, L,
+        if constexpr (!NESTED) ups_issue_interior_loads<AOFMT, FINAL, TILE_H, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L,
                                                                                        MEAO_X_HOT_PATH_ONLY || (HX0 + kUpsTileW <= hw && HY0 + kTileH <= hh));
         auto &wd = L.wd;
         auto &wa = L.wa;
@@ -850,7 +891,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
 #pragma unroll
                     for (int f = 0; f < 2; ++f) rawq[2 * pass + f] = hoist_hraw[pass][f];
                 float even[2 * kPasses][2];
-                lane_clean = hi_depth_words<RTNE, DIV, RAW_F32, 2 * kPasses>(rawq, raw_format, zp0, zp1, sky_depth, hd_words, even);
+                lane_clean = hi_depth_words<RTNE, DIV, RAW_F32, 2 * kPasses, LINEAR>(rawq, raw_format, zp0, zp1, sky_depth, hd_words, even);
                 if (from_raw) {
                     // the interior of the LoResDB window: the lane's own even-even texels before the f16 store
                     const int r0 = 3 + (tid >> 4), c = 3 + 2 * (tid & 15);
@@ -1001,7 +1042,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                         float rawd[4];
 #pragma unroll
                         for (int e = 0; e < 4; ++e) rawd[e] = (hx0 + e < hw) ? raw_depth_texel(hi->raw[frame], raw_format, hrow_raw + e) : 0.5f;
-                        redo |= !hi_depth_quad<RTNE, DIV>(rawd, zp0, zp1, sky_depth, hd);
+                        redo |= !hi_depth_quad<RTNE, DIV, LINEAR>(rawd, zp0, zp1, sky_depth, hd);
                     }
                 } else {
                     const float *p = frame_ptr(static_cast<const float *>(a.hi_depth), a.frame_stride, frame) + hrow;
@@ -1109,7 +1150,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                     const size_t at_raw = PITCHED ? static_cast<size_t>(hy) * raw_pitch + hx : at;
                     const size_t at_dst = PITCHED ? static_cast<size_t>(hy) * dst_pitch + hx : at;
                     const float rawv = raw_depth_texel(hi->raw[frame], raw_format, at_raw);
-                    const float hdv = through_f16<RTNE>(linearize<DIV_IEEE>(rawv, zp0, zp1, sky_depth));
+                    const float hdv = through_f16<RTNE>(linear01<LINEAR, DIV_IEEE>(rawv, zp0, zp1, sky_depth));
                     const int cc = ((e + 1) >> 1) + 1, rr = f + 1;                        // as above
                     const int comp = (e & 1) ? (f ? 3 : 0) : (f ? 2 : 1);
                     float gd[4], ga[4];
@@ -1136,17 +1177,17 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
 
 // The (rare) hostile-frame variant of a tile: the same code with IEEE division.
 template <int AOFMT, bool RTNE, bool FINAL, int DIV, typename Hook = NoHook, int TILE_H = ups_tile_h(FINAL), bool RAW_F32 = true,
-          bool PITCHED = false>
+          bool PITCHED = false, bool LINEAR = false>
 __device__ __forceinline__ void upsample_tile_checked(const UpsampleArgs &a, float *smem, int tile, int frame, Hook hook = Hook(),
                                                       const HiDepthArgs *hi = nullptr)
 {
     if constexpr (DIV == DIV_EXACT_RCP) {
         if (frame_is_hostile(a.hostile, a.generation, frame)) {       // wave-uniform, decided per frame
-            upsample_tile<AOFMT, RTNE, FINAL, DIV_IEEE, false, Hook, TILE_H, RAW_F32, PITCHED>(a, smem, tile, frame, hook, hi);
+            upsample_tile<AOFMT, RTNE, FINAL, DIV_IEEE, false, Hook, TILE_H, RAW_F32, PITCHED, LINEAR>(a, smem, tile, frame, hook, hi);
             return;
         }
     }
-    upsample_tile<AOFMT, RTNE, FINAL, DIV, false, Hook, TILE_H, RAW_F32, PITCHED>(a, smem, tile, frame, hook, hi);
+    upsample_tile<AOFMT, RTNE, FINAL, DIV, false, Hook, TILE_H, RAW_F32, PITCHED, LINEAR>(a, smem, tile, frame, hook, hi);
 }
 
 

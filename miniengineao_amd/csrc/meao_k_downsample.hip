@@ -26,6 +26,7 @@ void launch_downsample_t(const DownsampleArgs &a, dim3 grid, hipStream_t s)
 
 hipError_t launch_downsample(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf)
 {
+    if (linear_depth(a.depth_format)) return launch_downsample_linear(a, frames, s, pf);
     if (downsample_pitched(a)) return launch_downsample_pitched(a, frames, s, pf);
     if (pf) return launch_downsample_frames(a, frames, s, pf);
     if (a.rows_per_lane != 1 && a.rows_per_lane != kMipRowsPerLane) return hipErrorInvalidValue;

@@ -209,6 +209,7 @@ hipError_t launch_tile_atlas(const TileAtlasArgs &a, hipStream_t s)
 
 hipError_t launch_linear_depth(const LinearDepthArgs &a, hipStream_t s)
 {
+    if (linear_depth(a.depth_format)) return launch_linear_depth_view(a, s);
     const dim3 grid(static_cast<int>(std::min<int64_t>((a.pixels + kThreads - 1) / kThreads, 256 * 32))), block(kThreads);
     if (a.f16_rtne) linear_depth_kernel<true><<<grid, block, 0, s>>>(a);
     else linear_depth_kernel<false><<<grid, block, 0, s>>>(a);

@@ -69,6 +69,7 @@ static void launch_upsample_t(const UpsampleArgs &a, const HiDepthArgs *hi, dim3
 hipError_t launch_upsample(const UpsampleArgs &a, const HiDepthArgs *hi, int ao_format, int frames, hipStream_t s,
                            const UpsampleArgs *pf, const HiDepthArgs *pf_hi)
 {
+    if (hi && linear_depth(hi->depth_format)) return launch_upsample_final_linear(a, *hi, ao_format, frames, s, pf, pf_hi);
     if (hi && final_pitched(a)) return launch_upsample_final_pitched(a, *hi, ao_format, frames, s, pf, pf_hi);
     if (pf) return launch_upsample_frames(a, hi, ao_format, frames, s, pf, pf_hi);
     const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);

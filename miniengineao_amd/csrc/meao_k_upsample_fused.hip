@@ -39,7 +39,10 @@ __global__ __launch_bounds__(kThreads, 7) void upsample_final_with_next_downsamp
 // and a grid that has a workgroup for every carried tile.  `d` must be tiled for the lean tile: tiles of kLeanW x kLeanRows.
 bool fused_downsample_applicable(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, int frames)
 {
-    return hi.depth_format == MEAO_DEPTH_F32 && d.depth_format == MEAO_DEPTH_F32 && d.vec_ok != 0 && a.tile_h == ups_tile_h(true) &&
+    // (f32 depth: the raw format, or linear view-space depth -- meao_k_linear_fused.hip)
+    const bool f32 = (hi.depth_format == MEAO_DEPTH_F32 && d.depth_format == MEAO_DEPTH_F32) ||
+                     (hi.depth_format == MEAO_DEPTH_LINEAR_F32 && d.depth_format == MEAO_DEPTH_LINEAR_F32);
+    return f32 && d.vec_ok != 0 && a.tile_h == ups_tile_h(true) &&
            d.tiles_x * d.tiles_y <= a.tiles_x * a.tiles_y && d.frames <= frames;
 }
 
@@ -54,6 +57,7 @@ hipError_t launch_upsample_final_with_downsample(const UpsampleArgs &a, const Hi
                                                  const DownsampleArgs *pf_d)
 {
     if (!fused_downsample_applicable(a, hi, d, frames)) return hipErrorInvalidValue;      // the caller asks first
+    if (linear_depth(hi.depth_format)) return launch_upsample_final_with_downsample_linear(a, hi, d, ao_format, frames, s, pf, pf_hi, pf_d);
     if (final_pitched(a) || downsample_pitched(d))
         return launch_upsample_final_with_downsample_pitched(a, hi, d, ao_format, frames, s, pf, pf_hi, pf_d);
     if (pf || pf_hi || pf_d) return launch_upsample_final_with_downsample_frames(a, ao_format, frames, s, pf, pf_hi, pf_d);

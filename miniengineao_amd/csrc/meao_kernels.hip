@@ -68,3 +68,6 @@
 #include "meao_k_pitched.hip"
 #include "meao_k_pitched_frames.hip"
 #include "meao_k_pitched_fused.hip"
+#include "meao_k_linear.hip"
+#include "meao_k_linear_frames.hip"
+#include "meao_k_linear_fused.hip"

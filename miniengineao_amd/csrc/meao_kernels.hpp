@@ -216,6 +216,21 @@ hipError_t launch_upsample_final_pitched_frames(const UpsampleArgs &a, const HiD
 hipError_t launch_upsample_final_with_downsample_pitched(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, int ao_format,
                                                          int frames, hipStream_t s, const UpsampleArgs *pf, const HiDepthArgs *pf_hi,
                                                          const DownsampleArgs *pf_d);
+// Linear view-space depth (MEAO_DEPTH_LINEAR_F32 / _F16; meao_k_linear*.hip): the launchers above hand the passes that read the
+// depth frames over to these.  Linear01 = z * s with s = RN(1 / far_clip) in the zp0 field of DownsampleArgs / HiDepthArgs /
+// LinearDepthArgs (zp1 and reversed_z are not read).  The linear kernels always address the depth and result rows through the
+// pitch fields (a packed side carries its packed row): one instance serves packed and pitched calls.  pf != nullptr selects the
+// per-frame kernels.
+inline bool linear_depth(int depth_format) { return depth_format == MEAO_DEPTH_LINEAR_F32 || depth_format == MEAO_DEPTH_LINEAR_F16; }
+hipError_t launch_downsample_linear(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf);
+hipError_t launch_downsample_linear_frames(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf);
+hipError_t launch_upsample_final_linear(const UpsampleArgs &a, const HiDepthArgs &hi, int ao_format, int frames, hipStream_t s,
+                                        const UpsampleArgs *pf, const HiDepthArgs *pf_hi);
+hipError_t launch_upsample_final_linear_frames(const UpsampleArgs &a, const HiDepthArgs &hi, int ao_format, int frames, hipStream_t s,
+                                               const UpsampleArgs *pf, const HiDepthArgs *pf_hi);
+hipError_t launch_upsample_final_with_downsample_linear(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, int ao_format,
+                                                        int frames, hipStream_t s, const UpsampleArgs *pf, const HiDepthArgs *pf_hi,
+                                                        const DownsampleArgs *pf_d);
 hipError_t launch_tile_atlas(const TileAtlasArgs &a, hipStream_t s);
 // LinearDepth (debug id 1) on demand: dst[i] = f16(Linearize(depth[i])) for one frame (DS1:37-48).
 struct LinearDepthArgs {
@@ -226,6 +241,7 @@ struct LinearDepthArgs {
     float zp0, zp1;
 };
 hipError_t launch_linear_depth(const LinearDepthArgs &a, hipStream_t s);
+hipError_t launch_linear_depth_view(const LinearDepthArgs &a, hipStream_t s);     // the linear formats (meao_k_linear.hip)
 // Debug view (PushDebugBlitCommands): src in `src_format` (meao_format), [slices][sh][sw] -> dst AO W x H.
 struct DebugViewArgs {
     const void *src;

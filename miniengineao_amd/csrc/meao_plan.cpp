@@ -126,6 +126,17 @@ void upsample_constants(int width, int height, const meao_params &p, int low_lev
     out->upsample_tolerance = upsample;
 }
 
+void depth_decode_constants(int depth_format, const float zp[4], const meao_params &p, float out[2])
+{
+    if (depth_format == MEAO_DEPTH_LINEAR_F32 || depth_format == MEAO_DEPTH_LINEAR_F16) {
+        out[0] = 1.0f / p.far_clip;    // s = RN(1 / far_clip): Linear01 = z * s
+        out[1] = 0.0f;
+    } else {
+        out[0] = zp[0];
+        out[1] = zp[1];
+    }
+}
+
 float linearize_out_of_range(const float zp[4], bool reversed_z)
 {
     // Depth[st] out of range loads 0 (Downsample1.compute:39); reversed Z then takes the
@@ -209,7 +220,7 @@ bool describe_buffer(int width, int height, int ao_format, int debug_id, meao_de
 
 uint64_t depth_elem(int depth_format)
 {
-    return (depth_format == MEAO_DEPTH_F32 || depth_format == MEAO_DEPTH_UNORM24) ? 4 : 2;
+    return (depth_format == MEAO_DEPTH_F32 || depth_format == MEAO_DEPTH_UNORM24 || depth_format == MEAO_DEPTH_LINEAR_F32) ? 4 : 2;
 }
 
 void algorithmic_bytes(int width, int height, int num_levels, int hq_levels, int ao_format, int depth_format,

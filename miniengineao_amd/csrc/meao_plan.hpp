@@ -49,6 +49,9 @@ void render_constants(int width, int height, const meao_params &p, int level, bo
                       int sample_set, meao_render_constants *out);
 void upsample_constants(int width, int height, const meao_params &p, int low_level,
                         meao_upsample_constants *out);
+// The two constants the kernels that read depth frames linearize with (the zp0 / zp1 fields of their argument blocks):
+// ZBufferParams.xy for hardware depth, (s, 0) with s = RN(1 / far_clip) for linear view-space depth (MEAO_DEPTH_LINEAR_*).
+void depth_decode_constants(int depth_format, const float zp[4], const meao_params &p, float out[2]);
 // Linearize() of an out-of-range depth load (Downsample1.compute:39-46).
 float linearize_out_of_range(const float zp[4], bool reversed_z);
 bool params_valid(const meao_params &p);
