@@ -112,6 +112,99 @@ def hostile_frame(w, h, seed, cam=synth.DEFAULT_CAMERA, density=0.01, kinds=None
 
 
 
+# ---- the parameter domain (tests/test_abi.py, tests/test_param_domain_gpu.py, tools/fuzz_gpu.py)
+
+# values far outside the inspector ranges of AmbientOcclusion.cs (still valid: any finite value is accepted): overflow and
+# underflow of 10^x, zero and negative thickness / intensity
+FAR_OUTSIDE = {"upsample_tolerance": (-20.0, -40.0, -46.0, 20.0, 39.0), "noise_filter_tolerance": (-46.0, 20.0, 39.0),
+               "blur_tolerance": (-46.0, 3.0, 39.0), "thickness_modifier": (-1.0, 1e-30, 1e30), "intensity": (-1.0, 3.0, 1e30)}
+
+
+def upsample_constants(lib, w=516, h=260, level=1, **fields):
+    """meao_upsample_constants_for with the default parameters and `fields` (meao_params names)."""
+    import ctypes as C
+    from miniengineao_amd import _lib as L
+    p = L.Params()
+    lib.meao_default_params(C.byref(p))
+    for k, v in fields.items():
+        setattr(p, k, v)
+    u = L.UpsampleConstants()
+    assert lib.meao_upsample_constants_for(w, h, C.byref(p), level, C.byref(u)) == 0
+    return u
+
+
+def in_exact_range(lib, **fields):
+    """Whether a context with these parameters divides with the exact v_rcp_f32 sequences under RTZ storage: the range
+    meao_api.cpp exact_rcp_div_applicable accepts for the upsample constants."""
+    u = upsample_constants(lib, **fields)
+    return 2.0 ** -44 <= u.upsample_tolerance <= 2.0 ** 20 and 2.0 ** -30 <= u.noise_filter_strength <= 2.0 ** 50
+
+
+def exact_range_edges(lib):
+    """{edge: (last float32 value inside the exact range, first one outside)}, bisected over float32 values on the library's
+    own constants: upsampleTolerance below and above, noiseFilterTolerance above (at the default upsampleTolerance)."""
+    def edge(field, inside, outside):
+        inside, outside = np.float32(inside), np.float32(outside)
+        assert in_exact_range(lib, **{field: float(inside)}) and not in_exact_range(lib, **{field: float(outside)})
+        while np.nextafter(inside, outside, dtype=np.float32) != outside:
+            mid = np.float32((float(inside) + float(outside)) / 2)
+            if mid in (inside, outside):
+                mid = np.nextafter(inside, outside, dtype=np.float32)
+            if in_exact_range(lib, **{field: float(mid)}):
+                inside = mid
+            else:
+                outside = mid
+        return float(inside), float(outside)
+    return {"upsample_low": ("upsample_tolerance",) + edge("upsample_tolerance", -12.0, -16.0),
+            "upsample_high": ("upsample_tolerance",) + edge("upsample_tolerance", 0.0, 8.0),
+            "noise_high": ("noise_filter_tolerance",) + edge("noise_filter_tolerance", 0.0, 12.0)}
+
+
+# ---- which kernels a child process launches (rocprofv3 kernel trace)
+
+def kernel_trace(tmp_path, script, args=()):
+    """Runs `script` (Python source) as a child under rocprofv3 --kernel-trace.  Returns a Count: launches of kernel template
+    `name` by count["name"]; .names: the trace's kernel names in start order; .short: those of the meao kernels normalised the
+    way tests/kernel_inventory.py names the library's instantiations; .stdout / .stderr of the child."""
+    import csv
+    import glob
+    import os
+    import shutil
+    import subprocess
+    import sys
+
+    import pytest
+    prof = shutil.which("rocprofv3") or ("/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else None)
+    if prof is None:
+        pytest.skip("rocprofv3 is not installed")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = tmp_path / "child.py"
+    src.write_text(script)
+    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([prof, "--kernel-trace", "--output-format", "csv", "-d", str(tmp_path / "kt"), "-o", "kt", "--",
+                        sys.executable, str(src), *args], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    files = glob.glob(str(tmp_path / "kt" / "**" / "*kernel_trace.csv"), recursive=True)
+    assert files, r.stdout[-2000:]
+    rows = []
+    for f in files:
+        with open(f) as fh:
+            rows += [(int(row.get("Start_Timestamp") or 0), row["Kernel_Name"]) for row in csv.DictReader(fh)]
+    names = [n for _, n in sorted(rows, key=lambda t: t[0])]
+
+    class Count(dict):
+        """launches of kernel template `name`, demangled (::name<) or mangled (<len>nameI) in the trace"""
+        def __missing__(self, name):
+            return sum(1 for k in names if "::%s<" % name in k or "%d%sI" % (len(name), name) in k)
+
+        def __repr__(self):
+            return repr(sorted({k[:90] for k in names}))
+    from tests import kernel_inventory
+    count = Count()
+    count.names, count.short, count.stdout, count.stderr = names, kernel_inventory.normalise(names), r.stdout, r.stderr
+    return count
+
+
 def run_against_testhooks(script):
     """Run tests/<script> in its own process against the `testhooks` variant library (-DMEAO_TESTING=1: the only build that exports
     meao_test_*).  The library is built on the spot when it is missing -- a GPU run must never skip these checks silently

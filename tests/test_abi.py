@@ -113,6 +113,38 @@ def test_plan_constants_match_oracle_bitwise(meao_lib, oracle, seed):
         assert (ow.value, oh.value) == oracle.level_dims(w, h, level) == (-(-w // 2 ** level), -(-h // 2 ** level))
 
 
+@pytest.mark.parametrize("field,value", [(f, v) for f, vs in H.FAR_OUTSIDE.items() for v in vs])
+def test_plan_constants_far_outside_the_inspector_ranges_match_oracle_bitwise(meao_lib, oracle, field, value):
+    """Any finite parameter is valid (meao_plan.cpp params_valid, AmbientOcclusion.cs setters do not clamp): constants that
+    overflow to inf, underflow to 0 or turn NaN must be the oracle's bit for bit too."""
+    for w, h in ((516, 260), (1920, 1080)):
+        s = H.settings(oracle, w, h, **{field: value})
+        p = _params(meao_lib, s)
+        for level in (1, 2, 3, 4):
+            for tiled, want in ((1, oracle.render_constants(s, level)), (0, oracle.render_constants_hq(s, level))):
+                b = L.RenderConstants()
+                assert meao_lib.meao_render_constants_variant(w, h, C.byref(p), level, tiled, s.sample_set, C.byref(b)) == 0
+                assert bytes(want) == bytes(b), (w, h, level, tiled)
+            a, b = oracle.upsample_constants(s, level), L.UpsampleConstants()
+            assert meao_lib.meao_upsample_constants_for(w, h, C.byref(p), level, C.byref(b)) == 0
+            assert bytes(a) == bytes(b), (w, h, level)
+
+
+def test_exact_division_range_edges(meao_lib):
+    """The float32 edges of the parameter range the exact division sequences take (tests/test_param_domain_gpu.py runs both
+    sides of each on the GPU)."""
+    edges = H.exact_range_edges(meao_lib)
+    f = np.float32
+    assert (f(edges["upsample_low"][1]), f(edges["upsample_low"][2])) == (f(-13.245319), f(-13.24532))
+    assert (f(edges["upsample_high"][1]), f(edges["upsample_high"][2])) == (f(6.0206), f(6.0206003))
+    assert (f(edges["noise_high"][1]), f(edges["noise_high"][2])) == (f(9.030899), f(9.0309))
+    for field, inside, outside in edges.values():
+        u_in, u_out = H.upsample_constants(meao_lib, **{field: inside}), H.upsample_constants(meao_lib, **{field: outside})
+        assert H.in_exact_range(meao_lib, **{field: inside}) and not H.in_exact_range(meao_lib, **{field: outside})
+        assert np.nextafter(f(inside), f(outside), dtype=np.float32) == f(outside)
+        assert (u_in.upsample_tolerance, u_in.noise_filter_strength) != (u_out.upsample_tolerance, u_out.noise_filter_strength)
+
+
 def test_buffer_table(meao_lib, oracle):
     """The 17 debug-visible buffers of AO.cs:453-475 / 789-808: dims, format, slices."""
     cfg = L.Config()

@@ -382,42 +382,8 @@ ao.close()
 """
 
 
-def kernel_trace(tmp_path, script):
-    import csv
-    import glob
-    import os
-    import shutil
-    import subprocess
-    import sys
-    prof = shutil.which("rocprofv3") or ("/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else None)
-    if prof is None:
-        pytest.skip("rocprofv3 is not installed")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = tmp_path / "child.py"
-    src.write_text(script)
-    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run([prof, "--kernel-trace", "--output-format", "csv", "-d", str(tmp_path / "kt"), "-o", "kt", "--",
-                        sys.executable, str(src)], cwd=root, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    files = glob.glob(str(tmp_path / "kt" / "**" / "*kernel_trace.csv"), recursive=True)
-    assert files, r.stdout[-2000:]
-    names = []
-    for f in files:
-        with open(f) as fh:
-            names += [row["Kernel_Name"] for row in csv.DictReader(fh)]
-
-    class Count(dict):
-        """launches of kernel template `name`, demangled (::name<) or mangled (<len>nameI) in the trace"""
-        def __missing__(self, name):
-            return sum(1 for k in names if "::%s<" % name in k or "%d%sI" % (len(name), name) in k)
-
-        def __repr__(self):
-            return repr(sorted({k[:90] for k in names}))
-    return Count()
-
-
 def test_per_frame_calls_reach_every_launch_structure(tmp_path):
-    k = kernel_trace(tmp_path, TRACE_STRUCTURES)
+    k = H.kernel_trace(tmp_path, TRACE_STRUCTURES)
     for name in ("downsample_frames_kernel", "render_frames_kernel", "render_small_frames_kernel", "render_wide_frames_kernel",
                  "upsample_frames_kernel", "upsample_blend_tall_frames_kernel", "upsample_two_level_frames_kernel",
                  "upsample_three_level_frames_kernel", "upsample_final_frames_kernel", "upsample_final_small_frames_kernel"):
@@ -429,7 +395,7 @@ def test_per_frame_calls_reach_every_launch_structure(tmp_path):
 
 
 def test_pipelined_per_frame_stream_kernels(tmp_path):
-    k = kernel_trace(tmp_path, TRACE_PIPELINED)
+    k = H.kernel_trace(tmp_path, TRACE_PIPELINED)
     # step 0: own downsample + fused last kernel carrying batch 1; step 1: batch 1's pass reused + fused kernel carrying batch 2;
     # step 2: announced with another near plane -> its pass re-runs, plain last kernel
     assert k["upsample_final_with_next_downsample_frames_kernel"] == 2, k

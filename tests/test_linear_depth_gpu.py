@@ -26,12 +26,11 @@ PASS_DOWNSAMPLE = 0
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="session")
-def linearize_c(tmp_path_factory):
+def build_linearize(directory):
     """Linearize exactly as the oracle evaluates it (fmaf of the C library: exact whatever the compiler flags)."""
-    d = tmp_path_factory.mktemp("lin")
-    src, lib = d / "lin.c", d / "liblin.so"
-    src.write_text(r"""
+    src, lib = os.path.join(directory, "lin.c"), os.path.join(directory, "liblin.so")
+    with open(src, "w") as f:
+        f.write(r"""
 #include <math.h>
 #include <stddef.h>
 void linearize(const float *d, float *out, size_t n, float zp0, float zp1, float sky)
@@ -39,10 +38,15 @@ void linearize(const float *d, float *out, size_t n, float zp0, float zp1, float
     for (size_t i = 0; i < n; i++) out[i] = d[i] == sky ? 1e5f : 1.0f / fmaf(zp0, d[i], zp1);
 }
 """)
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", str(src), "-o", str(lib), "-lm"], check=True)
-    so = C.CDLL(str(lib))
+    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", lib, "-lm"], check=True)
+    so = C.CDLL(lib)
     so.linearize.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_float]
     return so
+
+
+@pytest.fixture(scope="session")
+def linearize_c(tmp_path_factory):
+    return build_linearize(str(tmp_path_factory.mktemp("lin")))
 
 
 def to_linear(lin_c, d, cam, far=None):

@@ -1,10 +1,12 @@
 """Long randomized GPU-vs-oracle sweep (not part of the default suite; run on demand):
     python tools/fuzz_gpu.py [count] [seed0]
-Emphasises the vector fast paths (widths that are multiples of 4 / 8 / 64) and tile-edge cases."""
+Emphasises the vector fast paths (widths that are multiples of 4 / 8 / 64) and tile-edge cases; a quarter of the cases draw
+their upsample or noise-filter tolerance outside the exact-division range (the IEEE-division column of RTZ contexts)."""
 import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 from miniengineao_amd import synth  # noqa: E402
@@ -13,6 +15,8 @@ from tests import helpers as H  # noqa: E402
 
 count = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 5000
+from miniengineao_amd import _lib, codehash  # noqa: E402
+print("library", os.path.relpath(_lib.LIB_PATH, ROOT), "device code sha256", codehash.device_code_sha256(_lib.LIB_PATH), flush=True)
 bad = 0
 for k in range(count):
     rng = np.random.default_rng(seed0 + k)
@@ -34,6 +38,14 @@ for k in range(count):
                    blur_tolerance=float(rng.uniform(-8, -1)), upsample_tolerance=float(rng.uniform(-12, -1)),
                    thickness_modifier=float(rng.uniform(1, 10)), intensity=float(rng.uniform(0, 2)),
                    depth_format=depth_format)
+    if k % 8 in (1, 6):     # a quarter of the cases: tolerances outside the exact-division range (RTZ contexts run DIV = 1)
+        which = int(rng.integers(0, 3))
+        if which == 0:
+            s.upsample_tolerance = float(rng.uniform(-46, -13.25))
+        elif which == 1:
+            s.upsample_tolerance = float(rng.uniform(6.03, 40))
+        else:
+            s.noise_filter_tolerance = float(rng.uniform(9.04, 40))
     if k % 2:
         s.hq_levels, s.sample_set = int(rng.integers(0, s.num_levels + 1)), int(rng.integers(0, 2))
         s.single_pass_stereo = bool(rng.integers(0, 2))
@@ -48,7 +60,7 @@ for k in range(count):
         raw = np.where(mask, bad_px, raw).astype(np.float32)
     depth = O.encode_depth(raw, depth_format) if not hostile else raw
     want = O.run(depth, s, nthreads=8)
-    same = (lambda a, b: H.nan_aware_equal(a, b)[0]) if hostile else np.array_equal
+    same = (lambda a, b: H.nan_aware_equal(a, b)[0]) if hostile or k % 8 in (1, 6) else np.array_equal
     from miniengineao_amd import AmbientOcclusion
     ao = AmbientOcclusion(w, h, num_levels=s.num_levels, ao_format=s.ao_format, f16_rounding=s.f16_rounding,
                           depth_format=depth_format, near_clip=s.near_clip, far_clip=s.far_clip,
