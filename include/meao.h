@@ -278,7 +278,9 @@ MEAO_API int32_t meao_prefetch_batch(meao_ctx *ctx, int32_t n, const void *const
  * its frame's constants from a context-owned table filled by one copy on `stream`.  The tables form a ring of 8 slots
  * (meao_create allocates it: 8 x max_batch x ~6 KB of device memory and as much pinned host memory): a per-frame call made
  * while the per-frame call 8 calls before it has not yet completed on the device waits for that call first (back-pressure;
- * a host that stays fewer than 8 per-frame calls ahead of the device never waits). */
+ * a host that stays fewer than 8 per-frame calls ahead of the device never waits).  "A per-frame call" is every call that reads
+ * its constants from such a table: one given params[], and also a meao_execute_batch that carries an announcement made with
+ * params[] (meao_prefetch_batch_params). */
 MEAO_API int32_t meao_execute_batch_params(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc,
                                            void *const *ao_out, int32_t out_loc, const meao_params *params,
                                            meao_stream stream);
@@ -359,7 +361,9 @@ MEAO_API int32_t meao_composite(meao_ctx *ctx, int32_t mode, const void *ao, voi
  * by an earlier meao_execute*; same formats and modes as meao_composite); the NEXT meao_execute* on
  * this context carries it inside its render kernel (every render workgroup first streams its share of
  * the texel pairs), on that call's stream, i.e. ordered behind the kernels that wrote ao[f] when the
- * same stream is used.  Results are identical to meao_composite.  One batch can wait at a time: a
+ * same stream is used.  (A per-frame call -- see meao_execute_batch_params -- and a context with MEAO_SAMPLES_EXHAUSTIVE carry
+ * nothing in their render kernels: they run the waiting batch first, as plain launches on the call's stream.)
+ * Results are identical to meao_composite.  One batch can wait at a time: a
  * second enqueue, meao_resize and meao_composite_flush run the waiting batch as plain composite
  * launches, on the stream of the execute that preceded its enqueue -- i.e. the one that produced
  * ao[f] -- or on the stream given to meao_composite_flush.  meao_destroy DISCARDS a batch that still
@@ -423,7 +427,11 @@ MEAO_API int32_t meao_pool_execute_batch(meao_pool *pool, int32_t n, const void 
 /* meao_prefetch_batch for the pool: announces the n DEVICE depth frames of the call after next, dealt to
  * the members exactly like meao_pool_execute_batch deals them (frame f -> member f mod G), so that each
  * member's next execute carries its share of the next batch's downsample pass.  Create the pool with
- * cfg.pipelined = 1 to keep this call free of allocation. */
+ * cfg.pipelined = 1 to keep this call free of allocation.
+ * "The call after next" is the POOL's.  An announcement replaces the one before it in every member, also in members it deals
+ * no frame to (n < members).  A member that a meao_pool_execute_batch* deals no frame to has been passed by that call: it drops
+ * the announcement and the ready downsample set it may hold, so nothing announced for one pool call is carried or reused by a
+ * later one (that member runs its own downsample pass in its next call). */
 MEAO_API int32_t meao_pool_prefetch_batch(meao_pool *pool, int32_t n, const void *const *depth);
 /* The per-frame forms for the pool: params[f] goes with frame f to member f mod G. */
 MEAO_API int32_t meao_pool_execute_batch_params(meao_pool *pool, int32_t n, const void *const *depth, int32_t depth_loc,

@@ -1108,6 +1108,14 @@ static int pitch_texels(meao_ctx *ctx, uint64_t pitch, uint64_t elem, const char
     return MEAO_OK;
 }
 
+void meao::drop_announcement(meao_ctx *ctx, bool ready_too)
+{
+    if (!ctx) return;
+    ctx->next_n = 0;
+    ctx->next_per_frame = false;
+    if (ready_too) drop_prefetch(ctx);
+}
+
 int meao::execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
                                  int32_t out_loc, meao_stream stream_, bool wait_for_host, const meao_params *params,
                                  uint64_t depth_pitch, uint64_t ao_pitch)

@@ -280,5 +280,10 @@ hipError_t launch_selftest(int which, unsigned long long *count, hipStream_t s);
 int execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
                            int32_t out_loc, meao_stream stream, bool wait_for_host, const meao_params *params = nullptr,
                            uint64_t depth_pitch = 0, uint64_t ao_pitch = 0);
+// meao_api.cpp, for meao_pool.cpp: what a member that is dealt no frame of a pool call does instead of that call.
+// ready_too = false (a pool announcement passed it by): an announcement it still holds is withdrawn, as a newer one would
+// replace it.  ready_too = true (a pool execute passed it by): a ready prefetched set goes as well -- the pool-level "call
+// after next" any of them was made for is over.  Bookkeeping only; costs that member one downsample pass at most.
+void drop_announcement(meao_ctx *ctx, bool ready_too);
 
 }  // namespace meao

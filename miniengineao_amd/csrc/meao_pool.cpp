@@ -432,6 +432,11 @@ static int32_t pool_execute_batch(meao_pool *p, int32_t n, const void *const *de
     if (status != MEAO_OK)
         status = pool_fail(p, status, std::string("meao_pool_execute_batch: member ") + std::to_string(failed) + ": " +
                                           meao_last_error(p->ctx[failed]));
+    // A member that was dealt no frame (n < members) sat this call out, but the pool-level "call after next" of whatever it
+    // still holds has passed: left alone it would carry that announcement in some later call, behind the frames it announced,
+    // and keep a ready set keyed on buffers the host is free to refill by then.  Also when another member failed: the pool
+    // call has passed it all the same, and dropping costs one downsample pass.  (Every worker has handed its context back.)
+    for (int32_t m = n; m < G; ++m) meao::drop_announcement(p->ctx[m], true);
     if (host) {     // the host buffers are the caller's again when the call returns: wait for every member, also one that
                     // failed -- it may have put copies from / to the caller's buffers in flight before it failed
         for (int32_t m = 0; m < G; ++m)
@@ -491,6 +496,8 @@ static int32_t pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *d
         return pool_fail(p, status, std::string("meao_pool_prefetch_batch: member ") + std::to_string(failed) + ": " +
                                         (set_device_failed ? "hipSetDevice(" + std::to_string(p->device[failed]) + ") failed"
                                                            : std::string(meao_last_error(p->ctx[failed]))));
+    // an announcement replaces the one before it in every member, also in those this one deals no frame to
+    for (int32_t m = n; m < G; ++m) meao::drop_announcement(p->ctx[m], false);
     return MEAO_OK;
 }
 

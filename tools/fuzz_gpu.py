@@ -1,5 +1,6 @@
 """Long randomized GPU-vs-oracle sweep (not part of the default suite; run on demand):
     python tools/fuzz_gpu.py [count] [seed0]
+    python tools/fuzz_gpu.py --sequences N [seed0]     N call sequences with fresh seeds, one long-lived context (or pool) each
 Emphasises the vector fast paths (widths that are multiples of 4 / 8 / 64) and tile-edge cases; a quarter of the cases draw
 their upsample or noise-filter tolerance outside the exact-division range (the IEEE-division column of RTZ contexts)."""
 import os
@@ -12,6 +13,50 @@ import numpy as np  # noqa: E402
 from miniengineao_amd import synth  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from tests import helpers as H  # noqa: E402
+
+
+def run_sequences(count, seed0):
+    """The generator and model of tests/call_model.py with fresh seeds, driven by the stepped Driver of
+    tests/test_call_sequences_gpu.py: every case of the suite's stepped and pool modes in turn, both forms of the carried pass."""
+    import tempfile
+    import pytest
+    from miniengineao_amd import _lib as L
+    from tests import call_model as M
+    from tests.test_call_sequences_gpu import Driver
+    from tests.test_linear_depth_gpu import build_linearize
+    O.build()
+    lin_c = build_linearize(tempfile.mkdtemp())
+    cases = [("stepped", n) for n in sorted(M.CASES)] + [("pool_stepped", n) for n in sorted(M.POOL_CASES)]
+    bad = 0
+    for k in range(count):
+        kind, name = cases[k % len(cases)]
+        seed, own_launch = seed0 + k, (k // len(cases)) % 2
+        if kind == "stepped":
+            cfg, prof = M.CASES[name], M.STEPPED
+        else:
+            cfg = M.POOL_CASES[name]
+            prof = M.Profile(pool=cfg["members"], **M.POOL)
+        kw = dict(linear=cfg.get("linear", False), rtz=cfg.get("rtz", True), pipelined=cfg.get("pipelined", True))
+        pal = M.palette(kw["linear"])
+        ops = M.generate(seed, prof, pal, pal[0], **kw)
+        w, h = prof.sizes[0]
+        model = (M.PoolModel(prof.pool, w, h, prof.max_batch, pal[0], **kw) if prof.pool
+                 else M.ContextModel(w, h, prof.max_batch, pal[0], **kw))
+        d = Driver(O, cfg, prof, own_launch, lin_c, stepped=True, seed=seed)
+        try:
+            d.run(ops, model)
+        except (AssertionError, L.MeaoError, pytest.fail.Exception) as e:     # (pytest.raises that did not raise is no AssertionError)
+            bad += 1
+            print("MISMATCH sequence", kind, name, "seed", seed, "own_launch", own_launch, str(e)[:600], flush=True)
+        finally:
+            d.close()
+    print(f"fuzz: {count} sequences, {bad} failing")
+    return bad
+
+
+if "--sequences" in sys.argv:
+    at = sys.argv.index("--sequences")
+    sys.exit(1 if run_sequences(int(sys.argv[at + 1]), int(sys.argv[at + 2]) if len(sys.argv) > at + 2 else 7000) else 0)
 
 count = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 5000
