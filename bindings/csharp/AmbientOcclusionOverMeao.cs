@@ -114,6 +114,18 @@ namespace MiniEngineAO
                                               mode == (int)MeaoCompositeMode.AmbientOnly ? new IntPtr[] { deviceGBuffer0 } : null));
         }
 
+        // The same into row-pitched render targets (meao_composite_enqueue_pitched): pitches in bytes, 0 = tightly packed.
+        public void CompositeWithNextFramePitched(IntPtr deviceAo, ulong aoPitch, IntPtr deviceColorRgba16f, ulong colorPitch,
+                                                  IntPtr deviceGBuffer0, ulong gbuffer0Pitch, bool debug)
+        {
+            int mode = debug ? (int)MeaoCompositeMode.Debug
+                             : (ambientOnly && deviceGBuffer0 != IntPtr.Zero ? (int)MeaoCompositeMode.AmbientOnly
+                                                                             : (int)MeaoCompositeMode.Multiply);
+            Check(Meao.meao_composite_enqueue_pitched(_ctx, mode, 1, new IntPtr[] { deviceAo }, aoPitch, new IntPtr[] { deviceColorRgba16f },
+                                                      colorPitch, mode == (int)MeaoCompositeMode.AmbientOnly ? new IntPtr[] { deviceGBuffer0 } : null,
+                                                      gbuffer0Pitch));
+        }
+
         public void FlushComposite(IntPtr stream)
         {
             Check(Meao.meao_composite_flush(_ctx, stream));

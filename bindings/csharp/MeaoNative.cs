@@ -138,6 +138,8 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_selftest(IntPtr ctx, int which, out ulong mismatches);
         [DllImport(Lib)] public static extern int meao_set_tracing(IntPtr ctx, int enable);
         [DllImport(Lib)] public static extern int meao_composite_enqueue(IntPtr ctx, int mode, int n, IntPtr[] ao, IntPtr[] color_rgba16f, IntPtr[] gbuffer0_rgba8);
+        // row-pitched composite surfaces: pitches in bytes, 0 = tightly packed; gbuffer0_pitch is ignored where gbuffer0 is null
+        [DllImport(Lib)] public static extern int meao_composite_enqueue_pitched(IntPtr ctx, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color_rgba16f, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
         [DllImport(Lib)] public static extern int meao_composite_flush(IntPtr ctx, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_composite_pending(IntPtr ctx, out int out_frames);
 
@@ -156,6 +158,7 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_pool_execute_batch_pitched(IntPtr pool, int n, IntPtr[] depth, ulong depth_pitch, int depth_loc, IntPtr[] ao_out, ulong ao_pitch, int out_loc, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_pool_prefetch_batch_pitched(IntPtr pool, int n, IntPtr[] depth, ulong depth_pitch, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue(IntPtr pool, int mode, int n, IntPtr[] ao, IntPtr[] color_rgba16f, IntPtr[] gbuffer0_rgba8);
+        [DllImport(Lib)] public static extern int meao_pool_composite_enqueue_pitched(IntPtr pool, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color_rgba16f, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
         [DllImport(Lib)] public static extern int meao_pool_composite_flush(IntPtr pool);
         [DllImport(Lib)] public static extern int meao_pool_composite_pending(IntPtr pool, out int out_frames);
         [DllImport(Lib)] public static extern int meao_pool_gather_to_device(IntPtr pool, int n, IntPtr[] ao_src, IntPtr[] dst, int dst_device);
@@ -169,5 +172,6 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_debug_set(IntPtr ctx, int key, int value);   // launch-structure overrides (tests, A/B runs)
         [DllImport(Lib)] public static extern int meao_debug_view(IntPtr ctx, int frame, int debug_id, IntPtr dst, int out_loc, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_composite(IntPtr ctx, int mode, IntPtr ao, IntPtr color_rgba16f, IntPtr gbuffer0_rgba8, int loc, IntPtr stream);
+        [DllImport(Lib)] public static extern int meao_composite_pitched(IntPtr ctx, int mode, IntPtr ao, ulong ao_pitch, IntPtr color_rgba16f, ulong color_pitch, IntPtr gbuffer0_rgba8, ulong gbuffer0_pitch, int loc, IntPtr stream);
     }
 }

@@ -305,8 +305,8 @@ MEAO_API int32_t meao_prefetch_batch_params(meao_ctx *ctx, int32_t n, const void
  * results copied back into the pitched rows; bytes of a surface outside its width x height texels are never read or written.
  * Pipelining: a prefetched downsample is reused only by a call with the same pointers, the same depth pitch (0 and the packed
  * row count as the same) and the near / far / reversed_z rule of meao_prefetch_batch_params.  Debug ids 1 and 17
- * (meao_get_intermediate, meao_debug_view) honour the last call's pitches.  meao_composite* and meao_pool_gather_to_device take
- * tightly packed surfaces only. */
+ * (meao_get_intermediate, meao_debug_view) honour the last call's pitches.  The composite has pitched forms of its own
+ * (meao_composite_pitched); meao_pool_gather_to_device takes tightly packed surfaces only. */
 MEAO_API int32_t meao_execute_batch_pitched(meao_ctx *ctx, int32_t n, const void *const *depth, uint64_t depth_pitch, int32_t depth_loc,
                                             void *const *ao_out, uint64_t ao_pitch, int32_t out_loc, const meao_params *params,
                                             meao_stream stream);
@@ -377,6 +377,34 @@ MEAO_API int32_t meao_composite_flush(meao_ctx *ctx, meao_stream stream);
  * (0 = nothing waits).  Hosts ask the library instead of mirroring this state (a batch rides only in the members / calls
  * that actually execute; an execute that fails leaves it waiting). */
 MEAO_API int32_t meao_composite_pending(const meao_ctx *ctx, int32_t *out_frames);
+/* The composite into row-pitched surfaces (render targets with a row pitch, a viewport inside a larger target, a cropped tensor):
+ * meao_composite / meao_composite_enqueue with ao_pitch / color_pitch / gbuffer0_pitch, the bytes between the starts of consecutive
+ * rows of the AO, RGBA16F and RGBA8 surfaces; 0 = tightly packed.  One pitch per surface kind per call; the per-frame pointers
+ * give every frame its own origin.  gbuffer0_pitch is ignored where gbuffer0 is NULL.  Pitches of 0 or of the packed row run
+ * exactly the code of meao_composite / meao_composite_enqueue, which are the pitch-0 forms.  (The ABI version is unchanged:
+ * hosts probe for these symbols.)
+ * Validation, before anything is launched or enqueued (a refused enqueue leaves a waiting batch waiting, untouched;
+ * meao_last_error names the argument):
+ *   MEAO_ERR_INVALID_ARGUMENT  a non-zero pitch smaller than width x element size, or not a multiple of the element size
+ *                              (AO: 1 R8 / 2 F16 bytes; colour: 8; GBuffer0: 4);
+ *   MEAO_ERR_UNSUPPORTED       pitch / element size >= 2^24, or (height - 1) x pitch + width x element size > 2^32 - 1
+ *                              (offsets into caller memory are 32-bit byte offsets).
+ * DEVICE surfaces are used in place by the kernels that composite packed surfaces (a kernel-uniform branch, no other kernel, no
+ * pack copy); bytes of a surface outside its width x height texels are never read or written.  A row has ceil(width / 2) texel
+ * pairs (pairs do not run across row ends).  No alignment is required.  The vector form (16-byte colour accesses, two AO texels
+ * per load) runs where the colour base and pitch are multiples of 16 bytes and the AO base and pitch multiples of two AO texels --
+ * for an enqueued batch, where that holds for every frame; otherwise a per-texel scalar form runs, with the same results.
+ * HOST `loc` (meao_composite_pitched only, as for meao_composite) stages the surfaces packed (hipMemcpy2DAsync) and copies the
+ * results back into the pitched rows.  A waiting batch remembers its pitches: carried by the next execute's render kernel, run
+ * by meao_composite_flush, a second enqueue or meao_resize, or flushed first by a per-frame call or an EXHAUSTIVE context, it
+ * composites into the same texels.  The carrying kernel takes the vector-eligible full pairs of a MULTIPLY batch with one
+ * composite frame per render frame into its texel loop, as for packed surfaces. */
+MEAO_API int32_t meao_composite_pitched(meao_ctx *ctx, int32_t mode, const void *ao, uint64_t ao_pitch,
+                                        void *color_rgba16f, uint64_t color_pitch, void *gbuffer0_rgba8, uint64_t gbuffer0_pitch,
+                                        int32_t loc, meao_stream stream);
+MEAO_API int32_t meao_composite_enqueue_pitched(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
+                                                void *const *color_rgba16f, uint64_t color_pitch,
+                                                void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch);
 
 /* Per-pass device timing: when enabled, meao_execute* brackets every pass with HIP events on
  * the launch stream; meao_get_pass_times averages each pass over the executes that ran it since
@@ -448,6 +476,11 @@ MEAO_API int32_t meao_pool_prefetch_batch_pitched(meao_pool *pool, int32_t n, co
  * of frame f rides inside the next execute of the member that owns (and produced) it. */
 MEAO_API int32_t meao_pool_composite_enqueue(meao_pool *pool, int32_t mode, int32_t n, const void *const *ao,
                                              void *const *color_rgba16f, void *const *gbuffer0_rgba8);
+/* meao_composite_enqueue_pitched for the pool: the pitches go to every member, and every member's share is validated before
+ * any member enqueues. */
+MEAO_API int32_t meao_pool_composite_enqueue_pitched(meao_pool *pool, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
+                                                     void *const *color_rgba16f, uint64_t color_pitch,
+                                                     void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch);
 MEAO_API int32_t meao_pool_composite_flush(meao_pool *pool);
 MEAO_API int32_t meao_pool_composite_pending(const meao_pool *pool, int32_t *out_frames);   /* summed over the members */
 /* Copies the n DEVICE results ao_src[f] (on their owning devices) to dst[f] on dst_device with

@@ -159,6 +159,21 @@ public:
         check(meao_composite_enqueue(ctx_, mode, static_cast<int32_t>(deviceAo.size()), deviceAo.data(), deviceColorRgba16f.data(),
                                      deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data()));
     }
+    // The same into row-pitched surfaces (meao_composite_pitched / meao_composite_enqueue_pitched): pitches in bytes, 0 = tightly packed.
+    void CompositePitched(meao_composite_mode mode, const void *deviceAo, uint64_t aoPitch, void *deviceColorRgba16f, uint64_t colorPitch,
+                          void *deviceGBuffer0 = nullptr, uint64_t gbuffer0Pitch = 0, meao_stream stream = nullptr)
+    {
+        check(meao_composite_pitched(ctx_, mode, deviceAo, aoPitch, deviceColorRgba16f, colorPitch, deviceGBuffer0, gbuffer0Pitch,
+                                     MEAO_MEM_DEVICE, stream));
+    }
+    void CompositeWithNextFramePitched(meao_composite_mode mode, const std::vector<const void *> &deviceAo, uint64_t aoPitch,
+                                       const std::vector<void *> &deviceColorRgba16f, uint64_t colorPitch,
+                                       const std::vector<void *> &deviceGBuffer0 = {}, uint64_t gbuffer0Pitch = 0)
+    {
+        check(meao_composite_enqueue_pitched(ctx_, mode, static_cast<int32_t>(deviceAo.size()), deviceAo.data(), aoPitch,
+                                             deviceColorRgba16f.data(), colorPitch, deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(),
+                                             gbuffer0Pitch));
+    }
     void FlushComposite(meao_stream stream = nullptr) { check(meao_composite_flush(ctx_, stream)); }
     bool CompositePending()            // a batch given to CompositeWithNextFrame that no Render* / flush / resize has run yet
     {
@@ -280,6 +295,15 @@ public:
         if (params.size() != nextDeviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
         check(meao_pool_prefetch_batch_params(pool_, static_cast<int32_t>(nextDeviceDepth.size()), nextDeviceDepth.data(),
                                               params.data()));
+    }
+    // the composite of device frames into row-pitched surfaces, carried by the members' next calls (meao_pool_composite_enqueue_pitched)
+    void CompositeWithNextFramePitched(meao_composite_mode mode, const std::vector<const void *> &deviceAo, uint64_t aoPitch,
+                                       const std::vector<void *> &deviceColorRgba16f, uint64_t colorPitch,
+                                       const std::vector<void *> &deviceGBuffer0 = {}, uint64_t gbuffer0Pitch = 0)
+    {
+        check(meao_pool_composite_enqueue_pitched(pool_, mode, static_cast<int32_t>(deviceAo.size()), deviceAo.data(), aoPitch,
+                                                  deviceColorRgba16f.data(), colorPitch,
+                                                  deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(), gbuffer0Pitch));
     }
     // row-pitched device surfaces (meao_pool_execute_batch_pitched); params empty = the members' own parameters
     void RenderDeviceBatchPitched(const std::vector<const void *> &deviceDepth, uint64_t depthPitch, const std::vector<void *> &deviceAo,

@@ -123,6 +123,8 @@ SIGNATURES = {
     "meao_set_tracing": (C.c_int32, [C.c_void_p, C.c_int32]),
     "meao_composite_enqueue": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                            C.POINTER(C.c_void_p)]),
+    "meao_composite_enqueue_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,
+                                                   C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64]),
     "meao_composite_flush": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "meao_composite_pending": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
     "meao_pool_create": (C.c_int32, [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),
@@ -145,6 +147,8 @@ SIGNATURES = {
     "meao_pool_prefetch_batch_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(Params)]),
     "meao_pool_composite_enqueue": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_void_p)]),
+    "meao_pool_composite_enqueue_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,
+                                                        C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64]),
     "meao_pool_composite_flush": (C.c_int32, [C.c_void_p]),
     "meao_pool_composite_pending": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
     "meao_pool_gather_path": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
@@ -155,6 +159,8 @@ SIGNATURES = {
     "meao_debug_set": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
     "meao_debug_view": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "meao_composite": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "meao_composite_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                           C.c_int32, C.c_void_p]),
 }
 
 _lib = None

@@ -234,18 +234,51 @@ class AmbientOcclusion:
         L.check(self._lib.meao_composite(self._ctx, mode, ao.ctypes.data, color_rgba16f.ctypes.data, g,
                                          L.MEM_HOST, None), self._ctx)
 
-    def composite_device(self, mode: int, ao_ptr: int, color_ptr: int, gbuffer0_ptr: int = 0, stream: int = 0) -> None:
-        L.check(self._lib.meao_composite(self._ctx, mode, ao_ptr, color_ptr, gbuffer0_ptr or None, L.MEM_DEVICE,
-                                         C.c_void_p(stream) if stream else None), self._ctx)
+    def composite_device(self, mode: int, ao_ptr: int, color_ptr: int, gbuffer0_ptr: int = 0, stream: int = 0, *,
+                         ao_pitch: int = 0, color_pitch: int = 0, gbuffer0_pitch: int = 0) -> None:
+        """ao_pitch / color_pitch / gbuffer0_pitch: bytes between consecutive rows of the surfaces (meao_composite_pitched);
+        0 = tightly packed."""
+        s = C.c_void_p(stream) if stream else None
+        if ao_pitch or color_pitch or gbuffer0_pitch:
+            L.check(self._lib.meao_composite_pitched(self._ctx, mode, ao_ptr, ao_pitch, color_ptr, color_pitch, gbuffer0_ptr or None,
+                                                     gbuffer0_pitch, L.MEM_DEVICE, s), self._ctx)
+        else:
+            L.check(self._lib.meao_composite(self._ctx, mode, ao_ptr, color_ptr, gbuffer0_ptr or None, L.MEM_DEVICE, s), self._ctx)
 
     def composite_enqueue_device(self, mode: int, ao_ptrs: Sequence[int], color_ptrs: Sequence[int],
-                                 gbuffer0_ptrs: Optional[Sequence[int]] = None) -> None:
+                                 gbuffer0_ptrs: Optional[Sequence[int]] = None, *,
+                                 ao_pitch: int = 0, color_pitch: int = 0, gbuffer0_pitch: int = 0) -> None:
         """Composite of device frames an earlier execute produced; rides inside the NEXT execute's render
-        kernel (meao_composite_enqueue).  composite_flush() runs whatever still waits."""
+        kernel (meao_composite_enqueue).  composite_flush() runs whatever still waits.  ao_pitch / color_pitch / gbuffer0_pitch:
+        row pitches in bytes of every frame's surfaces (meao_composite_enqueue_pitched); 0 = tightly packed."""
         n = len(ao_ptrs)
         g = (C.c_void_p * n)(*gbuffer0_ptrs) if gbuffer0_ptrs else None
-        L.check(self._lib.meao_composite_enqueue(self._ctx, mode, n, (C.c_void_p * n)(*ao_ptrs),
-                                                 (C.c_void_p * n)(*color_ptrs), g), self._ctx)
+        if ao_pitch or color_pitch or gbuffer0_pitch:
+            L.check(self._lib.meao_composite_enqueue_pitched(self._ctx, mode, n, (C.c_void_p * n)(*ao_ptrs), ao_pitch,
+                                                             (C.c_void_p * n)(*color_ptrs), color_pitch, g, gbuffer0_pitch), self._ctx)
+        else:
+            L.check(self._lib.meao_composite_enqueue(self._ctx, mode, n, (C.c_void_p * n)(*ao_ptrs),
+                                                     (C.c_void_p * n)(*color_ptrs), g), self._ctx)
+
+    def composite_tensors(self, ao, color, gbuffer0=None, mode: int = L.COMPOSITE_MULTIPLY, enqueue: bool = False) -> None:
+        """Torch tensors on this context's device, composited in place (meao_composite_pitched / meao_composite_enqueue_pitched).
+        ao: an (N, H, W) tensor or a list of (H, W) in the AO dtype (uint8 for R8, float16 for F16 storage); color: (N, H, W, 4)
+        int16 / float16 holding RGBA16F; gbuffer0: (N, H, W, 4) uint8, for COMPOSITE_AMBIENT_ONLY -- e.g. crops
+        ``target[:, y0:y0 + H, x0:x0 + W, :]`` of larger targets.  The channels of a texel and the texels of a row must be contiguous
+        and all frames of a surface must share one row stride, which becomes its pitch; any other layout raises ValueError
+        (nothing is copied).  enqueue=False: one composite per frame now, on torch.cuda.current_stream(); enqueue=True: the
+        batch waits for the next execute's render kernel (composite_enqueue_device)."""
+        import torch
+        from .surfaces import composite_surfaces
+        ao_dt = torch.uint8 if self._cfg.ao_format == L.AO_R8 else torch.float16
+        dev = torch.device("cuda", self._cfg.device)
+        a, ap, c, cp, g, gp = composite_surfaces(ao, color, gbuffer0, self.height, self.width, ao_dt, device=dev)
+        if enqueue:
+            self.composite_enqueue_device(mode, a, c, g, ao_pitch=ap, color_pitch=cp, gbuffer0_pitch=gp)
+            return
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for f in range(len(a)):
+            self.composite_device(mode, a[f], c[f], g[f] if g else 0, stream, ao_pitch=ap, color_pitch=cp, gbuffer0_pitch=gp)
 
     def composite_flush(self, stream: int = 0) -> None:
         L.check(self._lib.meao_composite_flush(self._ctx, C.c_void_p(stream) if stream else None), self._ctx)
@@ -427,11 +460,29 @@ class AmbientOcclusionPool:
                                                                   params_array(params, n, self._prm)))
 
     def composite_enqueue_device(self, mode: int, ao_ptrs: Sequence[int], color_ptrs: Sequence[int],
-                                 gbuffer0_ptrs: Optional[Sequence[int]] = None) -> None:
+                                 gbuffer0_ptrs: Optional[Sequence[int]] = None, *,
+                                 ao_pitch: int = 0, color_pitch: int = 0, gbuffer0_pitch: int = 0) -> None:
+        """ao_pitch / color_pitch / gbuffer0_pitch: row pitches in bytes of every frame's surfaces
+        (meao_pool_composite_enqueue_pitched); 0 = tightly packed."""
         n = len(ao_ptrs)
         g = (C.c_void_p * n)(*gbuffer0_ptrs) if gbuffer0_ptrs else None
-        self._check(self._lib.meao_pool_composite_enqueue(self._pool, mode, n, (C.c_void_p * n)(*ao_ptrs),
-                                                          (C.c_void_p * n)(*color_ptrs), g))
+        if ao_pitch or color_pitch or gbuffer0_pitch:
+            self._check(self._lib.meao_pool_composite_enqueue_pitched(self._pool, mode, n, (C.c_void_p * n)(*ao_ptrs), ao_pitch,
+                                                                      (C.c_void_p * n)(*color_ptrs), color_pitch, g, gbuffer0_pitch))
+        else:
+            self._check(self._lib.meao_pool_composite_enqueue(self._pool, mode, n, (C.c_void_p * n)(*ao_ptrs),
+                                                              (C.c_void_p * n)(*color_ptrs), g))
+
+    def composite_tensors(self, ao, color, gbuffer0=None, mode: int = L.COMPOSITE_MULTIPLY, enqueue: bool = True) -> None:
+        """AmbientOcclusion.composite_tensors for the pool, frame f resident on device_of_frame(f).  The pool composites only
+        through its members' next calls: enqueue must stay True."""
+        import torch
+        from .surfaces import composite_surfaces
+        if not enqueue:
+            raise ValueError("AmbientOcclusionPool.composite_tensors: the pool has no stand-alone composite (enqueue=True)")
+        ao_dt = torch.uint8 if self._cfg.ao_format == L.AO_R8 else torch.float16
+        a, ap, c, cp, g, gp = composite_surfaces(ao, color, gbuffer0, self._cfg.height, self._cfg.width, ao_dt)
+        self.composite_enqueue_device(mode, a, c, g, ao_pitch=ap, color_pitch=cp, gbuffer0_pitch=gp)
 
     def composite_flush(self) -> None:
         self._check(self._lib.meao_pool_composite_flush(self._pool))

@@ -332,6 +332,7 @@ int flush_pending_composite(meao_ctx *ctx, hipStream_t stream)
         CompositeArgs ca{};
         ca.ao = pc.ao[f]; ca.color = pc.color[f]; ca.gbuffer0 = pc.gbuffer0[f];
         ca.pixels = pc.pixels; ca.mode = pc.mode;
+        ca.pitch = pc.pitch;       // the waiting batch remembers its pitches (meao_composite_enqueue_pitched)
         MEAO_HIP(ctx, launch_composite(ca, ctx->cfg.ao_format, stream));
     }
     return MEAO_OK;
@@ -1501,15 +1502,50 @@ int32_t meao_set_tracing(meao_ctx *ctx, int32_t enable)
     return MEAO_OK;
 }
 
-int32_t meao_composite(meao_ctx *ctx, int32_t mode, const void *ao, void *color_rgba16f, void *gbuffer0_rgba8,
-                       int32_t loc, meao_stream stream_)
+}  // extern "C"
+
+// The pitches of meao_composite*_pitched (bytes, 0 = tightly packed) -> CompositePitches; `fn` names the entry point in the error.
+// on = 0 where every surface is tightly packed: exactly the packed kernels' path.
+static int composite_pitches(meao_ctx *ctx, const char *fn, uint64_t ao_pitch, uint64_t color_pitch, uint64_t gbuffer0_pitch,
+                             bool has_gbuffer0, CompositePitches *out)
+{
+    int32_t ao_row = ctx->cfg.width, color_row = ctx->cfg.width, g_row = ctx->cfg.width;
+    if (ao_pitch != 0 || color_pitch != 0 || (gbuffer0_pitch != 0 && has_gbuffer0)) {       // packed calls have nothing to check
+        // the argument's name is built only where a pitch is given (0 cannot fail)
+        const auto texels = [&](uint64_t pitch, uint64_t elem, const char *which, int32_t *row) {
+            return pitch_texels(ctx, pitch, elem, pitch ? (std::string(fn) + ": " + which).c_str() : "", row);
+        };
+        int rc = texels(ao_pitch, ao_elem(ctx->cfg), "ao_pitch", &ao_row);
+        if (rc == MEAO_OK) rc = texels(color_pitch, 8, "color_pitch", &color_row);
+        if (rc == MEAO_OK && has_gbuffer0) rc = texels(gbuffer0_pitch, 4, "gbuffer0_pitch", &g_row);
+        if (rc != MEAO_OK) return rc;
+    }
+    *out = CompositePitches{};
+    out->ao = static_cast<uint32_t>(ao_row); out->color = static_cast<uint32_t>(color_row); out->gbuffer0 = static_cast<uint32_t>(g_row);
+    out->w = ctx->cfg.width; out->h = ctx->cfg.height;
+    out->on = ao_row != ctx->cfg.width || color_row != ctx->cfg.width || g_row != ctx->cfg.width;
+    out->vec = (color_row & 1) == 0 && (ao_row & 1) == 0;      // colour rows 16 bytes apart, AO rows two texels apart; the bases: composite_vec_base
+    return MEAO_OK;
+}
+
+// The vector form's conditions on a frame's bases: colour a multiple of 16 bytes, AO a multiple of two AO texels.
+static bool composite_vec_base(const meao_ctx *ctx, const void *ao, const void *color)
+{
+    return aligned_to(color, 16) && aligned_to(ao, 2 * ao_elem(ctx->cfg));
+}
+
+static int composite_one(meao_ctx *ctx, const char *fn, int32_t mode, const void *ao, uint64_t ao_pitch, void *color_rgba16f,
+                         uint64_t color_pitch, void *gbuffer0_rgba8, uint64_t gbuffer0_pitch, int32_t loc, meao_stream stream_)
 {
     if (!ctx || !ao || !color_rgba16f) return MEAO_ERR_INVALID_ARGUMENT;
-    if (mode < MEAO_COMPOSITE_MULTIPLY || mode > MEAO_COMPOSITE_DEBUG) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_composite: unknown mode");
+    if (mode < MEAO_COMPOSITE_MULTIPLY || mode > MEAO_COMPOSITE_DEBUG) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": unknown mode");
     if (mode == MEAO_COMPOSITE_AMBIENT_ONLY && !gbuffer0_rgba8)
-        return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_composite: AMBIENT_ONLY needs the GBuffer0 target");
-    if (loc != MEAO_MEM_HOST && loc != MEAO_MEM_DEVICE) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_composite: bad memory location");
-    int rc = use_device(ctx);
+        return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": AMBIENT_ONLY needs the GBuffer0 target");
+    if (loc != MEAO_MEM_HOST && loc != MEAO_MEM_DEVICE) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad memory location");
+    CompositePitches pitch{};
+    int rc = composite_pitches(ctx, fn, ao_pitch, color_pitch, gbuffer0_pitch, gbuffer0_rgba8 != nullptr, &pitch);
+    if (rc != MEAO_OK) return rc;
+    rc = use_device(ctx);
     if (rc != MEAO_OK) return rc;
     hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->own_stream;
     const uint64_t px = static_cast<uint64_t>(ctx->cfg.width) * ctx->cfg.height;
@@ -1518,38 +1554,51 @@ int32_t meao_composite(meao_ctx *ctx, int32_t mode, const void *ao, void *color_
     ca.pixels = static_cast<int64_t>(px);
     ca.mode = mode;
     char *scratch = nullptr;
-    if (loc == MEAO_MEM_HOST) {     // tools / tests: stage through one temporary device buffer
+    if (loc == MEAO_MEM_HOST) {     // tools / tests: stage through one temporary device buffer (packed there, whatever the host pitches)
+        const uint64_t h = static_cast<uint64_t>(ctx->cfg.height);
+        const uint64_t ao_row = ao_bytes / h, color_row = color_bytes / h, g_row = g_bytes / h;
+        const uint64_t ao_src = uint64_t(pitch.ao) * ao_elem(ctx->cfg), color_src = uint64_t(pitch.color) * 8, g_src = uint64_t(pitch.gbuffer0) * 4;
         MEAO_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&scratch), align_up(ao_bytes) + align_up(color_bytes) + g_bytes));
         char *d_ao = scratch, *d_color = scratch + align_up(ao_bytes), *d_g = d_color + align_up(color_bytes);
-        hipError_t e = hipMemcpyAsync(d_ao, ao, ao_bytes, hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_color, color_rgba16f, color_bytes, hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess && gbuffer0_rgba8) e = hipMemcpyAsync(d_g, gbuffer0_rgba8, g_bytes, hipMemcpyHostToDevice, stream);
+        auto copy = [&](void *dst, uint64_t dst_pitch, const void *src, uint64_t src_pitch, uint64_t row, hipMemcpyKind kind) {
+            if (dst_pitch == row && src_pitch == row) return hipMemcpyAsync(dst, src, row * h, kind, stream);      // packed: one copy, as ever
+            return hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, row, h, kind, stream);
+        };
+        hipError_t e = copy(d_ao, ao_row, ao, ao_src, ao_row, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = copy(d_color, color_row, color_rgba16f, color_src, color_row, hipMemcpyHostToDevice);
+        if (e == hipSuccess && gbuffer0_rgba8) e = copy(d_g, g_row, gbuffer0_rgba8, g_src, g_row, hipMemcpyHostToDevice);
         ca.ao = d_ao; ca.color = d_color; ca.gbuffer0 = gbuffer0_rgba8 ? d_g : nullptr;
         if (e == hipSuccess) e = launch_composite(ca, ctx->cfg.ao_format, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(color_rgba16f, d_color, color_bytes, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess && gbuffer0_rgba8) e = hipMemcpyAsync(gbuffer0_rgba8, d_g, g_bytes, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = copy(color_rgba16f, color_src, d_color, color_row, color_row, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && gbuffer0_rgba8) e = copy(gbuffer0_rgba8, g_src, d_g, g_row, g_row, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         (void)hipFree(scratch);
-        if (e != hipSuccess) return fail_hip(ctx, e, "meao_composite (host staging)");
+        if (e != hipSuccess) return fail_hip(ctx, e, (std::string(fn) + " (host staging)").c_str());
         return MEAO_OK;
     }
     ca.ao = ao; ca.color = color_rgba16f; ca.gbuffer0 = gbuffer0_rgba8;
+    ca.pitch = pitch;
+    ca.pitch.vec = pitch.vec && composite_vec_base(ctx, ao, color_rgba16f);
     MEAO_HIP(ctx, launch_composite(ca, ctx->cfg.ao_format, stream));
     return MEAO_OK;
 }
 
-int32_t meao_composite_enqueue(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, void *const *color_rgba16f,
-                               void *const *gbuffer0_rgba8)
+int meao::composite_enqueue_internal(meao_ctx *ctx, const char *fn, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
+                                     void *const *color_rgba16f, uint64_t color_pitch, void *const *gbuffer0_rgba8,
+                                     uint64_t gbuffer0_pitch, bool validate_only)
 {
     if (!ctx || !ao || !color_rgba16f) return MEAO_ERR_INVALID_ARGUMENT;
-    if (mode < MEAO_COMPOSITE_MULTIPLY || mode > MEAO_COMPOSITE_DEBUG) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_composite_enqueue: unknown mode");
-    if (n < 1 || n > MEAO_MAX_BATCH) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_composite_enqueue: n must be 1..MEAO_MAX_BATCH");
+    if (mode < MEAO_COMPOSITE_MULTIPLY || mode > MEAO_COMPOSITE_DEBUG) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": unknown mode");
+    if (n < 1 || n > MEAO_MAX_BATCH) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": n must be 1..MEAO_MAX_BATCH");
     if (mode == MEAO_COMPOSITE_AMBIENT_ONLY && !gbuffer0_rgba8)
-        return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_composite_enqueue: AMBIENT_ONLY needs the GBuffer0 targets");
+        return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": AMBIENT_ONLY needs the GBuffer0 targets");
     for (int f = 0; f < n; ++f)
         if (!ao[f] || !color_rgba16f[f] || (mode == MEAO_COMPOSITE_AMBIENT_ONLY && !gbuffer0_rgba8[f]))
-            return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_composite_enqueue: null frame pointer");
-    int rc = use_device(ctx);
+            return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": null frame pointer");
+    CompositePitches pitch{};
+    int rc = composite_pitches(ctx, fn, ao_pitch, color_pitch, gbuffer0_pitch, gbuffer0_rgba8 != nullptr, &pitch);
+    if (rc != MEAO_OK || validate_only) return rc;     // a refused enqueue leaves a waiting batch waiting, untouched
+    rc = use_device(ctx);
     if (rc != MEAO_OK) return rc;
     if (ctx->pending_comp.frames > 0) {        // one batch can wait at a time: the older one runs now, in order
         rc = flush_pending_composite(ctx, ctx->pending_stream);
@@ -1561,11 +1610,42 @@ int32_t meao_composite_enqueue(meao_ctx *ctx, int32_t mode, int32_t n, const voi
         pc.ao[f] = ao[f];
         pc.color[f] = color_rgba16f[f];
         pc.gbuffer0[f] = gbuffer0_rgba8 ? gbuffer0_rgba8[f] : nullptr;
+        pitch.vec = pitch.vec && composite_vec_base(ctx, ao[f], color_rgba16f[f]);      // one form for the batch
     }
     pc.pixels = static_cast<int64_t>(ctx->cfg.width) * ctx->cfg.height;
     pc.mode = mode;
     pc.frames = n;
+    pc.pitch = pitch;
     return MEAO_OK;
+}
+
+extern "C" {
+
+int32_t meao_composite(meao_ctx *ctx, int32_t mode, const void *ao, void *color_rgba16f, void *gbuffer0_rgba8,
+                       int32_t loc, meao_stream stream_)
+{
+    return composite_one(ctx, "meao_composite", mode, ao, 0, color_rgba16f, 0, gbuffer0_rgba8, 0, loc, stream_);
+}
+
+int32_t meao_composite_pitched(meao_ctx *ctx, int32_t mode, const void *ao, uint64_t ao_pitch, void *color_rgba16f, uint64_t color_pitch,
+                               void *gbuffer0_rgba8, uint64_t gbuffer0_pitch, int32_t loc, meao_stream stream_)
+{
+    return composite_one(ctx, "meao_composite_pitched", mode, ao, ao_pitch, color_rgba16f, color_pitch, gbuffer0_rgba8, gbuffer0_pitch,
+                         loc, stream_);
+}
+
+int32_t meao_composite_enqueue(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, void *const *color_rgba16f,
+                               void *const *gbuffer0_rgba8)
+{
+    return meao::composite_enqueue_internal(ctx, "meao_composite_enqueue", mode, n, ao, 0, color_rgba16f, 0, gbuffer0_rgba8, 0, false);
+}
+
+int32_t meao_composite_enqueue_pitched(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
+                                       void *const *color_rgba16f, uint64_t color_pitch, void *const *gbuffer0_rgba8,
+                                       uint64_t gbuffer0_pitch)
+{
+    return meao::composite_enqueue_internal(ctx, "meao_composite_enqueue_pitched", mode, n, ao, ao_pitch, color_rgba16f, color_pitch,
+                                            gbuffer0_rgba8, gbuffer0_pitch, false);
 }
 
 int32_t meao_composite_pending(const meao_ctx *ctx, int32_t *out_frames)

@@ -123,10 +123,17 @@ template <int AOFMT>
 __global__ __launch_bounds__(kThreads) void composite_kernel(const CompositeArgs a)
 {
     // one lane = 2 texels = one 16-byte colour load/store; consecutive lanes are contiguous
-    const int64_t pairs = (a.pixels + 1) / 2;
-    for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < pairs;
-         q += static_cast<int64_t>(gridDim.x) * kThreads)
-        composite_pair<AOFMT>(a.ao, a.color, a.gbuffer0, a.pixels, a.mode, q);
+    if (__builtin_expect(!a.pitch.on, 1)) {     // tightly packed: laid out first, the kernel's entry falls through into it
+        const int64_t pairs = (a.pixels + 1) / 2;
+        for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < pairs;
+             q += static_cast<int64_t>(gridDim.x) * kThreads)
+            composite_pair<AOFMT>(a.ao, a.color, a.gbuffer0, a.pixels, a.mode, q);
+        return;
+    }
+    // kernel-uniform: row-pitched surfaces, rows dealt to (2^row_lanes_log2 lanes x rows) workgroups
+    const uint32_t lanes = 1u << a.row_lanes_log2, rows = static_cast<uint32_t>(kThreads) >> a.row_lanes_log2;
+    for (uint32_t row = blockIdx.x * rows + (threadIdx.x >> a.row_lanes_log2); row < static_cast<uint32_t>(a.pitch.h); row += gridDim.x * rows)
+        composite_row<AOFMT>(a.ao, a.color, a.gbuffer0, a.pitch, a.mode, row, threadIdx.x & (lanes - 1u), lanes);
 }
 
 // which = 4: rcp_strict, 5: div_const<3>, div_const<9>, 6: div_strict on hashed operand pairs
@@ -230,10 +237,18 @@ hipError_t launch_debug_view(const DebugViewArgs &a, int ao_format, hipStream_t 
     return hipGetLastError();
 }
 
-hipError_t launch_composite(const CompositeArgs &a, int ao_format, hipStream_t s)
+hipError_t launch_composite(const CompositeArgs &args, int ao_format, hipStream_t s)
 {
+    CompositeArgs a = args;
     const int64_t pairs = (a.pixels + 1) / 2;
-    const int blocks = static_cast<int>(std::min<int64_t>((pairs + kThreads - 1) / kThreads, 256 * 32));
+    int blocks = static_cast<int>(std::min<int64_t>((pairs + kThreads - 1) / kThreads, 256 * 32));
+    if (a.pitch.on) {       // the narrowest power of two of lanes that spans a row's pairs (at most the workgroup), rows beside each other
+        const int row_pairs = (a.pitch.w + 1) / 2;
+        a.row_lanes_log2 = 0;
+        while ((1 << a.row_lanes_log2) < row_pairs && (1 << a.row_lanes_log2) < kThreads) ++a.row_lanes_log2;
+        const int rows = kThreads >> a.row_lanes_log2;
+        blocks = std::min((a.pitch.h + rows - 1) / rows, 256 * 32);
+    }
     if (ao_format == MEAO_AO_R8) composite_kernel<MEAO_AO_R8><<<dim3(blocks), dim3(kThreads), 0, s>>>(a);
     else composite_kernel<MEAO_AO_F16><<<dim3(blocks), dim3(kThreads), 0, s>>>(a);
     return hipGetLastError();

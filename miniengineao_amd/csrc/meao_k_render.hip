@@ -81,38 +81,49 @@ __global__ __launch_bounds__(kThreads) void render_wide_kernel(const RenderArgs 
 // carried composite (multiply mode): two pixel pairs per lane in flight under every texel-loop iteration (three: 0.830 vs 0.834 ms, not kept)
 constexpr int kCompositePerIteration = 2;
 constexpr int kCompositePairsInLoop = kCompositePerIteration * (kRenTileH / 8);
+constexpr int kCarriedThreads = ren_tile_w(false) * 4;          // the workgroup of render_with_composite_kernel
 
 // Pass 2 of Blit.shader (dst * src.a) for pixel pairs of ONE frame, as the hook of the render texel loop:
 // begin(k) issues the 16-byte colour and 2/4-byte AO loads of two pairs, end(k) multiplies and stores them.
-// Pair j of a lane is q = (j * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x (a workgroup touches 8 KB
-// of contiguous colour per j); j < kCompositePairsInLoop here, the rest in the plain loop before the tile.
+// Slot j of a lane is pair q = q0 + j * q_step: its colour 16 q bytes from `color`, its AO j * ao_step bytes behind the lane's first
+// AO pair; taken while q < full_pairs (0: the loop takes nothing).  j < kCompositePairsInLoop here, the rest in the plain loop
+// before the tile.
+// Packed: q = (j * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x, the pair index in the frame (a workgroup touches 8 KB of
+// contiguous colour per j), ao_step = q_step pairs of AO, full_pairs = the pairs of the frame with both pixels.
+// Row-pitched (meao_composite_enqueue_pitched; vector-eligible surfaces only, so a colour row is a whole number of 16-byte steps):
+// a row is 2^L chunks of kCarriedThreads pairs and workgroup b of the first G = gridDim.x & ~(2^L - 1) owns chunk b mod 2^L of the
+// rows (b >> L) + j * (G >> L).  `color` and `ao` point at that chunk in its first row, q0 = the lane, q_step = the 16-byte steps
+// and ao_step the bytes from one of its rows to the next, full_pairs = q_step * its rows within the slots; a lane beyond the row's
+// full pairs gets a q0 no slot takes.  So both layouts are the same loop code and the same six words of state (one in a VGPR).
 template <int AOFMT>
 struct CarriedComposite {
     typedef AoTexel<AOFMT> AO;
     const typename AO::type *ao;
     uint16_t *color;
-    uint32_t q0, q_step, full_pairs;          // q0 = pair of j = 0; pairs below full_pairs have both pixels
-    bool active;
+    uint32_t q0, q_step, ao_step, full_pairs;
+    static constexpr uint32_t kNoPair = 0x80000000u;      // as q0: no slot is below full_pairs (q_step < 2^28 where it is set, so nothing wraps)
     uint4v col[kCompositePerIteration];
     typedef typename std::conditional<sizeof(typename AO::type) == 1, uint16_t, uint32_t>::type ao_pair_bits;
     uint32_t ao2[kCompositePerIteration];     // two AO texels, undecoded (taken apart in end(), not next to the load)
     __device__ __forceinline__ uint32_t pair_of(int k, int s) const { return q0 + static_cast<uint32_t>(kCompositePerIteration * k + s) * q_step; }
+    __device__ __forceinline__ uint32_t ao_offset(int k, int s) const
+    {
+        return q0 * static_cast<uint32_t>(sizeof(ao_pair_bits)) + static_cast<uint32_t>(kCompositePerIteration * k + s) * ao_step;
+    }
     __device__ __forceinline__ void begin(int k)
     {
-        if (!active) return;
 #pragma unroll
         for (int s = 0; s < kCompositePerIteration; ++s) {
             const uint32_t q = pair_of(k, s);
             if (q < full_pairs) {
                 col[s] = __builtin_nontemporal_load(reinterpret_cast<const uint4v *>(at_byte_offset(color, q * 16u)));
-                ao2[s] = *reinterpret_cast<const ao_pair_bits *>(at_byte_offset(ao, q * static_cast<uint32_t>(sizeof(ao_pair_bits))));
+                ao2[s] = *reinterpret_cast<const ao_pair_bits *>(at_byte_offset(ao, ao_offset(k, s)));
             }
         }
         __builtin_amdgcn_sched_barrier(0);        // the loads stay here; their first use is behind the texel arithmetic
     }
     __device__ __forceinline__ void end(int k)
     {
-        if (!active) return;
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < kCompositePerIteration; ++s) {
@@ -147,28 +158,72 @@ __global__ __launch_bounds__(ren_tile_w(false) * 4, 8) void render_with_composit
     const bool in_loop = c.mode == MEAO_COMPOSITE_MULTIPLY && c.frames == static_cast<int32_t>(gridDim.y) &&
                          c.pixels < (int64_t(1) << 29);
     CarriedComposite<AOFMT> carried;
-    carried.active = in_loop;
-    if (in_loop) {
-        const int64_t pairs = (c.pixels + 1) / 2;
-        carried.ao = static_cast<const typename AoTexel<AOFMT>::type *>(c.ao[frame]);
-        carried.color = static_cast<uint16_t *>(c.color[frame]);
-        carried.q_step = gridDim.x * blockDim.x;
-        carried.q0 = blockIdx.x * blockDim.x + threadIdx.x;
-        carried.full_pairs = static_cast<uint32_t>(c.pixels / 2);
-        // what the loop does not take: pairs j >= kCompositePairsInLoop of this lane and the half pair of an odd frame
-        for (int64_t q = static_cast<int64_t>(carried.q0) + static_cast<int64_t>(kCompositePairsInLoop) * carried.q_step; q < pairs; q += carried.q_step)
-            composite_pair<AOFMT>(c.ao[frame], c.color[frame], c.gbuffer0[frame], c.pixels, c.mode, q);
-        if (c.pixels & 1) {     // the half pair at the end of an odd frame: the lane that owns it, if the loop would have had it
-            const int64_t last = pairs - 1;
-            if (last % carried.q_step == carried.q0 && last / carried.q_step < kCompositePairsInLoop)
-                composite_pair<AOFMT>(c.ao[frame], c.color[frame], c.gbuffer0[frame], c.pixels, c.mode, last);
+    typedef typename CarriedComposite<AOFMT>::ao_pair_bits ao_pair_bits;
+    carried.ao = static_cast<const typename AoTexel<AOFMT>::type *>(c.ao[frame]);
+    carried.color = static_cast<uint16_t *>(c.color[frame]);
+    carried.q0 = carried.q_step = carried.ao_step = carried.full_pairs = 0;       // the loop takes nothing
+    if (__builtin_expect(!c.pitch.on, 1)) {     // tightly packed: laid out first
+        if (in_loop) {
+            const int64_t pairs = (c.pixels + 1) / 2;
+            carried.q_step = gridDim.x * blockDim.x;
+            carried.ao_step = carried.q_step * static_cast<uint32_t>(sizeof(ao_pair_bits));
+            carried.q0 = blockIdx.x * blockDim.x + threadIdx.x;
+            carried.full_pairs = static_cast<uint32_t>(c.pixels / 2);
+            // what the loop does not take: pairs j >= kCompositePairsInLoop of this lane and the half pair of an odd frame
+            for (int64_t q = static_cast<int64_t>(carried.q0) + static_cast<int64_t>(kCompositePairsInLoop) * carried.q_step; q < pairs; q += carried.q_step)
+                composite_pair<AOFMT>(c.ao[frame], c.color[frame], c.gbuffer0[frame], c.pixels, c.mode, q);
+            if (c.pixels & 1) {     // the half pair at the end of an odd frame: the lane that owns it, if the loop would have had it
+                const int64_t last = pairs - 1;
+                if (last % carried.q_step == carried.q0 && last / carried.q_step < kCompositePairsInLoop)
+                    composite_pair<AOFMT>(c.ao[frame], c.color[frame], c.gbuffer0[frame], c.pixels, c.mode, last);
+            }
+        } else {
+            const int64_t pairs = (c.pixels + 1) / 2, total = pairs * c.frames;
+            const int64_t stride = static_cast<int64_t>(gridDim.x) * gridDim.y * blockDim.x;
+            for (int64_t i = (static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += stride) {
+                const int f = static_cast<int>(i / pairs);
+                composite_pair<AOFMT>(c.ao[f], c.color[f], c.gbuffer0[f], c.pixels, c.mode, i - f * pairs);
+            }
         }
-    } else {
-        const int64_t pairs = (c.pixels + 1) / 2, total = pairs * c.frames;
-        const int64_t stride = static_cast<int64_t>(gridDim.x) * gridDim.y * blockDim.x;
-        for (int64_t i = (static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += stride) {
-            const int f = static_cast<int>(i / pairs);
-            composite_pair<AOFMT>(c.ao[f], c.color[f], c.gbuffer0[f], c.pixels, c.mode, i - f * pairs);
+    } else {                // kernel-uniform: row-pitched surfaces
+        const CompositePitches &p = c.pitch;
+        const uint32_t row_pairs = (static_cast<uint32_t>(p.w) + 1u) / 2u, h = static_cast<uint32_t>(p.h);
+        if (in_loop) {
+            typedef typename AoTexel<AOFMT>::type ao_t;
+            const uint32_t lg = static_cast<uint32_t>(c.chunks_log2), mask = (1u << lg) - 1u;
+            const uint32_t owners = gridDim.x & ~mask;          // at least 2^L (the launcher's choice of L); the others only render
+            if (blockIdx.x < owners) {
+                const uint32_t chunk = blockIdx.x & mask, row0 = blockIdx.x >> lg, row_step = owners >> lg;
+                const uint32_t px0 = chunk * kCarriedThreads + threadIdx.x, row_full = p.vec ? static_cast<uint32_t>(p.w) / 2u : 0u;
+                // what the loop does not take: rows beyond its slots, pairs beyond the 2^L chunks, half pairs, and every pair of a
+                // scalar-form surface
+                uint32_t mine = 0;
+                for (uint32_t row = row0; row < h; row += row_step, ++mine) {
+                    for (uint32_t px = px0; px < row_pairs; px += static_cast<uint32_t>(kCarriedThreads) << lg) {
+                        const bool slot = mine < static_cast<uint32_t>(kCompositePairsInLoop) && px == px0 && px < row_full;
+                        if (!slot) composite_pair<AOFMT>(c.ao[frame], c.color[frame], c.gbuffer0[frame], p, c.mode, row, px);
+                    }
+                }
+                if (row_full != 0) {        // vector-eligible: p.color is even
+                    const uint32_t chunk_pair = chunk * kCarriedThreads;
+                    carried.ao = at_byte_offset(carried.ao, (__umul24(row0, p.ao) + 2u * chunk_pair) * static_cast<uint32_t>(sizeof(ao_t)));
+                    carried.color = at_byte_offset(carried.color, (__umul24(row0, p.color) + 2u * chunk_pair) * 8u);
+                    carried.q0 = px0 < row_full ? threadIdx.x : CarriedComposite<AOFMT>::kNoPair;
+                    // Two rows of a frame are less than 2^32 bytes apart (meao_composite_enqueue_pitched), so with a second row
+                    // q_step < 2^28 and no q wraps, kNoPair's included; the owner of one row never steps, and any q_step from
+                    // the row's full pairs up serves it.  __umul24: row_step <= 32768, the limit of a configuration's extent
+                    // (config_valid), and a pitch is below 2^24 texels.
+                    carried.q_step = mine > 1 ? __umul24(row_step, p.color >> 1) : row_full;
+                    carried.ao_step = __umul24(row_step, p.ao) * static_cast<uint32_t>(sizeof(ao_t));
+                    carried.full_pairs = min(mine, static_cast<uint32_t>(kCompositePairsInLoop)) * carried.q_step;
+                }
+            }
+        } else {
+            const uint32_t units = h * static_cast<uint32_t>(c.frames);        // (frame, row), dealt to all workgroups of the grid
+            for (uint32_t u = blockIdx.y * gridDim.x + blockIdx.x; u < units; u += gridDim.x * gridDim.y) {
+                const uint32_t f = u / h;
+                composite_row<AOFMT>(c.ao[f], c.color[f], c.gbuffer0[f], p, c.mode, u - f * h, threadIdx.x, kCarriedThreads);
+            }
         }
     }
     if constexpr (DIV == DIV_EXACT_RCP) {
@@ -226,12 +281,16 @@ hipError_t launch_render(const RenderArgs &a, int ao_format, int frames, hipStre
 template <int AOFMT, bool RTNE, int DIV>
 static void launch_render_composite_t(const RenderArgs &a, const CompositeBatchArgs &c, dim3 grid, hipStream_t s)
 {
-    render_with_composite_kernel<AOFMT, RTNE, DIV><<<grid, dim3(ren_tile_w(false) * 4), 0, s>>>(a, c);
+    render_with_composite_kernel<AOFMT, RTNE, DIV><<<grid, dim3(kCarriedThreads), 0, s>>>(a, c);
 }
 
-hipError_t launch_render_with_composite(const RenderArgs &a, const CompositeBatchArgs &c, int ao_format, int frames, hipStream_t s)
+hipError_t launch_render_with_composite(const RenderArgs &a, const CompositeBatchArgs &batch, int ao_format, int frames, hipStream_t s)
 {
     if (a.exhaustive) return hipErrorInvalidValue;     // the 68-sample variant keeps its own launch; the caller flushes instead
+    CompositeBatchArgs c = batch;
+    c.chunks_log2 = 0;      // a row as 2^L chunks of a workgroup's lanes: the least L that spans its pairs, at most 3 and 2^L workgroups
+    while ((kCarriedThreads << c.chunks_log2) < (c.pitch.w + 1) / 2 && c.chunks_log2 < 3 && (a.blocks_per_frame >> (c.chunks_log2 + 1)) > 0)
+        ++c.chunks_log2;
     const dim3 grid(a.blocks_per_frame, frames, 1);
     if (ao_format == MEAO_AO_R8) {
         if (a.f16_rtne) launch_render_composite_t<MEAO_AO_R8, true, DIV_IEEE>(a, c, grid, s);
