@@ -32,6 +32,10 @@ namespace MiniEngineAO
         public float thicknessModifier { get { return _thicknessModifier; } set { _thicknessModifier = value; } }
         public float intensity { get { return _intensity; } set { _intensity = value; } }
         public bool ambientOnly { get { return _ambientOnly; } set { _ambientOnly = value; } }
+        // The format of the camera target CompositeWithNextFrameFormat blends into: ARGBHalf (the HDR one, the default), ARGBFloat,
+        // ARGB32 on a camera without HDR, RGB111110Float where the graphics tier selects the packed HDR format.
+        MeaoColorFormat _colorFormat = MeaoColorFormat.Rgba16F;
+        public MeaoColorFormat colorFormat { get { return _colorFormat; } set { _colorFormat = value; } }
 
         // ---- Camera terms the reference read from UnityEngine.Camera ----------------------
         public float nearClipPlane = 0.3f;
@@ -124,6 +128,20 @@ namespace MiniEngineAO
             Check(Meao.meao_composite_enqueue_pitched(_ctx, mode, 1, new IntPtr[] { deviceAo }, aoPitch, new IntPtr[] { deviceColorRgba16f },
                                                       colorPitch, mode == (int)MeaoCompositeMode.AmbientOnly ? new IntPtr[] { deviceGBuffer0 } : null,
                                                       gbuffer0Pitch));
+        }
+
+        // The same into a camera target in `colorFormat` (meao_composite_enqueue_format).  A target that is not RGBA16F does not
+        // ride in the render kernel: the next Render call runs its composite first, as a launch of its own.
+        public void CompositeWithNextFrameFormat(IntPtr deviceAo, ulong aoPitch, IntPtr deviceColor, ulong colorPitch,
+                                                 IntPtr deviceGBuffer0, ulong gbuffer0Pitch, bool debug)
+        {
+            int mode = debug ? (int)MeaoCompositeMode.Debug
+                             : (ambientOnly && deviceGBuffer0 != IntPtr.Zero ? (int)MeaoCompositeMode.AmbientOnly
+                                                                             : (int)MeaoCompositeMode.Multiply);
+            Check(Meao.meao_composite_enqueue_format(_ctx, mode, 1, new IntPtr[] { deviceAo }, aoPitch, new IntPtr[] { deviceColor },
+                                                     (int)_colorFormat, colorPitch,
+                                                     mode == (int)MeaoCompositeMode.AmbientOnly ? new IntPtr[] { deviceGBuffer0 } : null,
+                                                     gbuffer0Pitch));
         }
 
         public void FlushComposite(IntPtr stream)

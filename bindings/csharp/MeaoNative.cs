@@ -23,6 +23,8 @@ namespace MiniEngineAO.Native
     public enum MeaoMem { Host = 0, Device = 1 }
     public enum MeaoDepthFormat { F32 = 0, Unorm16 = 1, Unorm24 = 2, F16 = 3, LinearF32 = 4, LinearF16 = 5 }   // Linear*: view-space z (meao.h)
     public enum MeaoCompositeMode { Multiply = 0, AmbientOnly = 1, Debug = 2 }
+    // meao_color_format: ARGBHalf / ARGBFloat / ARGB32 (BGRA32 alike) / RGB111110Float camera targets
+    public enum MeaoColorFormat { Rgba16F = 0, Rgba32F = 1, Rgba8 = 2, R11G11B10F = 3 }
     public enum MeaoFormat { F32 = 0, F16 = 1, Unorm8 = 2 }
     public enum MeaoSampleSet { Checker = 0, Exhaustive = 1 }
     public enum MeaoPoolOption { SpinUs = 0, BindNuma = 1 }
@@ -140,6 +142,8 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_composite_enqueue(IntPtr ctx, int mode, int n, IntPtr[] ao, IntPtr[] color_rgba16f, IntPtr[] gbuffer0_rgba8);
         // row-pitched composite surfaces: pitches in bytes, 0 = tightly packed; gbuffer0_pitch is ignored where gbuffer0 is null
         [DllImport(Lib)] public static extern int meao_composite_enqueue_pitched(IntPtr ctx, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color_rgba16f, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
+        // the same with the colour target's format (MeaoColorFormat) as an argument
+        [DllImport(Lib)] public static extern int meao_composite_enqueue_format(IntPtr ctx, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
         [DllImport(Lib)] public static extern int meao_composite_flush(IntPtr ctx, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_composite_pending(IntPtr ctx, out int out_frames);
 
@@ -159,6 +163,7 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_pool_prefetch_batch_pitched(IntPtr pool, int n, IntPtr[] depth, ulong depth_pitch, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue(IntPtr pool, int mode, int n, IntPtr[] ao, IntPtr[] color_rgba16f, IntPtr[] gbuffer0_rgba8);
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue_pitched(IntPtr pool, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color_rgba16f, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
+        [DllImport(Lib)] public static extern int meao_pool_composite_enqueue_format(IntPtr pool, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
         [DllImport(Lib)] public static extern int meao_pool_composite_flush(IntPtr pool);
         [DllImport(Lib)] public static extern int meao_pool_composite_pending(IntPtr pool, out int out_frames);
         [DllImport(Lib)] public static extern int meao_pool_gather_to_device(IntPtr pool, int n, IntPtr[] ao_src, IntPtr[] dst, int dst_device);
@@ -173,5 +178,6 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_debug_view(IntPtr ctx, int frame, int debug_id, IntPtr dst, int out_loc, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_composite(IntPtr ctx, int mode, IntPtr ao, IntPtr color_rgba16f, IntPtr gbuffer0_rgba8, int loc, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_composite_pitched(IntPtr ctx, int mode, IntPtr ao, ulong ao_pitch, IntPtr color_rgba16f, ulong color_pitch, IntPtr gbuffer0_rgba8, ulong gbuffer0_pitch, int loc, IntPtr stream);
+        [DllImport(Lib)] public static extern int meao_composite_format(IntPtr ctx, int mode, IntPtr ao, ulong ao_pitch, IntPtr color, int color_format, ulong color_pitch, IntPtr gbuffer0_rgba8, ulong gbuffer0_pitch, int loc, IntPtr stream);
     }
 }

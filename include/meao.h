@@ -406,6 +406,54 @@ MEAO_API int32_t meao_composite_enqueue_pitched(meao_ctx *ctx, int32_t mode, int
                                                 void *const *color_rgba16f, uint64_t color_pitch,
                                                 void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch);
 
+/* The composite into colour targets of other formats.  The reference blends into the camera target whatever its format
+ * (AO.cs:822-839): ARGB32 on a camera without HDR, RGB111110Float where the graphics tier selects the packed HDR format, ARGBHalf
+ * otherwise; torch pipelines hold float32 images. */
+typedef enum meao_color_format {
+    MEAO_COLOR_RGBA16F = 0,     /* 8 bytes per texel; what meao_composite* take today */
+    MEAO_COLOR_RGBA32F = 1,     /* 16 bytes per texel */
+    MEAO_COLOR_RGBA8 = 2,       /* 4 bytes per texel, UNORM, alpha in the top byte: RGBA8 and BGRA8 alike (every mode treats
+                                   r, g, b the same) */
+    MEAO_COLOR_R11G11B10F = 3   /* 4 bytes per texel: R bits 0-10, G 11-21, B 22-31 (DXGI R11G11B10_FLOAT,
+                                   VK B10G11R11_UFLOAT_PACK32, Unity RGB111110Float); no alpha */
+} meao_color_format;
+/* meao_composite_pitched / meao_composite_enqueue_pitched (and, below, meao_pool_composite_enqueue_pitched) with the format of
+ * `color` as an argument; pitch 0 = tightly packed.  With MEAO_COLOR_RGBA16F they run exactly the code of the _pitched calls,
+ * which are the RGBA16F forms.  (The ABI version is unchanged: hosts probe for these symbols.)  sRGB targets are out of scope:
+ * blending in linear light needs a transfer function, and the reference gives no bit-level definition of one.
+ * Canonical reading, as above: operands widened to f32, ONE f32 multiply per channel (f = ao in MULTIPLY, keep = 1 - (1 - ao) in
+ * AMBIENT_ONLY), the result rounded to the target format:
+ *                MULTIPLY                          AMBIENT_ONLY                       DEBUG
+ *   RGBA32F      rgba = rgba * ao, as computed     rgb = rgb * keep, a untouched      rgba = ao
+ *                (a -0 texel stays -0)
+ *   RGBA8        c = unorm8(f32(c) * ao)           rgb = unorm8(f32(c) * keep),       rgba = unorm8(ao)
+ *                per channel                       a untouched
+ *   R11G11B10F   rgb = enc(dec(c) * ao)            rgb = enc(dec(c) * keep)           rgb = enc(ao)
+ * unorm8 / f32 are the conversions of the AO stores and of GBuffer0.a: saturate with NaN -> 0, x 255 and + 0.5 as two roundings,
+ * truncate; code / 255 correctly rounded.  GBuffer0 is RGBA8 in every colour format and touched in AMBIENT_ONLY only.
+ * R11G11B10F channels are unsigned small floats with a 5-bit exponent of bias 15 and M mantissa bits (6 for R and G, 5 for B).
+ *   dec, exact:  e = 0: m * 2^(-14 - M);  0 < e < 31: (1 + m / 2^M) * 2^(e - 15);  e = 31: m = 0 +inf, else NaN.
+ *   enc(x):      NaN of either sign -> e = 31 with every mantissa bit set (0x7FF / 0x3FF); anything with the sign bit set (-0,
+ *                negatives, -inf) -> 0; +inf -> e = 31, m = 0; otherwise round to nearest even with gradual underflow, and a
+ *                value that rounds past the largest finite code (65024 for M = 6, 64512 for M = 5) becomes +inf.
+ * That is the f16 output-merger rule of the RGBA16F stores restated for a format without a sign.  D3D leaves the float11 /
+ * float10 rounding to the implementation: like the f16 stores, this is ONE reading of the blend, the one the tests pin.
+ * Validation is that of the _pitched forms with colour element sizes of 8 / 16 / 4 / 4 bytes; an unknown color_format is
+ * MEAO_ERR_INVALID_ARGUMENT (meao_last_error names the argument), and a tightly packed frame of more than 2^32 - 1 bytes of colour
+ * MEAO_ERR_UNSUPPORTED.  Surfaces are aligned to their own words (RGBA32F and R11G11B10F: 4 bytes), no further.
+ * Where it runs: inside the kernels that composite RGBA16F (a kernel-uniform branch).  Vector form: 16 bytes of colour per lane
+ * (one RGBA32F texel, four RGBA8 / R11G11B10F texels) and their AO in one load, where colour base and pitch are multiples of 16
+ * bytes and AO base and pitch multiples of the AO texels a lane takes (1 / 4); the last width mod 4 texels of a row, and every
+ * surface that is not eligible, run a per-texel scalar form with the same results.  An enqueued batch in a format other than
+ * RGBA16F is never carried by a render kernel: the next meao_execute* runs it first, as plain launches (one per frame) on its
+ * stream -- the rule for per-frame calls and EXHAUSTIVE contexts; flush, second enqueue, resize and destroy are as documented. */
+MEAO_API int32_t meao_composite_format(meao_ctx *ctx, int32_t mode, const void *ao, uint64_t ao_pitch,
+                                       void *color, int32_t color_format, uint64_t color_pitch, void *gbuffer0_rgba8,
+                                       uint64_t gbuffer0_pitch, int32_t loc, meao_stream stream);
+MEAO_API int32_t meao_composite_enqueue_format(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
+                                               void *const *color, int32_t color_format, uint64_t color_pitch,
+                                               void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch);
+
 /* Per-pass device timing: when enabled, meao_execute* brackets every pass with HIP events on
  * the launch stream; meao_get_pass_times averages each pass over the executes that ran it since
  * the last reset (it waits for the stream of the last execute first); *out_samples = executes measured.
@@ -481,6 +529,10 @@ MEAO_API int32_t meao_pool_composite_enqueue(meao_pool *pool, int32_t mode, int3
 MEAO_API int32_t meao_pool_composite_enqueue_pitched(meao_pool *pool, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
                                                      void *const *color_rgba16f, uint64_t color_pitch,
                                                      void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch);
+/* meao_composite_enqueue_format for the pool, dealt and validated as meao_pool_composite_enqueue_pitched. */
+MEAO_API int32_t meao_pool_composite_enqueue_format(meao_pool *pool, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
+                                                    void *const *color, int32_t color_format, uint64_t color_pitch,
+                                                    void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch);
 MEAO_API int32_t meao_pool_composite_flush(meao_pool *pool);
 MEAO_API int32_t meao_pool_composite_pending(const meao_pool *pool, int32_t *out_frames);   /* summed over the members */
 /* Copies the n DEVICE results ao_src[f] (on their owning devices) to dst[f] on dst_device with
@@ -545,7 +597,8 @@ MEAO_API int32_t meao_set_tracing(meao_ctx *ctx, int32_t enable);
  *        3 = f16->f32 (65536), 4 = exact reciprocal vs 1/x (all x, 2^-100<=|x|<=2^100),
  *        (and: the uncorrected v_rcp_f32 within one ulp of it), 5 = exact 3/x and 9/x (same range), 6 = exact a/b on hashed
  *        pairs (2^-60<=|a|,|b|<=2^60), 7 = the UNORM8 bilateral result that skips the correction steps away from rounding
- *        boundaries vs the code of the exact chain, 2^32 hashed operand sets. */
+ *        boundaries vs the code of the exact chain, 2^32 hashed operand sets, 8 = f32->float11 and f32->float10 of the
+ *        R11G11B10F stores (meao_color_format; all 2^32 inputs, both mantissa widths). */
 MEAO_API int32_t meao_selftest(meao_ctx *ctx, int32_t which, uint64_t *out_mismatches);
 
 #ifdef __cplusplus

@@ -34,6 +34,8 @@ public:
     float thicknessModifier = 1.0f;      // Range(1, 10)
     float intensity = 1.0f;              // Range(0, 2)
     bool ambientOnly = true;             // composite-side flag (AO.cs:62-68)
+    // the camera target's format for CompositeFormat / CompositeWithNextFrameFormat; the HDR one (ARGBHalf) by default
+    meao_color_format colorFormat = MEAO_COLOR_RGBA16F;
 
     // ---- camera terms Unity supplied implicitly (AO.cs:563-573) -----------------------------
     float nearClipPlane = 0.3f;
@@ -174,6 +176,21 @@ public:
                                              deviceColorRgba16f.data(), colorPitch, deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(),
                                              gbuffer0Pitch));
     }
+    // The same into colour targets in `colorFormat` (meao_composite_format / meao_composite_enqueue_format): RGBA16F, RGBA32F, RGBA8 or
+    // R11G11B10F.  A batch in another format than RGBA16F does not ride in the render kernel: the next Render* call runs it first.
+    void CompositeFormat(meao_composite_mode mode, const void *deviceAo, uint64_t aoPitch, void *deviceColor, uint64_t colorPitch,
+                         void *deviceGBuffer0 = nullptr, uint64_t gbuffer0Pitch = 0, meao_stream stream = nullptr)
+    {
+        check(meao_composite_format(ctx_, mode, deviceAo, aoPitch, deviceColor, colorFormat, colorPitch, deviceGBuffer0, gbuffer0Pitch,
+                                    MEAO_MEM_DEVICE, stream));
+    }
+    void CompositeWithNextFrameFormat(meao_composite_mode mode, const std::vector<const void *> &deviceAo, uint64_t aoPitch,
+                                      const std::vector<void *> &deviceColor, uint64_t colorPitch,
+                                      const std::vector<void *> &deviceGBuffer0 = {}, uint64_t gbuffer0Pitch = 0)
+    {
+        check(meao_composite_enqueue_format(ctx_, mode, static_cast<int32_t>(deviceAo.size()), deviceAo.data(), aoPitch, deviceColor.data(),
+                                            colorFormat, colorPitch, deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(), gbuffer0Pitch));
+    }
     void FlushComposite(meao_stream stream = nullptr) { check(meao_composite_flush(ctx_, stream)); }
     bool CompositePending()            // a batch given to CompositeWithNextFrame that no Render* / flush / resize has run yet
     {
@@ -304,6 +321,15 @@ public:
         check(meao_pool_composite_enqueue_pitched(pool_, mode, static_cast<int32_t>(deviceAo.size()), deviceAo.data(), aoPitch,
                                                   deviceColorRgba16f.data(), colorPitch,
                                                   deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(), gbuffer0Pitch));
+    }
+    // the same into colour targets of another format (meao_pool_composite_enqueue_format)
+    void CompositeWithNextFrameFormat(meao_composite_mode mode, const std::vector<const void *> &deviceAo, uint64_t aoPitch,
+                                      const std::vector<void *> &deviceColor, meao_color_format colorFormat, uint64_t colorPitch,
+                                      const std::vector<void *> &deviceGBuffer0 = {}, uint64_t gbuffer0Pitch = 0)
+    {
+        check(meao_pool_composite_enqueue_format(pool_, mode, static_cast<int32_t>(deviceAo.size()), deviceAo.data(), aoPitch,
+                                                 deviceColor.data(), colorFormat, colorPitch,
+                                                 deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(), gbuffer0Pitch));
     }
     // row-pitched device surfaces (meao_pool_execute_batch_pitched); params empty = the members' own parameters
     void RenderDeviceBatchPitched(const std::vector<const void *> &deviceDepth, uint64_t depthPitch, const std::vector<void *> &deviceAo,

@@ -38,6 +38,9 @@ MEM_HOST, MEM_DEVICE = 0, 1
 DEPTH_F32, DEPTH_UNORM16, DEPTH_UNORM24, DEPTH_F16 = 0, 1, 2, 3
 DEPTH_LINEAR_F32, DEPTH_LINEAR_F16 = 4, 5      # linear view-space depth z (meao.h: Linear01 = z * RN(1 / far_clip))
 COMPOSITE_MULTIPLY, COMPOSITE_AMBIENT_ONLY, COMPOSITE_DEBUG = 0, 1, 2
+# meao_color_format: the composite's colour target (meao_composite_format); bytes per texel of each
+COLOR_RGBA16F, COLOR_RGBA32F, COLOR_RGBA8, COLOR_R11G11B10F = 0, 1, 2, 3
+COLOR_TEXEL_BYTES = {COLOR_RGBA16F: 8, COLOR_RGBA32F: 16, COLOR_RGBA8: 4, COLOR_R11G11B10F: 4}
 FMT_F32, FMT_F16, FMT_UNORM8 = 0, 1, 2
 SAMPLES_CHECKER, SAMPLES_EXHAUSTIVE = 0, 1
 DEBUG_OCCLUSION_HQ1 = 18
@@ -125,6 +128,8 @@ SIGNATURES = {
                                            C.POINTER(C.c_void_p)]),
     "meao_composite_enqueue_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,
                                                    C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64]),
+    "meao_composite_enqueue_format": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,
+                                                  C.POINTER(C.c_void_p), C.c_int32, C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64]),
     "meao_composite_flush": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "meao_composite_pending": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
     "meao_pool_create": (C.c_int32, [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),
@@ -149,6 +154,8 @@ SIGNATURES = {
                                                 C.POINTER(C.c_void_p)]),
     "meao_pool_composite_enqueue_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,
                                                         C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64]),
+    "meao_pool_composite_enqueue_format": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,
+                                                       C.POINTER(C.c_void_p), C.c_int32, C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64]),
     "meao_pool_composite_flush": (C.c_int32, [C.c_void_p]),
     "meao_pool_composite_pending": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
     "meao_pool_gather_path": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
@@ -161,6 +168,8 @@ SIGNATURES = {
     "meao_composite": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "meao_composite_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                            C.c_int32, C.c_void_p]),
+    "meao_composite_format": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p,
+                                          C.c_uint64, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

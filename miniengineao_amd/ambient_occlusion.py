@@ -217,12 +217,18 @@ class AmbientOcclusion:
         L.check(self._lib.meao_synchronize(self._ctx, C.c_void_p(stream) if stream else None), self._ctx)
 
     # ---- composite (PushCompositeCommands, AO.cs:822-839) ------------------------------
+    # color_format -> (numpy dtype, trailing shape) of a host colour array
+    _HOST_COLOR = {L.COLOR_RGBA16F: (np.uint16, (4,)), L.COLOR_RGBA32F: (np.float32, (4,)), L.COLOR_RGBA8: (np.uint8, (4,)),
+                   L.COLOR_R11G11B10F: (np.uint32, ())}
+
     def composite(self, ao: np.ndarray, color_rgba16f: np.ndarray, gbuffer0_rgba8: Optional[np.ndarray] = None,
-                  debug: bool = False) -> None:
+                  debug: bool = False, color_format: int = L.COLOR_RGBA16F) -> None:
         """Host arrays, in place.  Mode follows the reference: debug view if ``debug`` (AO.cs:826),
         ambient-only into GBuffer0 + the HDR target if ``ambientOnly`` and a GBuffer0 is given
-        (AO.cs:830-834), else the standard multiply (AO.cs:837)."""
-        assert color_rgba16f.dtype == np.uint16 and color_rgba16f.shape == (self.height, self.width, 4)
+        (AO.cs:830-834), else the standard multiply (AO.cs:837).  color_format: the meao_color_format of the colour array --
+        (H, W, 4) uint16 (RGBA16F bits), float32 or uint8, or (H, W) uint32 for R11G11B10F (meao_composite_format)."""
+        dt, tail = self._HOST_COLOR[color_format]
+        assert color_rgba16f.dtype == dt and color_rgba16f.shape == (self.height, self.width) + tail
         assert ao.dtype == self.ao_dtype and ao.shape == (self.height, self.width)
         if debug:
             mode, g = L.COMPOSITE_DEBUG, None
@@ -231,15 +237,22 @@ class AmbientOcclusion:
             mode, g = L.COMPOSITE_AMBIENT_ONLY, gbuffer0_rgba8.ctypes.data
         else:
             mode, g = L.COMPOSITE_MULTIPLY, None
+        if color_format != L.COLOR_RGBA16F:
+            L.check(self._lib.meao_composite_format(self._ctx, mode, ao.ctypes.data, 0, color_rgba16f.ctypes.data, color_format, 0, g, 0,
+                                                    L.MEM_HOST, None), self._ctx)
+            return
         L.check(self._lib.meao_composite(self._ctx, mode, ao.ctypes.data, color_rgba16f.ctypes.data, g,
                                          L.MEM_HOST, None), self._ctx)
 
     def composite_device(self, mode: int, ao_ptr: int, color_ptr: int, gbuffer0_ptr: int = 0, stream: int = 0, *,
-                         ao_pitch: int = 0, color_pitch: int = 0, gbuffer0_pitch: int = 0) -> None:
+                         ao_pitch: int = 0, color_pitch: int = 0, gbuffer0_pitch: int = 0, color_format: int = L.COLOR_RGBA16F) -> None:
         """ao_pitch / color_pitch / gbuffer0_pitch: bytes between consecutive rows of the surfaces (meao_composite_pitched);
-        0 = tightly packed."""
+        0 = tightly packed.  color_format: the meao_color_format of the colour surface (meao_composite_format)."""
         s = C.c_void_p(stream) if stream else None
-        if ao_pitch or color_pitch or gbuffer0_pitch:
+        if color_format != L.COLOR_RGBA16F:
+            L.check(self._lib.meao_composite_format(self._ctx, mode, ao_ptr, ao_pitch, color_ptr, color_format, color_pitch,
+                                                    gbuffer0_ptr or None, gbuffer0_pitch, L.MEM_DEVICE, s), self._ctx)
+        elif ao_pitch or color_pitch or gbuffer0_pitch:
             L.check(self._lib.meao_composite_pitched(self._ctx, mode, ao_ptr, ao_pitch, color_ptr, color_pitch, gbuffer0_ptr or None,
                                                      gbuffer0_pitch, L.MEM_DEVICE, s), self._ctx)
         else:
@@ -247,38 +260,48 @@ class AmbientOcclusion:
 
     def composite_enqueue_device(self, mode: int, ao_ptrs: Sequence[int], color_ptrs: Sequence[int],
                                  gbuffer0_ptrs: Optional[Sequence[int]] = None, *,
-                                 ao_pitch: int = 0, color_pitch: int = 0, gbuffer0_pitch: int = 0) -> None:
+                                 ao_pitch: int = 0, color_pitch: int = 0, gbuffer0_pitch: int = 0,
+                                 color_format: int = L.COLOR_RGBA16F) -> None:
         """Composite of device frames an earlier execute produced; rides inside the NEXT execute's render
         kernel (meao_composite_enqueue).  composite_flush() runs whatever still waits.  ao_pitch / color_pitch / gbuffer0_pitch:
-        row pitches in bytes of every frame's surfaces (meao_composite_enqueue_pitched); 0 = tightly packed."""
+        row pitches in bytes of every frame's surfaces (meao_composite_enqueue_pitched); 0 = tightly packed.  color_format: the
+        meao_color_format of the colour surfaces (meao_composite_enqueue_format); a batch in another format than RGBA16F is run
+        by the next execute as launches of its own, in front of its passes."""
         n = len(ao_ptrs)
         g = (C.c_void_p * n)(*gbuffer0_ptrs) if gbuffer0_ptrs else None
-        if ao_pitch or color_pitch or gbuffer0_pitch:
+        if color_format != L.COLOR_RGBA16F:
+            L.check(self._lib.meao_composite_enqueue_format(self._ctx, mode, n, (C.c_void_p * n)(*ao_ptrs), ao_pitch,
+                                                            (C.c_void_p * n)(*color_ptrs), color_format, color_pitch, g, gbuffer0_pitch),
+                    self._ctx)
+        elif ao_pitch or color_pitch or gbuffer0_pitch:
             L.check(self._lib.meao_composite_enqueue_pitched(self._ctx, mode, n, (C.c_void_p * n)(*ao_ptrs), ao_pitch,
                                                              (C.c_void_p * n)(*color_ptrs), color_pitch, g, gbuffer0_pitch), self._ctx)
         else:
             L.check(self._lib.meao_composite_enqueue(self._ctx, mode, n, (C.c_void_p * n)(*ao_ptrs),
                                                      (C.c_void_p * n)(*color_ptrs), g), self._ctx)
 
-    def composite_tensors(self, ao, color, gbuffer0=None, mode: int = L.COMPOSITE_MULTIPLY, enqueue: bool = False) -> None:
+    def composite_tensors(self, ao, color, gbuffer0=None, mode: int = L.COMPOSITE_MULTIPLY, enqueue: bool = False,
+                          color_format: int = L.COLOR_RGBA16F) -> None:
         """Torch tensors on this context's device, composited in place (meao_composite_pitched / meao_composite_enqueue_pitched).
         ao: an (N, H, W) tensor or a list of (H, W) in the AO dtype (uint8 for R8, float16 for F16 storage); color: (N, H, W, 4)
         int16 / float16 holding RGBA16F; gbuffer0: (N, H, W, 4) uint8, for COMPOSITE_AMBIENT_ONLY -- e.g. crops
         ``target[:, y0:y0 + H, x0:x0 + W, :]`` of larger targets.  The channels of a texel and the texels of a row must be contiguous
         and all frames of a surface must share one row stride, which becomes its pitch; any other layout raises ValueError
         (nothing is copied).  enqueue=False: one composite per frame now, on torch.cuda.current_stream(); enqueue=True: the
-        batch waits for the next execute's render kernel (composite_enqueue_device)."""
+        batch waits for the next execute's render kernel (composite_enqueue_device).  color_format: another meao_color_format
+        for ``color`` -- (N, H, W, 4) float32 for RGBA32F or uint8 for RGBA8, (N, H, W) int32 for R11G11B10F."""
         import torch
         from .surfaces import composite_surfaces
         ao_dt = torch.uint8 if self._cfg.ao_format == L.AO_R8 else torch.float16
         dev = torch.device("cuda", self._cfg.device)
-        a, ap, c, cp, g, gp = composite_surfaces(ao, color, gbuffer0, self.height, self.width, ao_dt, device=dev)
+        a, ap, c, cp, g, gp = composite_surfaces(ao, color, gbuffer0, self.height, self.width, ao_dt, device=dev, color_format=color_format)
         if enqueue:
-            self.composite_enqueue_device(mode, a, c, g, ao_pitch=ap, color_pitch=cp, gbuffer0_pitch=gp)
+            self.composite_enqueue_device(mode, a, c, g, ao_pitch=ap, color_pitch=cp, gbuffer0_pitch=gp, color_format=color_format)
             return
         stream = torch.cuda.current_stream(dev).cuda_stream
         for f in range(len(a)):
-            self.composite_device(mode, a[f], c[f], g[f] if g else 0, stream, ao_pitch=ap, color_pitch=cp, gbuffer0_pitch=gp)
+            self.composite_device(mode, a[f], c[f], g[f] if g else 0, stream, ao_pitch=ap, color_pitch=cp, gbuffer0_pitch=gp,
+                                  color_format=color_format)
 
     def composite_flush(self, stream: int = 0) -> None:
         L.check(self._lib.meao_composite_flush(self._ctx, C.c_void_p(stream) if stream else None), self._ctx)
@@ -461,19 +484,26 @@ class AmbientOcclusionPool:
 
     def composite_enqueue_device(self, mode: int, ao_ptrs: Sequence[int], color_ptrs: Sequence[int],
                                  gbuffer0_ptrs: Optional[Sequence[int]] = None, *,
-                                 ao_pitch: int = 0, color_pitch: int = 0, gbuffer0_pitch: int = 0) -> None:
+                                 ao_pitch: int = 0, color_pitch: int = 0, gbuffer0_pitch: int = 0,
+                                 color_format: int = L.COLOR_RGBA16F) -> None:
         """ao_pitch / color_pitch / gbuffer0_pitch: row pitches in bytes of every frame's surfaces
-        (meao_pool_composite_enqueue_pitched); 0 = tightly packed."""
+        (meao_pool_composite_enqueue_pitched); 0 = tightly packed.  color_format: the meao_color_format of the colour surfaces
+        (meao_pool_composite_enqueue_format)."""
         n = len(ao_ptrs)
         g = (C.c_void_p * n)(*gbuffer0_ptrs) if gbuffer0_ptrs else None
-        if ao_pitch or color_pitch or gbuffer0_pitch:
+        if color_format != L.COLOR_RGBA16F:
+            self._check(self._lib.meao_pool_composite_enqueue_format(self._pool, mode, n, (C.c_void_p * n)(*ao_ptrs), ao_pitch,
+                                                                     (C.c_void_p * n)(*color_ptrs), color_format, color_pitch, g,
+                                                                     gbuffer0_pitch))
+        elif ao_pitch or color_pitch or gbuffer0_pitch:
             self._check(self._lib.meao_pool_composite_enqueue_pitched(self._pool, mode, n, (C.c_void_p * n)(*ao_ptrs), ao_pitch,
                                                                       (C.c_void_p * n)(*color_ptrs), color_pitch, g, gbuffer0_pitch))
         else:
             self._check(self._lib.meao_pool_composite_enqueue(self._pool, mode, n, (C.c_void_p * n)(*ao_ptrs),
                                                               (C.c_void_p * n)(*color_ptrs), g))
 
-    def composite_tensors(self, ao, color, gbuffer0=None, mode: int = L.COMPOSITE_MULTIPLY, enqueue: bool = True) -> None:
+    def composite_tensors(self, ao, color, gbuffer0=None, mode: int = L.COMPOSITE_MULTIPLY, enqueue: bool = True,
+                          color_format: int = L.COLOR_RGBA16F) -> None:
         """AmbientOcclusion.composite_tensors for the pool, frame f resident on device_of_frame(f).  The pool composites only
         through its members' next calls: enqueue must stay True."""
         import torch
@@ -481,8 +511,8 @@ class AmbientOcclusionPool:
         if not enqueue:
             raise ValueError("AmbientOcclusionPool.composite_tensors: the pool has no stand-alone composite (enqueue=True)")
         ao_dt = torch.uint8 if self._cfg.ao_format == L.AO_R8 else torch.float16
-        a, ap, c, cp, g, gp = composite_surfaces(ao, color, gbuffer0, self._cfg.height, self._cfg.width, ao_dt)
-        self.composite_enqueue_device(mode, a, c, g, ao_pitch=ap, color_pitch=cp, gbuffer0_pitch=gp)
+        a, ap, c, cp, g, gp = composite_surfaces(ao, color, gbuffer0, self._cfg.height, self._cfg.width, ao_dt, color_format=color_format)
+        self.composite_enqueue_device(mode, a, c, g, ao_pitch=ap, color_pitch=cp, gbuffer0_pitch=gp, color_format=color_format)
 
     def composite_flush(self) -> None:
         self._check(self._lib.meao_pool_composite_flush(self._pool))

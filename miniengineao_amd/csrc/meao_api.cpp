@@ -91,6 +91,7 @@ struct meao_ctx {
     // a composite batch waiting to ride inside the next execute's render kernel (meao_composite_enqueue),
     // and the stream its AO frames were produced on (where a flush that is not given a stream runs it)
     CompositeBatchArgs pending_comp{};
+    int32_t pending_comp_format = MEAO_COLOR_RGBA16F;     // meao_color_format of its colour surfaces; only an RGBA16F batch is ever carried
     hipStream_t pending_stream = nullptr;
 
 #if MEAO_TESTING
@@ -333,6 +334,7 @@ int flush_pending_composite(meao_ctx *ctx, hipStream_t stream)
         ca.ao = pc.ao[f]; ca.color = pc.color[f]; ca.gbuffer0 = pc.gbuffer0[f];
         ca.pixels = pc.pixels; ca.mode = pc.mode;
         ca.pitch = pc.pitch;       // the waiting batch remembers its pitches (meao_composite_enqueue_pitched)
+        ca.color_format = ctx->pending_comp_format;     // ... and its colour format (meao_composite_enqueue_format)
         MEAO_HIP(ctx, launch_composite(ca, ctx->cfg.ao_format, stream));
     }
     return MEAO_OK;
@@ -380,7 +382,9 @@ struct LaunchList {
 struct BatchShape {           // what the structure of a call depends on
     int frames;
     bool prefetched;          // an earlier call carried this batch's downsample pass
-    bool carry_composite;     // a composite batch waits for a render launch to ride in
+    bool carry_composite;     // a composite batch waits for a render launch to ride in: set for a waiting RGBA16F batch ONLY (the
+                              // carrying kernels read 16-byte RGBA16F pairs); a batch in another meao_color_format is flushed
+                              // before the shape is filled in, and whoever fills in a BatchShape keeps that rule
     int next;                 // 0 = nothing announced; the announced pass 1 = rides in the final kernel, 2 = runs as its own launch
 };
 
@@ -698,12 +702,13 @@ int run_batch(meao_ctx *ctx, int n, const void *const *depth_dev, void *const *o
     ctx->ds_cur = shape.prefetched ? ctx->ready_set : 0;
     ctx->ready_n = 0;
     if (!shape.prefetched) ctx->set_gen[ctx->ds_cur] = next_generation(ctx);      // direct launches take a fresh generation per pass: no flag clearing
-    if (ctx->pending_comp.frames > 0 && (c.sample_set == MEAO_SAMPLES_EXHAUSTIVE || per_frame)) {
-        // the 68-sample render kernel carries nothing, and the per-frame render kernels neither
+    if (ctx->pending_comp.frames > 0 && (c.sample_set == MEAO_SAMPLES_EXHAUSTIVE || per_frame || ctx->pending_comp_format != MEAO_COLOR_RGBA16F)) {
+        // the 68-sample render kernel carries nothing, and the per-frame render kernels neither; the carrying kernel takes
+        // RGBA16F batches only (meao_composite_enqueue_format)
         const int rc = flush_pending_composite(ctx, stream);
         if (rc != MEAO_OK) return rc;
     }
-    shape.carry_composite = ctx->pending_comp.frames > 0;
+    shape.carry_composite = ctx->pending_comp.frames > 0 && ctx->pending_comp_format == MEAO_COLOR_RGBA16F;    // the others were flushed above
 
     const ArgBuilder args{ctx, n, depth_dev, out_dev, ctx->hostile_of(ctx->ds_cur), ctx->set_gen[ctx->ds_cur], &ctx->plan, &ctx->prm, exact,
                           depth_pitch, out_pitch};
@@ -1506,9 +1511,23 @@ int32_t meao_set_tracing(meao_ctx *ctx, int32_t enable)
 
 // The pitches of meao_composite*_pitched (bytes, 0 = tightly packed) -> CompositePitches; `fn` names the entry point in the error.
 // on = 0 where every surface is tightly packed: exactly the packed kernels' path.
-static int composite_pitches(meao_ctx *ctx, const char *fn, uint64_t ao_pitch, uint64_t color_pitch, uint64_t gbuffer0_pitch,
-                             bool has_gbuffer0, CompositePitches *out)
+// Bytes per texel of a meao_color_format, 0 = not one; the texels of it that a lane of the vector form takes (16 bytes of colour).
+static uint64_t color_elem(int32_t color_format)
 {
+    switch (color_format) {
+    case MEAO_COLOR_RGBA16F: return 8;
+    case MEAO_COLOR_RGBA32F: return 16;
+    case MEAO_COLOR_RGBA8: case MEAO_COLOR_R11G11B10F: return 4;
+    default: return 0;
+    }
+}
+static uint32_t color_lane_texels(int32_t color_format) { return static_cast<uint32_t>(16 / color_elem(color_format)); }
+
+static int composite_pitches(meao_ctx *ctx, const char *fn, uint64_t ao_pitch, int32_t color_format, uint64_t color_pitch,
+                             uint64_t gbuffer0_pitch, bool has_gbuffer0, CompositePitches *out)
+{
+    const uint64_t celem = color_elem(color_format);
+    if (celem == 0) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": color_format: not a meao_color_format");
     int32_t ao_row = ctx->cfg.width, color_row = ctx->cfg.width, g_row = ctx->cfg.width;
     if (ao_pitch != 0 || color_pitch != 0 || (gbuffer0_pitch != 0 && has_gbuffer0)) {       // packed calls have nothing to check
         // the argument's name is built only where a pitch is given (0 cannot fail)
@@ -1516,7 +1535,7 @@ static int composite_pitches(meao_ctx *ctx, const char *fn, uint64_t ao_pitch, u
             return pitch_texels(ctx, pitch, elem, pitch ? (std::string(fn) + ": " + which).c_str() : "", row);
         };
         int rc = texels(ao_pitch, ao_elem(ctx->cfg), "ao_pitch", &ao_row);
-        if (rc == MEAO_OK) rc = texels(color_pitch, 8, "color_pitch", &color_row);
+        if (rc == MEAO_OK) rc = texels(color_pitch, celem, "color_pitch", &color_row);
         if (rc == MEAO_OK && has_gbuffer0) rc = texels(gbuffer0_pitch, 4, "gbuffer0_pitch", &g_row);
         if (rc != MEAO_OK) return rc;
     }
@@ -1525,39 +1544,48 @@ static int composite_pitches(meao_ctx *ctx, const char *fn, uint64_t ao_pitch, u
     out->w = ctx->cfg.width; out->h = ctx->cfg.height;
     out->on = ao_row != ctx->cfg.width || color_row != ctx->cfg.width || g_row != ctx->cfg.width;
     out->vec = (color_row & 1) == 0 && (ao_row & 1) == 0;      // colour rows 16 bytes apart, AO rows two texels apart; the bases: composite_vec_base
+    if (color_format != MEAO_COLOR_RGBA16F) {
+        // a packed frame is one row of width x height texels to the kernel, with 32-bit byte offsets like any row
+        if (static_cast<uint64_t>(ctx->cfg.width) * ctx->cfg.height * celem > 0xffffffffull)
+            return fail(ctx, MEAO_ERR_UNSUPPORTED, std::string(fn) + ": color: a frame spans more than 2^32 - 1 bytes");
+        // rows of whole 16-byte colour accesses, each with its AO texels in one aligned load (nothing to ask of a packed frame's rows)
+        out->vec = !out->on || (static_cast<uint64_t>(color_row) * celem % 16 == 0 && static_cast<uint32_t>(ao_row) % color_lane_texels(color_format) == 0);
+    }
     return MEAO_OK;
 }
 
-// The vector form's conditions on a frame's bases: colour a multiple of 16 bytes, AO a multiple of two AO texels.
-static bool composite_vec_base(const meao_ctx *ctx, const void *ao, const void *color)
+// The vector form's conditions on a frame's bases: colour a multiple of 16 bytes, AO a multiple of the AO texels of a lane (two for RGBA16F).
+static bool composite_vec_base(const meao_ctx *ctx, const void *ao, const void *color, int32_t color_format)
 {
-    return aligned_to(color, 16) && aligned_to(ao, 2 * ao_elem(ctx->cfg));
+    return aligned_to(color, 16) && aligned_to(ao, color_lane_texels(color_format) * ao_elem(ctx->cfg));
 }
 
-static int composite_one(meao_ctx *ctx, const char *fn, int32_t mode, const void *ao, uint64_t ao_pitch, void *color_rgba16f,
+static int composite_one(meao_ctx *ctx, const char *fn, int32_t mode, const void *ao, uint64_t ao_pitch, void *color, int32_t color_format,
                          uint64_t color_pitch, void *gbuffer0_rgba8, uint64_t gbuffer0_pitch, int32_t loc, meao_stream stream_)
 {
-    if (!ctx || !ao || !color_rgba16f) return MEAO_ERR_INVALID_ARGUMENT;
+    if (!ctx || !ao || !color) return MEAO_ERR_INVALID_ARGUMENT;
     if (mode < MEAO_COMPOSITE_MULTIPLY || mode > MEAO_COMPOSITE_DEBUG) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": unknown mode");
     if (mode == MEAO_COMPOSITE_AMBIENT_ONLY && !gbuffer0_rgba8)
         return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": AMBIENT_ONLY needs the GBuffer0 target");
     if (loc != MEAO_MEM_HOST && loc != MEAO_MEM_DEVICE) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad memory location");
     CompositePitches pitch{};
-    int rc = composite_pitches(ctx, fn, ao_pitch, color_pitch, gbuffer0_pitch, gbuffer0_rgba8 != nullptr, &pitch);
+    int rc = composite_pitches(ctx, fn, ao_pitch, color_format, color_pitch, gbuffer0_pitch, gbuffer0_rgba8 != nullptr, &pitch);
     if (rc != MEAO_OK) return rc;
     rc = use_device(ctx);
     if (rc != MEAO_OK) return rc;
     hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->own_stream;
     const uint64_t px = static_cast<uint64_t>(ctx->cfg.width) * ctx->cfg.height;
-    const uint64_t ao_bytes = px * ao_elem(ctx->cfg), color_bytes = px * 8, g_bytes = px * 4;
+    const uint64_t celem = color_elem(color_format);
+    const uint64_t ao_bytes = px * ao_elem(ctx->cfg), color_bytes = px * celem, g_bytes = px * 4;
     CompositeArgs ca{};
     ca.pixels = static_cast<int64_t>(px);
     ca.mode = mode;
+    ca.color_format = color_format;
     char *scratch = nullptr;
     if (loc == MEAO_MEM_HOST) {     // tools / tests: stage through one temporary device buffer (packed there, whatever the host pitches)
         const uint64_t h = static_cast<uint64_t>(ctx->cfg.height);
         const uint64_t ao_row = ao_bytes / h, color_row = color_bytes / h, g_row = g_bytes / h;
-        const uint64_t ao_src = uint64_t(pitch.ao) * ao_elem(ctx->cfg), color_src = uint64_t(pitch.color) * 8, g_src = uint64_t(pitch.gbuffer0) * 4;
+        const uint64_t ao_src = uint64_t(pitch.ao) * ao_elem(ctx->cfg), color_src = uint64_t(pitch.color) * celem, g_src = uint64_t(pitch.gbuffer0) * 4;
         MEAO_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&scratch), align_up(ao_bytes) + align_up(color_bytes) + g_bytes));
         char *d_ao = scratch, *d_color = scratch + align_up(ao_bytes), *d_g = d_color + align_up(color_bytes);
         auto copy = [&](void *dst, uint64_t dst_pitch, const void *src, uint64_t src_pitch, uint64_t row, hipMemcpyKind kind) {
@@ -1565,38 +1593,39 @@ static int composite_one(meao_ctx *ctx, const char *fn, int32_t mode, const void
             return hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, row, h, kind, stream);
         };
         hipError_t e = copy(d_ao, ao_row, ao, ao_src, ao_row, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = copy(d_color, color_row, color_rgba16f, color_src, color_row, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = copy(d_color, color_row, color, color_src, color_row, hipMemcpyHostToDevice);
         if (e == hipSuccess && gbuffer0_rgba8) e = copy(d_g, g_row, gbuffer0_rgba8, g_src, g_row, hipMemcpyHostToDevice);
         ca.ao = d_ao; ca.color = d_color; ca.gbuffer0 = gbuffer0_rgba8 ? d_g : nullptr;
+        ca.pitch.vec = 1;       // packed at aligned bases (read by the colour formats other than RGBA16F only)
         if (e == hipSuccess) e = launch_composite(ca, ctx->cfg.ao_format, stream);
-        if (e == hipSuccess) e = copy(color_rgba16f, color_src, d_color, color_row, color_row, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = copy(color, color_src, d_color, color_row, color_row, hipMemcpyDeviceToHost);
         if (e == hipSuccess && gbuffer0_rgba8) e = copy(gbuffer0_rgba8, g_src, d_g, g_row, g_row, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         (void)hipFree(scratch);
         if (e != hipSuccess) return fail_hip(ctx, e, (std::string(fn) + " (host staging)").c_str());
         return MEAO_OK;
     }
-    ca.ao = ao; ca.color = color_rgba16f; ca.gbuffer0 = gbuffer0_rgba8;
+    ca.ao = ao; ca.color = color; ca.gbuffer0 = gbuffer0_rgba8;
     ca.pitch = pitch;
-    ca.pitch.vec = pitch.vec && composite_vec_base(ctx, ao, color_rgba16f);
+    ca.pitch.vec = pitch.vec && composite_vec_base(ctx, ao, color, color_format);
     MEAO_HIP(ctx, launch_composite(ca, ctx->cfg.ao_format, stream));
     return MEAO_OK;
 }
 
 int meao::composite_enqueue_internal(meao_ctx *ctx, const char *fn, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
-                                     void *const *color_rgba16f, uint64_t color_pitch, void *const *gbuffer0_rgba8,
+                                     void *const *color, int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8,
                                      uint64_t gbuffer0_pitch, bool validate_only)
 {
-    if (!ctx || !ao || !color_rgba16f) return MEAO_ERR_INVALID_ARGUMENT;
+    if (!ctx || !ao || !color) return MEAO_ERR_INVALID_ARGUMENT;
     if (mode < MEAO_COMPOSITE_MULTIPLY || mode > MEAO_COMPOSITE_DEBUG) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": unknown mode");
     if (n < 1 || n > MEAO_MAX_BATCH) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": n must be 1..MEAO_MAX_BATCH");
     if (mode == MEAO_COMPOSITE_AMBIENT_ONLY && !gbuffer0_rgba8)
         return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": AMBIENT_ONLY needs the GBuffer0 targets");
     for (int f = 0; f < n; ++f)
-        if (!ao[f] || !color_rgba16f[f] || (mode == MEAO_COMPOSITE_AMBIENT_ONLY && !gbuffer0_rgba8[f]))
+        if (!ao[f] || !color[f] || (mode == MEAO_COMPOSITE_AMBIENT_ONLY && !gbuffer0_rgba8[f]))
             return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": null frame pointer");
     CompositePitches pitch{};
-    int rc = composite_pitches(ctx, fn, ao_pitch, color_pitch, gbuffer0_pitch, gbuffer0_rgba8 != nullptr, &pitch);
+    int rc = composite_pitches(ctx, fn, ao_pitch, color_format, color_pitch, gbuffer0_pitch, gbuffer0_rgba8 != nullptr, &pitch);
     if (rc != MEAO_OK || validate_only) return rc;     // a refused enqueue leaves a waiting batch waiting, untouched
     rc = use_device(ctx);
     if (rc != MEAO_OK) return rc;
@@ -1608,14 +1637,15 @@ int meao::composite_enqueue_internal(meao_ctx *ctx, const char *fn, int32_t mode
     CompositeBatchArgs &pc = ctx->pending_comp;
     for (int f = 0; f < n; ++f) {
         pc.ao[f] = ao[f];
-        pc.color[f] = color_rgba16f[f];
+        pc.color[f] = color[f];
         pc.gbuffer0[f] = gbuffer0_rgba8 ? gbuffer0_rgba8[f] : nullptr;
-        pitch.vec = pitch.vec && composite_vec_base(ctx, ao[f], color_rgba16f[f]);      // one form for the batch
+        pitch.vec = pitch.vec && composite_vec_base(ctx, ao[f], color[f], color_format);      // one form for the batch
     }
     pc.pixels = static_cast<int64_t>(ctx->cfg.width) * ctx->cfg.height;
     pc.mode = mode;
     pc.frames = n;
     pc.pitch = pitch;
+    ctx->pending_comp_format = color_format;
     return MEAO_OK;
 }
 
@@ -1624,27 +1654,42 @@ extern "C" {
 int32_t meao_composite(meao_ctx *ctx, int32_t mode, const void *ao, void *color_rgba16f, void *gbuffer0_rgba8,
                        int32_t loc, meao_stream stream_)
 {
-    return composite_one(ctx, "meao_composite", mode, ao, 0, color_rgba16f, 0, gbuffer0_rgba8, 0, loc, stream_);
+    return composite_one(ctx, "meao_composite", mode, ao, 0, color_rgba16f, MEAO_COLOR_RGBA16F, 0, gbuffer0_rgba8, 0, loc, stream_);
 }
 
 int32_t meao_composite_pitched(meao_ctx *ctx, int32_t mode, const void *ao, uint64_t ao_pitch, void *color_rgba16f, uint64_t color_pitch,
                                void *gbuffer0_rgba8, uint64_t gbuffer0_pitch, int32_t loc, meao_stream stream_)
 {
-    return composite_one(ctx, "meao_composite_pitched", mode, ao, ao_pitch, color_rgba16f, color_pitch, gbuffer0_rgba8, gbuffer0_pitch,
+    return composite_one(ctx, "meao_composite_pitched", mode, ao, ao_pitch, color_rgba16f, MEAO_COLOR_RGBA16F, color_pitch, gbuffer0_rgba8,
+                         gbuffer0_pitch, loc, stream_);
+}
+
+int32_t meao_composite_format(meao_ctx *ctx, int32_t mode, const void *ao, uint64_t ao_pitch, void *color, int32_t color_format,
+                              uint64_t color_pitch, void *gbuffer0_rgba8, uint64_t gbuffer0_pitch, int32_t loc, meao_stream stream_)
+{
+    return composite_one(ctx, "meao_composite_format", mode, ao, ao_pitch, color, color_format, color_pitch, gbuffer0_rgba8, gbuffer0_pitch,
                          loc, stream_);
 }
 
 int32_t meao_composite_enqueue(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, void *const *color_rgba16f,
                                void *const *gbuffer0_rgba8)
 {
-    return meao::composite_enqueue_internal(ctx, "meao_composite_enqueue", mode, n, ao, 0, color_rgba16f, 0, gbuffer0_rgba8, 0, false);
+    return meao::composite_enqueue_internal(ctx, "meao_composite_enqueue", mode, n, ao, 0, color_rgba16f, MEAO_COLOR_RGBA16F, 0, gbuffer0_rgba8, 0,
+                                            false);
 }
 
 int32_t meao_composite_enqueue_pitched(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
                                        void *const *color_rgba16f, uint64_t color_pitch, void *const *gbuffer0_rgba8,
                                        uint64_t gbuffer0_pitch)
 {
-    return meao::composite_enqueue_internal(ctx, "meao_composite_enqueue_pitched", mode, n, ao, ao_pitch, color_rgba16f, color_pitch,
+    return meao::composite_enqueue_internal(ctx, "meao_composite_enqueue_pitched", mode, n, ao, ao_pitch, color_rgba16f, MEAO_COLOR_RGBA16F,
+                                            color_pitch, gbuffer0_rgba8, gbuffer0_pitch, false);
+}
+
+int32_t meao_composite_enqueue_format(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch, void *const *color,
+                                      int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch)
+{
+    return meao::composite_enqueue_internal(ctx, "meao_composite_enqueue_format", mode, n, ao, ao_pitch, color, color_format, color_pitch,
                                             gbuffer0_rgba8, gbuffer0_pitch, false);
 }
 
@@ -1714,7 +1759,7 @@ __attribute__((visibility("default"))) int32_t meao_test_fail_next_allocs(meao_c
 
 int32_t meao_selftest(meao_ctx *ctx, int32_t which, uint64_t *out_mismatches)
 {
-    if (!ctx || !out_mismatches || which < 0 || which > 7) return MEAO_ERR_INVALID_ARGUMENT;
+    if (!ctx || !out_mismatches || which < 0 || which > 8) return MEAO_ERR_INVALID_ARGUMENT;
     int rc = use_device(ctx);
     if (rc != MEAO_OK) return rc;
     if (!ctx->counter) MEAO_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->counter), sizeof(unsigned long long)));

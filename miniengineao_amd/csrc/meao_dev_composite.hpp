@@ -120,6 +120,192 @@ __device__ __forceinline__ void composite_row(const void *ao_base, void *color_b
     for (uint32_t px = lane; px < row_pairs; px += lanes) composite_pair<AOFMT>(ao_base, color_base, gbuffer0_base, p, mode, row, px);
 }
 
+// ------------------------------------------------------------------------------------------
+// The other colour formats (meao_composite_format): RGBA32F, RGBA8 and R11G11B10F targets, in composite_kernel behind one
+// kernel-uniform branch.  One lane = 16 bytes of colour = one RGBA32F texel or four RGBA8 / R11G11B10F texels, and their AO in
+// one load; rows are dealt as in the pitched RGBA16F form, a tightly packed frame is one long row dealt to the whole grid.
+
+// Unsigned small floats (5-bit exponent of bias 15, M mantissa bits: 6 for R and G, 5 for B).  Every code is the f16 value of
+// the same exponent and left-aligned mantissa, so the decode is the f16 one, exact.
+template <int M>
+__device__ __forceinline__ float ufloat_to_f32(uint32_t code) { return f16_bits_to_f32(static_cast<uint16_t>(code << (10 - M))); }
+
+// f32 -> small float: NaN -> all ones, anything with the sign bit -> 0, round to nearest even with gradual underflow, past the
+// largest finite code -> +inf (the output-merger rule of f32_to_f16_bits<true>, for a format without a sign).
+template <int M>
+__device__ __forceinline__ uint32_t f32_to_ufloat(float x)
+{
+    asm volatile("" : "+v"(x));              // the value itself, in a VGPR: no folding of the product that made it into what follows
+    const uint32_t u = __builtin_bit_cast(uint32_t, x);
+    constexpr uint32_t kInf = 31u << M;
+    if ((u & 0x7fffffffu) > 0x7f800000u) return kInf | ((1u << M) - 1u);
+    if (u >> 31) return 0u;
+    if (u >= (113u << 23)) {                 // a normal number of the target (or +inf): rebias, round the 23 - M low bits away
+        constexpr uint32_t kShift = 23 - M;
+        const uint32_t v = u - (112u << 23);
+        const uint32_t r = (v + ((1u << (kShift - 1)) - 1u) + ((v >> kShift) & 1u)) >> kShift;
+        return min(r, kInf);
+    }
+    // below 2^-14: the f32 sum with 2^(9 - M) has the target's subnormal step as its unit in the last place, so the addition
+    // rounds (to nearest even) and its low bits are the code -- 2^M, the smallest normal, where the value rounds up to 2^-14
+    constexpr float kMagic = static_cast<float>(1u << (9 - M));
+    return __builtin_bit_cast(uint32_t, x + kMagic) - __builtin_bit_cast(uint32_t, kMagic);
+}
+
+__device__ __forceinline__ uint32_t f32_to_r11g11b10f(float r, float g, float b)
+{
+    return f32_to_ufloat<6>(r) | (f32_to_ufloat<6>(g) << 11) | (f32_to_ufloat<5>(b) << 22);
+}
+
+// What a texel is multiplied by: MULTIPLY ao (pass 2), AMBIENT_ONLY 1 - (1 - ao) (pass 1); DEBUG does not multiply.
+__device__ __forceinline__ float composite_factor(float ao, int32_t mode)
+{
+    if (mode == MEAO_COMPOSITE_MULTIPLY) return ao;
+    const float occ = 1.0f - ao;             // Blit.shader:84
+    return 1.0f - occ;                       // OneMinusSrcColor / OneMinusSrcAlpha
+}
+
+__device__ __forceinline__ uint32_t unorm8_times(uint32_t code, float f) { return f32_to_unorm8(unorm8_to_f32(code) * f); }
+
+// One texel of each format, in registers.  RGBA8: r, g, b in the low three bytes, alpha in the top one.
+__device__ __forceinline__ uint32_t composite_rgba8(uint32_t t, float ao, int32_t mode)
+{
+    if (mode == MEAO_COMPOSITE_DEBUG) return f32_to_unorm8(ao) * 0x01010101u;
+    const float f = composite_factor(ao, mode);
+    const uint32_t a = mode == MEAO_COMPOSITE_MULTIPLY ? unorm8_times(t >> 24, f) : t >> 24;
+    return unorm8_times(t & 255u, f) | (unorm8_times((t >> 8) & 255u, f) << 8) | (unorm8_times((t >> 16) & 255u, f) << 16) | (a << 24);
+}
+
+__device__ __forceinline__ uint32_t composite_r11g11b10f(uint32_t t, float ao, int32_t mode)
+{
+    if (mode == MEAO_COMPOSITE_DEBUG) return f32_to_r11g11b10f(ao, ao, ao);
+    const float f = composite_factor(ao, mode);
+    return f32_to_r11g11b10f(ufloat_to_f32<6>(t & 0x7ffu) * f, ufloat_to_f32<6>((t >> 11) & 0x7ffu) * f, ufloat_to_f32<5>(t >> 22) * f);
+}
+
+__device__ __forceinline__ float4v composite_rgba32f(float4v t, float ao, int32_t mode)
+{
+    if (mode == MEAO_COMPOSITE_DEBUG) return float4v{ao, ao, ao, ao};
+    const float f = composite_factor(ao, mode);
+    return float4v{t.x * f, t.y * f, t.z * f, mode == MEAO_COMPOSITE_MULTIPLY ? t.w * f : t.w};
+}
+
+__device__ __forceinline__ uint8_t composite_gbuffer0_alpha(uint8_t a, float ao)
+{
+    return static_cast<uint8_t>(unorm8_times(a, composite_factor(ao, MEAO_COMPOSITE_AMBIENT_ONLY)));       // GBuffer0.a = occlusion
+}
+
+// Texels per 16-byte colour access.
+template <int CFMT>
+struct ColorGroup { static constexpr uint32_t kTexels = CFMT == MEAO_COLOR_RGBA32F ? 1u : 4u, kTexelBytes = 16u / kTexels; };
+
+// Group gx of a row (texels kTexels * gx ...), vector form: every load of the lane is issued before the first use.  ao_at /
+// color_at / g_at: the row's first texel, in texels of its surface from the frame base.
+template <int AOFMT, int CFMT>
+__device__ __forceinline__ void composite_format_group(const void *ao_base, void *color_base, void *gbuffer0_base, uint32_t ao_at,
+                                                       uint32_t color_at, uint32_t g_at, int32_t mode, uint32_t gx)
+{
+    typedef AoTexel<AOFMT> AO;
+    typedef typename AO::type ao_t;
+    constexpr uint32_t T = ColorGroup<CFMT>::kTexels;
+    const uint32_t x0 = gx * T;
+    const ao_t *ap = at_byte_offset(static_cast<const ao_t *>(ao_base), (ao_at + x0) * static_cast<uint32_t>(sizeof(ao_t)));
+    uint4v *cp = at_byte_offset(static_cast<uint4v *>(color_base), (color_at + x0) * ColorGroup<CFMT>::kTexelBytes);
+    uint8_t *gp = at_byte_offset(static_cast<uint8_t *>(gbuffer0_base), (g_at + x0) * 4u);
+    const bool ambient = mode == MEAO_COMPOSITE_AMBIENT_ONLY;
+    uint4v raw = *cp;
+    float aov[T];
+    uint8_t ga[T] = {};
+    if constexpr (T == 1) {
+        const ao_t a1 = *ap;
+        if (ambient) ga[0] = gp[3];
+        aov[0] = AO::decode(a1);
+    } else {
+        const typename AO::type4 a4 = *reinterpret_cast<const typename AO::type4 *>(ap);
+        if (ambient) {
+#pragma unroll
+            for (uint32_t e = 0; e < T; ++e) ga[e] = gp[4u * e + 3u];
+        }
+        aov[0] = AO::decode(a4.x); aov[1] = AO::decode(a4.y); aov[2] = AO::decode(a4.z); aov[3] = AO::decode(a4.w);
+    }
+    if constexpr (CFMT == MEAO_COLOR_RGBA32F) {
+        raw = __builtin_bit_cast(uint4v, composite_rgba32f(__builtin_bit_cast(float4v, raw), aov[0], mode));
+    } else if constexpr (CFMT == MEAO_COLOR_RGBA8) {
+        raw.x = composite_rgba8(raw.x, aov[0], mode); raw.y = composite_rgba8(raw.y, aov[1], mode);
+        raw.z = composite_rgba8(raw.z, aov[2], mode); raw.w = composite_rgba8(raw.w, aov[3], mode);
+    } else {
+        raw.x = composite_r11g11b10f(raw.x, aov[0], mode); raw.y = composite_r11g11b10f(raw.y, aov[1], mode);
+        raw.z = composite_r11g11b10f(raw.z, aov[2], mode); raw.w = composite_r11g11b10f(raw.w, aov[3], mode);
+    }
+    *cp = raw;
+    if (ambient) {
+#pragma unroll
+        for (uint32_t e = 0; e < T; ++e) gp[4u * e + 3u] = composite_gbuffer0_alpha(ga[e], aov[e]);
+    }
+}
+
+// Texel x of a row, scalar form: the widest accesses a surface without any alignment beyond its channel type allows (RGBA8 by
+// bytes, RGBA32F and R11G11B10F by 32-bit words), with the results of the vector form.
+template <int AOFMT, int CFMT>
+__device__ __forceinline__ void composite_format_texel(const void *ao_base, void *color_base, void *gbuffer0_base, uint32_t ao_at,
+                                                       uint32_t color_at, uint32_t g_at, int32_t mode, uint32_t x)
+{
+    typedef AoTexel<AOFMT> AO;
+    typedef typename AO::type ao_t;
+    const float ao = AO::decode(*at_byte_offset(static_cast<const ao_t *>(ao_base), (ao_at + x) * static_cast<uint32_t>(sizeof(ao_t))));
+    const uint32_t color_byte = (color_at + x) * ColorGroup<CFMT>::kTexelBytes;
+    if constexpr (CFMT == MEAO_COLOR_RGBA32F) {
+        float *cp = at_byte_offset(static_cast<float *>(color_base), color_byte);
+        const float4v t = composite_rgba32f(float4v{cp[0], cp[1], cp[2], cp[3]}, ao, mode);
+        cp[0] = t.x; cp[1] = t.y; cp[2] = t.z; cp[3] = t.w;
+    } else if constexpr (CFMT == MEAO_COLOR_RGBA8) {
+        uint8_t *cp = at_byte_offset(static_cast<uint8_t *>(color_base), color_byte);
+        const uint32_t t = composite_rgba8(cp[0] | (uint32_t(cp[1]) << 8) | (uint32_t(cp[2]) << 16) | (uint32_t(cp[3]) << 24), ao, mode);
+        cp[0] = static_cast<uint8_t>(t); cp[1] = static_cast<uint8_t>(t >> 8); cp[2] = static_cast<uint8_t>(t >> 16); cp[3] = static_cast<uint8_t>(t >> 24);
+    } else {
+        uint32_t *cp = at_byte_offset(static_cast<uint32_t *>(color_base), color_byte);
+        *cp = composite_r11g11b10f(*cp, ao, mode);
+    }
+    if (mode == MEAO_COMPOSITE_AMBIENT_ONLY) {
+        uint8_t *gp = at_byte_offset(static_cast<uint8_t *>(gbuffer0_base), (g_at + x) * 4u + 3u);
+        *gp = composite_gbuffer0_alpha(*gp, ao);
+    }
+}
+
+// The w texels of one row, dealt to `lanes` lanes: whole groups in the vector form where the surfaces are eligible, the last
+// w mod kTexels texels -- or, on other surfaces, every texel -- in the scalar form.
+template <int AOFMT, int CFMT>
+__device__ __forceinline__ void composite_format_row(const void *ao_base, void *color_base, void *gbuffer0_base, uint32_t ao_at,
+                                                     uint32_t color_at, uint32_t g_at, uint32_t w, bool vec, int32_t mode,
+                                                     uint32_t lane, uint32_t lanes)
+{
+    constexpr uint32_t T = ColorGroup<CFMT>::kTexels;
+    uint32_t done = 0;
+    if (vec) {
+        const uint32_t groups = w / T;
+        for (uint32_t gx = lane; gx < groups; gx += lanes)
+            composite_format_group<AOFMT, CFMT>(ao_base, color_base, gbuffer0_base, ao_at, color_at, g_at, mode, gx);
+        done = groups * T;
+    }
+    for (uint32_t x = done + lane; x < w; x += lanes)
+        composite_format_texel<AOFMT, CFMT>(ao_base, color_base, gbuffer0_base, ao_at, color_at, g_at, mode, x);
+}
+
+// A frame in colour format CFMT: tightly packed = one row of `pixels` texels for the whole grid, else rows as in the RGBA16F form.
+template <int AOFMT, int CFMT>
+__device__ __forceinline__ void composite_format_frame(const CompositeArgs &a)
+{
+    if (!a.pitch.on) {
+        composite_format_row<AOFMT, CFMT>(a.ao, a.color, a.gbuffer0, 0u, 0u, 0u, static_cast<uint32_t>(a.pixels), a.pitch.vec != 0, a.mode,
+                                          blockIdx.x * kThreads + threadIdx.x, gridDim.x * kThreads);
+        return;
+    }
+    const uint32_t lanes = 1u << a.row_lanes_log2, rows = static_cast<uint32_t>(kThreads) >> a.row_lanes_log2;
+    for (uint32_t row = blockIdx.x * rows + (threadIdx.x >> a.row_lanes_log2); row < static_cast<uint32_t>(a.pitch.h); row += gridDim.x * rows)
+        composite_format_row<AOFMT, CFMT>(a.ao, a.color, a.gbuffer0, __umul24(row, a.pitch.ao), __umul24(row, a.pitch.color),
+                                          __umul24(row, a.pitch.gbuffer0), static_cast<uint32_t>(a.pitch.w), a.pitch.vec != 0, a.mode,
+                                          threadIdx.x & (lanes - 1u), lanes);
+}
 
 }  // namespace
 }  // namespace meao

@@ -123,11 +123,17 @@ template <int AOFMT>
 __global__ __launch_bounds__(kThreads) void composite_kernel(const CompositeArgs a)
 {
     // one lane = 2 texels = one 16-byte colour load/store; consecutive lanes are contiguous
-    if (__builtin_expect(!a.pitch.on, 1)) {     // tightly packed: laid out first, the kernel's entry falls through into it
+    if (__builtin_expect((a.pitch.on | a.color_format) == 0, 1)) {     // tightly packed RGBA16F: laid out first, the kernel's entry falls through into it
         const int64_t pairs = (a.pixels + 1) / 2;
         for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < pairs;
              q += static_cast<int64_t>(gridDim.x) * kThreads)
             composite_pair<AOFMT>(a.ao, a.color, a.gbuffer0, a.pixels, a.mode, q);
+        return;
+    }
+    if (a.color_format != MEAO_COLOR_RGBA16F) {     // kernel-uniform: the other colour formats (meao_composite_format), packed and pitched
+        if (a.color_format == MEAO_COLOR_RGBA32F) composite_format_frame<AOFMT, MEAO_COLOR_RGBA32F>(a);
+        else if (a.color_format == MEAO_COLOR_RGBA8) composite_format_frame<AOFMT, MEAO_COLOR_RGBA8>(a);
+        else composite_format_frame<AOFMT, MEAO_COLOR_R11G11B10F>(a);
         return;
     }
     // kernel-uniform: row-pitched surfaces, rows dealt to (2^row_lanes_log2 lanes x rows) workgroups
@@ -136,11 +142,32 @@ __global__ __launch_bounds__(kThreads) void composite_kernel(const CompositeArgs
         composite_row<AOFMT>(a.ao, a.color, a.gbuffer0, a.pitch, a.mode, row, threadIdx.x & (lanes - 1u), lanes);
 }
 
-// which = 4: rcp_strict, 5: div_const<3>, div_const<9>, 6: div_strict on hashed operand pairs
+// which = 4: rcp_strict, 5: div_const<3>, div_const<9>, 6: div_strict on hashed operand pairs, 8: f32_to_ufloat<6|5> (the R11G11B10F stores)
 __device__ __forceinline__ bool in_exact_range(float x, float lo, float hi)
 {
     const float ax = __builtin_fabsf(x);
     return ax >= lo && ax <= hi;
+}
+
+// which = 8: the bit-level model of f32 -> unsigned small float (M mantissa bits) that f32_to_ufloat<M> is checked against: the
+// significand as an integer, shifted down to the target's quantum at that magnitude with the dropped bits compared against half.
+template <int M>
+__device__ __forceinline__ uint32_t ufloat_model(uint32_t u)
+{
+    constexpr uint32_t kInf = 31u << M;
+    if ((u & 0x7fffffffu) > 0x7f800000u) return kInf | ((1u << M) - 1u);
+    if (u >> 31) return 0u;
+    if (u == 0x7f800000u) return kInf;
+    const int e = static_cast<int>(u >> 23);
+    const uint32_t sig = e ? 0x800000u | (u & 0x7fffffu) : u;       // value = sig * 2^(max(e, 1) - 150)
+    const int target = max(e - 127, -14);                            // the exponent whose quantum 2^(target - M) the result is a multiple of
+    const int drop = target - M - (max(e, 1) - 150);                 // >= 23 - M bits
+    if (drop > 25) return 0u;                                        // below a quarter of the smallest subnormal
+    uint32_t q = sig >> drop;
+    const uint32_t rest = sig & ((1u << drop) - 1u), half = 1u << (drop - 1);
+    q += (rest > half || (rest == half && (q & 1u))) ? 1u : 0u;
+    const uint32_t code = e - 127 >= -14 ? (static_cast<uint32_t>(e - 127 + 14) << M) + q : q;     // q carries the leading one of a normal number
+    return min(code, kInf);
 }
 
 __global__ __launch_bounds__(kThreads) void selftest_div_kernel(unsigned long long *count, int which)
@@ -149,7 +176,10 @@ __global__ __launch_bounds__(kThreads) void selftest_div_kernel(unsigned long lo
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kThreads;
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x; i < (1ull << 32); i += stride) {
         const float x = __builtin_bit_cast(float, static_cast<uint32_t>(i));
-        if (which == 4) {
+        if (which == 8) {
+            bad += f32_to_ufloat<6>(x) != ufloat_model<6>(static_cast<uint32_t>(i));
+            bad += f32_to_ufloat<5>(x) != ufloat_model<5>(static_cast<uint32_t>(i));
+        } else if (which == 4) {
             if (!in_exact_range(x, 0x1p-100f, 0x1p100f)) continue;
             const float exact = 1.0f / x;
             bad += rcp_strict<DIV_EXACT_RCP>(x) != exact;
@@ -240,10 +270,12 @@ hipError_t launch_debug_view(const DebugViewArgs &a, int ao_format, hipStream_t 
 hipError_t launch_composite(const CompositeArgs &args, int ao_format, hipStream_t s)
 {
     CompositeArgs a = args;
-    const int64_t pairs = (a.pixels + 1) / 2;
+    // what one lane takes at a time: a texel pair (RGBA16F), a 16-byte group of 1 or 4 texels (the other formats' vector form), a texel
+    const int64_t per_lane = a.color_format == MEAO_COLOR_RGBA16F ? 2 : !a.pitch.vec || a.color_format == MEAO_COLOR_RGBA32F ? 1 : 4;
+    const int64_t pairs = (a.pixels + per_lane - 1) / per_lane;
     int blocks = static_cast<int>(std::min<int64_t>((pairs + kThreads - 1) / kThreads, 256 * 32));
     if (a.pitch.on) {       // the narrowest power of two of lanes that spans a row's pairs (at most the workgroup), rows beside each other
-        const int row_pairs = (a.pitch.w + 1) / 2;
+        const int row_pairs = static_cast<int>((a.pitch.w + per_lane - 1) / per_lane);
         a.row_lanes_log2 = 0;
         while ((1 << a.row_lanes_log2) < row_pairs && (1 << a.row_lanes_log2) < kThreads) ++a.row_lanes_log2;
         const int rows = kThreads >> a.row_lanes_log2;
@@ -261,7 +293,7 @@ hipError_t launch_selftest(int which, unsigned long long *count, hipStream_t s)
     case 1: selftest_f16_kernel<true><<<dim3(4096), dim3(kThreads), 0, s>>>(count); break;
     case 2: selftest_unorm8_decode_kernel<<<dim3(1), dim3(256), 0, s>>>(count); break;
     case 3: selftest_f16_decode_kernel<<<dim3(65536 / kThreads), dim3(kThreads), 0, s>>>(count); break;
-    case 4: case 5: case 6: case 7: selftest_div_kernel<<<dim3(4096), dim3(kThreads), 0, s>>>(count, which); break;
+    case 4: case 5: case 6: case 7: case 8: selftest_div_kernel<<<dim3(4096), dim3(kThreads), 0, s>>>(count, which); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -251,7 +251,7 @@ struct DebugViewArgs {
     int32_t f16_rtne;
 };
 hipError_t launch_debug_view(const DebugViewArgs &a, int ao_format, hipStream_t s);
-// Composite (Blit.shader passes 1-3): ao in ao_format, color RGBA16F in place, gbuffer0 RGBA8 or null.
+// Composite (Blit.shader passes 1-3): ao in ao_format, color in color_format in place, gbuffer0 RGBA8 or null.
 // Row-pitched surfaces (meao_composite_pitched): the row pitches in texels of their surface, the extent, and whether the 16-byte
 // colour / two-texel AO accesses are aligned in every row of every frame.  on = 0: tightly packed, nothing else is read.
 struct CompositePitches {
@@ -267,6 +267,7 @@ struct CompositeArgs {
     int32_t mode;
     CompositePitches pitch;
     int32_t row_lanes_log2;     // pitched form, filled by the launcher: a workgroup is 2^row_lanes_log2 lanes along a row
+    int32_t color_format;       // meao_color_format of `color`; pitch.color is in texels of it (in what was the struct's tail padding)
 };
 hipError_t launch_composite(const CompositeArgs &a, int ao_format, hipStream_t s);
 // A batch of composites carried by a render launch (meao_composite_enqueue): frame f = ao[f] x color[f].
@@ -279,7 +280,8 @@ struct CompositeBatchArgs {
     int32_t mode;
     CompositePitches pitch;
     int32_t chunks_log2;    // pitched, filled by the launcher: the carrying kernel takes a row as 2^chunks_log2 chunks of its workgroup's lanes
-};
+};      // RGBA16F colour only: a waiting batch keeps its meao_color_format next to this struct (meao_ctx::pending_comp_format), because a
+        // field here, even in the tail padding, moves the hidden arguments of the six carrying kernels and so changes their code
 hipError_t launch_render_with_composite(const RenderArgs &a, const CompositeBatchArgs &c, int ao_format, int frames,
                                         hipStream_t s);
 // Exhaustive conversion self-tests; *count (device) receives the number of mismatches.
@@ -291,11 +293,11 @@ hipError_t launch_selftest(int which, unsigned long long *count, hipStream_t s);
 int execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
                            int32_t out_loc, meao_stream stream, bool wait_for_host, const meao_params *params = nullptr,
                            uint64_t depth_pitch = 0, uint64_t ao_pitch = 0);
-// meao_api.cpp, for meao_pool.cpp: meao_composite_enqueue_pitched under the name `fn` (the errors carry it); validate_only = every
+// meao_api.cpp, for meao_pool.cpp: meao_composite_enqueue_format under the name `fn` (the errors carry it); validate_only = every
 // check and nothing else (no device is touched, a waiting batch stays as it is).
 int composite_enqueue_internal(meao_ctx *ctx, const char *fn, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
-                               void *const *color_rgba16f, uint64_t color_pitch, void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch,
-                               bool validate_only);
+                               void *const *color, int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8,
+                               uint64_t gbuffer0_pitch, bool validate_only);
 // meao_api.cpp, for meao_pool.cpp: what a member that is dealt no frame of a pool call does instead of that call.
 // ready_too = false (a pool announcement passed it by): an announcement it still holds is withdrawn, as a newer one would
 // replace it.  ready_too = true (a pool execute passed it by): a ready prefetched set goes as well -- the pool-level "call

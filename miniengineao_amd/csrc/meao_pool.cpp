@@ -536,8 +536,8 @@ int32_t meao_pool_prefetch_batch_pitched(meao_pool *p, int32_t n, const void *co
 
 // pitched: the pitches go to every member and every member's share is validated before any member enqueues.
 static int32_t pool_composite_enqueue(meao_pool *p, const char *fn, bool pitched, int32_t mode, int32_t n, const void *const *ao,
-                                      uint64_t ao_pitch, void *const *color_rgba16f, uint64_t color_pitch, void *const *gbuffer0_rgba8,
-                                      uint64_t gbuffer0_pitch)
+                                      uint64_t ao_pitch, void *const *color_rgba16f, int32_t color_format, uint64_t color_pitch,
+                                      void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch)
 {
     if (!p || !ao || !color_rgba16f) return MEAO_ERR_INVALID_ARGUMENT;
     const int32_t G = static_cast<int32_t>(p->ctx.size());
@@ -552,7 +552,7 @@ static int32_t pool_composite_enqueue(meao_pool *p, const char *fn, bool pitched
             share_of(m, G, n, color_rgba16f, c);
             if (gbuffer0_rgba8) share_of(m, G, n, gbuffer0_rgba8, g);
             if (k == 0) continue;
-            const int32_t rc = pitched ? meao::composite_enqueue_internal(p->ctx[m], fn, mode, k, a, ao_pitch, c, color_pitch,
+            const int32_t rc = pitched ? meao::composite_enqueue_internal(p->ctx[m], fn, mode, k, a, ao_pitch, c, color_format, color_pitch,
                                                                           gbuffer0_rgba8 ? g : nullptr, gbuffer0_pitch, pass == 0)
                                        : meao_composite_enqueue(p->ctx[m], mode, k, a, c, gbuffer0_rgba8 ? g : nullptr);
             if (rc != MEAO_OK)
@@ -565,14 +565,21 @@ static int32_t pool_composite_enqueue(meao_pool *p, const char *fn, bool pitched
 int32_t meao_pool_composite_enqueue(meao_pool *p, int32_t mode, int32_t n, const void *const *ao, void *const *color_rgba16f,
                                     void *const *gbuffer0_rgba8)
 {
-    return pool_composite_enqueue(p, "meao_pool_composite_enqueue", false, mode, n, ao, 0, color_rgba16f, 0, gbuffer0_rgba8, 0);
+    return pool_composite_enqueue(p, "meao_pool_composite_enqueue", false, mode, n, ao, 0, color_rgba16f, MEAO_COLOR_RGBA16F, 0, gbuffer0_rgba8, 0);
 }
 
 int32_t meao_pool_composite_enqueue_pitched(meao_pool *p, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
                                             void *const *color_rgba16f, uint64_t color_pitch, void *const *gbuffer0_rgba8,
                                             uint64_t gbuffer0_pitch)
 {
-    return pool_composite_enqueue(p, "meao_pool_composite_enqueue_pitched", true, mode, n, ao, ao_pitch, color_rgba16f, color_pitch,
+    return pool_composite_enqueue(p, "meao_pool_composite_enqueue_pitched", true, mode, n, ao, ao_pitch, color_rgba16f, MEAO_COLOR_RGBA16F,
+                                  color_pitch, gbuffer0_rgba8, gbuffer0_pitch);
+}
+
+int32_t meao_pool_composite_enqueue_format(meao_pool *p, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch, void *const *color,
+                                           int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch)
+{
+    return pool_composite_enqueue(p, "meao_pool_composite_enqueue_format", true, mode, n, ao, ao_pitch, color, color_format, color_pitch,
                                   gbuffer0_rgba8, gbuffer0_pitch);
 }
 

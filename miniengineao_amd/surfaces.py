@@ -83,14 +83,28 @@ def _channel_frame_pointers(frames, height, width, dtype, what, device, channels
     return ptrs, row_stride * seq[0].element_size()
 
 
-def composite_surfaces(ao, color, gbuffer0, height: int, width: int, ao_dtype, device=None):
+def color_layout(color_format: int):
+    """meao_color_format -> (accepted torch dtypes, channels of the tensor's last dimension or 0 for none, bytes per texel):
+    RGBA16F (N, H, W, 4) float16 / int16, RGBA32F (N, H, W, 4) float32, RGBA8 (N, H, W, 4) uint8, R11G11B10F (N, H, W) int32."""
+    import torch
+    layouts = {0: ((torch.float16, torch.int16), 4, 8), 1: ((torch.float32,), 4, 16), 2: ((torch.uint8,), 4, 4), 3: ((torch.int32,), 0, 4)}
+    if color_format not in layouts:
+        raise ValueError(f"color_format {color_format}: not a meao_color_format")
+    return layouts[color_format]
+
+
+def composite_surfaces(ao, color, gbuffer0, height: int, width: int, ao_dtype, device=None, color_format: int = 0):
     """The surfaces of ``composite_tensors`` -> (ao_ptrs, ao_pitch, color_ptrs, color_pitch, gbuffer0_ptrs | None, gbuffer0_pitch),
     pitches as the C ABI takes them (0 where tightly packed).  ao: (N, H, W) / list of (H, W) in ``ao_dtype``; color: (N, H, W, 4)
-    int16 / float16 (RGBA16F bits); gbuffer0: (N, H, W, 4) uint8 or None.  The same frame count everywhere."""
+    int16 / float16 (RGBA16F bits) -- or, where ``color_format`` names another meao_color_format, that format's layout and nothing
+    else (``color_layout``); gbuffer0: (N, H, W, 4) uint8 or None.  The same frame count everywhere."""
     import torch
-    color_dt = (torch.float16, torch.int16)
+    color_dt, color_channels, color_elem = color_layout(color_format)
     a_ptrs, a_pitch = frame_pointers(ao, height, width, ao_dtype, "ao", device=device)
-    c_ptrs, c_pitch = frame_pointers(color, height, width, color_dt, "color", device=device, channels=4)
+    if color_channels:
+        c_ptrs, c_pitch = frame_pointers(color, height, width, color_dt, "color", device=device, channels=color_channels)
+    else:
+        c_ptrs, c_pitch = frame_pointers(color, height, width, color_dt[0], "color", device=device)
     if len(c_ptrs) != len(a_ptrs):
         raise ValueError(f"color has {len(c_ptrs)} frames, ao {len(a_ptrs)}")
     g_ptrs, g_pitch = None, 0
@@ -100,7 +114,7 @@ def composite_surfaces(ao, color, gbuffer0, height: int, width: int, ao_dtype, d
             raise ValueError(f"gbuffer0 has {len(g_ptrs)} frames, ao {len(a_ptrs)}")
         g_pitch = packed_pitch(g_pitch, width, 4)
     ao_elem = (ao[0] if not hasattr(ao, "dim") else ao).element_size()
-    return a_ptrs, packed_pitch(a_pitch, width, ao_elem), c_ptrs, packed_pitch(c_pitch, width, 8), g_ptrs, g_pitch
+    return a_ptrs, packed_pitch(a_pitch, width, ao_elem), c_ptrs, packed_pitch(c_pitch, width, color_elem), g_ptrs, g_pitch
 
 
 def packed_pitch(pitch: int, width: int, element_size: int) -> int:
