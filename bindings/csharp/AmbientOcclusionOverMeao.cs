@@ -144,6 +144,30 @@ namespace MiniEngineAO
                                                      gbuffer0Pitch));
         }
 
+        // AO and the shaded camera target from one call (meao_execute_batch_shaded): the execute, then one composite launch
+        // behind its last kernel on the same stream, in any target format.  Nothing waits for the next Render call.
+        public void RenderDeviceShaded(IntPtr deviceDepth, ulong depthPitch, IntPtr deviceAo, ulong aoPitch, IntPtr deviceColor,
+                                       ulong colorPitch, IntPtr deviceGBuffer0, ulong gbuffer0Pitch, bool debug, IntPtr stream)
+        {
+            int mode = debug ? (int)MeaoCompositeMode.Debug
+                             : (ambientOnly && deviceGBuffer0 != IntPtr.Zero ? (int)MeaoCompositeMode.AmbientOnly
+                                                                             : (int)MeaoCompositeMode.Multiply);
+            Check(Meao.meao_execute_batch_shaded(_ctx, 1, new IntPtr[] { deviceDepth }, depthPitch, new IntPtr[] { deviceAo }, aoPitch, null,
+                                                 mode, new IntPtr[] { deviceColor }, (int)_colorFormat, colorPitch,
+                                                 mode == (int)MeaoCompositeMode.AmbientOnly ? new IntPtr[] { deviceGBuffer0 } : null,
+                                                 gbuffer0Pitch, stream));
+        }
+
+        // Several AO frames into their targets in ONE launch, now (meao_composite_batch); a waiting batch is left alone.
+        public void CompositeBatch(IntPtr[] deviceAo, ulong aoPitch, IntPtr[] deviceColor, ulong colorPitch, IntPtr[] deviceGBuffer0,
+                                   ulong gbuffer0Pitch, bool debug, IntPtr stream)
+        {
+            int mode = debug ? (int)MeaoCompositeMode.Debug
+                             : (ambientOnly && deviceGBuffer0 != null ? (int)MeaoCompositeMode.AmbientOnly : (int)MeaoCompositeMode.Multiply);
+            Check(Meao.meao_composite_batch(_ctx, mode, deviceAo.Length, deviceAo, aoPitch, deviceColor, (int)_colorFormat, colorPitch,
+                                            mode == (int)MeaoCompositeMode.AmbientOnly ? deviceGBuffer0 : null, gbuffer0Pitch, stream));
+        }
+
         public void FlushComposite(IntPtr stream)
         {
             Check(Meao.meao_composite_flush(_ctx, stream));

@@ -144,6 +144,8 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_composite_enqueue_pitched(IntPtr ctx, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color_rgba16f, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
         // the same with the colour target's format (MeaoColorFormat) as an argument
         [DllImport(Lib)] public static extern int meao_composite_enqueue_format(IntPtr ctx, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
+        [DllImport(Lib)] public static extern int meao_composite_batch(IntPtr ctx, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch, IntPtr stream);
+        [DllImport(Lib)] public static extern int meao_execute_batch_shaded(IntPtr ctx, int n, IntPtr[] depth, ulong depth_pitch, IntPtr[] ao_out, ulong ao_pitch, [In] MeaoParams[] prm, int mode, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_composite_flush(IntPtr ctx, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_composite_pending(IntPtr ctx, out int out_frames);
 
@@ -164,6 +166,7 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue(IntPtr pool, int mode, int n, IntPtr[] ao, IntPtr[] color_rgba16f, IntPtr[] gbuffer0_rgba8);
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue_pitched(IntPtr pool, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color_rgba16f, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue_format(IntPtr pool, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
+        [DllImport(Lib)] public static extern int meao_pool_execute_batch_shaded(IntPtr pool, int n, IntPtr[] depth, ulong depth_pitch, IntPtr[] ao_out, ulong ao_pitch, [In] MeaoParams[] prm, int mode, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
         [DllImport(Lib)] public static extern int meao_pool_composite_flush(IntPtr pool);
         [DllImport(Lib)] public static extern int meao_pool_composite_pending(IntPtr pool, out int out_frames);
         [DllImport(Lib)] public static extern int meao_pool_gather_to_device(IntPtr pool, int n, IntPtr[] ao_src, IntPtr[] dst, int dst_device);

@@ -454,6 +454,32 @@ MEAO_API int32_t meao_composite_enqueue_format(meao_ctx *ctx, int32_t mode, int3
                                                void *const *color, int32_t color_format, uint64_t color_pitch,
                                                void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch);
 
+/* The batch in one launch, and shaded frames from the execute call.  (The ABI version is unchanged: hosts probe for these symbols.)
+ * meao_composite_batch: the n frames (1..cfg.max_batch) ao[f] x color[f] are composited by ONE composite_kernel launch on `stream`
+ * (NULL = the context's own stream), now: nothing waits afterwards, meao_composite_pending is unchanged, and a batch that waits
+ * from an earlier meao_composite_enqueue* is neither run nor disturbed.  Arguments, formats, modes, pitches, validation and results
+ * are those of meao_composite_enqueue_format (n is checked against cfg.max_batch).  DEVICE surfaces only.  The frames' origins
+ * travel in a context-owned table filled by a copy on `stream`; the vector form runs where every frame's bases and the pitches
+ * are eligible (the rule above), else every frame runs the per-texel form, with the same results.
+ * meao_execute_batch_shaded: meao_execute_batch_pitched (DEVICE / DEVICE; params NULL or one per frame) followed, on the same
+ * stream, by the batched composite of ao_out[f] into color[f]: when the call has completed, the colour targets are shaded.  The
+ * execute half IS that call: the same launches (the fused last kernel included), the same handling of an announced batch and of
+ * a waiting enqueued batch (carried by this call's render kernel, or run first), the same state for meao_synchronize(ctx, NULL),
+ * the debug buffers and the pass times.  Its own composite is one composite_kernel launch behind the last AO kernel -- in any
+ * mode, colour format and pitches, with shared or per-frame parameters, in an EXHAUSTIVE context -- and never waits.
+ * Validation comes first, for both calls: every check of the execute and of the composite runs before anything is enqueued.  A
+ * refused call launches nothing and leaves the AO, the colour, an announced batch and a waiting enqueued batch as they were;
+ * meao_last_error names the call and the argument.
+ * Surfaces: the colour targets of distinct frames must not overlap, and no AO surface may overlap a colour target; the
+ * behaviour is undefined otherwise (not checked). */
+MEAO_API int32_t meao_composite_batch(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
+                                      void *const *color, int32_t color_format, uint64_t color_pitch,
+                                      void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch, meao_stream stream);
+MEAO_API int32_t meao_execute_batch_shaded(meao_ctx *ctx, int32_t n, const void *const *depth, uint64_t depth_pitch,
+                                           void *const *ao_out, uint64_t ao_pitch, const meao_params *params,
+                                           int32_t mode, void *const *color, int32_t color_format, uint64_t color_pitch,
+                                           void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch, meao_stream stream);
+
 /* Per-pass device timing: when enabled, meao_execute* brackets every pass with HIP events on
  * the launch stream; meao_get_pass_times averages each pass over the executes that ran it since
  * the last reset (it waits for the stream of the last execute first); *out_samples = executes measured.
@@ -533,6 +559,14 @@ MEAO_API int32_t meao_pool_composite_enqueue_pitched(meao_pool *pool, int32_t mo
 MEAO_API int32_t meao_pool_composite_enqueue_format(meao_pool *pool, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
                                                     void *const *color, int32_t color_format, uint64_t color_pitch,
                                                     void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch);
+/* meao_execute_batch_shaded for the pool (DEVICE surfaces on the frames' devices): frame f goes to member f mod G; every member's
+ * share is validated (both halves) before any member enqueues; each member that is dealt frames runs its execute and ONE batched
+ * composite launch on its stream, from its worker thread.  Members dealt nothing do what they do for
+ * meao_pool_execute_batch_pitched. */
+MEAO_API int32_t meao_pool_execute_batch_shaded(meao_pool *pool, int32_t n, const void *const *depth, uint64_t depth_pitch,
+                                                void *const *ao_out, uint64_t ao_pitch, const meao_params *params,
+                                                int32_t mode, void *const *color, int32_t color_format, uint64_t color_pitch,
+                                                void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch);
 MEAO_API int32_t meao_pool_composite_flush(meao_pool *pool);
 MEAO_API int32_t meao_pool_composite_pending(const meao_pool *pool, int32_t *out_frames);   /* summed over the members */
 /* Copies the n DEVICE results ao_src[f] (on their owning devices) to dst[f] on dst_device with

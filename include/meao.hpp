@@ -191,6 +191,28 @@ public:
         check(meao_composite_enqueue_format(ctx_, mode, static_cast<int32_t>(deviceAo.size()), deviceAo.data(), aoPitch, deviceColor.data(),
                                             colorFormat, colorPitch, deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(), gbuffer0Pitch));
     }
+    // The whole batch in ONE launch on `stream`, now (meao_composite_batch): nothing waits afterwards, a waiting batch is left alone.
+    void CompositeBatch(meao_composite_mode mode, const std::vector<const void *> &deviceAo, uint64_t aoPitch,
+                        const std::vector<void *> &deviceColor, uint64_t colorPitch, const std::vector<void *> &deviceGBuffer0 = {},
+                        uint64_t gbuffer0Pitch = 0, meao_stream stream = nullptr)
+    {
+        check(meao_composite_batch(ctx_, mode, static_cast<int32_t>(deviceAo.size()), deviceAo.data(), aoPitch, deviceColor.data(),
+                                   colorFormat, colorPitch, deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(), gbuffer0Pitch, stream));
+    }
+    // AO and shaded frames from one call (meao_execute_batch_shaded): RenderDeviceBatchPitched, then the batched composite of
+    // deviceAo[f] into deviceColor[f] on the same stream.  params empty = the context's parameters.
+    void RenderDeviceBatchShaded(const std::vector<const void *> &deviceDepth, uint64_t depthPitch, const std::vector<void *> &deviceAo,
+                                 uint64_t aoPitch, meao_composite_mode mode, const std::vector<void *> &deviceColor, uint64_t colorPitch,
+                                 const std::vector<void *> &deviceGBuffer0 = {}, uint64_t gbuffer0Pitch = 0,
+                                 const std::vector<meao_params> &params = {}, meao_stream stream = nullptr)
+    {
+        if (deviceAo.size() != deviceDepth.size() || deviceColor.size() != deviceDepth.size())
+            throw std::invalid_argument("meao: one AO and one colour surface per frame");
+        if (!params.empty() && params.size() != deviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        check(meao_execute_batch_shaded(ctx_, static_cast<int32_t>(deviceDepth.size()), deviceDepth.data(), depthPitch, deviceAo.data(),
+                                        aoPitch, params.empty() ? nullptr : params.data(), mode, deviceColor.data(), colorFormat, colorPitch,
+                                        deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(), gbuffer0Pitch, stream));
+    }
     void FlushComposite(meao_stream stream = nullptr) { check(meao_composite_flush(ctx_, stream)); }
     bool CompositePending()            // a batch given to CompositeWithNextFrame that no Render* / flush / resize has run yet
     {
@@ -330,6 +352,19 @@ public:
         check(meao_pool_composite_enqueue_format(pool_, mode, static_cast<int32_t>(deviceAo.size()), deviceAo.data(), aoPitch,
                                                  deviceColor.data(), colorFormat, colorPitch,
                                                  deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(), gbuffer0Pitch));
+    }
+    // AO and shaded frames from one pool call (meao_pool_execute_batch_shaded): one batched composite launch per member
+    void RenderDeviceBatchShaded(const std::vector<const void *> &deviceDepth, uint64_t depthPitch, const std::vector<void *> &deviceAo,
+                                 uint64_t aoPitch, meao_composite_mode mode, const std::vector<void *> &deviceColor,
+                                 meao_color_format colorFormat, uint64_t colorPitch, const std::vector<void *> &deviceGBuffer0 = {},
+                                 uint64_t gbuffer0Pitch = 0, const std::vector<meao_params> &params = {})
+    {
+        if (deviceAo.size() != deviceDepth.size() || deviceColor.size() != deviceDepth.size())
+            throw std::invalid_argument("meao: one AO and one colour surface per frame");
+        if (!params.empty() && params.size() != deviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        check(meao_pool_execute_batch_shaded(pool_, static_cast<int32_t>(deviceDepth.size()), deviceDepth.data(), depthPitch, deviceAo.data(),
+                                             aoPitch, params.empty() ? nullptr : params.data(), mode, deviceColor.data(), colorFormat,
+                                             colorPitch, deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(), gbuffer0Pitch));
     }
     // row-pitched device surfaces (meao_pool_execute_batch_pitched); params empty = the members' own parameters
     void RenderDeviceBatchPitched(const std::vector<const void *> &deviceDepth, uint64_t depthPitch, const std::vector<void *> &deviceAo,

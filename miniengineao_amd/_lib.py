@@ -130,6 +130,11 @@ SIGNATURES = {
                                                    C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64]),
     "meao_composite_enqueue_format": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,
                                                   C.POINTER(C.c_void_p), C.c_int32, C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64]),
+    "meao_composite_batch": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,
+                                         C.POINTER(C.c_void_p), C.c_int32, C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64, C.c_void_p]),
+    "meao_execute_batch_shaded": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64,
+                                              C.POINTER(Params), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_uint64,
+                                              C.POINTER(C.c_void_p), C.c_uint64, C.c_void_p]),
     "meao_composite_flush": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "meao_composite_pending": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
     "meao_pool_create": (C.c_int32, [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),
@@ -156,6 +161,9 @@ SIGNATURES = {
                                                         C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64]),
     "meao_pool_composite_enqueue_format": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,
                                                        C.POINTER(C.c_void_p), C.c_int32, C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64]),
+    "meao_pool_execute_batch_shaded": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(C.c_void_p),
+                                                   C.c_uint64, C.POINTER(Params), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_uint64,
+                                                   C.POINTER(C.c_void_p), C.c_uint64]),
     "meao_pool_composite_flush": (C.c_int32, [C.c_void_p]),
     "meao_pool_composite_pending": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
     "meao_pool_gather_path": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -169,6 +169,23 @@ class AmbientOcclusion:
             prm = params_array(params, n, self._prm)
             L.check(self._lib.meao_execute_batch_params(self._ctx, n, pin, L.MEM_DEVICE, pout, L.MEM_DEVICE, prm, s), self._ctx)
 
+    def execute_shaded_device(self, depth_ptrs: Sequence[int], out_ptrs: Sequence[int], mode: int, color_ptrs: Sequence[int],
+                              gbuffer0_ptrs: Optional[Sequence[int]] = None, stream: int = 0,
+                              params: Optional[Sequence[Optional[FrameParams]]] = None, *, depth_pitch: int = 0, out_pitch: int = 0,
+                              color_pitch: int = 0, gbuffer0_pitch: int = 0, color_format: int = L.COLOR_RGBA16F) -> None:
+        """execute_device() followed, on the same stream, by ONE composite launch of out_ptrs[f] into color_ptrs[f]
+        (meao_execute_batch_shaded): when the call has completed the colour targets are shaded, whatever their format.  Every
+        argument of both halves is checked before anything is enqueued."""
+        n = len(depth_ptrs)
+        if len(out_ptrs) != n or len(color_ptrs) != n or (gbuffer0_ptrs and len(gbuffer0_ptrs) != n):
+            raise ValueError("execute_shaded_device: one AO, one colour (and one GBuffer0) surface per depth frame")
+        self._sync_params()
+        prm = None if params is None else params_array(params, n, self._prm)
+        g = (C.c_void_p * n)(*gbuffer0_ptrs) if gbuffer0_ptrs else None
+        L.check(self._lib.meao_execute_batch_shaded(self._ctx, n, (C.c_void_p * n)(*depth_ptrs), depth_pitch, (C.c_void_p * n)(*out_ptrs),
+                                                    out_pitch, prm, mode, (C.c_void_p * n)(*color_ptrs), color_format, color_pitch, g,
+                                                    gbuffer0_pitch, C.c_void_p(stream) if stream else None), self._ctx)
+
     def prefetch_device(self, depth_ptrs: Sequence[int], params: Optional[Sequence[Optional[FrameParams]]] = None, *,
                         depth_pitch: int = 0) -> None:
         """Announce the device depth frames of the call after next (meao_prefetch_batch): the next
@@ -186,12 +203,15 @@ class AmbientOcclusion:
         else:
             L.check(self._lib.meao_prefetch_batch_params(self._ctx, n, pin, params_array(params, n, self._prm)), self._ctx)
 
-    def execute_tensors(self, depth, out=None, params: Optional[Sequence[Optional[FrameParams]]] = None):
+    def execute_tensors(self, depth, out=None, params: Optional[Sequence[Optional[FrameParams]]] = None, *, color=None, gbuffer0=None,
+                        mode: int = L.COMPOSITE_MULTIPLY, color_format: int = L.COLOR_RGBA16F):
         """Torch tensors on this context's device, used in place (meao_execute_batch_pitched), on torch.cuda.current_stream().
         depth: an (N, H, W) tensor or a list of (H, W) tensors in the dtype of depth_format (float32, float16, uint16 for UNORM16,
         int32 for UNORM24; float32 / float16 for LINEAR_F32 / LINEAR_F16) -- e.g. a crop ``surface[:, y0:y0 + H, x0:x0 + W]`` of larger targets.  Rows must be contiguous and all
         frames must share one row stride, which becomes the pitch; any other layout raises ValueError (nothing is copied).
-        out: the same for the AO (uint8 for R8, float16 for F16 storage), or None: allocated packed.  Returns out."""
+        out: the same for the AO (uint8 for R8, float16 for F16 storage), or None: allocated packed.  Returns out.
+        color: colour targets as composite_tensors takes them (with gbuffer0, mode and color_format): they are shaded in place by
+        the same call (meao_execute_batch_shaded), one composite launch behind the last AO kernel."""
         import torch
         from .surfaces import frame_pointers, packed_pitch
         depth_dt = getattr(torch, DEPTH_TORCH[self._cfg.depth_format])
@@ -208,6 +228,18 @@ class AmbientOcclusion:
         if len(o_ptrs) != n:
             raise ValueError(f"out has {len(o_ptrs)} frames, depth {n}")
         stream = torch.cuda.current_stream(dev).cuda_stream
+        if color is not None:
+            from .surfaces import composite_surfaces
+            a, ap, c, cp, g, gp = composite_surfaces(out, color, gbuffer0, self.height, self.width, ao_dt, device=dev,
+                                                     color_format=color_format)
+            if len(c) != n:
+                raise ValueError(f"color has {len(c)} frames, depth {n}")
+            self.execute_shaded_device(d_ptrs, a, mode, c, g, stream=stream, params=params,
+                                       depth_pitch=packed_pitch(d_pitch, self.width, first.element_size()), out_pitch=ap,
+                                       color_pitch=cp, gbuffer0_pitch=gp, color_format=color_format)
+            return out
+        if gbuffer0 is not None:
+            raise ValueError("execute_tensors: gbuffer0 without color")
         self.execute_device(d_ptrs, o_ptrs, stream=stream, params=params,
                             depth_pitch=packed_pitch(d_pitch, self.width, first.element_size()),
                             out_pitch=packed_pitch(o_pitch, self.width, o_frames[0].element_size()))
@@ -280,8 +312,19 @@ class AmbientOcclusion:
             L.check(self._lib.meao_composite_enqueue(self._ctx, mode, n, (C.c_void_p * n)(*ao_ptrs),
                                                      (C.c_void_p * n)(*color_ptrs), g), self._ctx)
 
+    def composite_batch_device(self, mode: int, ao_ptrs: Sequence[int], color_ptrs: Sequence[int],
+                               gbuffer0_ptrs: Optional[Sequence[int]] = None, stream: int = 0, *, ao_pitch: int = 0,
+                               color_pitch: int = 0, gbuffer0_pitch: int = 0, color_format: int = L.COLOR_RGBA16F) -> None:
+        """The frames (1..max_batch) composited by ONE launch on ``stream``, now (meao_composite_batch): nothing waits
+        afterwards, and a batch that waits from composite_enqueue_device() is left alone.  Arguments as composite_enqueue_device."""
+        n = len(ao_ptrs)
+        g = (C.c_void_p * n)(*gbuffer0_ptrs) if gbuffer0_ptrs else None
+        L.check(self._lib.meao_composite_batch(self._ctx, mode, n, (C.c_void_p * n)(*ao_ptrs), ao_pitch, (C.c_void_p * n)(*color_ptrs),
+                                               color_format, color_pitch, g, gbuffer0_pitch, C.c_void_p(stream) if stream else None),
+                self._ctx)
+
     def composite_tensors(self, ao, color, gbuffer0=None, mode: int = L.COMPOSITE_MULTIPLY, enqueue: bool = False,
-                          color_format: int = L.COLOR_RGBA16F) -> None:
+                          color_format: int = L.COLOR_RGBA16F, batched: bool = False) -> None:
         """Torch tensors on this context's device, composited in place (meao_composite_pitched / meao_composite_enqueue_pitched).
         ao: an (N, H, W) tensor or a list of (H, W) in the AO dtype (uint8 for R8, float16 for F16 storage); color: (N, H, W, 4)
         int16 / float16 holding RGBA16F; gbuffer0: (N, H, W, 4) uint8, for COMPOSITE_AMBIENT_ONLY -- e.g. crops
@@ -289,16 +332,22 @@ class AmbientOcclusion:
         and all frames of a surface must share one row stride, which becomes its pitch; any other layout raises ValueError
         (nothing is copied).  enqueue=False: one composite per frame now, on torch.cuda.current_stream(); enqueue=True: the
         batch waits for the next execute's render kernel (composite_enqueue_device).  color_format: another meao_color_format
-        for ``color`` -- (N, H, W, 4) float32 for RGBA32F or uint8 for RGBA8, (N, H, W) int32 for R11G11B10F."""
+        for ``color`` -- (N, H, W, 4) float32 for RGBA32F or uint8 for RGBA8, (N, H, W) int32 for R11G11B10F.  batched=True (with
+        enqueue=False): the frames in one launch now (composite_batch_device) instead of one launch each."""
         import torch
         from .surfaces import composite_surfaces
         ao_dt = torch.uint8 if self._cfg.ao_format == L.AO_R8 else torch.float16
         dev = torch.device("cuda", self._cfg.device)
         a, ap, c, cp, g, gp = composite_surfaces(ao, color, gbuffer0, self.height, self.width, ao_dt, device=dev, color_format=color_format)
         if enqueue:
+            if batched:
+                raise ValueError("composite_tensors: batched=True composites now; it cannot be combined with enqueue=True")
             self.composite_enqueue_device(mode, a, c, g, ao_pitch=ap, color_pitch=cp, gbuffer0_pitch=gp, color_format=color_format)
             return
         stream = torch.cuda.current_stream(dev).cuda_stream
+        if batched:
+            self.composite_batch_device(mode, a, c, g, stream, ao_pitch=ap, color_pitch=cp, gbuffer0_pitch=gp, color_format=color_format)
+            return
         for f in range(len(a)):
             self.composite_device(mode, a[f], c[f], g[f] if g else 0, stream, ao_pitch=ap, color_pitch=cp, gbuffer0_pitch=gp,
                                   color_format=color_format)
@@ -467,6 +516,21 @@ class AmbientOcclusionPool:
         else:
             self._check(self._lib.meao_pool_execute_batch_params(self._pool, n, pin, L.MEM_DEVICE, pout, L.MEM_DEVICE,
                                                                  params_array(params, n, self._prm)))
+
+    def execute_shaded_device(self, depth_ptrs: Sequence[int], out_ptrs: Sequence[int], mode: int, color_ptrs: Sequence[int],
+                              gbuffer0_ptrs: Optional[Sequence[int]] = None,
+                              params: Optional[Sequence[Optional[FrameParams]]] = None, *, depth_pitch: int = 0, out_pitch: int = 0,
+                              color_pitch: int = 0, gbuffer0_pitch: int = 0, color_format: int = L.COLOR_RGBA16F) -> None:
+        """AmbientOcclusion.execute_shaded_device for the pool (meao_pool_execute_batch_shaded): frame f resident on
+        device_of_frame(f); each member runs its execute and one batched composite launch.  Asynchronous (synchronize())."""
+        n = len(depth_ptrs)
+        if len(out_ptrs) != n or len(color_ptrs) != n or (gbuffer0_ptrs and len(gbuffer0_ptrs) != n):
+            raise ValueError("execute_shaded_device: one AO, one colour (and one GBuffer0) surface per depth frame")
+        prm = None if params is None else params_array(params, n, self._prm)
+        g = (C.c_void_p * n)(*gbuffer0_ptrs) if gbuffer0_ptrs else None
+        self._check(self._lib.meao_pool_execute_batch_shaded(self._pool, n, (C.c_void_p * n)(*depth_ptrs), depth_pitch,
+                                                             (C.c_void_p * n)(*out_ptrs), out_pitch, prm, mode,
+                                                             (C.c_void_p * n)(*color_ptrs), color_format, color_pitch, g, gbuffer0_pitch))
 
     def prefetch_device(self, depth_ptrs: Sequence[int], params: Optional[Sequence[Optional[FrameParams]]] = None, *,
                         depth_pitch: int = 0) -> None:

@@ -94,6 +94,15 @@ struct meao_ctx {
     int32_t pending_comp_format = MEAO_COLOR_RGBA16F;     // meao_color_format of its colour surfaces; only an RGBA16F batch is ever carried
     hipStream_t pending_stream = nullptr;
 
+    // The batched composite's tables (meao_composite_batch / meao_execute_batch_shaded): a ring of CompositeFrame tables
+    // (max_batch entries each), handled like the FrameArgs ring below: built in pinned host memory, copied to the device slot on
+    // the call's stream, both reused once the event recorded behind that call's launch has completed.  Allocated by meao_create.
+    static constexpr int kCompRing = 8;
+    CompositeFrame *comp_table = nullptr, *comp_stage = nullptr;
+    hipEvent_t comp_ev[kCompRing] = {};
+    bool comp_ev_pending[kCompRing] = {};
+    int comp_ring_pos = 0;
+
 #if MEAO_TESTING
     int debug_fail_allocs = 0;         // meao_test_fail_next_allocs: arena allocations still to fail (testhooks variant only)
 #endif
@@ -999,6 +1008,14 @@ int32_t meao_create(const meao_config *cfg, meao_ctx **out_ctx)
         for (int i = 0; e == hipSuccess && i < meao_ctx::kFrameRing; ++i) e = hipEventCreateWithFlags(&ctx->frame_ev[i], hipEventDisableTiming);
         if (e != hipSuccess) rc = fail_hip(ctx, e, "per-frame constant tables");
     }
+    if (rc == MEAO_OK) {
+        // the batched composite's frame tables (meao_composite_batch): the same kind of ring
+        const size_t bytes = sizeof(CompositeFrame) * meao_ctx::kCompRing * cfg->max_batch;
+        e = hipMalloc(reinterpret_cast<void **>(&ctx->comp_table), bytes);
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&ctx->comp_stage), bytes, hipHostMallocDefault);
+        for (int i = 0; e == hipSuccess && i < meao_ctx::kCompRing; ++i) e = hipEventCreateWithFlags(&ctx->comp_ev[i], hipEventDisableTiming);
+        if (e != hipSuccess) rc = fail_hip(ctx, e, "batched composite tables");
+    }
     // cfg.pipelined: the second downsample set exists from the start, so meao_prefetch_batch never re-allocates
     if (rc == MEAO_OK) rc = reallocate(ctx, *cfg, cfg->pipelined != 0);
     if (rc != MEAO_OK) {
@@ -1027,6 +1044,10 @@ int32_t meao_destroy(meao_ctx *ctx)
     if (ctx->frame_table) (void)hipFree(ctx->frame_table);
     if (ctx->frame_stage) (void)hipHostFree(ctx->frame_stage);
     for (hipEvent_t e : ctx->frame_ev)
+        if (e) (void)hipEventDestroy(e);
+    if (ctx->comp_table) (void)hipFree(ctx->comp_table);
+    if (ctx->comp_stage) (void)hipHostFree(ctx->comp_stage);
+    for (hipEvent_t e : ctx->comp_ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->roctx_lib) (void)dlclose(ctx->roctx_lib);
     for (hipEvent_t ev : ctx->events) (void)hipEventDestroy(ev);
@@ -1122,9 +1143,9 @@ void meao::drop_announcement(meao_ctx *ctx, bool ready_too)
     if (ready_too) drop_prefetch(ctx);
 }
 
-int meao::execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
-                                 int32_t out_loc, meao_stream stream_, bool wait_for_host, const meao_params *params,
-                                 uint64_t depth_pitch, uint64_t ao_pitch)
+// Every check of an execute call, before anything is enqueued; the row strides in texels on success.
+static int validate_execute_batch(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out, int32_t out_loc,
+                                  const meao_params *params, uint64_t depth_pitch, uint64_t ao_pitch, int32_t *depth_rows, int32_t *out_rows)
 {
     if (!ctx || !depth || !ao_out) return MEAO_ERR_INVALID_ARGUMENT;
     if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_execute_batch: n must be 1..max_batch");
@@ -1137,10 +1158,18 @@ int meao::execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *de
         const int vr = validate_frame_params(ctx, n, params, "meao_execute_batch_params");
         if (vr != MEAO_OK) return vr;
     }
+    int vr = pitch_texels(ctx, depth_pitch, depth_elem(ctx->cfg.depth_format), "meao_execute_batch_pitched: depth_pitch", depth_rows);
+    if (vr == MEAO_OK) vr = pitch_texels(ctx, ao_pitch, ao_elem(ctx->cfg), "meao_execute_batch_pitched: ao_pitch", out_rows);
+    return vr;
+}
+
+int meao::execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
+                                 int32_t out_loc, meao_stream stream_, bool wait_for_host, const meao_params *params,
+                                 uint64_t depth_pitch, uint64_t ao_pitch)
+{
     int32_t depth_rows = 0, out_rows = 0;     // row strides in texels
     {
-        int vr = pitch_texels(ctx, depth_pitch, depth_elem(ctx->cfg.depth_format), "meao_execute_batch_pitched: depth_pitch", &depth_rows);
-        if (vr == MEAO_OK) vr = pitch_texels(ctx, ao_pitch, ao_elem(ctx->cfg), "meao_execute_batch_pitched: ao_pitch", &out_rows);
+        const int vr = validate_execute_batch(ctx, n, depth, depth_loc, ao_out, out_loc, params, depth_pitch, ao_pitch, &depth_rows, &out_rows);
         if (vr != MEAO_OK) return vr;
     }
     int rc = use_device(ctx);
@@ -1649,7 +1678,99 @@ int meao::composite_enqueue_internal(meao_ctx *ctx, const char *fn, int32_t mode
     return MEAO_OK;
 }
 
+// The batched composite: frames 0 .. n-1 in ONE composite_kernel launch on `stream` (every argument already validated).  Their
+// origins go through a slot of the context's table ring; one form (vector or per-texel) for the whole batch, as for an enqueued one.
+static int composite_batch_launch(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, void *const *color, int32_t color_format,
+                                  void *const *gbuffer0_rgba8, CompositePitches pitch, hipStream_t stream)
+{
+    const int slot = ctx->comp_ring_pos;
+    ctx->comp_ring_pos = (ctx->comp_ring_pos + 1) % meao_ctx::kCompRing;
+    // back-pressure only: the slot's call is kCompRing calls old
+    if (ctx->comp_ev_pending[slot]) {
+        MEAO_HIP(ctx, hipEventSynchronize(ctx->comp_ev[slot]));
+        ctx->comp_ev_pending[slot] = false;
+    }
+    CompositeFrame *stage = ctx->comp_stage + static_cast<size_t>(slot) * ctx->cfg.max_batch;
+    CompositeFrame *dev = ctx->comp_table + static_cast<size_t>(slot) * ctx->cfg.max_batch;
+    for (int f = 0; f < n; ++f) {
+        stage[f] = CompositeFrame{ao[f], color[f], gbuffer0_rgba8 ? gbuffer0_rgba8[f] : nullptr};
+        pitch.vec = pitch.vec && composite_vec_base(ctx, ao[f], color[f], color_format);
+    }
+    CompositeArgs ca{};
+    ca.pixels = static_cast<int64_t>(ctx->cfg.width) * ctx->cfg.height;
+    ca.mode = mode;
+    ca.pitch = pitch;
+    ca.color_format = color_format;
+    ca.frames = dev;
+    hipError_t e = hipMemcpyAsync(dev, stage, sizeof(CompositeFrame) * n, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = launch_composite(ca, ctx->cfg.ao_format, stream, n);
+    // the slot is handed back guarded whatever happened: the copy may be in flight
+    if (hipEventRecord(ctx->comp_ev[slot], stream) == hipSuccess) {
+        ctx->comp_ev_pending[slot] = true;
+    } else {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(stream);
+    }
+    if (e != hipSuccess) return fail_hip(ctx, e, "composite_batch_launch");
+    return MEAO_OK;
+}
+
+// The checks of a batched composite under the name `fn`: n against the context's max_batch (the tables' size), then those of
+// meao_composite_enqueue_format.  Touches nothing.
+static int composite_batch_validate(meao_ctx *ctx, const char *fn, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
+                                    void *const *color, int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8,
+                                    uint64_t gbuffer0_pitch, CompositePitches *pitch)
+{
+    if (!ctx || !ao || !color) return MEAO_ERR_INVALID_ARGUMENT;
+    if (n < 1 || n > ctx->cfg.max_batch) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": n must be 1..max_batch");
+    const int rc = meao::composite_enqueue_internal(ctx, fn, mode, n, ao, ao_pitch, color, color_format, color_pitch, gbuffer0_rgba8,
+                                                    gbuffer0_pitch, true);
+    if (rc != MEAO_OK) return rc;
+    return composite_pitches(ctx, fn, ao_pitch, color_format, color_pitch, gbuffer0_pitch, gbuffer0_rgba8 != nullptr, pitch);
+}
+
+int meao::execute_batch_shaded_internal(meao_ctx *ctx, const char *fn, int32_t n, const void *const *depth, uint64_t depth_pitch,
+                                        void *const *ao_out, uint64_t ao_pitch, const meao_params *params, int32_t mode,
+                                        void *const *color, int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8,
+                                        uint64_t gbuffer0_pitch, meao_stream stream_, bool validate_only)
+{
+    if (!ctx || !depth || !ao_out || !color) return MEAO_ERR_INVALID_ARGUMENT;
+    // both halves' checks before anything is enqueued: a refused call launches nothing
+    int32_t depth_rows = 0, out_rows = 0;
+    int rc = validate_execute_batch(ctx, n, depth, MEAO_MEM_DEVICE, ao_out, MEAO_MEM_DEVICE, params, depth_pitch, ao_pitch, &depth_rows, &out_rows);
+    if (rc != MEAO_OK) return fail(ctx, rc, std::string(fn) + ": " + ctx->err);      // the execute half's message, under this call's name
+    CompositePitches pitch{};
+    rc = composite_batch_validate(ctx, fn, mode, n, ao_out, ao_pitch, color, color_format, color_pitch, gbuffer0_rgba8, gbuffer0_pitch, &pitch);
+    if (rc != MEAO_OK || validate_only) return rc;
+    rc = execute_batch_internal(ctx, n, depth, MEAO_MEM_DEVICE, ao_out, MEAO_MEM_DEVICE, stream_, false, params, depth_pitch, ao_pitch);
+    if (rc != MEAO_OK) return rc;
+    // behind the last AO kernel on the same stream (ctx->last_stream is the one the execute just ran on)
+    return composite_batch_launch(ctx, mode, n, ao_out, color, color_format, gbuffer0_rgba8, pitch, ctx->last_stream);
+}
+
 extern "C" {
+
+int32_t meao_composite_batch(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch, void *const *color,
+                             int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch,
+                             meao_stream stream_)
+{
+    CompositePitches pitch{};
+    int rc = composite_batch_validate(ctx, "meao_composite_batch", mode, n, ao, ao_pitch, color, color_format, color_pitch, gbuffer0_rgba8,
+                                      gbuffer0_pitch, &pitch);
+    if (rc != MEAO_OK) return rc;
+    rc = use_device(ctx);
+    if (rc != MEAO_OK) return rc;
+    return composite_batch_launch(ctx, mode, n, ao, color, color_format, gbuffer0_rgba8, pitch,
+                                  stream_ ? static_cast<hipStream_t>(stream_) : ctx->own_stream);
+}
+
+int32_t meao_execute_batch_shaded(meao_ctx *ctx, int32_t n, const void *const *depth, uint64_t depth_pitch, void *const *ao_out,
+                                  uint64_t ao_pitch, const meao_params *params, int32_t mode, void *const *color, int32_t color_format,
+                                  uint64_t color_pitch, void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch, meao_stream stream_)
+{
+    return meao::execute_batch_shaded_internal(ctx, "meao_execute_batch_shaded", n, depth, depth_pitch, ao_out, ao_pitch, params, mode, color,
+                                               color_format, color_pitch, gbuffer0_rgba8, gbuffer0_pitch, stream_, false);
+}
 
 int32_t meao_composite(meao_ctx *ctx, int32_t mode, const void *ao, void *color_rgba16f, void *gbuffer0_rgba8,
                        int32_t loc, meao_stream stream_)

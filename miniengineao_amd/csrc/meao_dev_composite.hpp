@@ -291,20 +291,30 @@ __device__ __forceinline__ void composite_format_row(const void *ao_base, void *
         composite_format_texel<AOFMT, CFMT>(ao_base, color_base, gbuffer0_base, ao_at, color_at, g_at, mode, x);
 }
 
-// A frame in colour format CFMT: tightly packed = one row of `pixels` texels for the whole grid, else rows as in the RGBA16F form.
+// A frame in colour format CFMT: tightly packed = one row of `pixels` texels for the frame's workgroups, else rows as in the RGBA16F form.
 template <int AOFMT, int CFMT>
-__device__ __forceinline__ void composite_format_frame(const CompositeArgs &a)
+__device__ __forceinline__ void composite_format_frame(const CompositeArgs &a, const void *ao, void *color, void *gbuffer0)
 {
     if (!a.pitch.on) {
-        composite_format_row<AOFMT, CFMT>(a.ao, a.color, a.gbuffer0, 0u, 0u, 0u, static_cast<uint32_t>(a.pixels), a.pitch.vec != 0, a.mode,
+        composite_format_row<AOFMT, CFMT>(ao, color, gbuffer0, 0u, 0u, 0u, static_cast<uint32_t>(a.pixels), a.pitch.vec != 0, a.mode,
                                           blockIdx.x * kThreads + threadIdx.x, gridDim.x * kThreads);
         return;
     }
     const uint32_t lanes = 1u << a.row_lanes_log2, rows = static_cast<uint32_t>(kThreads) >> a.row_lanes_log2;
     for (uint32_t row = blockIdx.x * rows + (threadIdx.x >> a.row_lanes_log2); row < static_cast<uint32_t>(a.pitch.h); row += gridDim.x * rows)
-        composite_format_row<AOFMT, CFMT>(a.ao, a.color, a.gbuffer0, __umul24(row, a.pitch.ao), __umul24(row, a.pitch.color),
+        composite_format_row<AOFMT, CFMT>(ao, color, gbuffer0, __umul24(row, a.pitch.ao), __umul24(row, a.pitch.color),
                                           __umul24(row, a.pitch.gbuffer0), static_cast<uint32_t>(a.pitch.w), a.pitch.vec != 0, a.mode,
                                           threadIdx.x & (lanes - 1u), lanes);
+}
+
+// Entry `frame` of the batched form's table (meao_composite_batch).  Read through the constant address space, as frame_block
+// reads the FrameArgs table: written by a copy ordered before the launch and never during it, so the three origins are
+// workgroup-uniform scalar loads.
+__device__ __forceinline__ const CompositeFrame &composite_frame(const CompositeFrame *table, uint32_t frame)
+{
+    typedef const __attribute__((address_space(4))) char *const_bytes;
+    const const_bytes p = (const_bytes)table + static_cast<uint32_t>(sizeof(CompositeFrame)) * frame;
+    return *(const CompositeFrame *)p;
 }
 
 }  // namespace

@@ -122,24 +122,32 @@ __global__ __launch_bounds__(kThreads) void debug_view_kernel(const DebugViewArg
 template <int AOFMT>
 __global__ __launch_bounds__(kThreads) void composite_kernel(const CompositeArgs a)
 {
+    // The frame is the grid's y: a batched launch (meao_composite_batch) takes frame blockIdx.y's origins from the table, a
+    // single-frame launch (one y, no table) its own from the kernarg.  Within a frame the x workgroups deal it as ever.
+    const void *ao = a.ao;
+    void *color = a.color, *gbuffer0 = a.gbuffer0;
+    if (a.frames != nullptr) {
+        const CompositeFrame &t = composite_frame(a.frames, blockIdx.y);
+        ao = t.ao; color = t.color; gbuffer0 = t.gbuffer0;
+    }
     // one lane = 2 texels = one 16-byte colour load/store; consecutive lanes are contiguous
     if (__builtin_expect((a.pitch.on | a.color_format) == 0, 1)) {     // tightly packed RGBA16F: laid out first, the kernel's entry falls through into it
         const int64_t pairs = (a.pixels + 1) / 2;
         for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < pairs;
              q += static_cast<int64_t>(gridDim.x) * kThreads)
-            composite_pair<AOFMT>(a.ao, a.color, a.gbuffer0, a.pixels, a.mode, q);
+            composite_pair<AOFMT>(ao, color, gbuffer0, a.pixels, a.mode, q);
         return;
     }
     if (a.color_format != MEAO_COLOR_RGBA16F) {     // kernel-uniform: the other colour formats (meao_composite_format), packed and pitched
-        if (a.color_format == MEAO_COLOR_RGBA32F) composite_format_frame<AOFMT, MEAO_COLOR_RGBA32F>(a);
-        else if (a.color_format == MEAO_COLOR_RGBA8) composite_format_frame<AOFMT, MEAO_COLOR_RGBA8>(a);
-        else composite_format_frame<AOFMT, MEAO_COLOR_R11G11B10F>(a);
+        if (a.color_format == MEAO_COLOR_RGBA32F) composite_format_frame<AOFMT, MEAO_COLOR_RGBA32F>(a, ao, color, gbuffer0);
+        else if (a.color_format == MEAO_COLOR_RGBA8) composite_format_frame<AOFMT, MEAO_COLOR_RGBA8>(a, ao, color, gbuffer0);
+        else composite_format_frame<AOFMT, MEAO_COLOR_R11G11B10F>(a, ao, color, gbuffer0);
         return;
     }
     // kernel-uniform: row-pitched surfaces, rows dealt to (2^row_lanes_log2 lanes x rows) workgroups
     const uint32_t lanes = 1u << a.row_lanes_log2, rows = static_cast<uint32_t>(kThreads) >> a.row_lanes_log2;
     for (uint32_t row = blockIdx.x * rows + (threadIdx.x >> a.row_lanes_log2); row < static_cast<uint32_t>(a.pitch.h); row += gridDim.x * rows)
-        composite_row<AOFMT>(a.ao, a.color, a.gbuffer0, a.pitch, a.mode, row, threadIdx.x & (lanes - 1u), lanes);
+        composite_row<AOFMT>(ao, color, gbuffer0, a.pitch, a.mode, row, threadIdx.x & (lanes - 1u), lanes);
 }
 
 // which = 4: rcp_strict, 5: div_const<3>, div_const<9>, 6: div_strict on hashed operand pairs, 8: f32_to_ufloat<6|5> (the R11G11B10F stores)
@@ -267,7 +275,7 @@ hipError_t launch_debug_view(const DebugViewArgs &a, int ao_format, hipStream_t 
     return hipGetLastError();
 }
 
-hipError_t launch_composite(const CompositeArgs &args, int ao_format, hipStream_t s)
+hipError_t launch_composite(const CompositeArgs &args, int ao_format, hipStream_t s, int frames)
 {
     CompositeArgs a = args;
     // what one lane takes at a time: a texel pair (RGBA16F), a 16-byte group of 1 or 4 texels (the other formats' vector form), a texel
@@ -281,8 +289,9 @@ hipError_t launch_composite(const CompositeArgs &args, int ao_format, hipStream_
         const int rows = kThreads >> a.row_lanes_log2;
         blocks = std::min((a.pitch.h + rows - 1) / rows, 256 * 32);
     }
-    if (ao_format == MEAO_AO_R8) composite_kernel<MEAO_AO_R8><<<dim3(blocks), dim3(kThreads), 0, s>>>(a);
-    else composite_kernel<MEAO_AO_F16><<<dim3(blocks), dim3(kThreads), 0, s>>>(a);
+    // every frame of a batched launch gets the workgroups a launch of its own would: grid y = the frame
+    if (ao_format == MEAO_AO_R8) composite_kernel<MEAO_AO_R8><<<dim3(blocks, frames), dim3(kThreads), 0, s>>>(a);
+    else composite_kernel<MEAO_AO_F16><<<dim3(blocks, frames), dim3(kThreads), 0, s>>>(a);
     return hipGetLastError();
 }
 

@@ -259,6 +259,12 @@ struct CompositePitches {
     int32_t w, h;
     int32_t on, vec;
 };
+// One entry of the batched form's table: where a frame's AO, colour and GBuffer0 (or null) surfaces start.
+struct CompositeFrame {
+    const void *ao;
+    void *color;
+    void *gbuffer0;
+};
 struct CompositeArgs {
     const void *ao;
     void *color;
@@ -268,8 +274,13 @@ struct CompositeArgs {
     CompositePitches pitch;
     int32_t row_lanes_log2;     // pitched form, filled by the launcher: a workgroup is 2^row_lanes_log2 lanes along a row
     int32_t color_format;       // meao_color_format of `color`; pitch.color is in texels of it (in what was the struct's tail padding)
+    // The batched form (meao_composite_batch): frame blockIdx.y's origins from this table in device memory, written by a copy
+    // ordered before the launch; ao / color / gbuffer0 above are then unused.  nullptr = the single-frame launch, which reads
+    // nothing more than it did (one more kernarg pointer, tested once per workgroup).
+    const CompositeFrame *frames;
 };
-hipError_t launch_composite(const CompositeArgs &a, int ao_format, hipStream_t s);
+// frames: the launch's frames, a.frames[0 .. frames) (a.frames null: the single-frame launch, frames = 1).
+hipError_t launch_composite(const CompositeArgs &a, int ao_format, hipStream_t s, int frames = 1);
 // A batch of composites carried by a render launch (meao_composite_enqueue): frame f = ao[f] x color[f].
 struct CompositeBatchArgs {
     const void *ao[MEAO_MAX_BATCH];
@@ -298,6 +309,12 @@ int execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *depth, i
 int composite_enqueue_internal(meao_ctx *ctx, const char *fn, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
                                void *const *color, int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8,
                                uint64_t gbuffer0_pitch, bool validate_only);
+// meao_api.cpp, for meao_pool.cpp: meao_execute_batch_shaded under the name `fn`; validate_only = every check of both halves and
+// nothing else (no device is touched; AO, colour, an announcement and a waiting batch stay as they are).
+int execute_batch_shaded_internal(meao_ctx *ctx, const char *fn, int32_t n, const void *const *depth, uint64_t depth_pitch,
+                                  void *const *ao_out, uint64_t ao_pitch, const meao_params *params, int32_t mode, void *const *color,
+                                  int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch,
+                                  meao_stream stream, bool validate_only);
 // meao_api.cpp, for meao_pool.cpp: what a member that is dealt no frame of a pool call does instead of that call.
 // ready_too = false (a pool announcement passed it by): an announcement it still holds is withdrawn, as a newer one would
 // replace it.  ready_too = true (a pool execute passed it by): a ready prefetched set goes as well -- the pool-level "call

@@ -534,6 +534,46 @@ int32_t meao_pool_prefetch_batch_pitched(meao_pool *p, int32_t n, const void *co
     return pool_prefetch_batch(p, n, depth, params, depth_pitch);
 }
 
+// Every member's share is validated (both halves) before any member enqueues; then each member that is dealt frames runs its
+// execute and its one batched composite launch from its worker thread.
+int32_t meao_pool_execute_batch_shaded(meao_pool *p, int32_t n, const void *const *depth, uint64_t depth_pitch, void *const *ao_out,
+                                       uint64_t ao_pitch, const meao_params *params, int32_t mode, void *const *color, int32_t color_format,
+                                       uint64_t color_pitch, void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch)
+{
+    static const char fn[] = "meao_pool_execute_batch_shaded";
+    if (!p || !depth || !ao_out || !color) return MEAO_ERR_INVALID_ARGUMENT;
+    const int32_t G = static_cast<int32_t>(p->ctx.size());
+    if (n < 1 || n > p->max_batch * G) return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": n must be 1..max_batch * members");
+    if (params) {
+        const int32_t rc = pool_check_params(p, n, params, fn);
+        if (rc != MEAO_OK) return rc;
+    }
+    DeviceGuard guard;
+    int32_t failed = -1;
+    int32_t status = MEAO_OK;
+    for (int pass = 0; pass < 2 && status == MEAO_OK; ++pass) {
+        status = for_each_member(p, [&](int32_t m) -> int32_t {
+            const void *d[MEAO_MAX_BATCH];
+            void *o[MEAO_MAX_BATCH], *c[MEAO_MAX_BATCH], *g[MEAO_MAX_BATCH];
+            const int32_t k = share_of(m, G, n, depth, d);
+            share_of(m, G, n, ao_out, o);
+            share_of(m, G, n, color, c);
+            if (gbuffer0_rgba8) share_of(m, G, n, gbuffer0_rgba8, g);
+            if (k == 0) return MEAO_OK;
+            meao_params prm[MEAO_MAX_BATCH];
+            if (params)
+                for (int32_t f = m, i = 0; f < n; f += G) prm[i++] = params[f];
+            return meao::execute_batch_shaded_internal(p->ctx[m], fn, k, d, depth_pitch, o, ao_pitch, params ? prm : nullptr, mode, c, color_format,
+                                                       color_pitch, gbuffer0_rgba8 ? g : nullptr, gbuffer0_pitch, p->stream[m], pass == 0);
+        }, pass == 1, &failed);
+        if (status != MEAO_OK)
+            return pool_fail(p, status, std::string(fn) + ": member " + std::to_string(failed) + ": " + meao_last_error(p->ctx[failed]));
+    }
+    // members that were dealt no frame: as in meao_pool_execute_batch
+    for (int32_t m = n; m < G; ++m) meao::drop_announcement(p->ctx[m], true);
+    return status;
+}
+
 // pitched: the pitches go to every member and every member's share is validated before any member enqueues.
 static int32_t pool_composite_enqueue(meao_pool *p, const char *fn, bool pitched, int32_t mode, int32_t n, const void *const *ao,
                                       uint64_t ao_pitch, void *const *color_rgba16f, int32_t color_format, uint64_t color_pitch,

@@ -1,0 +1,116 @@
+"""meao_composite_batch, meao_execute_batch_shaded and meao_pool_execute_batch_shaded: the ABI surface in every binding, what
+needs no device of their argument checks, and the rule that the batched form lives inside composite_kernel<0|1>: no new
+instantiation, the resources of the two kernels as they were."""
+import ctypes as C
+import json
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+from miniengineao_amd import _lib as L
+from tests import kernel_inventory as K
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = open(os.path.join(ROOT, "include", "meao.h")).read()
+
+NEW = {"meao_composite_batch": 11, "meao_execute_batch_shaded": 14, "meao_pool_execute_batch_shaded": 13}
+
+
+@pytest.mark.parametrize("name", sorted(NEW))
+def test_entry_point_in_the_header(name):
+    m = re.search(r"MEAO_API\s+int32_t\s+%s\s*\((.*?)\);" % name, HEADER, re.S)
+    assert m, name
+    args = [" ".join(a.split()) for a in m.group(1).split(",")]
+    assert len(args) == NEW[name], args
+    at = args.index("int32_t color_format")
+    assert args[at - 1].endswith("color") and args[at + 1] == "uint64_t color_pitch"
+    for pitch in ("uint64_t ao_pitch", "uint64_t color_pitch", "uint64_t gbuffer0_pitch"):
+        assert pitch in args, (name, pitch)
+    assert ("meao_stream stream" in args) == (not name.startswith("meao_pool")), args
+    if "shaded" in name:
+        assert "uint64_t depth_pitch" in args and "const meao_params *params" in args
+
+
+def test_the_contracts_are_in_the_header():
+    text = " ".join(HEADER.split())
+    for phrase in ("ONE composite_kernel launch", "before anything is enqueued", "must not overlap", "neither run nor disturbed",
+                   "meao_composite_pending is unchanged"):
+        assert phrase in text, phrase
+
+
+@pytest.mark.parametrize("name", sorted(NEW))
+def test_entry_point_in_every_binding(name):
+    assert len(L.SIGNATURES[name][1]) == NEW[name]
+    cs = open(os.path.join(ROOT, "bindings", "csharp", "MeaoNative.cs")).read()
+    m = re.search(r"public static extern int %s\((.*?)\);" % name, cs)
+    assert m and len(m.group(1).split(",")) == NEW[name] and "int color_format" in m.group(1), name
+    assert "%s(" % name in open(os.path.join(ROOT, "include", "meao.hpp")).read()
+    if not name.startswith("meao_pool"):
+        assert "Meao.%s(" % name in open(os.path.join(ROOT, "bindings", "csharp", "AmbientOcclusionOverMeao.cs")).read()
+
+
+def test_abi_version_sizes_and_exports(meao_lib):
+    assert re.search(r"#define MEAO_ABI_VERSION 7\b", HEADER) and L.ABI_VERSION == 7
+    assert meao_lib.meao_abi_version() == 7
+    assert C.sizeof(L.Config) == 12 * 4 and C.sizeof(L.Params) == 11 * 4 and C.sizeof(L.Desc) == 32
+    for name in NEW:
+        assert hasattr(meao_lib, name), name
+
+
+def test_entry_points_reject_null_handles(meao_lib):
+    ptr = (C.c_void_p * 1)(None)
+    E = L.ERR_INVALID_ARGUMENT
+    assert meao_lib.meao_composite_batch(None, 0, 1, ptr, 0, ptr, 2, 0, None, 0, None) == E
+    assert meao_lib.meao_execute_batch_shaded(None, 1, ptr, 0, ptr, 0, None, 0, ptr, 2, 0, None, 0, None) == E
+    assert meao_lib.meao_pool_execute_batch_shaded(None, 1, ptr, 0, ptr, 0, None, 0, ptr, 2, 0, None, 0) == E
+
+
+def test_python_mirrors_keep_the_old_signatures():
+    import inspect
+    from miniengineao_amd import AmbientOcclusion, AmbientOcclusionPool
+    sig = inspect.signature(AmbientOcclusion.execute_tensors).parameters
+    assert list(sig)[:4] == ["self", "depth", "out", "params"] and sig["color"].default is None
+    assert all(sig[k].kind is inspect.Parameter.KEYWORD_ONLY for k in ("color", "gbuffer0", "mode", "color_format"))
+    sig = inspect.signature(AmbientOcclusion.composite_tensors).parameters
+    assert list(sig)[:7] == ["self", "ao", "color", "gbuffer0", "mode", "enqueue", "color_format"] and sig["batched"].default is False
+    assert sig["enqueue"].default is False
+    for cls in (AmbientOcclusion, AmbientOcclusionPool):
+        assert callable(getattr(cls, "execute_shaded_device"))
+    assert callable(AmbientOcclusion.composite_batch_device)
+
+
+# ---- the kernels: nothing new, the two that changed inside what they had
+
+COMPOSITE_KERNELS = {"composite_kernel<0>", "composite_kernel<1>"} | {
+    "render_with_composite_kernel<%s, %s, %s>" % col for col in K.COLUMNS}
+
+
+@pytest.fixture(scope="module")
+def rows():
+    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
+        pytest.skip("no hipcc here: the compile-time resource table cannot be produced")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "--json"],
+                         capture_output=True, text=True, check=True, cwd=ROOT, timeout=900)
+    return {r["name"]: r for r in json.loads(out.stdout)}
+
+
+def test_no_new_kernel_instantiation(rows):
+    """The library's inventory (tests/kernel_inventory.py, what the coverage tests launch name by name) is what the sources compile
+    to, and the kernels that composite are the eight there were: the batched form added none."""
+    names = K.instantiations()
+    assert {n for n in names if "composite" in n} == COMPOSITE_KERNELS
+    assert set(names) == set(rows), sorted(set(names) ^ set(rows))
+    assert len(names) == len(set(names))
+
+
+@pytest.mark.parametrize("name", ["composite_kernel<0>", "composite_kernel<1>"])
+def test_composite_kernels_keep_their_resources(rows, name):
+    r = rows[name]
+    assert int(r["Occupancy [waves/SIMD]"]) == 8, r
+    assert int(r["ScratchSize [bytes/lane]"]) == 0 and r["Dynamic Stack"] == "False", r
+    assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0 and int(r["LDS Size [bytes/block]"]) == 0, r
+    assert int(r["VGPRs"]) <= 64 and int(r["AGPRs"]) == 0, r       # (37 / 38 before and after the batched form)
