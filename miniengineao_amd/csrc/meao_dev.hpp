@@ -35,6 +35,10 @@
 #endif                             // inside the frame never reads LowDepth1 -- the 32 x 32 interior of its window ARE the pre-rounding values of its own
                                    // even-even raw texels (DS1:64-70), which hi_depth_words has in registers, and the 3-texel apron is linearized from
                                    // raw texels of the neighbouring tiles' lines (L2 hits: they are those tiles' HiResDB): 8.3 MB per 4K frame less
+#ifndef MEAO_X_WHITE_TILES
+#define MEAO_X_WHITE_TILES 1       // 0 = every tile of the full-resolution pass runs its blur and bilateral phases (the form up to round 6; variant
+#endif                             // `nowhite`).  1: a tile of the UNORM8 exact-reciprocal instance whose low-res AO window is all code 255 and whose
+                                   // lanes are all clean stores 255 behind the first barrier (upsample_tile, "white tile"; proof there)
 #ifndef MEAO_X_HOT_PATH_ONLY
 #define MEAO_X_HOT_PATH_ONLY 0  // ANALYSIS builds only (tools/kernel_isa.py -DMEAO_X_HOT_PATH_ONLY=1 --stats; never a library): the upsample
 #endif                          // and render kernels keep nothing but the path an interior tile of a clean frame takes, so that the
@@ -48,7 +52,7 @@
 #error "MEAO_X_PHASE_CLOCKS needs the single-translation-unit build (meao_kernels.hip): its device counters are one set of globals"
 #endif
 // [phase] summed 100 MHz ticks and [32 + phase] wave counts, per upsample-tile phase (0..7 full-resolution pass,
-// 8..15 blend passes); read and cleared by meao_x_phase_clocks
+// 8..15 blend passes, 23 the white path of a full-resolution tile); read and cleared by meao_x_phase_clocks
 __device__ unsigned long long g_phase_clocks[64];
 extern "C" __attribute__((visibility("default"))) int meao_x_phase_clocks(unsigned long long *out64)
 {

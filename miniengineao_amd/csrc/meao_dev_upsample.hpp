@@ -728,6 +728,43 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
     static_assert(!PITCHED || (FINAL && !NESTED), "only the full-resolution pass addresses caller memory");
     const int raw_pitch = PITCHED ? a.pitch.depth : hw, dst_pitch = PITCHED ? a.pitch.dst : hw;     // row strides of caller memory
 
+    // White tiles (MEAO_X_WHITE_TILES): a tile of the full-resolution pass whose low-res AO window -- the kRawW x kRawH taps, clamp-
+    // addressed as loaded -- holds code 255 in every texel, and whose lanes are all clean (hi_depth_words), stores code 255 to
+    // every texel behind the first barrier: no blur, no bilateral phase, two barriers fewer.  That IS the reference's result:
+    //   taps      unorm8_to_f32(255) = 255 / 255 correctly rounded = 1.0, every tap of the window.
+    //   blur      blur_run only SELECTS among its five taps (pa..pe are each one of a[n..n+4]; `keep`, whatever the depths make of
+    //             it -- NaN, inf included -- chooses which) and forms ((fma(pa + pe, 0.5, pb) + pc) + pd) * 0.25 = ((2 + 1) + 1) * 0.25
+    //             = 1.0 exactly.  The H-blurred rows are all 1.0, so the V-blurred ones are: every blurred AO the bilateral phase
+    //             gathers (rows / columns 0..kBlur-1, all inside the window) is 1.0.
+    //   sum       with a0..a3 = 1.0 the weighted sum is fma(1, w3, fma(1, w2, fma(1, w1, 1 * w0))) + noise: a product by 1.0 is exact,
+    //             so each fma rounds once, like the add of total = (((w0 + w1) + w2) + w3) + noise, in the same order: sum == total
+    //             bit for bit.  hi_ao is 1.0 in this pass (no hi-res AO operand), so the dividend hi_ao * sum is `total` itself.
+    //   total     finite and > 0: this is the DIV_EXACT_RCP instance of a frame that is not hostile, so every low-res depth is a
+    //             nice level texel, and the lane is clean, so every HiResDB word is finite and >= 0: x = |dHi - dLo| + tolerance
+    //             lies in [2^-44, 2^21] (exact_rcp_div_applicable), the weights {9, 3, 1, 3} / x in [2^-21, 2^48], the noise term in
+    //             [2^-30, 2^50] (same test): total in [2^-21, 2^52] -- inside div_strict's verified range [2^-60, 2^60].
+    //   quotient  div_strict(t, t) is the correctly rounded t / t = 1.0, code floor(255 + 0.5) = 255.  The estimate the product
+    //             instance runs instead (bilateral_upsample_r8) is within 35u of 1: v~ = 255.5 up to 2.3e-5, never within kR8Margin of
+    //             an integer, so it never takes its exact path and yields 255 as well.
+    // A lane that is NOT clean (hi-res NaN: the reference stores 0 there; inf, negative, denormal denominators) fails the test, and
+    // the whole tile takes the normal path with its IEEE redo.  The test is one compare per window item in front of the first
+    // barrier, a ballot and an LDS word per wave (row padding of s_inv: columns kRawW.. of rows 0..3, which the fill never writes,
+    // nothing writes behind the barrier, and only the scratch outputs of the last H-blur run read), four LDS reads behind it; the
+    // decision is uniform over the workgroup.  Tiles that fill their window by the masked paths (frame border) do not take part.
+    constexpr bool kWhiteTiles = MEAO_X_WHITE_TILES != 0 && FINAL && !NESTED && AOFMT == MEAO_AO_R8 && DIV == DIV_EXACT_RCP;
+    static_assert(T::kRawW < T::kRawPitch && kThreads / 64 <= T::kRawH, "one flag word per wave in the row padding of s_inv");
+    uint32_t *const s_white = reinterpret_cast<uint32_t *>(s_inv) + T::kRawW;      // wave w: s_white[w * T::kRawPitch]
+    bool lane_white = false;
+    // a window item's four AO codes (row quad k: columns 4k - 1 .. 4k + 2; those outside [0, kRawW) do not count)
+    auto quad_white = [&](const typename AO::type4 &q, int k) __attribute__((always_inline)) {
+        if constexpr (kWhiteTiles) {
+            const uint32_t outside = k == 0 ? 0xffu : (k == 9 ? 0xff000000u : 0u);
+            return (__builtin_bit_cast(uint32_t, q) | outside) == 0xffffffffu;
+        } else {
+            return false;
+        }
+    };
+
     PhaseClock clk(FINAL ? 0 : 8);
     __builtin_amdgcn_s_setprio(3);
     // The hi-res operands of the bilateral phase do not depend on anything computed here: their loads
@@ -757,6 +794,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
             asm volatile("" : "+v"(apron_r), "+v"(apron_k));
             ups_issue_from_raw_loads<AOFMT, TILE_H, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L, apron_r, apron_k);
             auto &wa = L.wa;
+            lane_white = kWhiteTiles;
 #pragma unroll
             for (int round = 0; round < kRounds; ++round) {
                 typedef typename std::conditional<sizeof(typename AO::type4) == 4, uint32_t, uint64_t>::type bits_t;
@@ -764,6 +802,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                 const int i = tid + round * kThreads;
                 if (i < kItems) {
                     const int r = tenth(i), k = i - 10 * r;
+                    if constexpr (kWhiteTiles) lane_white = lane_white && quad_white(wa[round], k);
                     const float av[4] = {AO::decode(wa[round].x), AO::decode(wa[round].y), AO::decode(wa[round].z), AO::decode(wa[round].w)};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -798,6 +837,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                                                                                        MEAO_X_HOT_PATH_ONLY || (HX0 + kUpsTileW <= hw && HY0 + kTileH <= hh));
         auto &wd = L.wd;
         auto &wa = L.wa;
+        lane_white = kWhiteTiles;
 #pragma unroll
         for (int round = 0; round < kRounds; ++round) {
             // an unconditional use: the compiler would otherwise sink the loads of the partial last round into
@@ -813,6 +853,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
             if (i < kItems) {
                 static_assert(kItems <= 1024, "tenth()");
                 const int r = tenth(i), k = i - 10 * r;
+                if constexpr (kWhiteTiles) lane_white = lane_white && quad_white(wa[round], k);
                 const float dv[4] = {wd[round].x, wd[round].y, wd[round].z, wd[round].w};
                 float av[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                 if constexpr (!NESTED) {
@@ -908,11 +949,46 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
         }
     };
     hi_depth_block();      // (at s_setprio 3 like the fill it ends: at priority 0 the pass is 16 us slower per 16 4K frames, r06 A/B)
+    if constexpr (kWhiteTiles) {
+        // (hoist_ok: only then has hi_depth_words tested the lane -- the masked path tests its quads in the bilateral phase)
+        const bool wave_white = __builtin_amdgcn_ballot_w64(lane_white && lane_clean && hoist_ok) == ~0ull;
+        s_white[(tid >> 6) * T::kRawPitch] = wave_white ? 1u : 0u;       // every lane of the wave: the same word, the same value
+    }
     clk.mark(0);         // 0: window loaded, converted, stored to LDS
     __syncthreads();
     clk.mark(1);         // 1: barrier
     __builtin_amdgcn_s_setprio(0);       // (3 kept through the blur phases: +10 % on the pass; rising through the phases: +2 %, r03)
     hook.after_prefetch();
+    if constexpr (kWhiteTiles) {
+        uint32_t all_white = s_white[0];
+#pragma unroll
+        for (int w = 1; w < kThreads / 64; ++w) all_white &= s_white[w * T::kRawPitch];
+        if (__builtin_amdgcn_readfirstlane(all_white) != 0) {       // the same four words in every lane: a scalar branch
+            // ---- white tile: code 255 to every texel of the tile inside the frame, with the stores of the bilateral phase
+            // (vec_ok holds: hoist_ok).  The hooks keep their order: the carried downsample tile's loads are issued here.
+            if constexpr (Hook::kBeforeBilateral) {
+                __builtin_amdgcn_sched_barrier(0);
+                hook.before_bilateral();
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            const int hx0 = HX0 + 4 * (tid & 15);
+            const bool whole = HX0 + kUpsTileW <= hw && HY0 + kTileH <= hh;
+            typename AO::type4 r4; r4.x = 255; r4.y = 255; r4.z = 255; r4.w = 255;
+#pragma unroll
+            for (int pass = 0; pass < kPasses; ++pass)
+#pragma unroll
+                for (int f = 0; f < 2; ++f) {
+                    const int hy = HY0 + 2 * ((tid >> 4) + 16 * pass) + f;
+                    if (whole || (hx0 < hw && hy < hh)) {
+                        ao_t *o = dst + (static_cast<size_t>(hy) * dst_pitch + hx0);
+                        if constexpr (MEAO_X_FINAL_NT_STORE) __builtin_nontemporal_store(r4, reinterpret_cast<typename AO::type4 *>(o));
+                        else *reinterpret_cast<typename AO::type4 *>(o) = r4;
+                    }
+                }
+            clk.mark(23);        // 23: white tile, first barrier to its stores issued (a slot of its own: phases 2..7 stay the normal path's)
+            return;
+        }
+    }
 
     // ---- BlurHorizontally: runs of 4 outputs; output (r, c) is centred on raw column c+2.
     // (Columns 34, 35 of the last run are scratch: they read the row padding.)

@@ -203,3 +203,35 @@ def make(kind: str, width: int, height: int, seed: int = 0x1234ABCD) -> np.ndarr
     if kind in ("S3", "atrium"):
         return atrium(width, height)
     raise ValueError(kind)
+
+
+# ---- the white-tile rule of the full-resolution upsample (meao_dev_upsample.hpp, "white tile"), on oracle outputs: a 64 x 64 tile of
+# the result whose low-res AO window -- the 38 x 38 `combined1` texels [32 tx - 3, 32 tx + 34] x [32 ty - 3, 32 ty + 34], clamp-
+# addressed -- is all code 255 (tests/test_white_tile_rule.py, tools/bench_passes.py --count-white-tiles)
+
+WHITE_TILE = 64
+
+
+def window_white(combined1: np.ndarray, tx: int, ty: int) -> bool:
+    """The clamp-addressed low-res window of tile (tx, ty) is all code 255."""
+    lh, lw = combined1.shape
+    ys = np.clip(np.arange(ty * 32 - 3, ty * 32 + 35), 0, lh - 1)
+    xs = np.clip(np.arange(tx * 32 - 3, tx * 32 + 35), 0, lw - 1)
+    return bool((combined1[np.ix_(ys, xs)] == 255).all())
+
+
+def interior_white(combined1: np.ndarray, tx: int, ty: int) -> bool:
+    """The low-res texels under the tile itself (no apron) are all code 255."""
+    return bool((combined1[ty * 32:(ty + 1) * 32, tx * 32:(tx + 1) * 32] == 255).all())
+
+
+def white_tile_map(combined1: np.ndarray, width: int, height: int) -> list:
+    """Rows of 'W' (window white), 'A' (interior white, apron not), '.' (neither), one character per 64 x 64 tile."""
+    nx, ny = (width + WHITE_TILE - 1) // WHITE_TILE, (height + WHITE_TILE - 1) // WHITE_TILE
+    return ["".join("W" if window_white(combined1, tx, ty) else "A" if interior_white(combined1, tx, ty) else "." for tx in range(nx))
+            for ty in range(ny)]
+
+
+def white_tiles(combined1: np.ndarray, width: int, height: int) -> list:
+    """(tx, ty) of the tiles whose window is white."""
+    return [(tx, ty) for ty, row in enumerate(white_tile_map(combined1, width, height)) for tx, c in enumerate(row) if c == "W"]

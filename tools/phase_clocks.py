@@ -62,4 +62,9 @@ for base, label in ((0, "full_resolution_pass"), (8, "blend_passes"), (24, "rend
             tab[nm] = {"us_per_wave": round(us, 3), "waves": int(cnt)}
     tab["sum_us_per_wave"] = round(tot, 3)
     res[label] = tab
+# white tiles of the full-resolution pass (MEAO_X_WHITE_TILES): their waves stamp phases 0, 1 and then 23 instead of 2..7
+if buf[32 + 23]:
+    res["full_resolution_pass"]["23 white tile: barrier to stores issued"] = {"us_per_wave": round(buf[23] / buf[32 + 23] / 100.0, 3),
+                                                                             "waves": int(buf[32 + 23])}
+    res["full_resolution_pass"]["white_share_of_sampled_waves"] = round(buf[32 + 23] / max(1, buf[32 + 1]), 4)
 print(json.dumps(res, indent=1))
