@@ -18,9 +18,9 @@ _INCLUDE = os.path.join(os.path.dirname(_PKG), "include")
 LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmeao_hip.so")
 
-# The kernels are six translation units over shared device headers (meao_dev*.hpp): they compile in parallel and a
-# change to one family rebuilds one unit.  csrc/meao_kernels.hip is the same code as ONE unit (it includes the six):
-# variants that need device globals (`clocks`) and the ISA tools build that.
+# The kernels are seventeen translation units over shared device headers (meao_dev*.hpp) and one launch header
+# (meao_launch.hpp): they compile in parallel and a change to one family rebuilds one unit.  csrc/meao_kernels.hip is the
+# same code as ONE unit (it includes the seventeen): variants that need device globals (`clocks`) and the ISA tools build that.
 KERNEL_UNITS = ["meao_k_downsample.hip", "meao_k_render.hip", "meao_k_upsample.hip",
                 "meao_k_upsample_nested.hip", "meao_k_upsample_fused.hip", "meao_k_misc.hip",
                 # the per-frame forms (meao_execute_batch_params) in units of their own: the shared kernels' units are unchanged
@@ -33,7 +33,8 @@ KERNEL_UNITS = ["meao_k_downsample.hip", "meao_k_render.hip", "meao_k_upsample.h
 HOST_UNITS = ["meao_plan.cpp", "meao_api.cpp", "meao_pool.cpp"]
 SOURCES = HOST_UNITS + KERNEL_UNITS
 HEADERS = ["meao_plan.hpp", "meao_kernels.hpp", "meao_dev.hpp", "meao_dev_downsample.hpp", "meao_dev_render.hpp",
-           "meao_dev_upsample.hpp", "meao_dev_blend.hpp", "meao_dev_composite.hpp", "meao_dev_fused.hpp", "meao_kernels.hip"]
+           "meao_dev_upsample.hpp", "meao_dev_blend.hpp", "meao_dev_composite.hpp", "meao_dev_fused.hpp", "meao_launch.hpp",
+           "meao_kernels.hip"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 # -ffp-contract=off: the only fused multiply-adds are the explicit mad()/fma2() calls, which

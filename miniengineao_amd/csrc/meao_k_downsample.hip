@@ -1,5 +1,6 @@
 // meao_k_downsample.hip -- the stand-alone downsample pass (the four point-sampled levels; meao_dev_downsample.hpp).
 #include "meao_dev_downsample.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {
@@ -12,13 +13,6 @@ __global__ __launch_bounds__(kThreads) void downsample_kernel(const DownsampleAr
     downsample_tile<VEC, DIV, ROWS>(a, blockIdx.x, blockIdx.z);
 }
 
-template <bool VEC, int DIV>
-void launch_downsample_t(const DownsampleArgs &a, dim3 grid, hipStream_t s)
-{
-    if (a.rows_per_lane == 1) downsample_kernel<VEC, DIV, 1><<<grid, dim3(kThreads), 0, s>>>(a);
-    else downsample_kernel<VEC, DIV, kMipRowsPerLane><<<grid, dim3(kThreads), 0, s>>>(a);
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -29,18 +23,9 @@ hipError_t launch_downsample(const DownsampleArgs &a, int frames, hipStream_t s,
     if (linear_depth(a.depth_format)) return launch_downsample_linear(a, frames, s, pf);
     if (downsample_pitched(a)) return launch_downsample_pitched(a, frames, s, pf);
     if (pf) return launch_downsample_frames(a, frames, s, pf);
-    if (a.rows_per_lane != 1 && a.rows_per_lane != kMipRowsPerLane) return hipErrorInvalidValue;
+    if (!rows_per_lane_valid(a)) return hipErrorInvalidValue;
     const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
-    // exact_rcp_div is only ever set together with RTZ depth storage; the pass itself stores f32 (no f16 conversion here)
-    if (a.exact_rcp_div) {
-        if (a.vec_ok) launch_downsample_t<true, DIV_EXACT_RCP>(a, grid, s);
-        else launch_downsample_t<false, DIV_EXACT_RCP>(a, grid, s);
-    } else {
-        if (a.vec_ok) launch_downsample_t<true, DIV_IEEE>(a, grid, s);
-        else launch_downsample_t<false, DIV_IEEE>(a, grid, s);
-    }
-    return hipGetLastError();
+    return for_downsample_variant(a, [&](auto v) { downsample_kernel<v.kVec, v.kDiv, v.kRows><<<grid, dim3(kThreads), 0, s>>>(a); });
 }
-
 
 }  // namespace meao

@@ -2,6 +2,7 @@
 // frame blockIdx.z's argument blocks from the FrameArgs table, whose zp0 is that frame's s.
 #include "meao_dev_downsample.hpp"
 #include "meao_dev_upsample.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {
@@ -30,58 +31,25 @@ __global__ __launch_bounds__(kThreads) void upsample_final_small_linear_frames_k
                                                                                         NoHook(), &frame_block(th, blockIdx.z));
 }
 
-template <bool VEC, int DIV>
-void launch_ds_linear_frames_t(const DownsampleArgs &a, const DownsampleArgs *pf, dim3 grid, hipStream_t s)
-{
-    if (a.rows_per_lane == 1) downsample_linear_frames_kernel<VEC, DIV, 1><<<grid, dim3(kThreads), 0, s>>>(pf);
-    else downsample_linear_frames_kernel<VEC, DIV, kMipRowsPerLane><<<grid, dim3(kThreads), 0, s>>>(pf);
-}
-
-template <int AOFMT, bool RTNE, int DIV>
-void launch_final_linear_frames_t(const UpsampleArgs &a, const HiDepthArgs &hi, const UpsampleArgs *pf, const HiDepthArgs *pf_hi,
-                                  dim3 grid, hipStream_t s)
-{
-    const dim3 block(kThreads);
-    const bool f32 = hi.depth_format == MEAO_DEPTH_LINEAR_F32;
-    if (a.tile_h == kUpsTileHSmall) {
-        if (f32) upsample_final_small_linear_frames_kernel<AOFMT, RTNE, DIV, true><<<grid, block, 0, s>>>(pf, pf_hi);
-        else upsample_final_small_linear_frames_kernel<AOFMT, RTNE, DIV, false><<<grid, block, 0, s>>>(pf, pf_hi);
-    } else {
-        if (f32) upsample_final_linear_frames_kernel<AOFMT, RTNE, DIV, true><<<grid, block, 0, s>>>(pf, pf_hi);
-        else upsample_final_linear_frames_kernel<AOFMT, RTNE, DIV, false><<<grid, block, 0, s>>>(pf, pf_hi);
-    }
-}
-
 }  // namespace
 
 hipError_t launch_downsample_linear_frames(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf)
 {
     const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
-    if (a.exact_rcp_div) {
-        if (a.vec_ok) launch_ds_linear_frames_t<true, DIV_EXACT_RCP>(a, pf, grid, s);
-        else launch_ds_linear_frames_t<false, DIV_EXACT_RCP>(a, pf, grid, s);
-    } else {
-        if (a.vec_ok) launch_ds_linear_frames_t<true, DIV_IEEE>(a, pf, grid, s);
-        else launch_ds_linear_frames_t<false, DIV_IEEE>(a, pf, grid, s);
-    }
-    return hipGetLastError();
+    return for_downsample_variant(a, [&](auto v) { downsample_linear_frames_kernel<v.kVec, v.kDiv, v.kRows><<<grid, dim3(kThreads), 0, s>>>(pf); });
 }
 
 hipError_t launch_upsample_final_linear_frames(const UpsampleArgs &a, const HiDepthArgs &hi, int ao_format, int frames, hipStream_t s,
                                                const UpsampleArgs *pf, const HiDepthArgs *pf_hi)
 {
     if (!pf_hi) return hipErrorInvalidValue;
-    const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
-    if (ao_format == MEAO_AO_R8) {
-        if (a.f16_rtne) launch_final_linear_frames_t<MEAO_AO_R8, true, DIV_IEEE>(a, hi, pf, pf_hi, grid, s);
-        else if (a.exact_rcp_div) launch_final_linear_frames_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(a, hi, pf, pf_hi, grid, s);
-        else launch_final_linear_frames_t<MEAO_AO_R8, false, DIV_IEEE>(a, hi, pf, pf_hi, grid, s);
-    } else {
-        if (a.f16_rtne) launch_final_linear_frames_t<MEAO_AO_F16, true, DIV_IEEE>(a, hi, pf, pf_hi, grid, s);
-        else if (a.exact_rcp_div) launch_final_linear_frames_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(a, hi, pf, pf_hi, grid, s);
-        else launch_final_linear_frames_t<MEAO_AO_F16, false, DIV_IEEE>(a, hi, pf, pf_hi, grid, s);
-    }
-    return hipGetLastError();
+    const dim3 grid(a.tiles_x * a.tiles_y, 1, frames), block(kThreads);
+    return for_column(ao_format, a, [&](auto c) {
+        for_final_variant<MEAO_DEPTH_LINEAR_F32>(a, hi, [&](auto v) {
+            if constexpr (v.kSmall) upsample_final_small_linear_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv, v.kF32><<<grid, block, 0, s>>>(pf, pf_hi);
+            else upsample_final_linear_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv, v.kF32><<<grid, block, 0, s>>>(pf, pf_hi);
+        });
+    });
 }
 
 }  // namespace meao

@@ -3,6 +3,7 @@
 // the frames (zp0 = s), the LoResDB interior comes from registers as in the raw form.  Rows through the pitch fields, like every
 // linear kernel.  Shared and per-frame forms.
 #include "meao_dev_fused.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {
@@ -43,14 +44,6 @@ __global__ __launch_bounds__(kThreads, 7) void upsample_final_with_next_downsamp
     }
 }
 
-template <int AOFMT, bool RTNE, int DIV>
-void launch_fused_linear_t(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, const UpsampleArgs *pf,
-                           const HiDepthArgs *pf_hi, const DownsampleArgs *pf_d, dim3 grid, hipStream_t s)
-{
-    if (pf) upsample_final_with_next_downsample_linear_frames_kernel<AOFMT, RTNE, DIV><<<grid, dim3(kThreads), 0, s>>>(pf, pf_hi, pf_d);
-    else upsample_final_with_next_downsample_linear_kernel<AOFMT, RTNE, DIV><<<grid, dim3(kThreads), 0, s>>>(a, hi, d);
-}
-
 }  // namespace
 
 // (the caller has checked fused_downsample_applicable; every stride of the blocks is set: packed sides carry their packed rows)
@@ -59,19 +52,12 @@ hipError_t launch_upsample_final_with_downsample_linear(const UpsampleArgs &a, c
                                                         const DownsampleArgs *pf_d)
 {
     if (hi.depth_format != MEAO_DEPTH_LINEAR_F32 || d.depth_format != MEAO_DEPTH_LINEAR_F32) return hipErrorInvalidValue;
-    if (a.pitch.depth < a.hw || a.pitch.dst < a.hw || d.depth_pitch < d.w[0]) return hipErrorInvalidValue;
-    if ((pf || pf_hi || pf_d) && !(pf && pf_hi && pf_d)) return hipErrorInvalidValue;
-    const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
-    if (ao_format == MEAO_AO_R8) {
-        if (a.f16_rtne) launch_fused_linear_t<MEAO_AO_R8, true, DIV_IEEE>(a, hi, d, pf, pf_hi, pf_d, grid, s);
-        else if (a.exact_rcp_div) launch_fused_linear_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(a, hi, d, pf, pf_hi, pf_d, grid, s);
-        else launch_fused_linear_t<MEAO_AO_R8, false, DIV_IEEE>(a, hi, d, pf, pf_hi, pf_d, grid, s);
-    } else {
-        if (a.f16_rtne) launch_fused_linear_t<MEAO_AO_F16, true, DIV_IEEE>(a, hi, d, pf, pf_hi, pf_d, grid, s);
-        else if (a.exact_rcp_div) launch_fused_linear_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(a, hi, d, pf, pf_hi, pf_d, grid, s);
-        else launch_fused_linear_t<MEAO_AO_F16, false, DIV_IEEE>(a, hi, d, pf, pf_hi, pf_d, grid, s);
-    }
-    return hipGetLastError();
+    if (!final_strides_set(a) || !depth_stride_set(d) || !all_or_none(pf, pf_hi, pf_d)) return hipErrorInvalidValue;
+    const dim3 grid(a.tiles_x * a.tiles_y, 1, frames), block(kThreads);
+    return for_column(ao_format, a, [&](auto c) {
+        if (pf) upsample_final_with_next_downsample_linear_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, block, 0, s>>>(pf, pf_hi, pf_d);
+        else upsample_final_with_next_downsample_linear_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, block, 0, s>>>(a, hi, d);
+    });
 }
 
 }  // namespace meao

@@ -2,6 +2,7 @@
 #include "meao_dev_upsample.hpp"
 #include "meao_dev_downsample.hpp"
 #include "meao_dev_composite.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {

@@ -2,6 +2,7 @@
 // for row-pitched surfaces: either side -- this batch's depth and results, the next batch's depth -- may be pitched; the strides
 // of a packed side are its packed rows.  Shared and per-frame forms.
 #include "meao_dev_fused.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {
@@ -42,14 +43,6 @@ __global__ __launch_bounds__(kThreads, 7) void upsample_final_with_next_downsamp
     }
 }
 
-template <int AOFMT, bool RTNE, int DIV>
-void launch_fused_pitched_t(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, const UpsampleArgs *pf,
-                            const HiDepthArgs *pf_hi, const DownsampleArgs *pf_d, dim3 grid, hipStream_t s)
-{
-    if (pf) upsample_final_with_next_downsample_pitched_frames_kernel<AOFMT, RTNE, DIV><<<grid, dim3(kThreads), 0, s>>>(pf, pf_hi, pf_d);
-    else upsample_final_with_next_downsample_pitched_kernel<AOFMT, RTNE, DIV><<<grid, dim3(kThreads), 0, s>>>(a, hi, d);
-}
-
 }  // namespace
 
 // (the caller has checked fused_downsample_applicable; every stride of the blocks is set: packed sides carry their packed rows)
@@ -57,19 +50,12 @@ hipError_t launch_upsample_final_with_downsample_pitched(const UpsampleArgs &a, 
                                                          int frames, hipStream_t s, const UpsampleArgs *pf, const HiDepthArgs *pf_hi,
                                                          const DownsampleArgs *pf_d)
 {
-    if (a.pitch.depth < a.hw || a.pitch.dst < a.hw || d.depth_pitch < d.w[0]) return hipErrorInvalidValue;
-    if ((pf || pf_hi || pf_d) && !(pf && pf_hi && pf_d)) return hipErrorInvalidValue;
-    const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
-    if (ao_format == MEAO_AO_R8) {
-        if (a.f16_rtne) launch_fused_pitched_t<MEAO_AO_R8, true, DIV_IEEE>(a, hi, d, pf, pf_hi, pf_d, grid, s);
-        else if (a.exact_rcp_div) launch_fused_pitched_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(a, hi, d, pf, pf_hi, pf_d, grid, s);
-        else launch_fused_pitched_t<MEAO_AO_R8, false, DIV_IEEE>(a, hi, d, pf, pf_hi, pf_d, grid, s);
-    } else {
-        if (a.f16_rtne) launch_fused_pitched_t<MEAO_AO_F16, true, DIV_IEEE>(a, hi, d, pf, pf_hi, pf_d, grid, s);
-        else if (a.exact_rcp_div) launch_fused_pitched_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(a, hi, d, pf, pf_hi, pf_d, grid, s);
-        else launch_fused_pitched_t<MEAO_AO_F16, false, DIV_IEEE>(a, hi, d, pf, pf_hi, pf_d, grid, s);
-    }
-    return hipGetLastError();
+    if (!final_strides_set(a) || !depth_stride_set(d) || !all_or_none(pf, pf_hi, pf_d)) return hipErrorInvalidValue;
+    const dim3 grid(a.tiles_x * a.tiles_y, 1, frames), block(kThreads);
+    return for_column(ao_format, a, [&](auto c) {
+        if (pf) upsample_final_with_next_downsample_pitched_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, block, 0, s>>>(pf, pf_hi, pf_d);
+        else upsample_final_with_next_downsample_pitched_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, block, 0, s>>>(a, hi, d);
+    });
 }
 
 }  // namespace meao

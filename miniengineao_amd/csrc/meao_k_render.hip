@@ -1,6 +1,7 @@
 // meao_k_render.hip -- render kernels: interleaved (all levels, one grid), small tiles, wide (Render.main), and the form that carries a composite.
 #include "meao_dev_render.hpp"
 #include "meao_dev_composite.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {
@@ -241,47 +242,27 @@ __global__ __launch_bounds__(ren_tile_w(false) * 4, 8) void render_with_composit
 // ------------------------------------------------------------------------------------------
 // launchers
 
-// WIDE selects render_wide_kernel; the (AOFMT, RTNE, DIV, EXH) choice is the same for both.
-template <bool WIDE, int AOFMT, bool RTNE, int DIV>
-static void launch_render_t(const RenderArgs &a, dim3 grid, hipStream_t s)
-{
-    const dim3 block(WIDE ? kThreads : ren_tile_w(a.exhaustive != 0) * 4);
-    if constexpr (WIDE) {
-        if (a.exhaustive) render_wide_kernel<AOFMT, RTNE, DIV, true><<<grid, block, 0, s>>>(a);
-        else render_wide_kernel<AOFMT, RTNE, DIV, false><<<grid, block, 0, s>>>(a);
-    } else {
-        if (a.exhaustive) render_kernel<AOFMT, RTNE, DIV, true><<<grid, block, 0, s>>>(a);
-        else if (a.tile_h == kRenTileHSmall) render_small_kernel<AOFMT, RTNE, DIV><<<grid, block, 0, s>>>(a);
-        else render_kernel<AOFMT, RTNE, DIV, false><<<grid, block, 0, s>>>(a);
-    }
-}
-
+// WIDE selects render_wide_kernel; the exhaustive / small-tile choice inside the column
 template <bool WIDE>
 static hipError_t launch_render_any(const RenderArgs &a, int ao_format, int frames, hipStream_t s)
 {
-    const dim3 grid(a.blocks_per_frame, frames, 1);
-    if (ao_format == MEAO_AO_R8) {
-        if (a.f16_rtne) launch_render_t<WIDE, MEAO_AO_R8, true, DIV_IEEE>(a, grid, s);
-        else if (a.exact_rcp_div) launch_render_t<WIDE, MEAO_AO_R8, false, DIV_EXACT_RCP>(a, grid, s);
-        else launch_render_t<WIDE, MEAO_AO_R8, false, DIV_IEEE>(a, grid, s);
-    } else {
-        if (a.f16_rtne) launch_render_t<WIDE, MEAO_AO_F16, true, DIV_IEEE>(a, grid, s);
-        else if (a.exact_rcp_div) launch_render_t<WIDE, MEAO_AO_F16, false, DIV_EXACT_RCP>(a, grid, s);
-        else launch_render_t<WIDE, MEAO_AO_F16, false, DIV_IEEE>(a, grid, s);
-    }
-    return hipGetLastError();
+    const dim3 grid(a.blocks_per_frame, frames, 1), block(WIDE ? kThreads : ren_tile_w(a.exhaustive != 0) * 4);
+    return for_column(ao_format, a, [&](auto c) {
+        if constexpr (WIDE) {
+            if (a.exhaustive) render_wide_kernel<c.kAoFmt, c.kRtne, c.kDiv, true><<<grid, block, 0, s>>>(a);
+            else render_wide_kernel<c.kAoFmt, c.kRtne, c.kDiv, false><<<grid, block, 0, s>>>(a);
+        } else {
+            if (a.exhaustive) render_kernel<c.kAoFmt, c.kRtne, c.kDiv, true><<<grid, block, 0, s>>>(a);
+            else if (a.tile_h == kRenTileHSmall) render_small_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, block, 0, s>>>(a);
+            else render_kernel<c.kAoFmt, c.kRtne, c.kDiv, false><<<grid, block, 0, s>>>(a);
+        }
+    });
 }
 
 hipError_t launch_render(const RenderArgs &a, int ao_format, int frames, hipStream_t s, const RenderArgs *pf)
 {
     if (pf) return launch_render_frames(a, ao_format, frames, s, pf, false);
     return launch_render_any<false>(a, ao_format, frames, s);
-}
-
-template <int AOFMT, bool RTNE, int DIV>
-static void launch_render_composite_t(const RenderArgs &a, const CompositeBatchArgs &c, dim3 grid, hipStream_t s)
-{
-    render_with_composite_kernel<AOFMT, RTNE, DIV><<<grid, dim3(kCarriedThreads), 0, s>>>(a, c);
 }
 
 hipError_t launch_render_with_composite(const RenderArgs &a, const CompositeBatchArgs &batch, int ao_format, int frames, hipStream_t s)
@@ -292,16 +273,9 @@ hipError_t launch_render_with_composite(const RenderArgs &a, const CompositeBatc
     while ((kCarriedThreads << c.chunks_log2) < (c.pitch.w + 1) / 2 && c.chunks_log2 < 3 && (a.blocks_per_frame >> (c.chunks_log2 + 1)) > 0)
         ++c.chunks_log2;
     const dim3 grid(a.blocks_per_frame, frames, 1);
-    if (ao_format == MEAO_AO_R8) {
-        if (a.f16_rtne) launch_render_composite_t<MEAO_AO_R8, true, DIV_IEEE>(a, c, grid, s);
-        else if (a.exact_rcp_div) launch_render_composite_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(a, c, grid, s);
-        else launch_render_composite_t<MEAO_AO_R8, false, DIV_IEEE>(a, c, grid, s);
-    } else {
-        if (a.f16_rtne) launch_render_composite_t<MEAO_AO_F16, true, DIV_IEEE>(a, c, grid, s);
-        else if (a.exact_rcp_div) launch_render_composite_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(a, c, grid, s);
-        else launch_render_composite_t<MEAO_AO_F16, false, DIV_IEEE>(a, c, grid, s);
-    }
-    return hipGetLastError();
+    return for_column(ao_format, a, [&](auto col) {
+        render_with_composite_kernel<col.kAoFmt, col.kRtne, col.kDiv><<<grid, dim3(kCarriedThreads), 0, s>>>(a, c);
+    });
 }
 
 hipError_t launch_render_wide(const RenderArgs &a, int ao_format, int frames, hipStream_t s, const RenderArgs *pf)
@@ -309,6 +283,5 @@ hipError_t launch_render_wide(const RenderArgs &a, int ao_format, int frames, hi
     if (pf) return launch_render_frames(a, ao_format, frames, s, pf, true);
     return launch_render_any<true>(a, ao_format, frames, s);
 }
-
 
 }  // namespace meao

@@ -2,6 +2,7 @@
 // RenderArgs from the FrameArgs table, then the same tiles as render_kernel / render_small_kernel / render_wide_kernel.  (A
 // composite waiting for a per-frame call is flushed as its own launch: there is no per-frame render_with_composite_kernel.)
 #include "meao_dev_render.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {
@@ -51,35 +52,21 @@ __global__ __launch_bounds__(kThreads) void render_wide_frames_kernel(const Rend
     render_wide_tile<AOFMT, RTNE, DIV, EXH>(a, tile, frame, block);
 }
 
-template <int AOFMT, bool RTNE, int DIV>
-void launch_render_frames_t(const RenderArgs &a, const RenderArgs *pf, bool wide, dim3 grid, hipStream_t s)
-{
-    if (wide) {
-        if (a.exhaustive) render_wide_frames_kernel<AOFMT, RTNE, DIV, true><<<grid, dim3(kThreads), 0, s>>>(pf);
-        else render_wide_frames_kernel<AOFMT, RTNE, DIV, false><<<grid, dim3(kThreads), 0, s>>>(pf);
-        return;
-    }
-    const dim3 block(ren_tile_w(a.exhaustive != 0) * 4);
-    if (a.exhaustive) render_frames_kernel<AOFMT, RTNE, DIV, true><<<grid, block, 0, s>>>(pf);
-    else if (a.tile_h == kRenTileHSmall) render_small_frames_kernel<AOFMT, RTNE, DIV><<<grid, block, 0, s>>>(pf);
-    else render_frames_kernel<AOFMT, RTNE, DIV, false><<<grid, block, 0, s>>>(pf);
-}
-
 }  // namespace
 
 hipError_t launch_render_frames(const RenderArgs &a, int ao_format, int frames, hipStream_t s, const RenderArgs *pf, bool wide)
 {
-    const dim3 grid(a.blocks_per_frame, frames, 1);
-    if (ao_format == MEAO_AO_R8) {
-        if (a.f16_rtne) launch_render_frames_t<MEAO_AO_R8, true, DIV_IEEE>(a, pf, wide, grid, s);
-        else if (a.exact_rcp_div) launch_render_frames_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(a, pf, wide, grid, s);
-        else launch_render_frames_t<MEAO_AO_R8, false, DIV_IEEE>(a, pf, wide, grid, s);
-    } else {
-        if (a.f16_rtne) launch_render_frames_t<MEAO_AO_F16, true, DIV_IEEE>(a, pf, wide, grid, s);
-        else if (a.exact_rcp_div) launch_render_frames_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(a, pf, wide, grid, s);
-        else launch_render_frames_t<MEAO_AO_F16, false, DIV_IEEE>(a, pf, wide, grid, s);
-    }
-    return hipGetLastError();
+    const dim3 grid(a.blocks_per_frame, frames, 1), block(wide ? kThreads : ren_tile_w(a.exhaustive != 0) * 4);
+    return for_column(ao_format, a, [&](auto c) {
+        if (wide) {
+            if (a.exhaustive) render_wide_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv, true><<<grid, block, 0, s>>>(pf);
+            else render_wide_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv, false><<<grid, block, 0, s>>>(pf);
+        } else {
+            if (a.exhaustive) render_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv, true><<<grid, block, 0, s>>>(pf);
+            else if (a.tile_h == kRenTileHSmall) render_small_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, block, 0, s>>>(pf);
+            else render_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv, false><<<grid, block, 0, s>>>(pf);
+        }
+    });
 }
 
 }  // namespace meao

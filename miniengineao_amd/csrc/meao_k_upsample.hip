@@ -1,5 +1,6 @@
 // meao_k_upsample.hip -- upsample kernels: one blend pass / the full-resolution pass per launch.
 #include "meao_dev_upsample.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {
@@ -46,45 +47,25 @@ __global__ __launch_bounds__(kThreads, 6) void upsample_blend_tall_kernel(const 
 // ------------------------------------------------------------------------------------------
 // launchers
 
-template <int AOFMT, bool RTNE, int DIV>
-static void launch_upsample_t(const UpsampleArgs &a, const HiDepthArgs *hi, dim3 grid, hipStream_t s)
-{
-    const dim3 block(kThreads);
-    if (hi) {
-        const bool f32 = hi->depth_format == MEAO_DEPTH_F32;
-        if (a.tile_h == kUpsTileHSmall) {
-            if (f32) upsample_final_small_kernel<AOFMT, RTNE, DIV, true><<<grid, block, 0, s>>>(a, *hi);
-            else upsample_final_small_kernel<AOFMT, RTNE, DIV, false><<<grid, block, 0, s>>>(a, *hi);
-        } else {
-            if (f32) upsample_final_kernel<AOFMT, RTNE, DIV, true><<<grid, block, 0, s>>>(a, *hi);
-            else upsample_final_kernel<AOFMT, RTNE, DIV, false><<<grid, block, 0, s>>>(a, *hi);
-        }
-    } else if (a.tile_h == kUpsTileHTall) {
-        upsample_blend_tall_kernel<AOFMT, RTNE, DIV><<<grid, block, 0, s>>>(a);
-    } else {
-        upsample_kernel<AOFMT, RTNE, DIV><<<grid, block, 0, s>>>(a);
-    }
-}
-
 hipError_t launch_upsample(const UpsampleArgs &a, const HiDepthArgs *hi, int ao_format, int frames, hipStream_t s,
                            const UpsampleArgs *pf, const HiDepthArgs *pf_hi)
 {
     if (hi && linear_depth(hi->depth_format)) return launch_upsample_final_linear(a, *hi, ao_format, frames, s, pf, pf_hi);
     if (hi && final_pitched(a)) return launch_upsample_final_pitched(a, *hi, ao_format, frames, s, pf, pf_hi);
     if (pf) return launch_upsample_frames(a, hi, ao_format, frames, s, pf, pf_hi);
-    const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
-    // exact_rcp_div is only ever set together with RTZ depth storage (no inf operands)
-    if (ao_format == MEAO_AO_R8) {
-        if (a.f16_rtne) launch_upsample_t<MEAO_AO_R8, true, DIV_IEEE>(a, hi, grid, s);
-        else if (a.exact_rcp_div) launch_upsample_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(a, hi, grid, s);
-        else launch_upsample_t<MEAO_AO_R8, false, DIV_IEEE>(a, hi, grid, s);
-    } else {
-        if (a.f16_rtne) launch_upsample_t<MEAO_AO_F16, true, DIV_IEEE>(a, hi, grid, s);
-        else if (a.exact_rcp_div) launch_upsample_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(a, hi, grid, s);
-        else launch_upsample_t<MEAO_AO_F16, false, DIV_IEEE>(a, hi, grid, s);
-    }
-    return hipGetLastError();
+    const dim3 grid(a.tiles_x * a.tiles_y, 1, frames), block(kThreads);
+    return for_column(ao_format, a, [&](auto c) {
+        if (hi) {
+            for_final_variant<MEAO_DEPTH_F32>(a, *hi, [&](auto v) {
+                if constexpr (v.kSmall) upsample_final_small_kernel<c.kAoFmt, c.kRtne, c.kDiv, v.kF32><<<grid, block, 0, s>>>(a, *hi);
+                else upsample_final_kernel<c.kAoFmt, c.kRtne, c.kDiv, v.kF32><<<grid, block, 0, s>>>(a, *hi);
+            });
+        } else if (a.tile_h == kUpsTileHTall) {
+            upsample_blend_tall_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, block, 0, s>>>(a);
+        } else {
+            upsample_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, block, 0, s>>>(a);
+        }
+    });
 }
-
 
 }  // namespace meao

@@ -2,6 +2,7 @@
 // UpsampleArgs (and HiDepthArgs) from the FrameArgs table, then the same tiles as upsample_kernel / upsample_final_kernel /
 // upsample_final_small_kernel / upsample_blend_tall_kernel.
 #include "meao_dev_upsample.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {
@@ -39,26 +40,6 @@ __global__ __launch_bounds__(kThreads, 6) void upsample_blend_tall_frames_kernel
                                                                           xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z);
 }
 
-template <int AOFMT, bool RTNE, int DIV>
-void launch_ups_frames_t(const UpsampleArgs &a, const HiDepthArgs *hi, const UpsampleArgs *pf, const HiDepthArgs *pf_hi, dim3 grid, hipStream_t s)
-{
-    const dim3 block(kThreads);
-    if (hi) {
-        const bool f32 = hi->depth_format == MEAO_DEPTH_F32;
-        if (a.tile_h == kUpsTileHSmall) {
-            if (f32) upsample_final_small_frames_kernel<AOFMT, RTNE, DIV, true><<<grid, block, 0, s>>>(pf, pf_hi);
-            else upsample_final_small_frames_kernel<AOFMT, RTNE, DIV, false><<<grid, block, 0, s>>>(pf, pf_hi);
-        } else {
-            if (f32) upsample_final_frames_kernel<AOFMT, RTNE, DIV, true><<<grid, block, 0, s>>>(pf, pf_hi);
-            else upsample_final_frames_kernel<AOFMT, RTNE, DIV, false><<<grid, block, 0, s>>>(pf, pf_hi);
-        }
-    } else if (a.tile_h == kUpsTileHTall) {
-        upsample_blend_tall_frames_kernel<AOFMT, RTNE, DIV><<<grid, block, 0, s>>>(pf);
-    } else {
-        upsample_frames_kernel<AOFMT, RTNE, DIV><<<grid, block, 0, s>>>(pf);
-    }
-}
-
 }  // namespace
 
 // hi: the shared HiDepthArgs of a final pass (selects the raw-format kernel), nullptr = a blend pass; pf_hi: the frames' blocks
@@ -66,17 +47,19 @@ hipError_t launch_upsample_frames(const UpsampleArgs &a, const HiDepthArgs *hi, 
                                   const UpsampleArgs *pf, const HiDepthArgs *pf_hi)
 {
     if (hi && !pf_hi) return hipErrorInvalidValue;
-    const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
-    if (ao_format == MEAO_AO_R8) {
-        if (a.f16_rtne) launch_ups_frames_t<MEAO_AO_R8, true, DIV_IEEE>(a, hi, pf, pf_hi, grid, s);
-        else if (a.exact_rcp_div) launch_ups_frames_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(a, hi, pf, pf_hi, grid, s);
-        else launch_ups_frames_t<MEAO_AO_R8, false, DIV_IEEE>(a, hi, pf, pf_hi, grid, s);
-    } else {
-        if (a.f16_rtne) launch_ups_frames_t<MEAO_AO_F16, true, DIV_IEEE>(a, hi, pf, pf_hi, grid, s);
-        else if (a.exact_rcp_div) launch_ups_frames_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(a, hi, pf, pf_hi, grid, s);
-        else launch_ups_frames_t<MEAO_AO_F16, false, DIV_IEEE>(a, hi, pf, pf_hi, grid, s);
-    }
-    return hipGetLastError();
+    const dim3 grid(a.tiles_x * a.tiles_y, 1, frames), block(kThreads);
+    return for_column(ao_format, a, [&](auto c) {
+        if (hi) {
+            for_final_variant<MEAO_DEPTH_F32>(a, *hi, [&](auto v) {
+                if constexpr (v.kSmall) upsample_final_small_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv, v.kF32><<<grid, block, 0, s>>>(pf, pf_hi);
+                else upsample_final_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv, v.kF32><<<grid, block, 0, s>>>(pf, pf_hi);
+            });
+        } else if (a.tile_h == kUpsTileHTall) {
+            upsample_blend_tall_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, block, 0, s>>>(pf);
+        } else {
+            upsample_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, block, 0, s>>>(pf);
+        }
+    });
 }
 
 }  // namespace meao

@@ -1,5 +1,6 @@
 // meao_k_upsample_fused.hip -- the full-resolution upsample kernel that carries the next batch's downsample pass (meao_prefetch_batch).
 #include "meao_dev_fused.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {
@@ -46,12 +47,6 @@ bool fused_downsample_applicable(const UpsampleArgs &a, const HiDepthArgs &hi, c
            d.tiles_x * d.tiles_y <= a.tiles_x * a.tiles_y && d.frames <= frames;
 }
 
-template <int AOFMT, bool RTNE, int DIV>
-static void launch_upsample_fused_t(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, dim3 grid, hipStream_t s)
-{
-    upsample_final_with_next_downsample_kernel<AOFMT, RTNE, DIV><<<grid, dim3(kThreads), 0, s>>>(a, hi, d);
-}
-
 hipError_t launch_upsample_final_with_downsample(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, int ao_format,
                                                  int frames, hipStream_t s, const UpsampleArgs *pf, const HiDepthArgs *pf_hi,
                                                  const DownsampleArgs *pf_d)
@@ -62,17 +57,9 @@ hipError_t launch_upsample_final_with_downsample(const UpsampleArgs &a, const Hi
         return launch_upsample_final_with_downsample_pitched(a, hi, d, ao_format, frames, s, pf, pf_hi, pf_d);
     if (pf || pf_hi || pf_d) return launch_upsample_final_with_downsample_frames(a, ao_format, frames, s, pf, pf_hi, pf_d);
     const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
-    if (ao_format == MEAO_AO_R8) {
-        if (a.f16_rtne) launch_upsample_fused_t<MEAO_AO_R8, true, DIV_IEEE>(a, hi, d, grid, s);
-        else if (a.exact_rcp_div) launch_upsample_fused_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(a, hi, d, grid, s);
-        else launch_upsample_fused_t<MEAO_AO_R8, false, DIV_IEEE>(a, hi, d, grid, s);
-    } else {
-        if (a.f16_rtne) launch_upsample_fused_t<MEAO_AO_F16, true, DIV_IEEE>(a, hi, d, grid, s);
-        else if (a.exact_rcp_div) launch_upsample_fused_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(a, hi, d, grid, s);
-        else launch_upsample_fused_t<MEAO_AO_F16, false, DIV_IEEE>(a, hi, d, grid, s);
-    }
-    return hipGetLastError();
+    return for_column(ao_format, a, [&](auto c) {
+        upsample_final_with_next_downsample_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, dim3(kThreads), 0, s>>>(a, hi, d);
+    });
 }
-
 
 }  // namespace meao

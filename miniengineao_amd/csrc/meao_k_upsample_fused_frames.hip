@@ -2,6 +2,7 @@
 // per-frame constants (meao_execute_batch_params / meao_prefetch_batch_params): frame blockIdx.z's table entry holds this
 // batch's frame for the upsample tile and the next batch's frame blockIdx.z for the carried tile.
 #include "meao_dev_fused.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {
@@ -25,12 +26,6 @@ __global__ __launch_bounds__(kThreads, 7) void upsample_final_with_next_downsamp
     }
 }
 
-template <int AOFMT, bool RTNE, int DIV>
-void launch_fused_frames_t(const UpsampleArgs *pf, const HiDepthArgs *pf_hi, const DownsampleArgs *pf_d, dim3 grid, hipStream_t s)
-{
-    upsample_final_with_next_downsample_frames_kernel<AOFMT, RTNE, DIV><<<grid, dim3(kThreads), 0, s>>>(pf, pf_hi, pf_d);
-}
-
 }  // namespace
 
 // (the caller has checked fused_downsample_applicable on the shared blocks: the geometry is the same in every frame)
@@ -39,16 +34,9 @@ hipError_t launch_upsample_final_with_downsample_frames(const UpsampleArgs &a, i
 {
     if (!pf || !pf_hi || !pf_d) return hipErrorInvalidValue;
     const dim3 grid(a.tiles_x * a.tiles_y, 1, frames);
-    if (ao_format == MEAO_AO_R8) {
-        if (a.f16_rtne) launch_fused_frames_t<MEAO_AO_R8, true, DIV_IEEE>(pf, pf_hi, pf_d, grid, s);
-        else if (a.exact_rcp_div) launch_fused_frames_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(pf, pf_hi, pf_d, grid, s);
-        else launch_fused_frames_t<MEAO_AO_R8, false, DIV_IEEE>(pf, pf_hi, pf_d, grid, s);
-    } else {
-        if (a.f16_rtne) launch_fused_frames_t<MEAO_AO_F16, true, DIV_IEEE>(pf, pf_hi, pf_d, grid, s);
-        else if (a.exact_rcp_div) launch_fused_frames_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(pf, pf_hi, pf_d, grid, s);
-        else launch_fused_frames_t<MEAO_AO_F16, false, DIV_IEEE>(pf, pf_hi, pf_d, grid, s);
-    }
-    return hipGetLastError();
+    return for_column(ao_format, a, [&](auto c) {
+        upsample_final_with_next_downsample_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, dim3(kThreads), 0, s>>>(pf, pf_hi, pf_d);
+    });
 }
 
 }  // namespace meao

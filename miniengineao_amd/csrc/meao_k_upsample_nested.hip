@@ -1,5 +1,6 @@
 // meao_k_upsample_nested.hip -- blend passes evaluated inside the launch of the pass above them (two-level, three-level).
 #include "meao_dev_blend.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {
@@ -41,34 +42,14 @@ __global__ __launch_bounds__(kThreads) void upsample_three_level_kernel(const Up
 // ------------------------------------------------------------------------------------------
 // launchers
 
-template <int AOFMT, bool RTNE, int DIV>
-static void launch_upsample_two_level_t(const UpsampleArgs &outer, const UpsampleArgs &inner, dim3 grid, hipStream_t s)
-{
-    upsample_two_level_kernel<AOFMT, RTNE, DIV><<<grid, dim3(kThreads), 0, s>>>(outer, inner);
-}
-
 hipError_t launch_upsample_two_level(const UpsampleArgs &outer, const UpsampleArgs &inner, int ao_format, int frames, hipStream_t s,
                                      const UpsampleArgs *pf_outer, const UpsampleArgs *pf_inner)
 {
     if (pf_outer || pf_inner) return launch_upsample_two_level_frames(outer, ao_format, frames, s, pf_outer, pf_inner);
     const dim3 grid(outer.tiles_x * outer.tiles_y, 1, frames);
-    if (ao_format == MEAO_AO_R8) {
-        if (outer.f16_rtne) launch_upsample_two_level_t<MEAO_AO_R8, true, DIV_IEEE>(outer, inner, grid, s);
-        else if (outer.exact_rcp_div) launch_upsample_two_level_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(outer, inner, grid, s);
-        else launch_upsample_two_level_t<MEAO_AO_R8, false, DIV_IEEE>(outer, inner, grid, s);
-    } else {
-        if (outer.f16_rtne) launch_upsample_two_level_t<MEAO_AO_F16, true, DIV_IEEE>(outer, inner, grid, s);
-        else if (outer.exact_rcp_div) launch_upsample_two_level_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(outer, inner, grid, s);
-        else launch_upsample_two_level_t<MEAO_AO_F16, false, DIV_IEEE>(outer, inner, grid, s);
-    }
-    return hipGetLastError();
-}
-
-template <int AOFMT, bool RTNE, int DIV>
-static void launch_upsample_three_level_t(const UpsampleArgs &outer, const UpsampleArgs &mid, const UpsampleArgs &inner, dim3 grid,
-                                          hipStream_t s)
-{
-    upsample_three_level_kernel<AOFMT, RTNE, DIV><<<grid, dim3(kThreads), 0, s>>>(outer, mid, inner);
+    return for_column(ao_format, outer, [&](auto c) {
+        upsample_two_level_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, dim3(kThreads), 0, s>>>(outer, inner);
+    });
 }
 
 hipError_t launch_upsample_three_level(const UpsampleArgs &outer, const UpsampleArgs &mid, const UpsampleArgs &inner, int ao_format,
@@ -77,17 +58,9 @@ hipError_t launch_upsample_three_level(const UpsampleArgs &outer, const Upsample
 {
     if (pf_outer || pf_mid || pf_inner) return launch_upsample_three_level_frames(outer, ao_format, frames, s, pf_outer, pf_mid, pf_inner);
     const dim3 grid(outer.tiles_x * outer.tiles_y, 1, frames);
-    if (ao_format == MEAO_AO_R8) {
-        if (outer.f16_rtne) launch_upsample_three_level_t<MEAO_AO_R8, true, DIV_IEEE>(outer, mid, inner, grid, s);
-        else if (outer.exact_rcp_div) launch_upsample_three_level_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(outer, mid, inner, grid, s);
-        else launch_upsample_three_level_t<MEAO_AO_R8, false, DIV_IEEE>(outer, mid, inner, grid, s);
-    } else {
-        if (outer.f16_rtne) launch_upsample_three_level_t<MEAO_AO_F16, true, DIV_IEEE>(outer, mid, inner, grid, s);
-        else if (outer.exact_rcp_div) launch_upsample_three_level_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(outer, mid, inner, grid, s);
-        else launch_upsample_three_level_t<MEAO_AO_F16, false, DIV_IEEE>(outer, mid, inner, grid, s);
-    }
-    return hipGetLastError();
+    return for_column(ao_format, outer, [&](auto c) {
+        upsample_three_level_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, dim3(kThreads), 0, s>>>(outer, mid, inner);
+    });
 }
-
 
 }  // namespace meao

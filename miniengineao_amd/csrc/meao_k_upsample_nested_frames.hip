@@ -1,6 +1,7 @@
 // meao_k_upsample_nested_frames.hip -- the nested blend launches (two-level, three-level) with per-frame constants
 // (meao_execute_batch_params): frame blockIdx.z's UpsampleArgs of every pass from the FrameArgs table.
 #include "meao_dev_blend.hpp"
+#include "meao_launch.hpp"
 
 namespace meao {
 namespace {
@@ -37,27 +38,14 @@ __global__ __launch_bounds__(kThreads) void upsample_three_level_frames_kernel(c
 }
 
 // two-level: t_mid == nullptr
-template <int AOFMT, bool RTNE, int DIV>
-void launch_nested_frames_t(const UpsampleArgs *t_outer, const UpsampleArgs *t_mid, const UpsampleArgs *t_inner, dim3 grid, hipStream_t s)
-{
-    if (t_mid) upsample_three_level_frames_kernel<AOFMT, RTNE, DIV><<<grid, dim3(kThreads), 0, s>>>(t_outer, t_mid, t_inner);
-    else upsample_two_level_frames_kernel<AOFMT, RTNE, DIV><<<grid, dim3(kThreads), 0, s>>>(t_outer, t_inner);
-}
-
 hipError_t launch_nested_frames(const UpsampleArgs &outer, int ao_format, int frames, hipStream_t s, const UpsampleArgs *t_outer,
                                 const UpsampleArgs *t_mid, const UpsampleArgs *t_inner)
 {
     const dim3 grid(outer.tiles_x * outer.tiles_y, 1, frames);
-    if (ao_format == MEAO_AO_R8) {
-        if (outer.f16_rtne) launch_nested_frames_t<MEAO_AO_R8, true, DIV_IEEE>(t_outer, t_mid, t_inner, grid, s);
-        else if (outer.exact_rcp_div) launch_nested_frames_t<MEAO_AO_R8, false, DIV_EXACT_RCP>(t_outer, t_mid, t_inner, grid, s);
-        else launch_nested_frames_t<MEAO_AO_R8, false, DIV_IEEE>(t_outer, t_mid, t_inner, grid, s);
-    } else {
-        if (outer.f16_rtne) launch_nested_frames_t<MEAO_AO_F16, true, DIV_IEEE>(t_outer, t_mid, t_inner, grid, s);
-        else if (outer.exact_rcp_div) launch_nested_frames_t<MEAO_AO_F16, false, DIV_EXACT_RCP>(t_outer, t_mid, t_inner, grid, s);
-        else launch_nested_frames_t<MEAO_AO_F16, false, DIV_IEEE>(t_outer, t_mid, t_inner, grid, s);
-    }
-    return hipGetLastError();
+    return for_column(ao_format, outer, [&](auto c) {
+        if (t_mid) upsample_three_level_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, dim3(kThreads), 0, s>>>(t_outer, t_mid, t_inner);
+        else upsample_two_level_frames_kernel<c.kAoFmt, c.kRtne, c.kDiv><<<grid, dim3(kThreads), 0, s>>>(t_outer, t_inner);
+    });
 }
 
 }  // namespace

@@ -125,14 +125,6 @@ struct UpsampleArgs {
 static_assert(sizeof(DownsampleArgs) == 656 && offsetof(DownsampleArgs, low) == 520, "pitch field in former padding");
 static_assert(sizeof(UpsampleArgs) == 632 && offsetof(UpsampleArgs, hi_ao) == 32, "pitch fields in the final pass's unused hi_depth");
 
-// Pitched surfaces (meao_execute_batch_pitched): a pass whose caller-memory row strides differ from the packed ones runs the
-// pitched instance of its kernel (meao_k_pitched*.hip); a stride of 0 or of the packed row means packed.
-inline bool downsample_pitched(const DownsampleArgs &d) { return d.depth_pitch != 0 && d.depth_pitch != d.w[0]; }
-inline bool final_pitched(const UpsampleArgs &a)
-{
-    return (a.pitch.depth != 0 && a.pitch.depth != a.hw) || (a.pitch.dst != 0 && a.pitch.dst != a.hw);
-}
-
 // Final pass (Upsample.main): HiResDB = LinearZ = f16(Linearize(depth)) (DS1:37-48, UPS:217-223) is evaluated from the caller's raw
 // depth frame inside the bilateral phase -- same reciprocal sequence, same f16 round trip, hostile texels divided with IEEE '/'
 // per lane -- instead of being read back from a LinearDepth buffer nothing else reads.  UpsampleArgs::vec_ok then also says
@@ -170,7 +162,8 @@ struct FrameArgs {
 
 // The launchers below take, for each argument block, an optional per-frame source: nullptr = the shared block (the kernarg
 // copy of `a`, the kernels of the shared calls), else the block's address in frame 0's FrameArgs of a device table
-// (`a` still selects the kernel and the grid).
+// (`a` still selects the kernel and the grid).  They take every form of a pass -- per-frame, row-pitched, linear depth -- and
+// hand it to the kernel unit that has it (meao_launch.hpp).
 hipError_t launch_downsample(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf = nullptr);
 hipError_t launch_render(const RenderArgs &a, int ao_format, int frames, hipStream_t s, const RenderArgs *pf = nullptr);
 hipError_t launch_render_wide(const RenderArgs &a, int ao_format, int frames, hipStream_t s, const RenderArgs *pf = nullptr);
@@ -192,45 +185,9 @@ bool fused_downsample_applicable(const UpsampleArgs &a, const HiDepthArgs &hi, c
 hipError_t launch_upsample_final_with_downsample(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, int ao_format,
                                                  int frames, hipStream_t s, const UpsampleArgs *pf = nullptr,
                                                  const HiDepthArgs *pf_hi = nullptr, const DownsampleArgs *pf_d = nullptr);
-// The per-frame forms (meao_k_*_frames.hip: units of their own, so that the shared kernels compile exactly as they would
-// without them).  `a` / `outer` select the kernel and the grid; every argument block comes from the table.
-hipError_t launch_downsample_frames(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf);
-hipError_t launch_render_frames(const RenderArgs &a, int ao_format, int frames, hipStream_t s, const RenderArgs *pf, bool wide);
-hipError_t launch_upsample_frames(const UpsampleArgs &a, const HiDepthArgs *hi, int ao_format, int frames, hipStream_t s,
-                                  const UpsampleArgs *pf, const HiDepthArgs *pf_hi);
-hipError_t launch_upsample_two_level_frames(const UpsampleArgs &outer, int ao_format, int frames, hipStream_t s,
-                                            const UpsampleArgs *pf_outer, const UpsampleArgs *pf_inner);
-hipError_t launch_upsample_three_level_frames(const UpsampleArgs &outer, int ao_format, int frames, hipStream_t s,
-                                              const UpsampleArgs *pf_outer, const UpsampleArgs *pf_mid, const UpsampleArgs *pf_inner);
-hipError_t launch_upsample_final_with_downsample_frames(const UpsampleArgs &a, int ao_format, int frames, hipStream_t s,
-                                                        const UpsampleArgs *pf, const HiDepthArgs *pf_hi, const DownsampleArgs *pf_d);
-// The pitched forms (meao_k_pitched*.hip): the launchers above hand a pass over to them when downsample_pitched / final_pitched
-// says its caller-memory strides are not the packed ones; pf != nullptr selects the per-frame kernels.  Every stride of the blocks
-// must then be set (a packed side carries its packed row).
-hipError_t launch_downsample_pitched(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf);
-hipError_t launch_downsample_pitched_frames(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf);
-hipError_t launch_upsample_final_pitched(const UpsampleArgs &a, const HiDepthArgs &hi, int ao_format, int frames, hipStream_t s,
-                                         const UpsampleArgs *pf, const HiDepthArgs *pf_hi);
-hipError_t launch_upsample_final_pitched_frames(const UpsampleArgs &a, const HiDepthArgs &hi, int ao_format, int frames, hipStream_t s,
-                                                const UpsampleArgs *pf, const HiDepthArgs *pf_hi);
-hipError_t launch_upsample_final_with_downsample_pitched(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, int ao_format,
-                                                         int frames, hipStream_t s, const UpsampleArgs *pf, const HiDepthArgs *pf_hi,
-                                                         const DownsampleArgs *pf_d);
-// Linear view-space depth (MEAO_DEPTH_LINEAR_F32 / _F16; meao_k_linear*.hip): the launchers above hand the passes that read the
-// depth frames over to these.  Linear01 = z * s with s = RN(1 / far_clip) in the zp0 field of DownsampleArgs / HiDepthArgs /
-// LinearDepthArgs (zp1 and reversed_z are not read).  The linear kernels always address the depth and result rows through the
-// pitch fields (a packed side carries its packed row): one instance serves packed and pitched calls.  pf != nullptr selects the
-// per-frame kernels.
+// Linear view-space depth (MEAO_DEPTH_LINEAR_F32 / _F16): Linear01 = z * s with s = RN(1 / far_clip) in the zp0 field of
+// DownsampleArgs / HiDepthArgs / LinearDepthArgs (zp1 and reversed_z are not read).
 inline bool linear_depth(int depth_format) { return depth_format == MEAO_DEPTH_LINEAR_F32 || depth_format == MEAO_DEPTH_LINEAR_F16; }
-hipError_t launch_downsample_linear(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf);
-hipError_t launch_downsample_linear_frames(const DownsampleArgs &a, int frames, hipStream_t s, const DownsampleArgs *pf);
-hipError_t launch_upsample_final_linear(const UpsampleArgs &a, const HiDepthArgs &hi, int ao_format, int frames, hipStream_t s,
-                                        const UpsampleArgs *pf, const HiDepthArgs *pf_hi);
-hipError_t launch_upsample_final_linear_frames(const UpsampleArgs &a, const HiDepthArgs &hi, int ao_format, int frames, hipStream_t s,
-                                               const UpsampleArgs *pf, const HiDepthArgs *pf_hi);
-hipError_t launch_upsample_final_with_downsample_linear(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, int ao_format,
-                                                        int frames, hipStream_t s, const UpsampleArgs *pf, const HiDepthArgs *pf_hi,
-                                                        const DownsampleArgs *pf_d);
 hipError_t launch_tile_atlas(const TileAtlasArgs &a, hipStream_t s);
 // LinearDepth (debug id 1) on demand: dst[i] = f16(Linearize(depth[i])) for one frame (DS1:37-48).
 struct LinearDepthArgs {
@@ -241,7 +198,6 @@ struct LinearDepthArgs {
     float zp0, zp1;
 };
 hipError_t launch_linear_depth(const LinearDepthArgs &a, hipStream_t s);
-hipError_t launch_linear_depth_view(const LinearDepthArgs &a, hipStream_t s);     // the linear formats (meao_k_linear.hip)
 // Debug view (PushDebugBlitCommands): src in `src_format` (meao_format), [slices][sh][sw] -> dst AO W x H.
 struct DebugViewArgs {
     const void *src;
