@@ -83,21 +83,26 @@ def nan_aware_equal(got, want):
     return not bad.any(), bad
 
 
-def hostile_frame(w, h, seed, cam=synth.DEFAULT_CAMERA, density=0.01, kinds=None):
-    """S2 frame with hostile texels sprinkled in (isolated ones and small blocks)."""
-    rng = np.random.default_rng(seed)
-    d = synth.make("S2", w, h, seed=seed).copy()
+def hostile_values(cam=synth.DEFAULT_CAMERA):
+    """{kind: raw depth value} of the hostile texels (hostile_frame; tests/white_tiles.py examines every kind on the oracle)."""
     fpn = np.float32(cam.far) / np.float32(cam.near)
     zp0 = (fpn - np.float32(1)) if cam.reversed_z else (np.float32(1) - fpn)
     zp1 = np.float32(1) if cam.reversed_z else fpn
     zero_den = np.float32(-zp1 / zp0)          # ZBufferParams.x * d + ZBufferParams.y == 0 (or nearly)
-    values = {
+    return {
         "nan": np.float32(np.nan), "pinf": np.float32(np.inf), "ninf": np.float32(-np.inf),
         "neg": np.float32(-0.25), "big": np.float32(7.5), "huge": np.float32(3e38), "nhuge": np.float32(-3e38),
         "denorm": np.float32(1e-41), "negzero": np.float32(-0.0), "zero_den": zero_den,
         "tiny_den": np.nextafter(zero_den, np.float32(0), dtype=np.float32), "one": np.float32(1.0),
         "zero": np.float32(0.0),
     }
+
+
+def hostile_frame(w, h, seed, cam=synth.DEFAULT_CAMERA, density=0.01, kinds=None):
+    """S2 frame with hostile texels sprinkled in (isolated ones and small blocks)."""
+    rng = np.random.default_rng(seed)
+    d = synth.make("S2", w, h, seed=seed).copy()
+    values = hostile_values(cam)
     names = list(values) if kinds is None else list(kinds)
     n = max(1, int(w * h * density))
     ys, xs = rng.integers(0, h, n), rng.integers(0, w, n)

@@ -10,7 +10,14 @@ path and its IEEE redo -- the reference stores 0 for the NaN, 255 for the others
 shortcut compiled out).  Every path that instantiates the tile runs them: plain 64 x 64 and 64 x 32 tiles, the fused last
 kernel of pipelined batches (asserted from the launch record: steps 1 and 2 launch no downsample pass), the pitched and the per-frame-parameter entry points, linear depth, fp16 AO (compiled out), a
 frame whose last tile row is partial, and the variant libraries with the shortcut off / the window read from LowDepth1.  That the
-white path is the one that runs on white tiles is read from the phase stamps of the `clocks` variant (test_the_white_path_runs)."""
+white path is the one that runs on white tiles is read from the phase stamps of the `clocks` variant (test_the_white_path_runs).
+
+Second half: the input classes and entry points the shortcut meets in the field -- sky and half-sky frames under both Z conventions,
+the radial gradient, UNORM16 and linear f32 / f16 depth, both sides of the edges of the exact-division range, far-outside intensity and
+thickness, 1 and 2 levels, hq_levels, the exhaustive sample set, single-pass stereo, per-frame parameter batches inside the exact
+column and with one frame outside it, pitched surfaces with a vector pitch and with pitch 389, 380 x 320, 400 x 330, 384 x 312 and the
+shaded call.  The window, wave and lane tests are in tests/test_white_tiles_window_gpu.py."""
+import dataclasses
 import os
 import subprocess
 import sys
@@ -18,7 +25,7 @@ import sys
 import numpy as np
 import pytest
 
-from miniengineao_amd import FrameParams
+from miniengineao_amd import FrameParams, synth
 from miniengineao_amd import _lib as L
 from tests import helpers as H
 from tests import white_tiles as WT
@@ -214,3 +221,264 @@ def test_variant_libraries(variant):
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "white_tiles_variant_check.py")], cwd=ROOT,
                           env=dict(os.environ, MEAO_LIB_PATH=lib), capture_output=True, text=True, timeout=300)
     assert proc.returncode == 0, (proc.stdout[-1500:], proc.stderr[-1500:])
+
+
+# ---- input classes and entry points the shortcut meets in the field.  Every case: the whole result and the low-res AO against the
+# oracle for 64 x 64 and 64 x 32 tiles; the oracle must find white tiles in the frame, so that no case passes because the shortcut
+# never fires (which path DOES fire is read from the phase stamps: tests/white_tiles_clocks_check.py).
+
+CONV = dataclasses.replace(synth.DEFAULT_CAMERA, reversed_z=False)
+CAM128 = synth.Camera(near=0.1, far=128.0, reversed_z=True)
+RAW_Z2 = np.float32(63.0 / 1279.0)       # with CAM128: 1279 d + 1 rounds to 64, dist = 1 / 64, z = 2.0 -- exact in f16
+TILE_IDS = ["tiles64x64", "tiles64x32"]
+_WANT = {}
+
+
+def want_of(oracle, key, depth, s):
+    """Oracle outputs, computed once per (case, Settings) and shared by the tile heights; never modified."""
+    key = (key, tuple(sorted(vars(s).items())), depth.shape, str(depth.dtype))
+    if key not in _WANT:
+        _WANT[key] = oracle.run(depth, s)
+    return _WANT[key]
+
+
+def check_class(oracle, key, s, depth, debug, lib_depth=None, white=True, **kw):
+    want = want_of(oracle, key, depth, s)
+    tiles = WT.white_tiles_h(WT.low_ao(want, s), s.width, s.height, 64 if debug else 32)
+    assert bool([t for t in tiles if 32 * t[0] >= 4 and 32 * t[0] + 35 < (s.width + 1) // 2]) == white, (key, tiles)
+    ao = H.component(s, debug=debug, **kw)
+    try:
+        same(ao.render(depth if lib_depth is None else lib_depth), want["result"], key)
+        assert ao.hostile_frames() == 0          # no frame here is hostile: the column depends on the parameters alone
+        same(ao.debug_buffer(14 if s.num_levels > 1 else 10), WT.low_ao(want, s), "low-res AO")
+    finally:
+        ao.close()
+    return want
+
+
+def field_frame(name):
+    cam = CONV if name.endswith("_convz") else synth.DEFAULT_CAMERA
+    kind = name.replace("_convz", "")
+    d = {"sky": lambda: WT.sky_frame(cam.reversed_z), "half_sky": lambda: WT.half_sky_frame(cam), "flat": WT.flat_frame,
+         "radial": lambda: synth.radial_gradient(WT.W, WT.H, cam)}[kind]()
+    return cam, d
+
+
+@pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
+@pytest.mark.parametrize("name", ["sky", "sky_convz", "half_sky", "half_sky_convz", "radial"])
+def test_field_frames(oracle, name, debug):
+    cam, d = field_frame(name)
+    check_class(oracle, name, H.settings(oracle, WT.W, WT.H, cam=cam), d, debug)
+
+
+@pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
+@pytest.mark.parametrize("name", ["flat", "half_sky"])
+def test_unorm16_depth(oracle, name, debug):
+    _, d = field_frame(name)
+    s = H.settings(oracle, WT.W, WT.H, depth_format=oracle.DEPTH_UNORM16)
+    check_class(oracle, "u16_" + name, s, oracle.encode_depth(d, oracle.DEPTH_UNORM16), debug, depth_format=L.DEPTH_UNORM16)
+
+
+@pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
+@pytest.mark.parametrize("fmt", ["f32", "f16"])
+@pytest.mark.parametrize("name", ["flat", "half_sky"])
+def test_linear_depth_classes(oracle, name, fmt, debug):
+    """Linear view-space depth, far_clip 128: the plane at z = 2.0 (exact in f16), sky texels far or +inf, alternating."""
+    s = H.settings(oracle, WT.W, WT.H, cam=CAM128)
+    z_plane = WT.linear_z_of_constant(RAW_Z2, CAM128)
+    assert z_plane == np.float32(2.0)
+    d = np.full((WT.H, WT.W), RAW_Z2, np.float32)
+    z = np.full((WT.H, WT.W), z_plane, np.float32)
+    if name == "half_sky":
+        d[:, :WT.W // 2] = 0.0
+        sky = np.zeros(d.shape, bool)
+        sky[:, :WT.W // 2] = True
+        alt = (np.arange(d.size).reshape(d.shape) & 1) == 1
+        z[sky & alt], z[sky & ~alt] = np.inf, np.float32(128.0)
+    check_class(oracle, "lin_" + name, s, d, debug, lib_depth=z if fmt == "f32" else z.astype(np.float16),
+                depth_format=L.DEPTH_LINEAR_F32 if fmt == "f32" else L.DEPTH_LINEAR_F16)
+
+
+@pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
+@pytest.mark.parametrize("side", ["inside", "outside"])
+def test_exact_range_edges_on_white_frames(oracle, meao_lib, side, debug):
+    """Just inside each edge the context keeps the exact-reciprocal column (the shortcut's instance), just outside it runs IEEE
+    division.  Here both sides must equal the oracle; helpers.in_exact_range only restates the library's rule.  WHICH column ran
+    for these same frames and values is read from the kernel names in test_the_edges_select_the_column_on_white_frames, and that
+    the white path runs just inside from the phase stamps (tests/white_tiles_clocks_check.py)."""
+    for edge, (field, inside, outside) in sorted(H.exact_range_edges(meao_lib).items()):
+        v = inside if side == "inside" else outside
+        assert H.in_exact_range(meao_lib, **{field: v}) == (side == "inside")
+        for name in ("flat", "half_sky", "radial"):
+            cam, d = field_frame(name)
+            s = H.settings(oracle, WT.W, WT.H, cam=cam, **{field: v})
+            check_class(oracle, (edge, side, name), s, d, debug)
+
+
+@pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
+def test_far_outside_intensity_and_thickness(oracle, meao_lib, debug):
+    _, d = field_frame("half_sky")
+    for field in ("intensity", "thickness_modifier"):
+        for v in H.FAR_OUTSIDE[field]:
+            assert H.in_exact_range(meao_lib, **{field: v})              # these leave the exact range untouched
+            want = want_of(oracle, (field, v), d, H.settings(oracle, WT.W, WT.H, **{field: v}))
+            white = bool(WT.white_tiles_h(want["combined1"], WT.W, WT.H))
+            check_class(oracle, (field, v), H.settings(oracle, WT.W, WT.H, **{field: v}), d, debug, white=white)
+
+
+@pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
+@pytest.mark.parametrize("kw", [dict(num_levels=1), dict(num_levels=2), dict(hq_levels=2), dict(single_pass_stereo=True)],
+                         ids=["levels1", "levels2", "hq2", "stereo"])
+def test_level_counts_and_variants(oracle, kw, debug):
+    _, d = field_frame("half_sky")
+    s = H.settings(oracle, WT.W, WT.H, **kw)
+    want = want_of(oracle, str(kw), d, s)
+    check_class(oracle, str(kw), s, d, debug, white=bool(WT.white_tiles_h(WT.low_ao(want, s), WT.W, WT.H)))
+
+
+@pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
+def test_exhaustive_sample_set(oracle, debug):
+    _, d = field_frame("half_sky")
+    s = H.settings(oracle, WT.W, WT.H, sample_set=oracle.SAMPLES_EXHAUSTIVE)
+    want = want_of(oracle, "exhaustive", d, s)
+    check_class(oracle, "exhaustive", s, d, debug, white=bool(WT.white_tiles_h(want["combined1"], WT.W, WT.H)))
+
+
+def frame_settings(base, p):
+    names = {"intensity": "intensity", "blurTolerance": "blur_tolerance", "upsampleTolerance": "upsample_tolerance",
+             "noiseFilterTolerance": "noise_filter_tolerance", "thicknessModifier": "thickness_modifier"}
+    return dataclasses.replace(base, **{names[k]: v for k, v in dataclasses.asdict(p).items() if v is not None})
+
+
+@pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
+@pytest.mark.parametrize("mixed", [False, True], ids=["exact_column", "one_frame_outside"])
+def test_per_frame_parameter_batches(oracle, meao_lib, mixed, debug):
+    """Default, inside-edge and other blur / intensity values per frame: the call stays in the exact column; with one outside-edge
+    frame the whole call runs IEEE division and must still match."""
+    edges = H.exact_range_edges(meao_lib)
+    params = [FrameParams(), FrameParams(upsampleTolerance=edges["upsample_high"][1]), FrameParams(blurTolerance=-3.0, intensity=0.5),
+              FrameParams(noiseFilterTolerance=edges["noise_high"][1]), FrameParams(upsampleTolerance=edges["upsample_low"][1])]
+    if mixed:
+        params[3] = FrameParams(upsampleTolerance=edges["upsample_high"][2])
+    depths = [field_frame(n)[1] for n in ("flat", "half_sky", "radial", "half_sky", "flat")]
+    base = H.settings(oracle, WT.W, WT.H)
+    ao = H.component(base, max_batch=len(depths), debug=debug)
+    try:
+        got = ao.render_batch(depths, params=params)
+        white = 0
+        for f, (d, p) in enumerate(zip(depths, params)):
+            s = frame_settings(base, p)
+            want = want_of(oracle, ("pf", mixed, f), d, s)
+            white += len(WT.white_tiles_h(want["combined1"], WT.W, WT.H))
+            same(got[f], want["result"], (f, p))
+            same(ao.debug_buffer(14, frame=f), want["combined1"], ("combined1", f, p))
+        assert white > 0
+    finally:
+        ao.close()
+
+
+@pytest.mark.parametrize("pitch", [WT.W + 8, 389], ids=["vector_pitch", "pitch389"])
+@pytest.mark.parametrize("name", ["sky", "half_sky"])
+def test_pitched_surfaces_of_field_frames(oracle, name, pitch):
+    """Pitch 389: rows are not 16-byte aligned (vec_ok false), the shortcut stands down and the normal path stores the same 255s."""
+    torch = pytest.importorskip("torch")
+    _, d = field_frame(name)
+    s = H.settings(oracle, WT.W, WT.H)
+    want = want_of(oracle, name, d, s)
+    dev = torch.device("cuda", 0)
+    dsurf = torch.full((1, WT.H, pitch), 0.5, dtype=torch.float32, device=dev)
+    osurf = torch.full((1, WT.H, pitch), 7, dtype=torch.uint8, device=dev)
+    dsurf[0, :, :WT.W] = torch.from_numpy(np.array(d)).to(dev)
+    ao = H.component(s, debug=TALL)
+    try:
+        ao.execute_tensors(dsurf[:, :, :WT.W], osurf[:, :, :WT.W])
+        torch.cuda.synchronize(dev)
+        got = osurf.cpu().numpy()[0]
+        same(got[:, :WT.W], want["result"], (name, pitch))
+        assert (got[:, WT.W:] == 7).all()
+        same(ao.debug_buffer(14), want["combined1"], ("combined1", name, pitch))
+    finally:
+        ao.close()
+
+
+@pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
+@pytest.mark.parametrize("w,h", [(380, 320), (400, 330), (384, 312)])
+def test_frame_sizes_with_partial_tiles(oracle, w, h, debug):
+    """380 x 320: the constant plane, white everywhere on the oracle -- but the low width is 190, no multiple of 4, so no tile is
+    interior or from-raw and the shortcut never fires at this size: the normal path must store the same 255s.
+    384 x 312, all sky: twelve white tiles above tile rows that are not (the low-res AO of the reference is not code 255 where a
+    level's size is not whole -- for the plane and for the sky alike), and a partial last tile row with masked stores.
+    400 x 330, all sky: a partial right column and bottom row; NO tile is white at this size, for the sky or the plane (same
+    reason), so this case only shows that the result is the oracle's -- all 255 -- with the shortcut compiled in."""
+    d = WT.flat_frame(w, h) if (w, h) == (380, 320) else WT.sky_frame(True, w, h)
+    s = H.settings(oracle, w, h)
+    want = want_of(oracle, (w, h), d, s)
+    assert len(WT.white_tiles_h(want["combined1"], w, h)) == {(380, 320): 30, (384, 312): 12, (400, 330): 0}[(w, h)]
+    assert (want["result"] == 255).all()
+    ao = H.component(s, debug=debug)
+    try:
+        same(ao.render(d), want["result"], (w, h))
+        same(ao.debug_buffer(14), want["combined1"], ("combined1", w, h))
+    finally:
+        ao.close()
+
+
+def test_shaded_batch_on_half_sky(oracle):
+    """meao_execute_batch_shaded: the AO of the white path composited by the same call, against oracle.composite of the oracle's AO."""
+    torch = pytest.importorskip("torch")
+    _, d = field_frame("half_sky")
+    s = H.settings(oracle, WT.W, WT.H)
+    want = want_of(oracle, "half_sky", d, s)
+    rng = np.random.default_rng(5)
+    color = rng.random((WT.H, WT.W, 4), dtype=np.float32).astype(np.float16)
+    expect = color.copy()
+    oracle.composite(np.array(want["result"]), expect, L.COMPOSITE_MULTIPLY)
+    dev = torch.device("cuda", 0)
+    ct = torch.from_numpy(color.copy()).to(dev)[None]
+    ao = H.component(s, debug=TALL)
+    try:
+        out = ao.execute_tensors(torch.from_numpy(np.array(d)).to(dev)[None], color=ct, mode=L.COMPOSITE_MULTIPLY)
+        torch.cuda.synchronize(dev)
+        same(out.cpu().numpy()[0], want["result"], "AO")
+        same(ao.debug_buffer(14), want["combined1"], "combined1")
+        got = ct.cpu().numpy()[0]
+        assert np.array_equal(got.view(np.uint16), expect.view(np.uint16)), H.diff_report("colour", got.view(np.uint16), expect.view(np.uint16))
+    finally:
+        ao.close()
+
+
+EDGE_TRACE_CHILD = r"""
+import sys
+import numpy as np
+from oracle import oracle as O
+from miniengineao_amd import _lib as L
+from tests import helpers as H
+from tests import white_tiles as WT
+from tests.test_white_tiles_gpu import field_frame
+
+side = sys.argv[1]
+O.build()
+for edge, (field, inside, outside) in sorted(H.exact_range_edges(L.load()).items()):
+    for name in ("flat", "half_sky", "radial"):
+        cam, d = field_frame(name)
+        s = H.settings(O, WT.W, WT.H, cam=cam, **{field: inside if side == "inside" else outside})
+        for debug in ({L.DEBUG_FINAL_SMALL_MAX_TILES: 0}, None):
+            ao = H.component(s, debug=debug)
+            got = ao.render(d)
+            ao.close()
+            assert np.array_equal(got, O.run(d, s, result_only=True)["result"]), (edge, name, debug)
+print("white edges ok", side)
+"""
+
+
+@pytest.mark.parametrize("side,div", [("inside", "0"), ("outside", "1")])
+def test_the_edges_select_the_column_on_white_frames(tmp_path, side, div):
+    """The frames and values of test_exact_range_edges_on_white_frames in a child under the kernel trace: every kernel of the child
+    is of the exact-reciprocal column just inside the edges and of the IEEE column just outside (tests/kernel_inventory.py
+    column_of, as tests/test_param_domain_gpu.py reads it)."""
+    from tests import kernel_inventory as K
+    k = H.kernel_trace(tmp_path, EDGE_TRACE_CHILD, [side])
+    assert "white edges ok" in k.stdout
+    cols = {K.column_of(n) for n in k.short} - {None}
+    assert cols, k.short[:20]
+    assert {c[2] if c[0] != "ds" else c[1] for c in cols} == {div}, (side, sorted(cols))

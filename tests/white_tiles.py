@@ -61,5 +61,429 @@ from miniengineao_amd.synth import interior_white, white_tiles, window_white    
 from miniengineao_amd.synth import white_tile_map as tile_map                     # noqa: E402
 
 
-def result_tile(result, tx, ty):
-    return result[ty * TILE:(ty + 1) * TILE, tx * TILE:(tx + 1) * TILE]
+def result_tile(result, tx, ty, tile_h=TILE):
+    return result[ty * tile_h:(ty + 1) * tile_h, tx * TILE:(tx + 1) * TILE]
+
+
+# ---- the rule for both tile heights and any level count.  A 64 x tile_h tile (tile_h 64 or 32) has the (tile_h / 2 + 6)-row window
+# rows [ty tile_h / 2 - 3, ty tile_h / 2 + tile_h / 2 + 2] (64 x 32 tiles: [16 ty - 3, 16 ty + 18]) x columns [32 tx - 3, 32 tx + 34]
+# of the low-res AO the final pass reads: `combined1`, or `occlusion1` when there is one level only.
+
+SKY = {True: np.float32(0.0), False: np.float32(1.0)}        # reversed_z -> the raw depth of a sky texel
+
+
+def low_ao(r, s):
+    """The low-res AO the full-resolution pass upsamples, from the oracle's outputs r under Settings s."""
+    return r["combined1"] if s.num_levels > 1 else r["occlusion1"]
+
+
+def window(ao1, tx, ty, tile_h=TILE):
+    """The clamp-addressed window of tile (tx, ty): (tile_h / 2 + 6) x 38 codes."""
+    lh, lw = ao1.shape
+    half = tile_h // 2
+    ys = np.clip(np.arange(ty * half - 3, ty * half + half + 3), 0, lh - 1)
+    xs = np.clip(np.arange(tx * 32 - 3, tx * 32 + 35), 0, lw - 1)
+    return ao1[np.ix_(ys, xs)]
+
+
+def window_white_h(ao1, tx, ty, tile_h=TILE):
+    return bool((window(ao1, tx, ty, tile_h) == 255).all())
+
+
+def tile_counts(width, height, tile_h=TILE):
+    return (width + TILE - 1) // TILE, (height + tile_h - 1) // tile_h
+
+
+def white_tiles_h(ao1, width, height, tile_h=TILE):
+    """(tx, ty) of the 64 x tile_h tiles whose window is white."""
+    nx, ny = tile_counts(width, height, tile_h)
+    return [(tx, ty) for ty in range(ny) for tx in range(nx) if window_white_h(ao1, tx, ty, tile_h)]
+
+
+def broken_tiles(r, s, tile_h=TILE):
+    """(white tiles, those of them whose result tile is not all 255) of oracle outputs r."""
+    tiles = white_tiles_h(low_ao(r, s), s.width, s.height, tile_h)
+    return tiles, [t for t in tiles if (result_tile(r["result"], *t, tile_h) != 255).any()]
+
+
+def from_raw(tx, ty, width, height, tile_h=TILE):
+    """Tile (tx, ty) fills its window from the raw depth (meao_dev_upsample.hpp ups_tile_from_raw): no horizontal clamping, low
+    width a multiple of 4, and the tile row whole inside the frame."""
+    lw = (width + 1) // 2
+    return lw % 4 == 0 and 32 * tx >= 4 and 32 * tx + 35 < lw and (ty + 1) * tile_h <= height
+
+
+# ---- frames
+
+def sky_frame(reversed_z=True, w=W, h=H):
+    return np.full((h, w), SKY[reversed_z], np.float32)
+
+
+def half_sky_frame(cam=None, w=W, h=H, lin=0.37):
+    """A plane at Linear01 depth `lin`, columns 0 .. w / 2 - 1 sky."""
+    from miniengineao_amd import synth
+    cam = cam or synth.DEFAULT_CAMERA
+    d = np.full((h, w), synth.linear01_to_raw(np.float64(lin), cam), np.float32)
+    d[:, :w // 2] = SKY[cam.reversed_z]
+    return d
+
+
+def sky_and_flat_occluders(cam=None, w=W, h=H, seed=5):
+    """synth.occluder_field with a 176 x 176 sky block (top left) and a 176 x 208 block of the constant plane (bottom right).  The
+    flat block holds white tiles.  The sky block holds none, and no larger one would at this frame size: sky texels have low-res
+    AO 255 only far from geometry -- in half_sky_frame all 96 low-res sky columns are non-white -- so sky tiles are white in
+    frames that are (nearly) all sky; the oracle-side tests assert exactly that."""
+    from miniengineao_amd import synth
+    cam = cam or synth.DEFAULT_CAMERA
+    d = synth.occluder_field(w, h, seed, cam=cam).copy()
+    d[0:176, 0:176] = SKY[cam.reversed_z]
+    lin = 1.0 / ((float(np.float32(cam.far) / np.float32(cam.near)) - 1.0) * float(FLAT) + 1.0)      # the constant plane's Linear01 depth
+    d[144:320, 176:384] = FLAT if cam.reversed_z else synth.linear01_to_raw(np.float64(lin), cam)
+    return d
+
+
+BLOCK_VALUES = tuple(np.float32(v) for v in (0.1, 0.0975, 0.095))
+
+
+def block_frame(x0, y0, size=4, value=BLOCK_VALUES[0], w=W, h=H):
+    """The block family: the constant frame with ONE size x size block (4 or 8) of raw depth `value` (0.095 .. 0.1: a little nearer
+    than the plane) at even coordinates (x0, y0)."""
+    assert size in (4, 8) and x0 % 2 == 0 and y0 % 2 == 0 and np.float32(0.095) <= value <= np.float32(0.1)
+    d = flat_frame(w, h)
+    d[y0:y0 + size, x0:x0 + size] = value
+    return d
+
+
+def dark_lines(win):
+    """(rows, columns) of the window that hold a non-white texel, as sorted lists."""
+    ys, xs = np.nonzero(win != 255)
+    return sorted(set(ys.tolist())), sorted(set(xs.tolist()))
+
+
+def bands(lines):
+    """The sorted line numbers grouped into bands of adjacent lines: [[22, 23], [30, 31]]."""
+    out = []
+    for v in lines:
+        if out and v == out[-1][-1] + 1:
+            out[-1].append(v)
+        else:
+            out.append([v])
+    return out
+
+
+def narrow(lines):
+    """At most two bands, of at most two adjacent lines each."""
+    b = bands(lines)
+    return 0 < len(b) <= 2 and all(len(x) <= 2 for x in b)
+
+
+# ---- where a hi-res texel of a tile sits in the workgroup (meao_dev_upsample.hpp: lane tid owns the 4 columns 4 (tid & 15) .. + 3 of
+# the two rows 2 ((tid >> 4) + 16 pass) + f of each pass; a wave is 64 lanes: local rows 8 w .. 8 w + 7 of each 32-row pass)
+
+def lane_position(y, x, tile_h=TILE):
+    """{tile, wave, pass, row (of the pair), column (of the lane's quad), kind ('oo' odd row odd column, 'oe', 'eo')} of texel (y, x)."""
+    ly, lx = y % tile_h, x % TILE
+    return {"tile": (x // TILE, y // tile_h), "wave": (ly % 32) // 8, "pass": ly // 32, "row": ly & 1, "column": lx & 3,
+            "kind": "eo"[ly & 1] + "eo"[lx & 1]}
+
+
+def nan_frames(tile_h=TILE, w=W, h=H):
+    """Frames of the constant plane with ONE NaN per from-raw tile, never on a level texel (even row and even column).  Over the
+    frames the NaNs visit every (wave, pass, row of the pair) with each of the kinds 'oo', 'oe', 'eo' that row allows, and all four
+    columns of a lane's quad.  Returns [(depth, [(y, x), ...])]."""
+    nx, ny = tile_counts(w, h, tile_h)
+    tiles = [(tx, ty) for ty in range(ny) for tx in range(nx) if from_raw(tx, ty, w, h, tile_h)]
+    spots = []
+    for p in range(tile_h // 32):
+        for wave in range(4):
+            for row, kinds in ((0, ("eo",)), (1, ("oo", "oe"))):
+                for kind in kinds:
+                    for n, col in enumerate((1, 3) if kind[1] == "o" else (0, 2)):
+                        pair = (len(spots) + n) % 4                      # which of the wave's four row pairs
+                        lane = (5 * len(spots) + 3) % 16                 # which of the 16 lanes of that row pair
+                        spots.append((32 * p + 8 * wave + 2 * pair + row, 4 * lane + col))
+    frames = []
+    for i in range(0, len(spots), len(tiles)):
+        d, at = flat_frame(w, h), []
+        for (tx, ty), (ly, lx) in zip(tiles, spots[i:i + len(tiles)]):
+            y, x = ty * tile_h + ly, tx * TILE + lx
+            assert (y & 1) or (x & 1)
+            d[y, x] = np.nan
+            at.append((y, x))
+        frames.append((d, at))
+    return frames
+
+
+# ---- the window plan: block frames (block_frame: one 4 x 4 block of raw 0.1 each) placed so that ONE from-raw tile sees darkness only
+# in chosen lines of its window -- and its result tile changes.  Found by running the oracle over every even (x0, y0) of the frame
+# (30 369 frames) and kept here as data; check_window_plan() evaluates on the oracle what each frame is for, so a change of the
+# reference algorithm that moves the darkness fails on the CPU, not silently on the GPU.
+
+def _spot(x0, y0, tile, **need):
+    return dict(at=(x0, y0), tile=tile, need=need)
+
+
+def window_plan(tile_h):
+    """{group: [spot]}; a spot is {at: (x0, y0), tile: (tx, ty), need: {...}} with need keys
+    rows / cols: (lo, hi) all non-white window texels lie in these window lines;  sweep: 'rows' / 'cols' the spot belongs to that sweep."""
+    R = tile_h // 2 + 6
+    mid, last = (2, 4) if tile_h == TILE else (4, 9)            # an interior tile row (hi-res rows 128 ..) and the last full one
+    b0 = 226 if tile_h == TILE else 194                          # the block under the bottom apron of the interior tile
+    out = {"sides": [
+        _spot(90, 128, (2, mid), cols=(0, 1)), _spot(226, 128, (2, mid), cols=(36, 37)),
+        _spot(128, 90, (2, mid), rows=(0, 1)), _spot(128, b0, (2, mid), rows=(R - 2, R - 1)),
+        # tile row 0: the top apron is clamp-addressed; the last full tile row: the bottom apron is
+        _spot(90, 18, (2, 0), cols=(0, 1)), _spot(226, 18, (2, 0), cols=(36, 37)),
+        _spot(128, 98 if tile_h == TILE else 66, (2, 0), rows=(R - 2, R - 1)),
+        _spot(90, 320 - tile_h, (2, last), cols=(0, 1)), _spot(226, 320 - tile_h, (2, last), cols=(36, 37)),
+        # (64 x 32 tiles: a block that darkens rows 0..1 alone of a last-row tile does not exist in the family -- where it would
+        # stand the clamped bottom lines 18..21 darken too; the nearest frame has rows 1..2, columns 2..3)
+        _spot(128, 218, (2, last), rows=(0, 1)) if tile_h == TILE else _spot(102, 260, (2, last), rows=(0, 2)),
+    ]}
+    cb = (208, 224) if tile_h == TILE else (176, 192)
+    out["corners"] = [
+        _spot(92, 108, (2, mid), rows=(0, 2), cols=(0, 2)), _spot(208, 92, (2, mid), rows=(0, 2), cols=(35, 37)),
+        _spot(92, cb[0], (2, mid), rows=(R - 3, R - 1), cols=(0, 2)), _spot(208, cb[1], (2, mid), rows=(R - 3, R - 1), cols=(35, 37)),
+    ]
+    if tile_h == TILE:
+        ys = [114, 116, 118, 120, 124, 126, 128, 130, 132, 134, 136, 146, 154, 156, 158, 180, 182, 184, 186, 188, 190, 192, 196, 198, 200, 202]
+        ends = [(128, 90), (128, 226), (146, 92), (146, 94), (146, 222), (146, 224)]
+    else:
+        ys = [114, 116, 118, 120, 128, 130, 154, 156, 164, 166, 168, 170]
+        ends = [(128, 90), (128, 194), (146, 92), (146, 94), (146, 190), (146, 192)]
+    out["row_sweep"] = [_spot(94, y, (2, mid), sweep="rows") for y in ys] + [_spot(x, y, (2, mid), sweep="rows") for x, y in ends]
+    xs = [114, 116, 118, 120, 124, 126, 128, 130, 132, 134, 136, 146, 154, 156, 158, 180, 182, 184, 186, 188, 190, 192, 196, 198, 200, 202]
+    ends = [(90, 128), (92, 146), (94, 146), (222, 146), (224, 146), (226, 128)] if tile_h == TILE else \
+           [(90, 128), (92, 130), (94, 132), (222, 132), (224, 130), (226, 128)]
+    out["col_sweep"] = [_spot(x, 94, (2, mid), sweep="cols") for x in xs] + [_spot(x, y, (2, mid), sweep="cols") for x, y in ends]
+    for group in out.values():
+        assert len(group) <= 64
+    return out
+
+
+_SPOT_RUNS = {}
+
+
+def spot_view(oracle, s, spot, tile_h):
+    """(depth, oracle outputs, window of the spot's tile, changed result texels of that tile); one oracle run per frame, Settings
+    and process."""
+    key = (spot["at"], tuple(sorted(vars(s).items())))
+    if key not in _SPOT_RUNS:
+        d = block_frame(*spot["at"], w=s.width, h=s.height)
+        d.setflags(write=False)
+        _SPOT_RUNS[key] = (d, oracle.run(d, s))
+    d, r = _SPOT_RUNS[key]
+    win = window(low_ao(r, s), *spot["tile"], tile_h)
+    return d, r, win, int((result_tile(r["result"], *spot["tile"], tile_h) != 255).sum())
+
+
+# lines of a 38-line window axis that no block of the family reaches with two bands: the darkness of a block comes in up to three
+# bands 8 lines apart, and for a line 16..21 all three fit into the window whichever of them the line is in
+THREE_BANDS = range(16, 22)
+
+
+def check_window_plan(oracle, tile_h, log=None):
+    """Evaluates on the oracle what every frame of window_plan(tile_h) is for (asserts), and the band coverage of the two sweeps.
+    Returns {('rows' | 'cols', line): bands of the narrowest frame that hits the line}."""
+    from tests import helpers
+    s_ = helpers.settings(oracle, W, H)
+    plan = window_plan(tile_h)
+    R = tile_h // 2 + 6
+    best = {}
+    for group, spots in plan.items():
+        for spot in spots:
+            tx, ty = spot["tile"]
+            assert from_raw(tx, ty, W, H, tile_h), spot
+            _, r, win, changed = spot_view(oracle, s_, spot, tile_h)
+            rows, cols = dark_lines(win)
+            assert rows and changed > 0, (group, spot, rows, cols, changed)          # a frame that changes nothing is no evidence
+            need = spot["need"]
+            if "rows" in need:
+                assert need["rows"][0] <= rows[0] and rows[-1] <= need["rows"][1], (group, spot, rows)
+            if "cols" in need:
+                assert need["cols"][0] <= cols[0] and cols[-1] <= need["cols"][1], (group, spot, cols)
+            if "sweep" in need:
+                lines = rows if need["sweep"] == "rows" else cols
+                b = bands(lines)
+                for ln in lines:
+                    ok = narrow(lines) or (ln in THREE_BANDS and len(b) == 3 and all(len(x) <= 2 for x in b))
+                    key = (need["sweep"], ln)
+                    if ok and (key not in best or (len(b), len(lines)) < (len(best[key]), sum(map(len, best[key])))):
+                        best[key] = b
+    for axis, n in (("rows", R), ("cols", 38)):
+        missing = [ln for ln in range(n) if (axis, ln) not in best]
+        assert not missing, (tile_h, axis, missing)
+        for ln in range(n):
+            b = best[(axis, ln)]
+            three = axis == "cols" or tile_h == TILE
+            assert len(b) <= (3 if three and ln in THREE_BANDS else 2), (axis, ln, b)
+            if log:
+                log(f"tile_h {tile_h} {axis[:-1]} {ln:2d}: {b}")
+    return best
+
+
+# ---- the exact-division range (meao_api.cpp exact_rcp_div_applicable) on the ORACLE's constants, for tests that have no library
+
+def oracle_in_exact_range(oracle, s):
+    u = oracle.upsample_constants(s, 1)
+    return 2.0 ** -44 <= u.upsample_tolerance <= 2.0 ** 20 and 2.0 ** -30 <= u.noise_filter_strength <= 2.0 ** 50
+
+
+def oracle_exact_range_edges(oracle, s):
+    """{edge: (Settings field, last float32 value inside the exact range, first one outside)}: helpers.exact_range_edges, bisected on
+    oracle.upsample_constants instead of the library's."""
+    import dataclasses
+
+    def inside_at(field, v):
+        return oracle_in_exact_range(oracle, dataclasses.replace(s, **{field: float(v)}))
+
+    def edge(field, inside, outside):
+        inside, outside = np.float32(inside), np.float32(outside)
+        assert inside_at(field, inside) and not inside_at(field, outside)
+        while np.nextafter(inside, outside, dtype=np.float32) != outside:
+            mid = np.float32((float(inside) + float(outside)) / 2)
+            if mid in (inside, outside):
+                mid = np.nextafter(inside, outside, dtype=np.float32)
+            if inside_at(field, mid):
+                inside = mid
+            else:
+                outside = mid
+        return float(inside), float(outside)
+    return {"upsample_low": ("upsample_tolerance",) + edge("upsample_tolerance", -12.0, -16.0),
+            "upsample_high": ("upsample_tolerance",) + edge("upsample_tolerance", 0.0, 8.0),
+            "noise_high": ("noise_filter_tolerance",) + edge("noise_filter_tolerance", 0.0, 12.0)}
+
+
+# ---- unclean lanes
+
+def check_nan_frames(oracle, tile_h):
+    """nan_frames(tile_h) on the oracle: the low-res AO stays all 255, the result is 0 at exactly the NaN texels; the NaNs visit every
+    (wave, pass, row of the pair, kind) and at least two columns of the quad for each.  Returns [(depth, oracle outputs)]."""
+    from tests import helpers
+    s = helpers.settings(oracle, W, H)
+    seen, out = {}, []
+    for d, at in nan_frames(tile_h):
+        tiles = [lane_position(y, x, tile_h)["tile"] for y, x in at]
+        assert len(set(tiles)) == len(tiles) and all(from_raw(*t, W, H, tile_h) for t in tiles)      # one hostile texel per tile at most
+        r = oracle.run(d, s)
+        assert (r["combined1"] == 255).all()
+        assert sorted(map(tuple, np.argwhere(r["result"] != 255).tolist())) == sorted(at) and all(r["result"][p] == 0 for p in at)
+        for y, x in at:
+            p = lane_position(y, x, tile_h)
+            seen.setdefault((p["wave"], p["pass"], p["row"], p["kind"]), set()).add(p["column"])
+        d.setflags(write=False)
+        out.append((d, r))
+    want = {(w, p, row, kind) for w in range(4) for p in range(tile_h // 32) for row, kinds in ((0, ("eo",)), (1, ("oo", "oe"))) for kind in kinds}
+    assert set(seen) == want and all(len(c) >= 2 for c in seen.values()), seen
+    return out
+
+
+def hostile_kinds_that_show(oracle):
+    """The kinds of helpers.hostile_frame whose value, put on ODD_TEXEL of the constant frame, leaves the low-res AO all 255 and makes
+    the oracle's result differ from 255 there: found on the oracle, not assumed."""
+    from tests import helpers
+    s = helpers.settings(oracle, W, H)
+    values = helpers.hostile_values()
+    shows = []
+    for kind, v in values.items():
+        r = oracle.run(texel_frame(ODD_TEXEL, v), s)
+        assert (r["combined1"] == 255).all(), kind
+        if r["result"][ODD_TEXEL] != 255:
+            shows.append(kind)
+    return shows
+
+
+# ---- the partial last tile row: 384 x 312 with TWO levels.  (With 3 or 4 levels the reference's low-res AO is not code 255 from tile
+# row 2 down at this size -- a level's size is not whole -- and no tile of the partial row is ever white; with 1 or 2 levels the
+# constant plane is white everywhere.)  A tile of that row in tile columns 1..4 is interior but not from-raw: it fills its window
+# from the buffer, tests it there, and its white store loop masks the rows past the frame.
+
+PARTIAL_H, PARTIAL_LEVELS = 312, 2
+
+
+def partial_settings(oracle):
+    from tests import helpers
+    return helpers.settings(oracle, W, PARTIAL_H, num_levels=PARTIAL_LEVELS)
+
+
+def partial_plan(tile_h):
+    """{group: [spot]} for tile (2, ty) of the partial last tile row (hi-res rows 256 [288] .. 311)."""
+    ty = PARTIAL_H // tile_h
+    y = ty * tile_h
+    tile = (2, ty)
+    return {"sides": [_spot(90, y, tile, cols=(0, 1)), _spot(226, y, tile, cols=(36, 37)), _spot(128, y - 38, tile, rows=(0, 1)),
+                      _spot(92, y - 20, tile, rows=(0, 2), cols=(0, 2)), _spot(208, y - 36, tile, rows=(0, 2), cols=(35, 37))],
+            "row_sweep": [_spot(94, y0, tile, sweep="rows") for y0 in range(y - 14, PARTIAL_H - 3, 2)]}
+
+
+def check_partial_plan(oracle, tile_h, log=None):
+    """On the oracle: the constant plane at 384 x 312, two levels, is white in every tile, the partial row included; every frame of
+    partial_plan darkens its tile as asked and changes its result; over the sweep every window row holds a non-white texel in some
+    frame (the rows under the frame's last low-res row are clamped copies of it: they darken together), the top apron rows 0..3 in
+    narrow bands."""
+    s = partial_settings(oracle)
+    r = oracle.run(flat_frame(W, PARTIAL_H), s)
+    nx, ny = tile_counts(W, PARTIAL_H, tile_h)
+    assert PARTIAL_H % tile_h and white_tiles_h(low_ao(r, s), W, PARTIAL_H, tile_h) == [(tx, ty) for ty in range(ny) for tx in range(nx)]
+    assert (r["result"] == 255).all()
+    hit, narrow_hit = set(), set()
+    for group, spots in partial_plan(tile_h).items():
+        for spot in spots:
+            tx, ty = spot["tile"]
+            assert ty == ny - 1 and not from_raw(tx, ty, W, PARTIAL_H, tile_h) and 32 * tx >= 4 and 32 * tx + 35 < W // 2
+            _, _, win, changed = spot_view(oracle, s, spot, tile_h)
+            rows, cols = dark_lines(win)
+            assert rows and changed > 0, (group, spot, rows, cols, changed)
+            need = spot["need"]
+            if "rows" in need:
+                assert need["rows"][0] <= rows[0] and rows[-1] <= need["rows"][1], (group, spot, rows)
+            if "cols" in need:
+                assert need["cols"][0] <= cols[0] and cols[-1] <= need["cols"][1], (group, spot, cols)
+            if "sweep" in need:
+                hit.update(rows)
+                if narrow(rows):
+                    narrow_hit.update(rows)
+                if log:
+                    log(f"partial tile_h {tile_h} block {spot['at']}: rows {bands(rows)} columns {bands(cols)} changed {changed}")
+    assert hit == set(range(tile_h // 2 + 6)) and set(range(4)) <= narrow_hit, (sorted(hit), sorted(narrow_hit))
+
+
+def partial_nan_frames(tile_h):
+    """One NaN per tile (1..4, ty) of the partial row of the constant plane at 384 x 312, never on a level texel: every wave and pass
+    that has rows inside the frame, each with the kinds 'eo', 'oo', 'oe'.  Returns [(depth, [(y, x), ...])]."""
+    ty = PARTIAL_H // tile_h
+    rows_in = PARTIAL_H - ty * tile_h
+    spots = []
+    for p in range(tile_h // 32):
+        for wave in range(4):
+            if 32 * p + 8 * wave + 8 > rows_in:
+                continue
+            for row, kind in ((0, "eo"), (1, "oo"), (1, "oe")):
+                n = len(spots)
+                spots.append((32 * p + 8 * wave + 2 * (n % 4) + row, 4 * ((5 * n + 3) % 16) + (n % 2) * 2 + (1 if kind[1] == "o" else 0)))
+    frames = []
+    for i in range(0, len(spots), 4):
+        d, at = flat_frame(W, PARTIAL_H), []
+        for tx, (ly, lx) in zip(range(1, 5), spots[i:i + 4]):
+            y, x = ty * tile_h + ly, tx * TILE + lx
+            assert y < PARTIAL_H and ((y & 1) or (x & 1))
+            d[y, x] = np.nan
+            at.append((y, x))
+        frames.append((d, at))
+    return frames
+
+
+def check_partial_nan_frames(oracle, tile_h):
+    """The low-res AO stays all 255 and the result is 0 at exactly the NaN texels.  Returns [(depth, oracle outputs)]."""
+    s = partial_settings(oracle)
+    out, seen = [], set()
+    for d, at in partial_nan_frames(tile_h):
+        r = oracle.run(d, s)
+        assert (low_ao(r, s) == 255).all()
+        assert sorted(map(tuple, np.argwhere(r["result"] != 255).tolist())) == sorted(at) and all(r["result"][p] == 0 for p in at)
+        seen.update((lane_position(y, x, tile_h)["wave"], lane_position(y, x, tile_h)["pass"], lane_position(y, x, tile_h)["kind"]) for y, x in at)
+        d.setflags(write=False)
+        out.append((d, r))
+    rows_in = PARTIAL_H % tile_h
+    assert seen == {(w, p, k) for p in range(tile_h // 32) for w in range(4) if 32 * p + 8 * w + 8 <= rows_in for k in ("eo", "oo", "oe")}
+    return out

@@ -1,5 +1,5 @@
-"""Frames 1-3 of tests/test_white_tiles_gpu.py through ONE build of libmeao_hip.so (MEAO_LIB_PATH selects it), plain (64 x 64 and
-64 x 32 tiles) and as pipelined batches through the fused last kernel, the whole result against the oracle.  Run by
+"""Frames 1-3 of tests/test_white_tiles_gpu.py, and the side and NaN frames of tests/test_white_tiles_window_gpu.py, through ONE
+build of libmeao_hip.so (MEAO_LIB_PATH selects it), plain (64 x 64 and 64 x 32 tiles) and as pipelined batches through the fused last kernel, the whole result against the oracle.  Run by
 tests/test_white_tiles_gpu.py::test_variant_libraries, one child per variant library."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,6 +14,13 @@ O.build()
 dev = torch.device("cuda", 0)
 s = H.settings(O, WT.W, WT.H)
 frames = {"flat": WT.flat_frame(), "apron": WT.apron_frame(), "nan_odd": WT.texel_frame(WT.ODD_TEXEL, np.float32(np.nan))}
+# the four side frames of the window plan (darkness only in the two outermost lines of one side of tile (2, 2)) and two frames of
+# NaNs at every lane position (tests/test_white_tiles_window_gpu.py), for both tile heights
+for tile_h in (64, 32):
+    for i, spot in enumerate(WT.window_plan(tile_h)["sides"][:4]):
+        frames["side%d_%d" % (i, tile_h)] = WT.block_frame(*spot["at"])
+    for i, (d, _) in enumerate(WT.nan_frames(tile_h)[:2]):
+        frames["nans%d_%d" % (i, tile_h)] = d
 want = {k: O.run(d, s, result_only=True)["result"] for k, d in frames.items()}
 bad = 0
 for debug in ({L.DEBUG_FINAL_SMALL_MAX_TILES: 0}, None):
@@ -23,13 +30,13 @@ for debug in ({L.DEBUG_FINAL_SMALL_MAX_TILES: 0}, None):
             bad += 1
             print("MISMATCH plain", k, debug)
     ao.close()
-seq = [["flat", "apron"], ["apron", "nan_odd"], ["nan_odd", "flat"]]
+seq = [["flat", "apron"], ["apron", "nan_odd"], ["nan_odd", "flat"], ["side1_64", "nans0_64"], ["side3_64", "flat"]]
 dd = [[torch.from_numpy(frames[n]).to(dev) for n in b] for b in seq]
 out = [[torch.zeros((WT.H, WT.W), dtype=torch.uint8, device=dev) for _ in b] for b in seq]
 ao = H.component(s, max_batch=2, pipelined=True)
 st = torch.cuda.current_stream(dev).cuda_stream
-for k in range(3):
-    if k + 1 < 3:
+for k in range(len(seq)):
+    if k + 1 < len(seq):
         ao.prefetch_device([t.data_ptr() for t in dd[k + 1]])
     ao.execute_device([t.data_ptr() for t in dd[k]], [t.data_ptr() for t in out[k]], st)
 torch.cuda.synchronize(dev)
