@@ -30,9 +30,10 @@ KERNEL_UNITS = ["meao_k_downsample.hip", "meao_k_render.hip", "meao_k_upsample.h
                 "meao_k_pitched.hip", "meao_k_pitched_frames.hip", "meao_k_pitched_fused.hip",
                 # the kernels that read linear view-space depth (MEAO_DEPTH_LINEAR_*), likewise
                 "meao_k_linear.hip", "meao_k_linear_frames.hip", "meao_k_linear_fused.hip"]
-HOST_UNITS = ["meao_plan.cpp", "meao_api.cpp", "meao_pool.cpp"]
+# the C ABI layer: lifecycle and queries, the execute path, the composites, the intermediates, the multi-device pool
+HOST_UNITS = ["meao_plan.cpp", "meao_api.cpp", "meao_execute.cpp", "meao_composite.cpp", "meao_debug.cpp", "meao_pool.cpp"]
 SOURCES = HOST_UNITS + KERNEL_UNITS
-HEADERS = ["meao_plan.hpp", "meao_kernels.hpp", "meao_dev.hpp", "meao_dev_downsample.hpp", "meao_dev_render.hpp",
+HEADERS = ["meao_plan.hpp", "meao_kernels.hpp", "meao_ctx.hpp", "meao_dev.hpp", "meao_dev_downsample.hpp", "meao_dev_render.hpp",
            "meao_dev_upsample.hpp", "meao_dev_blend.hpp", "meao_dev_composite.hpp", "meao_dev_fused.hpp", "meao_launch.hpp",
            "meao_kernels.hip"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")

@@ -2,7 +2,7 @@
 
 Committed counter evidence (profiles/pmc_traffic.json: HBM bytes and VALU instructions per launch from rocprofv3 --pmc passes) is
 only valid for the kernels it was collected from: tools/make_pmc_traffic.py stores this hash, bench.py compares it with the
-library it loaded and marks the evidence stale when they differ.  Host-only changes (meao_api.cpp) do not change the hash."""
+library it loaded and marks the evidence stale when they differ.  Host-only changes (the meao_*.cpp units, meao_ctx.hpp) do not change the hash."""
 from __future__ import annotations
 
 import hashlib

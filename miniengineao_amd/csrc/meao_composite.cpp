@@ -1,0 +1,322 @@
+// meao_composite.cpp -- the composite calls of the C ABI (meao_composite*, meao_execute_batch_shaded): one frame now, a batch
+// waiting for the next execute's render launch, or a batch in one launch of its own.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "meao_ctx.hpp"
+
+using namespace meao;
+
+namespace {
+
+// Bytes per texel of a meao_color_format, 0 = not one; the texels of it that a lane of the vector form takes (16 bytes of colour).
+uint64_t color_elem(int32_t color_format)
+{
+    switch (color_format) {
+    case MEAO_COLOR_RGBA16F: return 8;
+    case MEAO_COLOR_RGBA32F: return 16;
+    case MEAO_COLOR_RGBA8: case MEAO_COLOR_R11G11B10F: return 4;
+    default: return 0;
+    }
+}
+uint32_t color_lane_texels(int32_t color_format) { return static_cast<uint32_t>(16 / color_elem(color_format)); }
+
+// The pitches of meao_composite*_pitched (bytes, 0 = tightly packed) -> CompositePitches; `fn` names the entry point in the error.
+// on = 0 where every surface is tightly packed: exactly the packed kernels' path.
+int composite_pitches(meao_ctx *ctx, const char *fn, const CompositeTargets &t, CompositePitches *out)
+{
+    const bool has_gbuffer0 = t.gbuffer0 != nullptr;
+    const uint64_t celem = color_elem(t.color_format);
+    if (celem == 0) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": color_format: not a meao_color_format");
+    int32_t ao_row = ctx->cfg.width, color_row = ctx->cfg.width, g_row = ctx->cfg.width;
+    if (t.ao_pitch != 0 || t.color_pitch != 0 || (t.gbuffer0_pitch != 0 && has_gbuffer0)) {       // packed calls have nothing to check
+        // the argument's name is built only where a pitch is given (0 cannot fail)
+        const auto texels = [&](uint64_t pitch, uint64_t elem, const char *which, int32_t *row) {
+            return pitch_texels(ctx, pitch, elem, pitch ? (std::string(fn) + ": " + which).c_str() : "", row);
+        };
+        int rc = texels(t.ao_pitch, ao_elem(ctx->cfg), "ao_pitch", &ao_row);
+        if (rc == MEAO_OK) rc = texels(t.color_pitch, celem, "color_pitch", &color_row);
+        if (rc == MEAO_OK && has_gbuffer0) rc = texels(t.gbuffer0_pitch, 4, "gbuffer0_pitch", &g_row);
+        if (rc != MEAO_OK) return rc;
+    }
+    *out = CompositePitches{};
+    out->ao = static_cast<uint32_t>(ao_row); out->color = static_cast<uint32_t>(color_row); out->gbuffer0 = static_cast<uint32_t>(g_row);
+    out->w = ctx->cfg.width; out->h = ctx->cfg.height;
+    out->on = ao_row != ctx->cfg.width || color_row != ctx->cfg.width || g_row != ctx->cfg.width;
+    out->vec = (color_row & 1) == 0 && (ao_row & 1) == 0;      // colour rows 16 bytes apart, AO rows two texels apart; the bases: composite_vec_base
+    if (t.color_format != MEAO_COLOR_RGBA16F) {
+        // a packed frame is one row of width x height texels to the kernel, with 32-bit byte offsets like any row
+        if (static_cast<uint64_t>(ctx->cfg.width) * ctx->cfg.height * celem > 0xffffffffull)
+            return fail(ctx, MEAO_ERR_UNSUPPORTED, std::string(fn) + ": color: a frame spans more than 2^32 - 1 bytes");
+        // rows of whole 16-byte colour accesses, each with its AO texels in one aligned load (nothing to ask of a packed frame's rows)
+        out->vec = !out->on || (static_cast<uint64_t>(color_row) * celem % 16 == 0 && static_cast<uint32_t>(ao_row) % color_lane_texels(t.color_format) == 0);
+    }
+    return MEAO_OK;
+}
+
+// The vector form's conditions on a frame's bases: colour a multiple of 16 bytes, AO a multiple of the AO texels of a lane (two for RGBA16F).
+bool composite_vec_base(const meao_ctx *ctx, const void *ao, const void *color, int32_t color_format)
+{
+    return aligned_to(color, 16) && aligned_to(ao, color_lane_texels(color_format) * ao_elem(ctx->cfg));
+}
+
+// meao_composite*: the one frame of `t` (n = 1) now, on the given stream; loc = where its surfaces live.
+int composite_one(meao_ctx *ctx, const char *fn, const CompositeTargets &t, int32_t loc, meao_stream stream_)
+{
+    const void *ao = t.ao[0];
+    void *color = t.color[0], *gbuffer0 = t.gbuffer0 ? t.gbuffer0[0] : nullptr;
+    if (!ctx || !ao || !color) return MEAO_ERR_INVALID_ARGUMENT;
+    if (t.mode < MEAO_COMPOSITE_MULTIPLY || t.mode > MEAO_COMPOSITE_DEBUG) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": unknown mode");
+    if (t.mode == MEAO_COMPOSITE_AMBIENT_ONLY && !gbuffer0)
+        return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": AMBIENT_ONLY needs the GBuffer0 target");
+    if (loc != MEAO_MEM_HOST && loc != MEAO_MEM_DEVICE) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad memory location");
+    CompositePitches pitch{};
+    int rc = composite_pitches(ctx, fn, t, &pitch);
+    if (rc != MEAO_OK) return rc;
+    rc = use_device(ctx);
+    if (rc != MEAO_OK) return rc;
+    hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->own_stream;
+    const uint64_t px = static_cast<uint64_t>(ctx->cfg.width) * ctx->cfg.height;
+    const uint64_t celem = color_elem(t.color_format);
+    const uint64_t ao_bytes = px * ao_elem(ctx->cfg), color_bytes = px * celem, g_bytes = px * 4;
+    CompositeArgs ca{};
+    ca.pixels = static_cast<int64_t>(px);
+    ca.mode = t.mode;
+    ca.color_format = t.color_format;
+    char *scratch = nullptr;
+    if (loc == MEAO_MEM_HOST) {     // tools / tests: stage through one temporary device buffer (packed there, whatever the host pitches)
+        const uint64_t h = static_cast<uint64_t>(ctx->cfg.height);
+        const uint64_t ao_row = ao_bytes / h, color_row = color_bytes / h, g_row = g_bytes / h;
+        const uint64_t ao_src = uint64_t(pitch.ao) * ao_elem(ctx->cfg), color_src = uint64_t(pitch.color) * celem, g_src = uint64_t(pitch.gbuffer0) * 4;
+        MEAO_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&scratch), align_up(ao_bytes) + align_up(color_bytes) + g_bytes));
+        char *d_ao = scratch, *d_color = scratch + align_up(ao_bytes), *d_g = d_color + align_up(color_bytes);
+        auto copy = [&](void *dst, uint64_t dst_pitch, const void *src, uint64_t src_pitch, uint64_t row, hipMemcpyKind kind) {
+            if (dst_pitch == row && src_pitch == row) return hipMemcpyAsync(dst, src, row * h, kind, stream);      // packed: one copy, as ever
+            return hipMemcpy2DAsync(dst, dst_pitch, src, src_pitch, row, h, kind, stream);
+        };
+        hipError_t e = copy(d_ao, ao_row, ao, ao_src, ao_row, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = copy(d_color, color_row, color, color_src, color_row, hipMemcpyHostToDevice);
+        if (e == hipSuccess && gbuffer0) e = copy(d_g, g_row, gbuffer0, g_src, g_row, hipMemcpyHostToDevice);
+        ca.ao = d_ao; ca.color = d_color; ca.gbuffer0 = gbuffer0 ? d_g : nullptr;
+        ca.pitch.vec = 1;       // packed at aligned bases (read by the colour formats other than RGBA16F only)
+        if (e == hipSuccess) e = launch_composite(ca, ctx->cfg.ao_format, stream);
+        if (e == hipSuccess) e = copy(color, color_src, d_color, color_row, color_row, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && gbuffer0) e = copy(gbuffer0, g_src, d_g, g_row, g_row, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        (void)hipFree(scratch);
+        if (e != hipSuccess) return fail_hip(ctx, e, (std::string(fn) + " (host staging)").c_str());
+        return MEAO_OK;
+    }
+    ca.ao = ao; ca.color = color; ca.gbuffer0 = gbuffer0;
+    ca.pitch = pitch;
+    ca.pitch.vec = pitch.vec && composite_vec_base(ctx, ao, color, t.color_format);
+    MEAO_HIP(ctx, launch_composite(ca, ctx->cfg.ao_format, stream));
+    return MEAO_OK;
+}
+
+// The single-frame entry points: one frame as a CompositeTargets of n = 1.
+int composite_single(meao_ctx *ctx, const char *fn, int32_t mode, const void *ao, uint64_t ao_pitch, void *color, int32_t color_format,
+                     uint64_t color_pitch, void *gbuffer0, uint64_t gbuffer0_pitch, int32_t loc, meao_stream stream)
+{
+    return composite_one(ctx, fn, CompositeTargets{mode, 1, &ao, ao_pitch, &color, color_format, color_pitch, gbuffer0 ? &gbuffer0 : nullptr, gbuffer0_pitch},
+                         loc, stream);
+}
+
+// The checks of meao_composite_enqueue_format under the name `fn`, the pitches on success.  Touches nothing.
+int composite_enqueue_validate(meao_ctx *ctx, const char *fn, const CompositeTargets &t, CompositePitches *pitch)
+{
+    if (!ctx || !t.ao || !t.color) return MEAO_ERR_INVALID_ARGUMENT;
+    if (t.mode < MEAO_COMPOSITE_MULTIPLY || t.mode > MEAO_COMPOSITE_DEBUG) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": unknown mode");
+    if (t.n < 1 || t.n > MEAO_MAX_BATCH) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": n must be 1..MEAO_MAX_BATCH");
+    if (t.mode == MEAO_COMPOSITE_AMBIENT_ONLY && !t.gbuffer0)
+        return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": AMBIENT_ONLY needs the GBuffer0 targets");
+    for (int f = 0; f < t.n; ++f)
+        if (!t.ao[f] || !t.color[f] || (t.mode == MEAO_COMPOSITE_AMBIENT_ONLY && !t.gbuffer0[f]))
+            return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": null frame pointer");
+    return composite_pitches(ctx, fn, t, pitch);
+}
+
+// The checks of a batched composite under the name `fn`: n against the context's max_batch (the tables' size), then those of
+// meao_composite_enqueue_format.  Touches nothing.
+int composite_batch_validate(meao_ctx *ctx, const char *fn, const CompositeTargets &t, CompositePitches *pitch)
+{
+    if (!ctx || !t.ao || !t.color) return MEAO_ERR_INVALID_ARGUMENT;
+    if (t.n < 1 || t.n > ctx->cfg.max_batch) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": n must be 1..max_batch");
+    return composite_enqueue_validate(ctx, fn, t, pitch);
+}
+
+// The batched composite: frames 0 .. n-1 in ONE composite_kernel launch on `stream` (every argument already validated).  Their
+// origins go through a slot of the context's table ring; one form (vector or per-texel) for the whole batch, as for an enqueued one.
+int composite_batch_launch(meao_ctx *ctx, const CompositeTargets &t, CompositePitches pitch, hipStream_t stream)
+{
+    TableRing<CompositeFrame, 8>::Lease lease;
+    const int rc = ctx->comp_ring.acquire(ctx, stream, &lease);
+    if (rc != MEAO_OK) return rc;
+    CompositeFrame *stage = lease.host();
+    for (int f = 0; f < t.n; ++f) {
+        stage[f] = CompositeFrame{t.ao[f], t.color[f], t.gbuffer0 ? t.gbuffer0[f] : nullptr};
+        pitch.vec = pitch.vec && composite_vec_base(ctx, t.ao[f], t.color[f], t.color_format);
+    }
+    CompositeArgs ca{};
+    ca.pixels = static_cast<int64_t>(ctx->cfg.width) * ctx->cfg.height;
+    ca.mode = t.mode;
+    ca.pitch = pitch;
+    ca.color_format = t.color_format;
+    ca.frames = lease.device();
+    lease.arm();       // the slot is handed back guarded whatever happens from here: the copy may be in flight
+    hipError_t e = hipMemcpyAsync(lease.device(), stage, sizeof(CompositeFrame) * t.n, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = launch_composite(ca, ctx->cfg.ao_format, stream, t.n);
+    if (e != hipSuccess) return fail_hip(ctx, e, "composite_batch_launch");
+    return MEAO_OK;
+}
+
+}  // namespace
+
+int meao::flush_pending_composite(meao_ctx *ctx, hipStream_t stream)
+{
+    CompositeBatchArgs &pc = ctx->pending_comp;
+    const int frames = pc.frames;
+    pc.frames = 0;
+    for (int f = 0; f < frames; ++f) {
+        CompositeArgs ca{};
+        ca.ao = pc.ao[f]; ca.color = pc.color[f]; ca.gbuffer0 = pc.gbuffer0[f];
+        ca.pixels = pc.pixels; ca.mode = pc.mode;
+        ca.pitch = pc.pitch;       // the waiting batch remembers its pitches (meao_composite_enqueue_pitched)
+        ca.color_format = ctx->pending_comp_format;     // ... and its colour format (meao_composite_enqueue_format)
+        MEAO_HIP(ctx, launch_composite(ca, ctx->cfg.ao_format, stream));
+    }
+    return MEAO_OK;
+}
+
+int meao::composite_enqueue_internal(meao_ctx *ctx, const char *fn, const CompositeTargets &t, bool validate_only)
+{
+    CompositePitches pitch{};
+    int rc = composite_enqueue_validate(ctx, fn, t, &pitch);
+    if (rc != MEAO_OK || validate_only) return rc;     // a refused enqueue leaves a waiting batch waiting, untouched
+    rc = use_device(ctx);
+    if (rc != MEAO_OK) return rc;
+    if (ctx->pending_comp.frames > 0) {        // one batch can wait at a time: the older one runs now, in order
+        rc = flush_pending_composite(ctx, ctx->pending_stream);
+        if (rc != MEAO_OK) return rc;
+    }
+    ctx->pending_stream = ctx->last.stream;    // the stream of the execute that (by contract) produced ao[f]
+    CompositeBatchArgs &pc = ctx->pending_comp;
+    for (int f = 0; f < t.n; ++f) {
+        pc.ao[f] = t.ao[f];
+        pc.color[f] = t.color[f];
+        pc.gbuffer0[f] = t.gbuffer0 ? t.gbuffer0[f] : nullptr;
+        pitch.vec = pitch.vec && composite_vec_base(ctx, t.ao[f], t.color[f], t.color_format);      // one form for the batch
+    }
+    pc.pixels = static_cast<int64_t>(ctx->cfg.width) * ctx->cfg.height;
+    pc.mode = t.mode;
+    pc.frames = t.n;
+    pc.pitch = pitch;
+    ctx->pending_comp_format = t.color_format;
+    return MEAO_OK;
+}
+
+int meao::execute_batch_shaded_internal(meao_ctx *ctx, const char *fn, const FrameSet &fs, const CompositeTargets &targets, meao_stream stream_,
+                                        bool validate_only)
+{
+    if (!ctx || !fs.depth || !fs.out || !targets.color) return MEAO_ERR_INVALID_ARGUMENT;
+    // both halves' checks before anything is enqueued: a refused call launches nothing
+    int32_t depth_rows = 0, out_rows = 0;
+    int rc = validate_execute_batch(ctx, fs, &depth_rows, &out_rows);
+    if (rc != MEAO_OK) return fail(ctx, rc, std::string(fn) + ": " + ctx->err);      // the execute half's message, under this call's name
+    CompositeTargets t = targets;      // the composite reads what the execute writes
+    t.n = fs.n; t.ao = fs.out; t.ao_pitch = fs.out_pitch;
+    CompositePitches pitch{};
+    rc = composite_batch_validate(ctx, fn, t, &pitch);
+    if (rc != MEAO_OK || validate_only) return rc;
+    rc = execute_batch_internal(ctx, fs, stream_, false);
+    if (rc != MEAO_OK) return rc;
+    // behind the last AO kernel on the same stream (ctx->last.stream is the one the execute just ran on)
+    return composite_batch_launch(ctx, t, pitch, ctx->last.stream);
+}
+
+// ------------------------------------------------------------------------------------------
+extern "C" {
+
+int32_t meao_composite(meao_ctx *ctx, int32_t mode, const void *ao, void *color_rgba16f, void *gbuffer0_rgba8,
+                       int32_t loc, meao_stream stream_)
+{
+    return composite_single(ctx, "meao_composite", mode, ao, 0, color_rgba16f, MEAO_COLOR_RGBA16F, 0, gbuffer0_rgba8, 0, loc, stream_);
+}
+
+int32_t meao_composite_pitched(meao_ctx *ctx, int32_t mode, const void *ao, uint64_t ao_pitch, void *color_rgba16f, uint64_t color_pitch,
+                               void *gbuffer0_rgba8, uint64_t gbuffer0_pitch, int32_t loc, meao_stream stream_)
+{
+    return composite_single(ctx, "meao_composite_pitched", mode, ao, ao_pitch, color_rgba16f, MEAO_COLOR_RGBA16F, color_pitch, gbuffer0_rgba8,
+                            gbuffer0_pitch, loc, stream_);
+}
+
+int32_t meao_composite_format(meao_ctx *ctx, int32_t mode, const void *ao, uint64_t ao_pitch, void *color, int32_t color_format,
+                              uint64_t color_pitch, void *gbuffer0_rgba8, uint64_t gbuffer0_pitch, int32_t loc, meao_stream stream_)
+{
+    return composite_single(ctx, "meao_composite_format", mode, ao, ao_pitch, color, color_format, color_pitch, gbuffer0_rgba8, gbuffer0_pitch,
+                            loc, stream_);
+}
+
+int32_t meao_composite_enqueue(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, void *const *color_rgba16f,
+                               void *const *gbuffer0_rgba8)
+{
+    return composite_enqueue_internal(ctx, "meao_composite_enqueue", CompositeTargets{mode, n, ao, 0, color_rgba16f, MEAO_COLOR_RGBA16F, 0, gbuffer0_rgba8, 0},
+                                      false);
+}
+
+int32_t meao_composite_enqueue_pitched(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
+                                       void *const *color_rgba16f, uint64_t color_pitch, void *const *gbuffer0_rgba8,
+                                       uint64_t gbuffer0_pitch)
+{
+    return composite_enqueue_internal(ctx, "meao_composite_enqueue_pitched",
+                                      CompositeTargets{mode, n, ao, ao_pitch, color_rgba16f, MEAO_COLOR_RGBA16F, color_pitch, gbuffer0_rgba8, gbuffer0_pitch},
+                                      false);
+}
+
+int32_t meao_composite_enqueue_format(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch, void *const *color,
+                                      int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch)
+{
+    return composite_enqueue_internal(ctx, "meao_composite_enqueue_format",
+                                      CompositeTargets{mode, n, ao, ao_pitch, color, color_format, color_pitch, gbuffer0_rgba8, gbuffer0_pitch}, false);
+}
+
+int32_t meao_composite_pending(const meao_ctx *ctx, int32_t *out_frames)
+{
+    if (!ctx || !out_frames) return MEAO_ERR_INVALID_ARGUMENT;
+    *out_frames = ctx->pending_comp.frames;
+    return MEAO_OK;
+}
+
+int32_t meao_composite_flush(meao_ctx *ctx, meao_stream stream_)
+{
+    if (!ctx) return MEAO_ERR_INVALID_ARGUMENT;
+    int rc = use_device(ctx);
+    if (rc != MEAO_OK) return rc;
+    if (ctx->pending_comp.frames == 0) return MEAO_OK;
+    return flush_pending_composite(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->pending_stream);
+}
+
+int32_t meao_composite_batch(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch, void *const *color,
+                             int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch,
+                             meao_stream stream_)
+{
+    const CompositeTargets t{mode, n, ao, ao_pitch, color, color_format, color_pitch, gbuffer0_rgba8, gbuffer0_pitch};
+    CompositePitches pitch{};
+    int rc = composite_batch_validate(ctx, "meao_composite_batch", t, &pitch);
+    if (rc != MEAO_OK) return rc;
+    rc = use_device(ctx);
+    if (rc != MEAO_OK) return rc;
+    return composite_batch_launch(ctx, t, pitch, stream_ ? static_cast<hipStream_t>(stream_) : ctx->own_stream);
+}
+
+int32_t meao_execute_batch_shaded(meao_ctx *ctx, int32_t n, const void *const *depth, uint64_t depth_pitch, void *const *ao_out,
+                                  uint64_t ao_pitch, const meao_params *params, int32_t mode, void *const *color, int32_t color_format,
+                                  uint64_t color_pitch, void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch, meao_stream stream_)
+{
+    return execute_batch_shaded_internal(ctx, "meao_execute_batch_shaded",
+                                         FrameSet{n, depth, depth_pitch, MEAO_MEM_DEVICE, ao_out, ao_pitch, MEAO_MEM_DEVICE, params},
+                                         CompositeTargets{mode, n, nullptr, 0, color, color_format, color_pitch, gbuffer0_rgba8, gbuffer0_pitch}, stream_, false);
+}
+
+}  // extern "C"

@@ -254,27 +254,4 @@ hipError_t launch_render_with_composite(const RenderArgs &a, const CompositeBatc
 // Exhaustive conversion self-tests; *count (device) receives the number of mismatches.
 hipError_t launch_selftest(int which, unsigned long long *count, hipStream_t s);
 
-// meao_api.cpp, for meao_pool.cpp: meao_execute_batch that can leave the staged copies of a HOST call in flight
-// (params: meao_execute_batch_params, one entry per frame; nullptr = the context's parameters)
-// (depth_pitch / ao_pitch: meao_execute_batch_pitched, bytes, 0 = tightly packed)
-int execute_batch_internal(meao_ctx *ctx, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
-                           int32_t out_loc, meao_stream stream, bool wait_for_host, const meao_params *params = nullptr,
-                           uint64_t depth_pitch = 0, uint64_t ao_pitch = 0);
-// meao_api.cpp, for meao_pool.cpp: meao_composite_enqueue_format under the name `fn` (the errors carry it); validate_only = every
-// check and nothing else (no device is touched, a waiting batch stays as it is).
-int composite_enqueue_internal(meao_ctx *ctx, const char *fn, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
-                               void *const *color, int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8,
-                               uint64_t gbuffer0_pitch, bool validate_only);
-// meao_api.cpp, for meao_pool.cpp: meao_execute_batch_shaded under the name `fn`; validate_only = every check of both halves and
-// nothing else (no device is touched; AO, colour, an announcement and a waiting batch stay as they are).
-int execute_batch_shaded_internal(meao_ctx *ctx, const char *fn, int32_t n, const void *const *depth, uint64_t depth_pitch,
-                                  void *const *ao_out, uint64_t ao_pitch, const meao_params *params, int32_t mode, void *const *color,
-                                  int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch,
-                                  meao_stream stream, bool validate_only);
-// meao_api.cpp, for meao_pool.cpp: what a member that is dealt no frame of a pool call does instead of that call.
-// ready_too = false (a pool announcement passed it by): an announcement it still holds is withdrawn, as a newer one would
-// replace it.  ready_too = true (a pool execute passed it by): a ready prefetched set goes as well -- the pool-level "call
-// after next" any of them was made for is over.  Bookkeeping only; costs that member one downsample pass at most.
-void drop_announcement(meao_ctx *ctx, bool ready_too);
-
 }  // namespace meao

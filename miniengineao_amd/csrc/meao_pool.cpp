@@ -31,12 +31,7 @@
 #include <thread>
 #include <vector>
 
-#include "meao_kernels.hpp"
-#include "meao_plan.hpp"
-
-#ifndef MEAO_TESTING
-#define MEAO_TESTING 0      // 1: the `testhooks` variant library (meao_test_* entry points), never the product
-#endif
+#include "meao_ctx.hpp"
 
 namespace {
 
@@ -218,15 +213,6 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-// frames of member m in a batch of n dealt round-robin over G members
-template <typename T>
-int32_t share_of(int32_t m, int32_t G, int32_t n, T *const *all, T **mine)
-{
-    int32_t k = 0;
-    for (int32_t f = m; f < n; f += G) mine[k++] = all[f];
-    return k;
-}
-
 // fn(m) for every member: on the members' worker threads (all at once) when the pool has several members, else here.
 // Returns the first failing member's status (every member is run and waited for either way).
 int32_t for_each_member(meao_pool *p, const std::function<int32_t(int32_t)> &fn, bool threaded, int32_t *failed_member)
@@ -234,14 +220,8 @@ int32_t for_each_member(meao_pool *p, const std::function<int32_t(int32_t)> &fn,
     const int32_t G = static_cast<int32_t>(p->ctx.size());
     int32_t status = MEAO_OK;
     *failed_member = -1;
-    if (!threaded || G < 2) {
-        for (int32_t m = 0; m < G; ++m) {
-            const int32_t rc = fn(m);
-            if (rc != MEAO_OK && status == MEAO_OK) { status = rc; *failed_member = m; }
-        }
-        return status;
-    }
-    if (p->worker.empty() && !p->workers_unavailable) {
+    threaded = threaded && G >= 2;
+    if (threaded && p->worker.empty() && !p->workers_unavailable) {
         try {
             for (int32_t m = 0; m < G; ++m) {
                 p->worker.emplace_back(new PoolWorker());
@@ -258,7 +238,7 @@ int32_t for_each_member(meao_pool *p, const std::function<int32_t(int32_t)> &fn,
             p->workers_unavailable = true;
         }
     }
-    if (p->worker.empty()) {
+    if (!threaded || p->worker.empty()) {
         for (int32_t m = 0; m < G; ++m) {
             const int32_t rc = fn(m);
             if (rc != MEAO_OK && status == MEAO_OK) { status = rc; *failed_member = m; }
@@ -390,44 +370,39 @@ int32_t meao_pool_set_params(meao_pool *p, const meao_params *prm)
     return MEAO_OK;
 }
 
-// every params[f] valid before any member is given work: an invalid entry launches nothing anywhere
-static int32_t pool_check_params(meao_pool *p, int32_t n, const meao_params *params, const char *what)
+// The checks of params[] (null = none given) of the pool call `fn`: every entry valid before any member is given work, so an
+// invalid one launches nothing anywhere.  An n out of range is left to the call itself, which refuses it under its own name.
+static int32_t pool_check_call(meao_pool *p, const char *fn, int32_t n, const meao_params *params)
 {
+    if (!params || n < 1 || n > p->max_batch * static_cast<int32_t>(p->ctx.size())) return MEAO_OK;
     for (int32_t f = 0; f < n; ++f)
         if (params[f].struct_size != sizeof(meao_params) || !meao::params_valid(params[f]))
-            return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, std::string(what) + ": params[" + std::to_string(f) + "] is invalid");
+            return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": params[" + std::to_string(f) + "] is invalid");
     return MEAO_OK;
 }
 
-// params: per-frame parameters (meao_pool_execute_batch_params), dealt with the frames; nullptr = the members' own.
-// depth_pitch / ao_pitch: meao_pool_execute_batch_pitched, passed to every member (they share the geometry, so an invalid pitch
-// fails in every member before anything is enqueued).
-static int32_t pool_execute_batch(meao_pool *p, int32_t n, const void *const *depth, int32_t depth_loc, void *const *ao_out,
-                                  int32_t out_loc, const meao_params *params, uint64_t depth_pitch = 0, uint64_t ao_pitch = 0)
+// fs.params: per-frame parameters (meao_pool_execute_batch_params), dealt with the frames; nullptr = the members' own.
+// fs.depth_pitch / out_pitch: meao_pool_execute_batch_pitched, passed to every member (they share the geometry, so an invalid
+// pitch fails in every member before anything is enqueued).
+static int32_t pool_execute_batch(meao_pool *p, const meao::FrameSet &fs)
 {
-    if (!p || !depth || !ao_out) return MEAO_ERR_INVALID_ARGUMENT;
-    const int32_t G = static_cast<int32_t>(p->ctx.size());
+    if (!p || !fs.depth || !fs.out) return MEAO_ERR_INVALID_ARGUMENT;
+    const int32_t G = static_cast<int32_t>(p->ctx.size()), n = fs.n;
     if (n < 1 || n > p->max_batch * G)
         return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, "meao_pool_execute_batch: n must be 1..max_batch * members");
     DeviceGuard guard;
     // frame f -> member f mod G; each member runs its share as ONE batched launch
     // sequence on its own stream.  With HOST memory every member's staged copies and launches are put in
     // flight first and all members are waited for afterwards: member m+1's upload overlaps member m's kernels.
-    const bool host = depth_loc == MEAO_MEM_HOST || out_loc == MEAO_MEM_HOST;
+    const bool host = fs.depth_loc == MEAO_MEM_HOST || fs.out_loc == MEAO_MEM_HOST;
     int32_t failed = -1;
     // DEVICE batches: every member's launch sequence is enqueued by its own worker thread (see the top of this file).
     // HOST batches are dominated by their staged copies and stay on the calling thread.
     int32_t status = for_each_member(p, [&](int32_t m) -> int32_t {
-        const void *d[MEAO_MAX_BATCH];
-        void *o[MEAO_MAX_BATCH];
-        const int32_t k = share_of(m, G, n, depth, d);
-        share_of(m, G, n, ao_out, o);
-        if (k == 0) return MEAO_OK;
-        meao_params prm[MEAO_MAX_BATCH];
-        if (params)
-            for (int32_t f = m, i = 0; f < n; f += G) prm[i++] = params[f];
-        return meao::execute_batch_internal(p->ctx[m], k, d, depth_loc, o, out_loc, p->stream[m], false, params ? prm : nullptr,
-                                            depth_pitch, ao_pitch);
+        meao::FrameSet::Storage mine;
+        const meao::FrameSet share = fs.share(m, G, &mine);
+        if (share.n == 0) return MEAO_OK;
+        return meao::execute_batch_internal(p->ctx[m], share, p->stream[m], false);
     }, !host, &failed);
     if (status != MEAO_OK)
         status = pool_fail(p, status, std::string("meao_pool_execute_batch: member ") + std::to_string(failed) + ": " +
@@ -451,24 +426,32 @@ static int32_t pool_execute_batch(meao_pool *p, int32_t n, const void *const *de
 int32_t meao_pool_execute_batch(meao_pool *p, int32_t n, const void *const *depth, int32_t depth_loc,
                                 void *const *ao_out, int32_t out_loc)
 {
-    return pool_execute_batch(p, n, depth, depth_loc, ao_out, out_loc, nullptr);
+    return pool_execute_batch(p, meao::FrameSet{n, depth, 0, depth_loc, ao_out, 0, out_loc, nullptr});
 }
 
 int32_t meao_pool_execute_batch_params(meao_pool *p, int32_t n, const void *const *depth, int32_t depth_loc,
                                        void *const *ao_out, int32_t out_loc, const meao_params *params)
 {
     if (!p || !params) return MEAO_ERR_INVALID_ARGUMENT;
-    if (n >= 1 && n <= p->max_batch * static_cast<int32_t>(p->ctx.size())) {
-        const int32_t rc = pool_check_params(p, n, params, "meao_pool_execute_batch_params");
-        if (rc != MEAO_OK) return rc;
-    }
-    return pool_execute_batch(p, n, depth, depth_loc, ao_out, out_loc, params);
+    const int32_t rc = pool_check_call(p, "meao_pool_execute_batch_params", n, params);
+    if (rc != MEAO_OK) return rc;
+    return pool_execute_batch(p, meao::FrameSet{n, depth, 0, depth_loc, ao_out, 0, out_loc, params});
 }
 
-static int32_t pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *depth, const meao_params *params, uint64_t depth_pitch = 0)
+int32_t meao_pool_execute_batch_pitched(meao_pool *p, int32_t n, const void *const *depth, uint64_t depth_pitch, int32_t depth_loc,
+                                        void *const *ao_out, uint64_t ao_pitch, int32_t out_loc, const meao_params *params)
 {
-    if (!p || !depth) return MEAO_ERR_INVALID_ARGUMENT;
-    const int32_t G = static_cast<int32_t>(p->ctx.size());
+    if (!p || !depth || !ao_out) return MEAO_ERR_INVALID_ARGUMENT;
+    const int32_t rc = pool_check_call(p, "meao_pool_execute_batch_pitched", n, params);
+    if (rc != MEAO_OK) return rc;
+    return pool_execute_batch(p, meao::FrameSet{n, depth, depth_pitch, depth_loc, ao_out, ao_pitch, out_loc, params});
+}
+
+// fs: n, depth, depth_pitch and params of the announcement (params[] already checked).
+static int32_t pool_prefetch_batch(meao_pool *p, const meao::FrameSet &fs)
+{
+    if (!p || !fs.depth) return MEAO_ERR_INVALID_ARGUMENT;
+    const int32_t G = static_cast<int32_t>(p->ctx.size()), n = fs.n;
     if (n < 1 || n > p->max_batch * G)
         return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, "meao_pool_prefetch_batch: n must be 1..max_batch * members");
     DeviceGuard guard;
@@ -477,20 +460,11 @@ static int32_t pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *d
     // (a context with cfg.pipelined = 1 never allocates or synchronises here: this is bookkeeping, cheaper than a hand-over
     // to the workers -- and the first call of a context created without it re-allocates, which must not race anything)
     const int32_t status = for_each_member(p, [&](int32_t m) -> int32_t {
-        const void *d[MEAO_MAX_BATCH];
-        const int32_t k = share_of(m, G, n, depth, d);
-        if (k == 0) return MEAO_OK;
+        meao::FrameSet::Storage mine;
+        const meao::FrameSet share = fs.share(m, G, &mine);
+        if (share.n == 0) return MEAO_OK;
         if (hipSetDevice(p->device[m]) != hipSuccess) { (void)hipGetLastError(); set_device_failed = true; return MEAO_ERR_HIP; }
-        if (depth_pitch != 0) {
-            meao_params prm[MEAO_MAX_BATCH];
-            if (params)
-                for (int32_t f = m, i = 0; f < n; f += G) prm[i++] = params[f];
-            return meao_prefetch_batch_pitched(p->ctx[m], k, d, depth_pitch, params ? prm : nullptr);
-        }
-        if (!params) return meao_prefetch_batch(p->ctx[m], k, d);
-        meao_params prm[MEAO_MAX_BATCH];
-        for (int32_t f = m, i = 0; f < n; f += G) prm[i++] = params[f];
-        return meao_prefetch_batch_params(p->ctx[m], k, d, prm);
+        return meao::prefetch_batch_internal(p->ctx[m], share);
     }, false, &failed);
     if (status != MEAO_OK)       // (a failed hipSetDevice never reached the context: its last error would name an older failure)
         return pool_fail(p, status, std::string("meao_pool_prefetch_batch: member ") + std::to_string(failed) + ": " +
@@ -501,37 +475,25 @@ static int32_t pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *d
     return MEAO_OK;
 }
 
-int32_t meao_pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *depth) { return pool_prefetch_batch(p, n, depth, nullptr); }
+int32_t meao_pool_prefetch_batch(meao_pool *p, int32_t n, const void *const *depth)
+{
+    return pool_prefetch_batch(p, meao::FrameSet{n, depth, 0, MEAO_MEM_DEVICE, nullptr, 0, MEAO_MEM_DEVICE, nullptr});
+}
 
 int32_t meao_pool_prefetch_batch_params(meao_pool *p, int32_t n, const void *const *depth, const meao_params *params)
 {
     if (!p || !params) return MEAO_ERR_INVALID_ARGUMENT;
-    if (n >= 1 && n <= p->max_batch * static_cast<int32_t>(p->ctx.size())) {
-        const int32_t rc = pool_check_params(p, n, params, "meao_pool_prefetch_batch_params");
-        if (rc != MEAO_OK) return rc;
-    }
-    return pool_prefetch_batch(p, n, depth, params);
-}
-
-int32_t meao_pool_execute_batch_pitched(meao_pool *p, int32_t n, const void *const *depth, uint64_t depth_pitch, int32_t depth_loc,
-                                        void *const *ao_out, uint64_t ao_pitch, int32_t out_loc, const meao_params *params)
-{
-    if (!p || !depth || !ao_out) return MEAO_ERR_INVALID_ARGUMENT;
-    if (params && n >= 1 && n <= p->max_batch * static_cast<int32_t>(p->ctx.size())) {
-        const int32_t rc = pool_check_params(p, n, params, "meao_pool_execute_batch_pitched");
-        if (rc != MEAO_OK) return rc;
-    }
-    return pool_execute_batch(p, n, depth, depth_loc, ao_out, out_loc, params, depth_pitch, ao_pitch);
+    const int32_t rc = pool_check_call(p, "meao_pool_prefetch_batch_params", n, params);
+    if (rc != MEAO_OK) return rc;
+    return pool_prefetch_batch(p, meao::FrameSet{n, depth, 0, MEAO_MEM_DEVICE, nullptr, 0, MEAO_MEM_DEVICE, params});
 }
 
 int32_t meao_pool_prefetch_batch_pitched(meao_pool *p, int32_t n, const void *const *depth, uint64_t depth_pitch, const meao_params *params)
 {
     if (!p || !depth) return MEAO_ERR_INVALID_ARGUMENT;
-    if (params && n >= 1 && n <= p->max_batch * static_cast<int32_t>(p->ctx.size())) {
-        const int32_t rc = pool_check_params(p, n, params, "meao_pool_prefetch_batch_pitched");
-        if (rc != MEAO_OK) return rc;
-    }
-    return pool_prefetch_batch(p, n, depth, params, depth_pitch);
+    const int32_t rc = pool_check_call(p, "meao_pool_prefetch_batch_pitched", n, params);
+    if (rc != MEAO_OK) return rc;
+    return pool_prefetch_batch(p, meao::FrameSet{n, depth, depth_pitch, MEAO_MEM_DEVICE, nullptr, 0, MEAO_MEM_DEVICE, params});
 }
 
 // Every member's share is validated (both halves) before any member enqueues; then each member that is dealt frames runs its
@@ -544,27 +506,19 @@ int32_t meao_pool_execute_batch_shaded(meao_pool *p, int32_t n, const void *cons
     if (!p || !depth || !ao_out || !color) return MEAO_ERR_INVALID_ARGUMENT;
     const int32_t G = static_cast<int32_t>(p->ctx.size());
     if (n < 1 || n > p->max_batch * G) return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": n must be 1..max_batch * members");
-    if (params) {
-        const int32_t rc = pool_check_params(p, n, params, fn);
-        if (rc != MEAO_OK) return rc;
-    }
+    int32_t status = pool_check_call(p, fn, n, params);
+    if (status != MEAO_OK) return status;
+    const meao::FrameSet fs{n, depth, depth_pitch, MEAO_MEM_DEVICE, ao_out, ao_pitch, MEAO_MEM_DEVICE, params};
+    const meao::CompositeTargets targets{mode, n, nullptr, 0, color, color_format, color_pitch, gbuffer0_rgba8, gbuffer0_pitch};
     DeviceGuard guard;
     int32_t failed = -1;
-    int32_t status = MEAO_OK;
     for (int pass = 0; pass < 2 && status == MEAO_OK; ++pass) {
         status = for_each_member(p, [&](int32_t m) -> int32_t {
-            const void *d[MEAO_MAX_BATCH];
-            void *o[MEAO_MAX_BATCH], *c[MEAO_MAX_BATCH], *g[MEAO_MAX_BATCH];
-            const int32_t k = share_of(m, G, n, depth, d);
-            share_of(m, G, n, ao_out, o);
-            share_of(m, G, n, color, c);
-            if (gbuffer0_rgba8) share_of(m, G, n, gbuffer0_rgba8, g);
-            if (k == 0) return MEAO_OK;
-            meao_params prm[MEAO_MAX_BATCH];
-            if (params)
-                for (int32_t f = m, i = 0; f < n; f += G) prm[i++] = params[f];
-            return meao::execute_batch_shaded_internal(p->ctx[m], fn, k, d, depth_pitch, o, ao_pitch, params ? prm : nullptr, mode, c, color_format,
-                                                       color_pitch, gbuffer0_rgba8 ? g : nullptr, gbuffer0_pitch, p->stream[m], pass == 0);
+            meao::FrameSet::Storage frames;
+            meao::CompositeTargets::Storage surfaces;
+            const meao::FrameSet share = fs.share(m, G, &frames);
+            if (share.n == 0) return MEAO_OK;
+            return meao::execute_batch_shaded_internal(p->ctx[m], fn, share, targets.share(m, G, &surfaces), p->stream[m], pass == 0);
         }, pass == 1, &failed);
         if (status != MEAO_OK)
             return pool_fail(p, status, std::string(fn) + ": member " + std::to_string(failed) + ": " + meao_last_error(p->ctx[failed]));
@@ -575,26 +529,20 @@ int32_t meao_pool_execute_batch_shaded(meao_pool *p, int32_t n, const void *cons
 }
 
 // pitched: the pitches go to every member and every member's share is validated before any member enqueues.
-static int32_t pool_composite_enqueue(meao_pool *p, const char *fn, bool pitched, int32_t mode, int32_t n, const void *const *ao,
-                                      uint64_t ao_pitch, void *const *color_rgba16f, int32_t color_format, uint64_t color_pitch,
-                                      void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch)
+static int32_t pool_composite_enqueue(meao_pool *p, const char *fn, bool pitched, const meao::CompositeTargets &t)
 {
-    if (!p || !ao || !color_rgba16f) return MEAO_ERR_INVALID_ARGUMENT;
+    if (!p || !t.ao || !t.color) return MEAO_ERR_INVALID_ARGUMENT;
     const int32_t G = static_cast<int32_t>(p->ctx.size());
-    if (n < 1 || n > p->max_batch * G)
+    if (t.n < 1 || t.n > p->max_batch * G)
         return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": n must be 1..max_batch * members");
     DeviceGuard guard;
     for (int pass = pitched ? 0 : 1; pass < 2; ++pass) {
         for (int32_t m = 0; m < G; ++m) {
-            const void *a[MEAO_MAX_BATCH];
-            void *c[MEAO_MAX_BATCH], *g[MEAO_MAX_BATCH];
-            const int32_t k = share_of(m, G, n, ao, a);
-            share_of(m, G, n, color_rgba16f, c);
-            if (gbuffer0_rgba8) share_of(m, G, n, gbuffer0_rgba8, g);
-            if (k == 0) continue;
-            const int32_t rc = pitched ? meao::composite_enqueue_internal(p->ctx[m], fn, mode, k, a, ao_pitch, c, color_format, color_pitch,
-                                                                          gbuffer0_rgba8 ? g : nullptr, gbuffer0_pitch, pass == 0)
-                                       : meao_composite_enqueue(p->ctx[m], mode, k, a, c, gbuffer0_rgba8 ? g : nullptr);
+            meao::CompositeTargets::Storage surfaces;
+            const meao::CompositeTargets share = t.share(m, G, &surfaces);
+            if (share.n == 0) continue;
+            // (the unpitched call's members report under the single-context name, as ever)
+            const int32_t rc = meao::composite_enqueue_internal(p->ctx[m], pitched ? fn : "meao_composite_enqueue", share, pass == 0);
             if (rc != MEAO_OK)
                 return pool_fail(p, rc, std::string(fn) + ": member " + std::to_string(m) + ": " + meao_last_error(p->ctx[m]));
         }
@@ -605,22 +553,23 @@ static int32_t pool_composite_enqueue(meao_pool *p, const char *fn, bool pitched
 int32_t meao_pool_composite_enqueue(meao_pool *p, int32_t mode, int32_t n, const void *const *ao, void *const *color_rgba16f,
                                     void *const *gbuffer0_rgba8)
 {
-    return pool_composite_enqueue(p, "meao_pool_composite_enqueue", false, mode, n, ao, 0, color_rgba16f, MEAO_COLOR_RGBA16F, 0, gbuffer0_rgba8, 0);
+    return pool_composite_enqueue(p, "meao_pool_composite_enqueue", false,
+                                  meao::CompositeTargets{mode, n, ao, 0, color_rgba16f, MEAO_COLOR_RGBA16F, 0, gbuffer0_rgba8, 0});
 }
 
 int32_t meao_pool_composite_enqueue_pitched(meao_pool *p, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch,
                                             void *const *color_rgba16f, uint64_t color_pitch, void *const *gbuffer0_rgba8,
                                             uint64_t gbuffer0_pitch)
 {
-    return pool_composite_enqueue(p, "meao_pool_composite_enqueue_pitched", true, mode, n, ao, ao_pitch, color_rgba16f, MEAO_COLOR_RGBA16F,
-                                  color_pitch, gbuffer0_rgba8, gbuffer0_pitch);
+    return pool_composite_enqueue(p, "meao_pool_composite_enqueue_pitched", true,
+                                  meao::CompositeTargets{mode, n, ao, ao_pitch, color_rgba16f, MEAO_COLOR_RGBA16F, color_pitch, gbuffer0_rgba8, gbuffer0_pitch});
 }
 
 int32_t meao_pool_composite_enqueue_format(meao_pool *p, int32_t mode, int32_t n, const void *const *ao, uint64_t ao_pitch, void *const *color,
                                            int32_t color_format, uint64_t color_pitch, void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch)
 {
-    return pool_composite_enqueue(p, "meao_pool_composite_enqueue_format", true, mode, n, ao, ao_pitch, color, color_format, color_pitch,
-                                  gbuffer0_rgba8, gbuffer0_pitch);
+    return pool_composite_enqueue(p, "meao_pool_composite_enqueue_format", true,
+                                  meao::CompositeTargets{mode, n, ao, ao_pitch, color, color_format, color_pitch, gbuffer0_rgba8, gbuffer0_pitch});
 }
 
 int32_t meao_pool_composite_pending(const meao_pool *p, int32_t *out_frames)

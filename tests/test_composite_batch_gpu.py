@@ -138,6 +138,34 @@ def test_table_bounds_at_max_batch(ao_format):
         ao.close()
 
 
+def test_ring_of_composite_tables_wraps_with_the_host_ahead():
+    """20 meao_composite_batch calls on one stream with nothing waited for in between: the ring of 8 table slots wraps twice with
+    the host running ahead.  Every call has its own AO and colours (n = 1..3 of max_batch 3, formats and layouts cycling; 72 x 40:
+    pitched rows that do not fill a workgroup's row of lanes), so a launch that read another call's table entries, or a slot
+    refilled before its copy was consumed, leaves wrong bytes in one particular call -- the one the failure names."""
+    from miniengineao_amd import AmbientOcclusion
+    w, h, calls = 72, 40, 20
+    rng = np.random.default_rng(8)
+    ao = AmbientOcclusion(w, h, max_batch=3)
+    try:
+        Ts = []
+        for k in range(calls):
+            frames = [rng.integers(0, 256, (h, w), dtype=np.uint8) for _ in range(1 + k % 3)]
+            Ts.append(BatchTargets(w, h, ALL_FORMATS[k % 4], L.AO_R8, ("packed", "vector", "oddbase")[k // 3 % 3], frames, seed=200 + k))
+        torch.cuda.synchronize()
+        s = stream()
+        for k, T in enumerate(Ts):
+            assert batch(ao, T, 0, stream_=s) == 0, (k, err(ao))
+        torch.cuda.synchronize()
+        for k, T in enumerate(Ts):
+            try:
+                T.check(0)
+            except AssertionError as e:
+                raise AssertionError(f"call {k} of {calls} (n = {T.n}, table slot {k % 8}): {e}") from e
+    finally:
+        ao.close()
+
+
 # ---- launch counts
 
 TRACE = r"""
