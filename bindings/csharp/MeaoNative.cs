@@ -119,6 +119,10 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_create(ref MeaoConfig cfg, out IntPtr ctx);
         [DllImport(Lib)] public static extern int meao_destroy(IntPtr ctx);
         [DllImport(Lib)] public static extern int meao_resize(IntPtr ctx, int width, int height);
+        // dynamic resolution: reserve a maximum size once; meao_resize inside it neither allocates nor synchronises
+        [DllImport(Lib)] public static extern int meao_reserve(IntPtr ctx, int max_width, int max_height);
+        [DllImport(Lib)] public static extern int meao_get_capacity(IntPtr ctx, out int width, out int height);
+        [DllImport(Lib)] public static extern int meao_reserve_bytes(ref MeaoConfig cfg, int max_width, int max_height, out ulong bytes);
         [DllImport(Lib)] public static extern int meao_set_params(IntPtr ctx, ref MeaoParams p);
         [DllImport(Lib)] public static extern int meao_get_params(IntPtr ctx, out MeaoParams p);
         [DllImport(Lib)] public static extern int meao_get_config(IntPtr ctx, out MeaoConfig cfg);
@@ -132,6 +136,8 @@ namespace MiniEngineAO.Native
         // row-pitched surfaces: pitches in bytes, 0 = tightly packed; prm = null for the context's parameters
         [DllImport(Lib)] public static extern int meao_execute_batch_pitched(IntPtr ctx, int n, IntPtr[] depth, ulong depth_pitch, int depth_loc, IntPtr[] ao_out, ulong ao_pitch, int out_loc, [In] MeaoParams[] prm, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_prefetch_batch_pitched(IntPtr ctx, int n, IntPtr[] depth, ulong depth_pitch, [In] MeaoParams[] prm);
+        // the announcement for frames of another size inside the reservation: it survives meao_resize to exactly that size
+        [DllImport(Lib)] public static extern int meao_prefetch_batch_sized(IntPtr ctx, int width, int height, int n, IntPtr[] depth, ulong depth_pitch, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_synchronize(IntPtr ctx, IntPtr stream);
 
         [DllImport(Lib)] public static extern int meao_get_intermediate(IntPtr ctx, int frame, int debug_id, IntPtr dst, ulong dst_capacity, int dst_loc, out MeaoDesc desc);
@@ -163,6 +169,9 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_pool_prefetch_batch_params(IntPtr pool, int n, IntPtr[] depth, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_pool_execute_batch_pitched(IntPtr pool, int n, IntPtr[] depth, ulong depth_pitch, int depth_loc, IntPtr[] ao_out, ulong ao_pitch, int out_loc, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_pool_prefetch_batch_pitched(IntPtr pool, int n, IntPtr[] depth, ulong depth_pitch, [In] MeaoParams[] prm);
+        [DllImport(Lib)] public static extern int meao_pool_reserve(IntPtr pool, int max_width, int max_height);
+        [DllImport(Lib)] public static extern int meao_pool_resize(IntPtr pool, int width, int height);
+        [DllImport(Lib)] public static extern int meao_pool_prefetch_batch_sized(IntPtr pool, int width, int height, int n, IntPtr[] depth, ulong depth_pitch, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue(IntPtr pool, int mode, int n, IntPtr[] ao, IntPtr[] color_rgba16f, IntPtr[] gbuffer0_rgba8);
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue_pitched(IntPtr pool, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color_rgba16f, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue_format(IntPtr pool, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);

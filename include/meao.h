@@ -223,6 +223,31 @@ MEAO_API int32_t meao_create(const meao_config *cfg, meao_ctx **out_ctx);
 MEAO_API int32_t meao_destroy(meao_ctx *ctx);
 /* Screen-size change (AO.cs:338-341,501): re-plans and re-allocates the intermediates. */
 MEAO_API int32_t meao_resize(meao_ctx *ctx, int32_t width, int32_t height);
+/* Dynamic resolution: reserve a maximum size once, then resize without allocating.  (The ABI version is unchanged: hosts probe
+ * for these symbols.)
+ * meao_reserve sizes the context's intermediates for max_width x max_height -- the arena for max_batch slots, with the second
+ * downsample set where the context has one.  It may allocate and synchronises the device once, like meao_resize; it changes no
+ * result.  The reservation must cover the current size in both dimensions (else MEAO_ERR_INVALID_ARGUMENT); (0, 0) drops it and
+ * returns the context to the exact fit.  On success a ready prefetched set and an announcement are dropped (the buffers moved);
+ * on failure the context is exactly as it was: geometry, buffers, reservation, a ready prefetch; a waiting composite batch stays
+ * waiting either way.  meao_get_capacity reports the reservation, (0, 0) = none.  meao_reserve_bytes is host-plan only, like
+ * meao_describe_buffer (cfg.width / height are validated but not used): the device memory a reservation of that size costs,
+ * max_batch slots with one (cfg.pipelined = 0) or two downsample sets, so that a host can budget before it reserves.
+ * Under a reservation every buffer of a slot sits at the offset the RESERVED geometry gives it, and the two downsample sets
+ * lie that geometry's set size apart; a buffer is packed for the extents of the current size, which fit because every level's
+ * ceil(w / 2^k) x ceil(h / 2^k) is monotone in w and in h.
+ * meao_resize to a size inside the reservation (both dimensions) moves nothing: no HIP allocation, no device, stream or event
+ * synchronisation, no launch -- except that a waiting composite batch is run as plain launches at the old size on its own
+ * stream, as in every resize, which is asynchronous.  It re-plans, and the debug state of the last call is gone, as in every
+ * resize.  It can be called in a free-running stream.  Ordering on the device is the rule that already holds between any two
+ * executes of one context: they share the intermediates, the stream orders them, and a host that changes streams between
+ * calls orders them itself.
+ * meao_resize outside the reservation behaves as without one -- it synchronises and allocates, and on failure nothing changes --
+ * and the reservation grows to the component-wise maximum of the old reservation and the new size.  On a context that was never
+ * given a reservation meao_resize is unchanged in every respect. */
+MEAO_API int32_t meao_reserve(meao_ctx *ctx, int32_t max_width, int32_t max_height);
+MEAO_API int32_t meao_get_capacity(const meao_ctx *ctx, int32_t *out_width, int32_t *out_height);
+MEAO_API int32_t meao_reserve_bytes(const meao_config *cfg, int32_t max_width, int32_t max_height, uint64_t *out_bytes);
 /* Property change (AO.cs:104-113): recomputes the per-level constant blocks. */
 MEAO_API int32_t meao_set_params(meao_ctx *ctx, const meao_params *p);
 MEAO_API int32_t meao_get_params(const meao_ctx *ctx, meao_params *out);
@@ -312,6 +337,21 @@ MEAO_API int32_t meao_execute_batch_pitched(meao_ctx *ctx, int32_t n, const void
                                             meao_stream stream);
 MEAO_API int32_t meao_prefetch_batch_pitched(meao_ctx *ctx, int32_t n, const void *const *depth, uint64_t depth_pitch,
                                              const meao_params *params);
+/* Announcements that survive a size change (dynamic resolution).  meao_prefetch_batch_pitched for frames of width x height, a size
+ * inside the reservation (meao_reserve) that need not be the context's: otherwise MEAO_ERR_INVALID_ARGUMENT, and meao_last_error
+ * names the argument; depth_pitch is validated against the ANNOUNCED size; params may be NULL.  The next meao_execute*, at the
+ * current size, runs the announced frames' downsample pass at the announced size into the other downsample set: inside its last
+ * kernel where the carried form is eligible (f32 depth, width % 8 == 0, aligned frames -- of the announced frames) and the pass's
+ * tiles fit that kernel's grid (ceil(w / 128) x ceil(h / 32) announced against ceil(W / 64) x ceil(H / 64) current tiles), else
+ * as one more launch behind it; host code decides, no kernel knows.  meao_resize(width, height) KEEPS an announcement or a ready
+ * set made by this call for exactly the new size and drops any other -- also every one made by the other meao_prefetch_batch*
+ * calls, as ever.  The consuming execute matches on the size as well: a host that announces one size and executes at another
+ * gets a correct result from a pass of its own.  With width x height equal to the current size the call IS
+ * meao_prefetch_batch_pitched.  The frame loop of a host that scales its resolution:
+ *   meao_prefetch_batch_sized(B, frames k+1) -> meao_execute*(frames k, at A) -> meao_resize(B) -> meao_execute*(frames k+1)
+ * never leaves the pipelined form. */
+MEAO_API int32_t meao_prefetch_batch_sized(meao_ctx *ctx, int32_t width, int32_t height, int32_t n, const void *const *depth,
+                                           uint64_t depth_pitch, const meao_params *params);
 /* Waits for `stream`; NULL = the stream of the last meao_execute* of this context.  meao_composite /
  * meao_composite_flush do not change what NULL means: a composite issued on another stream is waited for
  * by naming that stream here (or by synchronising it directly). */
@@ -546,6 +586,17 @@ MEAO_API int32_t meao_pool_execute_batch_pitched(meao_pool *pool, int32_t n, con
                                                  const meao_params *params);
 MEAO_API int32_t meao_pool_prefetch_batch_pitched(meao_pool *pool, int32_t n, const void *const *depth, uint64_t depth_pitch,
                                                   const meao_params *params);
+/* Dynamic resolution for the pool.  meao_pool_reserve: meao_reserve member by member; if member k fails, the members before it
+ * keep the larger reservation (a reservation changes no result), no member's size changes, and meao_pool_last_error names the
+ * member.  meao_pool_resize is for sizes that EVERY member's reservation covers; anything else is MEAO_ERR_INVALID_ARGUMENT,
+ * checked for every member before any member is touched.  It waits on the host until each worker has finished enqueuing the jobs
+ * it was handed (no device synchronisation) and then resizes every member inside its reservation: no allocation, no
+ * synchronisation.  meao_pool_gather_to_device copies frames of the new size afterwards.  meao_pool_prefetch_batch_sized: the sized
+ * announcement, dealt frame f -> member f mod G like every pool call. */
+MEAO_API int32_t meao_pool_reserve(meao_pool *pool, int32_t max_width, int32_t max_height);
+MEAO_API int32_t meao_pool_resize(meao_pool *pool, int32_t width, int32_t height);
+MEAO_API int32_t meao_pool_prefetch_batch_sized(meao_pool *pool, int32_t width, int32_t height, int32_t n, const void *const *depth,
+                                                uint64_t depth_pitch, const meao_params *params);
 /* meao_composite_enqueue / meao_composite_flush for the pool, frames dealt f -> member f mod G: the composite
  * of frame f rides inside the next execute of the member that owns (and produced) it. */
 MEAO_API int32_t meao_pool_composite_enqueue(meao_pool *pool, int32_t mode, int32_t n, const void *const *ao,

@@ -103,6 +103,26 @@ public:
         cfg_.width = pixelWidth;
         cfg_.height = pixelHeight;
     }
+    // Dynamic resolution: reserve the maximum size once (it may allocate and synchronises the device once); Resize to any size
+    // inside it then moves nothing -- no allocation, no synchronisation (meao_reserve).  (0, 0) drops the reservation.
+    void Reserve(int32_t maxWidth, int32_t maxHeight) { check(meao_reserve(ctx_, maxWidth, maxHeight)); }
+    void Capacity(int32_t *width, int32_t *height) { check(meao_get_capacity(ctx_, width, height)); }   // (0, 0) = no reservation
+    uint64_t ReserveBytes(int32_t maxWidth, int32_t maxHeight)    // the device memory such a reservation costs
+    {
+        uint64_t bytes = 0;
+        check(meao_reserve_bytes(&cfg_, maxWidth, maxHeight, &bytes));
+        return bytes;
+    }
+    // The announcement for frames of width x height, a size inside the reservation: Resize(width, height) keeps it
+    // (meao_prefetch_batch_sized).  depthPitch 0 = tightly packed.
+    void PrefetchBatchSized(int32_t width, int32_t height, const std::vector<const void *> &nextDeviceDepth, uint64_t depthPitch = 0,
+                            const std::vector<meao_params> &params = {})
+    {
+        if (!params.empty() && params.size() != nextDeviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        sync();
+        check(meao_prefetch_batch_sized(ctx_, width, height, static_cast<int32_t>(nextDeviceDepth.size()), nextDeviceDepth.data(), depthPitch,
+                                        params.empty() ? nullptr : params.data()));
+    }
 
     // Streams of frames: announce the device depth frames of the call after next; the next Render*
     // carries their downsample pass inside its last kernel (meao_prefetch_batch).
@@ -316,6 +336,17 @@ public:
     {
         check(meao_pool_execute_batch(pool_, static_cast<int32_t>(deviceDepth.size()), deviceDepth.data(), MEAO_MEM_DEVICE,
                                       deviceAo.data(), MEAO_MEM_DEVICE));
+    }
+    // Dynamic resolution (meao_pool_reserve / meao_pool_resize / meao_pool_prefetch_batch_sized): Resize takes sizes every
+    // member's reservation covers, and then neither allocates nor synchronises.
+    void Reserve(int32_t maxWidth, int32_t maxHeight) { check(meao_pool_reserve(pool_, maxWidth, maxHeight)); }
+    void Resize(int32_t width, int32_t height) { check(meao_pool_resize(pool_, width, height)); }
+    void PrefetchBatchSized(int32_t width, int32_t height, const std::vector<const void *> &nextDeviceDepth, uint64_t depthPitch = 0,
+                            const std::vector<meao_params> &params = {})
+    {
+        if (!params.empty() && params.size() != nextDeviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        check(meao_pool_prefetch_batch_sized(pool_, width, height, static_cast<int32_t>(nextDeviceDepth.size()), nextDeviceDepth.data(),
+                                             depthPitch, params.empty() ? nullptr : params.data()));
     }
     void PrefetchBatch(const std::vector<const void *> &nextDeviceDepth)
     {

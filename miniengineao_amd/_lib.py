@@ -103,6 +103,9 @@ SIGNATURES = {
     "meao_create": (C.c_int32, [C.POINTER(Config), C.POINTER(C.c_void_p)]),
     "meao_destroy": (C.c_int32, [C.c_void_p]),
     "meao_resize": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
+    "meao_reserve": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
+    "meao_get_capacity": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "meao_reserve_bytes": (C.c_int32, [C.POINTER(Config), C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
     "meao_set_params": (C.c_int32, [C.c_void_p, C.POINTER(Params)]),
     "meao_get_params": (C.c_int32, [C.c_void_p, C.POINTER(Params)]),
     "meao_get_config": (C.c_int32, [C.c_void_p, C.POINTER(Config)]),
@@ -117,6 +120,8 @@ SIGNATURES = {
     "meao_execute_batch_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.c_int32,
                                                C.POINTER(C.c_void_p), C.c_uint64, C.c_int32, C.POINTER(Params), C.c_void_p]),
     "meao_prefetch_batch_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(Params)]),
+    "meao_prefetch_batch_sized": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,
+                                              C.POINTER(Params)]),
     "meao_synchronize": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "meao_get_intermediate": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64,
                                           C.c_int32, C.POINTER(Desc)]),
@@ -155,6 +160,10 @@ SIGNATURES = {
     "meao_pool_execute_batch_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.c_int32,
                                                     C.POINTER(C.c_void_p), C.c_uint64, C.c_int32, C.POINTER(Params)]),
     "meao_pool_prefetch_batch_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(Params)]),
+    "meao_pool_reserve": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
+    "meao_pool_resize": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
+    "meao_pool_prefetch_batch_sized": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,
+                                                   C.POINTER(Params)]),
     "meao_pool_composite_enqueue": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                 C.POINTER(C.c_void_p)]),
     "meao_pool_composite_enqueue_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,

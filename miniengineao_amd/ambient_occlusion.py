@@ -116,9 +116,27 @@ class AmbientOcclusion:
     ao_dtype = property(lambda s: np.uint8 if s._cfg.ao_format == L.AO_R8 else np.uint16)
 
     def resize(self, width: int, height: int) -> None:
-        """Screen-size change (AO.cs:338-341)."""
+        """Screen-size change (AO.cs:338-341).  Inside a reservation (reserve()) it neither allocates nor synchronises."""
         L.check(self._lib.meao_resize(self._ctx, width, height), self._ctx)
         self._cfg.width, self._cfg.height = width, height
+
+    def reserve(self, max_width: int, max_height: int) -> None:
+        """Dynamic resolution (meao_reserve): size the intermediates for max_width x max_height once -- it may allocate and
+        synchronises the device once; every later resize() to a size inside it moves nothing.  (0, 0) drops the reservation."""
+        L.check(self._lib.meao_reserve(self._ctx, max_width, max_height), self._ctx)
+
+    @property
+    def capacity(self) -> tuple:
+        """The reservation as (width, height); (0, 0) = none (meao_get_capacity)."""
+        w, h = C.c_int32(), C.c_int32()
+        L.check(self._lib.meao_get_capacity(self._ctx, C.byref(w), C.byref(h)), self._ctx)
+        return w.value, h.value
+
+    def reserve_bytes(self, max_width: int, max_height: int) -> int:
+        """Device memory a reservation of that size costs this configuration (meao_reserve_bytes; host-plan only)."""
+        b = C.c_uint64()
+        L.check(self._lib.meao_reserve_bytes(C.byref(self._cfg), max_width, max_height, C.byref(b)))
+        return b.value
 
     def _sync_params(self) -> None:
         if self._dirty:
@@ -187,15 +205,20 @@ class AmbientOcclusion:
                                                     gbuffer0_pitch, C.c_void_p(stream) if stream else None), self._ctx)
 
     def prefetch_device(self, depth_ptrs: Sequence[int], params: Optional[Sequence[Optional[FrameParams]]] = None, *,
-                        depth_pitch: int = 0) -> None:
+                        depth_pitch: int = 0, size: Optional[tuple] = None) -> None:
         """Announce the device depth frames of the call after next (meao_prefetch_batch): the next
         execute_device() carries their downsample pass inside its last upsample kernel.  params: the frames' own
         parameters (meao_prefetch_batch_params), as they will be given to the consuming execute_device().  depth_pitch: their row
-        pitch in bytes (meao_prefetch_batch_pitched; 0 = tightly packed), as it will be given to the consuming call."""
+        pitch in bytes (meao_prefetch_batch_pitched; 0 = tightly packed), as it will be given to the consuming call.
+        size: (width, height) of the announced frames where it is not this context's size -- a size inside the reservation that a
+        resize() follows before the consuming call (meao_prefetch_batch_sized)."""
         n = len(depth_ptrs)
         self._sync_params()     # pending property changes first: meao_set_params would drop the announcement
         pin = (C.c_void_p * n)(*depth_ptrs)
-        if depth_pitch:
+        if size is not None:
+            prm = None if params is None else params_array(params, n, self._prm)
+            L.check(self._lib.meao_prefetch_batch_sized(self._ctx, int(size[0]), int(size[1]), n, pin, depth_pitch, prm), self._ctx)
+        elif depth_pitch:
             prm = None if params is None else params_array(params, n, self._prm)
             L.check(self._lib.meao_prefetch_batch_pitched(self._ctx, n, pin, depth_pitch, prm), self._ctx)
         elif params is None:
@@ -532,12 +555,26 @@ class AmbientOcclusionPool:
                                                              (C.c_void_p * n)(*out_ptrs), out_pitch, prm, mode,
                                                              (C.c_void_p * n)(*color_ptrs), color_format, color_pitch, g, gbuffer0_pitch))
 
+    def reserve(self, max_width: int, max_height: int) -> None:
+        """meao_pool_reserve: AmbientOcclusion.reserve for every member."""
+        self._check(self._lib.meao_pool_reserve(self._pool, max_width, max_height))
+
+    def resize(self, width: int, height: int) -> None:
+        """meao_pool_resize: a size every member's reservation covers (reserve() first); no allocation, no synchronisation."""
+        self._check(self._lib.meao_pool_resize(self._pool, width, height))
+        self._cfg.width, self._cfg.height = width, height
+
     def prefetch_device(self, depth_ptrs: Sequence[int], params: Optional[Sequence[Optional[FrameParams]]] = None, *,
-                        depth_pitch: int = 0) -> None:
+                        depth_pitch: int = 0, size: Optional[tuple] = None) -> None:
         """meao_pool_prefetch_batch: the frames of the call after next, dealt like execute_device deals them.  depth_pitch: their
-        row pitch in bytes (meao_pool_prefetch_batch_pitched; 0 = tightly packed)."""
+        row pitch in bytes (meao_pool_prefetch_batch_pitched; 0 = tightly packed).  size: (width, height) of the announced frames
+        where a resize() follows before the consuming call (meao_pool_prefetch_batch_sized)."""
         n = len(depth_ptrs)
-        if depth_pitch:
+        if size is not None:
+            prm = None if params is None else params_array(params, n, self._prm)
+            self._check(self._lib.meao_pool_prefetch_batch_sized(self._pool, int(size[0]), int(size[1]), n, (C.c_void_p * n)(*depth_ptrs),
+                                                                 depth_pitch, prm))
+        elif depth_pitch:
             prm = None if params is None else params_array(params, n, self._prm)
             self._check(self._lib.meao_pool_prefetch_batch_pitched(self._pool, n, (C.c_void_p * n)(*depth_ptrs), depth_pitch, prm))
         elif params is None:

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -20,7 +21,7 @@ thread_local std::string g_last_error;   // for failures that have no context (m
 
 bool config_valid(const meao_config &c, std::string *why)
 {
-    if (c.width < 1 || c.height < 1 || c.width > 32768 || c.height > 32768) { *why = "width/height out of range [1, 32768]"; return false; }
+    if (!size_valid(c.width, c.height)) { *why = "width/height out of range [1, 32768]"; return false; }
     if (c.num_levels < 1 || c.num_levels > 4) { *why = "num_levels must be 1..4"; return false; }
     if (c.ao_format != MEAO_AO_R8 && c.ao_format != MEAO_AO_F16) { *why = "unknown ao_format"; return false; }
     if (c.f16_rounding != MEAO_F16_RTZ_CLAMP && c.f16_rounding != MEAO_F16_RTNE) { *why = "unknown f16_rounding"; return false; }
@@ -48,11 +49,24 @@ SlotLayout layout_slot(const Plan &p, const meao_config &cfg, bool two_ds_sets)
     return l;
 }
 
+void replan(meao_ctx *ctx)
+{
+    build_plan(ctx->cfg.width, ctx->cfg.height, ctx->cfg.num_levels, ctx->cfg.sample_set, ctx->prm, &ctx->plan);
+    ctx->exact_rcp_div = exact_rcp_div_applicable(ctx->cfg, ctx->plan) ? 1 : 0;
+}
+
 void update_plan(meao_ctx *ctx)
 {
     ctx->prefetch.withdraw(true);   // a prefetched downsample was computed with the old Z-buffer parameters
-    build_plan(ctx->cfg.width, ctx->cfg.height, ctx->cfg.num_levels, ctx->cfg.sample_set, ctx->prm, &ctx->plan);
-    ctx->exact_rcp_div = exact_rcp_div_applicable(ctx->cfg, ctx->plan) ? 1 : 0;
+    replan(ctx);
+}
+
+// The reserved geometry, planned for layout_slot (only the level dimensions of the plan are read there).
+SlotLayout layout_for(const meao_config &cfg, bool two_ds_sets, int32_t w, int32_t h)
+{
+    Plan plan{};
+    for (int k = 0; k < kNumMips; ++k) plan.mip[k] = level_dims(w, h, k);
+    return layout_slot(plan, cfg, two_ds_sets);
 }
 
 void release_buffers(meao_ctx *ctx)
@@ -80,6 +94,13 @@ int meao::fail_hip(meao_ctx *ctx, hipError_t e, const char *what)
     return fail(ctx, e == hipErrorOutOfMemory ? MEAO_ERR_OUT_OF_MEMORY : MEAO_ERR_HIP, buf);
 }
 
+void meao::note_sync(meao_ctx *ctx)
+{
+    if (ctx) ++ctx->sync_calls;
+}
+
+bool meao::size_valid(int32_t width, int32_t height) { return width >= 1 && height >= 1 && width <= 32768 && height <= 32768; }
+
 int meao::use_device(meao_ctx *ctx)
 {
     MEAO_HIP(ctx, hipSetDevice(ctx->cfg.device));
@@ -105,13 +126,12 @@ bool meao::exact_rcp_div_applicable(const meao_config &c, const Plan &plan)
 
 // The new geometry is planned on the side and its arena allocated BEFORE anything of the context changes: on failure the
 // context is untouched -- geometry, buffers and a ready prefetch all stay as they were.
-int meao::reallocate(meao_ctx *ctx, const meao_config &cfg, bool two_ds_sets)
+int meao::reallocate(meao_ctx *ctx, const meao_config &cfg, bool two_ds_sets, int32_t cap_w, int32_t cap_h)
 {
-    Plan plan{};
-    build_plan(cfg.width, cfg.height, cfg.num_levels, cfg.sample_set, ctx->prm, &plan);
-    const SlotLayout lay = layout_slot(plan, cfg, two_ds_sets);
+    const SlotLayout lay = layout_for(cfg, two_ds_sets, cap_w > 0 ? cap_w : cfg.width, cap_h > 0 ? cap_h : cfg.height);
     char *fresh = nullptr;
     hipError_t e;
+    ++ctx->arena_allocs;
 #if MEAO_TESTING
     if (ctx->debug_fail_allocs > 0) {      // fault injection: exists only in the `testhooks` variant library (-DMEAO_TESTING=1)
         --ctx->debug_fail_allocs;
@@ -124,6 +144,7 @@ int meao::reallocate(meao_ctx *ctx, const meao_config &cfg, bool two_ds_sets)
     if (e != hipSuccess) return fail_hip(ctx, e, "hipMalloc (intermediates)");
     ctx->cfg = cfg;
     ctx->two_ds_sets = two_ds_sets;
+    ctx->cap_w = cap_w; ctx->cap_h = cap_h;
     update_plan(ctx);           // drops a ready prefetch: it refers to the old arena
     ctx->lay = lay;
     release_buffers(ctx);
@@ -137,6 +158,7 @@ void meao::Profiler::fold()
         for (int k = 0; k < kProfSlots; ++k) {
             if (!(ran_mask[r] >> k & 1u)) continue;
             hipEvent_t a = events[(r * kProfSlots + k) * 2], b = events[(r * kProfSlots + k) * 2 + 1];
+            note_sync(owner);
             (void)hipEventSynchronize(b);
             float ms = 0.0f;
             if (hipEventElapsedTime(&ms, a, b) != hipSuccess) continue;
@@ -286,6 +308,7 @@ int32_t meao_create(const meao_config *cfg, meao_ctx **out_ctx)
     meao_ctx *ctx = new (std::nothrow) meao_ctx();
     if (!ctx) return fail(nullptr, MEAO_ERR_OUT_OF_MEMORY, "meao_create: host allocation failed");
     ctx->cfg = *cfg;
+    ctx->profiler.owner = ctx;
     meao_default_params(&ctx->prm);
     int rc = use_device(ctx);
     if (rc == MEAO_OK) {
@@ -308,7 +331,7 @@ int32_t meao_create(const meao_config *cfg, meao_ctx **out_ctx)
     // the batched composite's frame tables (meao_composite_batch): the same kind of ring
     if (rc == MEAO_OK && (e = ctx->comp_ring.create(cfg->max_batch)) != hipSuccess) rc = fail_hip(ctx, e, "batched composite tables");
     // cfg.pipelined: the second downsample set exists from the start, so meao_prefetch_batch never re-allocates
-    if (rc == MEAO_OK) rc = reallocate(ctx, *cfg, cfg->pipelined != 0);
+    if (rc == MEAO_OK) rc = reallocate(ctx, *cfg, cfg->pipelined != 0, 0, 0);
     if (rc != MEAO_OK) {
         g_last_error = ctx->err;
         meao_destroy(ctx);
@@ -328,6 +351,7 @@ int32_t meao_destroy(meao_ctx *ctx)
     // A composite batch still waiting is DISCARDED (meao.h): its targets are caller memory whose lifetime has
     // typically ended by now (free the frames, then destroy); hosts that want it call meao_composite_flush first.
     ctx->pending_comp.frames = 0;
+    note_sync(ctx);
     (void)hipDeviceSynchronize();
     release_buffers(ctx);
     if (ctx->counter) (void)hipFree(ctx->counter);
@@ -356,9 +380,55 @@ int32_t meao_resize(meao_ctx *ctx, int32_t width, int32_t height)
         rc = flush_pending_composite(ctx, ctx->pending_stream);
         if (rc != MEAO_OK) return rc;
     }
+    if (ctx->within_reservation(width, height)) {
+        // Nothing moves: every buffer of a slot stays at the offset the reserved geometry gives it, and the launch arguments of
+        // the next call are built from the new plan.  No allocation, no synchronisation, no launch: the stream orders the next
+        // call behind the last one, as it orders any two executes of this context (they share the intermediates).
+        ctx->cfg = c;
+        replan(ctx);
+        ctx->prefetch.resized_to(width, height);
+        ctx->last.frames = 0;                  // the debug buffers of the last call are gone, as in every resize
+        return MEAO_OK;
+    }
+    note_sync(ctx);
     MEAO_HIP(ctx, hipDeviceSynchronize());
-    // on failure (e.g. out of memory) the context keeps its previous size and buffers
-    return reallocate(ctx, c, ctx->two_ds_sets);
+    // on failure (e.g. out of memory) the context keeps its previous size, buffers and reservation; a reservation grows to cover
+    // the new size
+    const bool reserved = ctx->cap_w > 0;
+    return reallocate(ctx, c, ctx->two_ds_sets, reserved ? std::max(ctx->cap_w, width) : 0, reserved ? std::max(ctx->cap_h, height) : 0);
+}
+
+int32_t meao_reserve(meao_ctx *ctx, int32_t max_width, int32_t max_height)
+{
+    if (!ctx) return MEAO_ERR_INVALID_ARGUMENT;
+    const bool drop = max_width == 0 && max_height == 0;
+    if (!drop) {
+        if (!size_valid(max_width, max_height)) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_reserve: max_width/max_height out of range [1, 32768]");
+        if (max_width < ctx->cfg.width || max_height < ctx->cfg.height)
+            return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_reserve: max_width/max_height: the reservation must cover the current size");
+    }
+    int rc = use_device(ctx);
+    if (rc != MEAO_OK) return rc;
+    note_sync(ctx);
+    MEAO_HIP(ctx, hipDeviceSynchronize());
+    // (a waiting composite batch stays: its surfaces are the caller's, and the size does not change)
+    return reallocate(ctx, ctx->cfg, ctx->two_ds_sets, drop ? 0 : max_width, drop ? 0 : max_height);
+}
+
+int32_t meao_get_capacity(const meao_ctx *ctx, int32_t *out_width, int32_t *out_height)
+{
+    if (!ctx || !out_width || !out_height) return MEAO_ERR_INVALID_ARGUMENT;
+    *out_width = ctx->cap_w;
+    *out_height = ctx->cap_h;
+    return MEAO_OK;
+}
+
+int32_t meao_reserve_bytes(const meao_config *cfg, int32_t max_width, int32_t max_height, uint64_t *out_bytes)
+{
+    std::string why;
+    if (!cfg || !out_bytes || !config_valid(*cfg, &why) || !size_valid(max_width, max_height)) return MEAO_ERR_INVALID_ARGUMENT;
+    *out_bytes = layout_for(*cfg, cfg->pipelined != 0, max_width, max_height).slot_bytes * static_cast<uint64_t>(cfg->max_batch);
+    return MEAO_OK;
 }
 
 int32_t meao_set_params(meao_ctx *ctx, const meao_params *p)
@@ -392,6 +462,7 @@ int32_t meao_synchronize(meao_ctx *ctx, meao_stream stream)
     if (!ctx) return MEAO_ERR_INVALID_ARGUMENT;
     int rc = use_device(ctx);
     if (rc != MEAO_OK) return rc;
+    note_sync(ctx);
     MEAO_HIP(ctx, hipStreamSynchronize(stream ? static_cast<hipStream_t>(stream) : ctx->last.stream));
     return MEAO_OK;
 }
@@ -406,6 +477,7 @@ int32_t meao_hostile_frames(meao_ctx *ctx, uint64_t *out_mask)
     uint32_t words[MEAO_MAX_BATCH];
     MEAO_HIP(ctx, hipMemcpyAsync(words, ctx->hostile_of(ctx->prefetch.ds_cur), sizeof(uint32_t) * ctx->last.frames, hipMemcpyDeviceToHost,
                                  ctx->last.stream));
+    note_sync(ctx);
     MEAO_HIP(ctx, hipStreamSynchronize(ctx->last.stream));
     for (int f = 0; f < ctx->last.frames; ++f)
         if (words[f] == ctx->prefetch.generation()) *out_mask |= uint64_t(1) << f;
@@ -448,6 +520,7 @@ int32_t meao_get_pass_times(meao_ctx *ctx, float ms[MEAO_NUM_PASSES], int32_t *o
     if (rc != MEAO_OK) return rc;
     // the documented contract: the call returns after the stream of the last execute has drained (executes that recorded no
     // events -- meao_set_profiling(N > 1), PROFILE_PASS_MASK -- included; the timing events themselves carry no fence)
+    note_sync(ctx);
     MEAO_HIP(ctx, hipStreamSynchronize(ctx->last.stream));
     Profiler &pr = ctx->profiler;
     pr.fold();
@@ -515,6 +588,17 @@ __attribute__((visibility("default"))) int32_t meao_test_fail_next_allocs(meao_c
     ctx->debug_fail_allocs = n < 0 ? 0 : n;
     return MEAO_OK;
 }
+
+// out[0]: arena allocations attempted since meao_create (an injected failure counts); out[1]: synchronising HIP calls the
+// context has made since then (device, stream and event synchronise).  What proves that a meao_resize inside a reservation
+// neither allocates nor waits (tests/dynamic_resolution_testhooks_check.py).
+__attribute__((visibility("default"))) int32_t meao_test_counters(const meao_ctx *ctx, uint64_t out[2])
+{
+    if (!ctx || !out) return MEAO_ERR_INVALID_ARGUMENT;
+    out[0] = ctx->arena_allocs;
+    out[1] = ctx->sync_calls;
+    return MEAO_OK;
+}
 #endif
 
 int32_t meao_selftest(meao_ctx *ctx, int32_t which, uint64_t *out_mismatches)
@@ -527,6 +611,7 @@ int32_t meao_selftest(meao_ctx *ctx, int32_t which, uint64_t *out_mismatches)
     MEAO_HIP(ctx, launch_selftest(which, ctx->counter, ctx->own_stream));
     unsigned long long host = 0;
     MEAO_HIP(ctx, hipMemcpyAsync(&host, ctx->counter, sizeof host, hipMemcpyDeviceToHost, ctx->own_stream));
+    note_sync(ctx);
     MEAO_HIP(ctx, hipStreamSynchronize(ctx->own_stream));
     *out_mismatches = host;
     return MEAO_OK;

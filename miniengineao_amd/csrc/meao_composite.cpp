@@ -103,6 +103,7 @@ int composite_one(meao_ctx *ctx, const char *fn, const CompositeTargets &t, int3
         if (e == hipSuccess) e = launch_composite(ca, ctx->cfg.ao_format, stream);
         if (e == hipSuccess) e = copy(color, color_src, d_color, color_row, color_row, hipMemcpyDeviceToHost);
         if (e == hipSuccess && gbuffer0) e = copy(gbuffer0, g_src, d_g, g_row, g_row, hipMemcpyDeviceToHost);
+        note_sync(ctx);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         (void)hipFree(scratch);
         if (e != hipSuccess) return fail_hip(ctx, e, (std::string(fn) + " (host staging)").c_str());

@@ -26,6 +26,9 @@ inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<ui
 
 int fail(meao_ctx *ctx, int status, const std::string &msg);
 int fail_hip(meao_ctx *ctx, hipError_t e, const char *what);
+// Every synchronising HIP call a context makes (device, stream, event) is counted: what meao_test_counters reports in the
+// `testhooks` variant library (a meao_resize inside a reservation must leave the count alone).
+void note_sync(meao_ctx *ctx);
 
 #define MEAO_HIP(ctx, expr)                                              \
     do {                                                                 \
@@ -33,7 +36,9 @@ int fail_hip(meao_ctx *ctx, hipError_t e, const char *what);
         if (e_ != hipSuccess) return ::meao::fail_hip((ctx), e_, #expr); \
     } while (0)
 
-// Where the intermediates of one frame live inside its slot; a pure function of (plan, cfg, two_ds_sets).
+// Where the intermediates of one frame live inside its slot; a pure function of (plan, cfg, two_ds_sets).  The plan is that of
+// the geometry the slots are laid out for: the context's size, or its reservation (meao_reserve) -- then every size inside the
+// reservation uses these offsets, each buffer packed for its own extents (ceil(w / 2^k) * ceil(h / 2^k) is monotone in w and h).
 struct SlotLayout {
     // Downsample outputs (LowDepth1..4; LinearDepth is never materialised on the hot path).  With meao_prefetch_batch in use the
     // slot holds two such sets: the passes of a call read set `ds_cur` while its last kernel fills the other one with the next
@@ -68,10 +73,15 @@ struct Tuning {
 struct Announcement {
     int n = 0;
     const void *depth[MEAO_MAX_BATCH] = {};
-    int32_t depth_pitch = 0;                      // row stride in texels, cfg.width when tightly packed
+    int32_t depth_pitch = 0;                      // row stride in texels, the frames' width when tightly packed
     bool per_frame = false;                       // it came with its own parameters (prm, plan)
     meao_params prm[MEAO_MAX_BATCH] = {};
     std::vector<Plan> plan;                       // MEAO_MAX_BATCH, sized by meao_create
+    // meao_prefetch_batch_sized: frames of another size than the context's (inside its reservation), and the plan of that size
+    // for the context's parameters.  sized = false: the context's size and plan at the time of the carrying call.
+    bool sized = false;
+    int32_t width = 0, height = 0;
+    Plan shared_plan{};
 };
 
 // ZBufferParams inputs (near, far, reversed_z) a frame of a ready set was downsampled with
@@ -84,6 +94,8 @@ struct ReadySet {
     int n = 0, set = 0;
     hipStream_t stream = nullptr;
     int32_t depth_pitch = 0;
+    bool sized = false;                           // it came from a sized announcement: a meao_resize to its size keeps it
+    int32_t width = 0, height = 0;                // the size its levels were built for
     const void *depth[MEAO_MAX_BATCH] = {};
     ZbInputs zb[MEAO_MAX_BATCH] = {};
     bool exact = false;
@@ -102,23 +114,38 @@ struct Prefetch {
     int other() const { return 1 - ds_cur; }
     uint32_t generation() const { return set_gen[ds_cur]; }
 
-    void announce(const meao_config &cfg, int n, const void *const *depth, int32_t pitch, const meao_params *params)
+    // width x height: the announced frames' size; sized (meao_prefetch_batch_sized): it is not the context's, and
+    // ctx_prm the context's parameters, for the plan of that size
+    void announce(const meao_config &cfg, int32_t width, int32_t height, bool sized, const meao_params &ctx_prm, int n,
+                  const void *const *depth, int32_t pitch, const meao_params *params)
     {
         next.n = n;
         next.depth_pitch = pitch;
+        next.sized = sized; next.width = width; next.height = height;
+        if (sized) build_plan(width, height, cfg.num_levels, cfg.sample_set, ctx_prm, &next.shared_plan);
         for (int f = 0; f < n; ++f) next.depth[f] = depth[f];
         next.per_frame = params != nullptr;
         if (params)
             for (int f = 0; f < n; ++f) {
                 next.prm[f] = params[f];
-                build_plan(cfg.width, cfg.height, cfg.num_levels, cfg.sample_set, params[f], &next.plan[f]);
+                build_plan(width, height, cfg.num_levels, cfg.sample_set, params[f], &next.plan[f]);
             }
     }
     // the announcement goes; ready_too: a ready set as well
     void withdraw(bool ready_too)
     {
-        next.n = 0; next.per_frame = false;
-        if (ready_too) { ready.n = 0; ready.stream = nullptr; }
+        next.n = 0; next.per_frame = false; next.sized = false;
+        if (ready_too) { ready.n = 0; ready.stream = nullptr; ready.sized = false; }
+    }
+    // meao_resize(width, height) inside a reservation: a sized announcement and a ready set made from one, for exactly the new
+    // size, stay (the buffers do not move and the parameters do not change); everything else goes, as in every resize.  A kept
+    // announcement becomes one for the context's size, like any other the next call carries.
+    void resized_to(int32_t width, int32_t height)
+    {
+        if (!(next.n > 0 && next.sized && next.width == width && next.height == height)) { next.n = 0; next.per_frame = false; }
+        next.sized = false;
+        if (!(ready.n > 0 && ready.sized && ready.width == width && ready.height == height)) { ready.n = 0; ready.stream = nullptr; }
+        ready.sized = false;
     }
     static bool same_zb(const ZbInputs &z, const meao_params &p, int depth_format)
     {
@@ -130,10 +157,10 @@ struct Prefetch {
                (z.reversed_z != 0) == (p.reversed_z != 0);
     }
     bool matches(int n, const void *const *depth, hipStream_t stream, int32_t pitch, bool exact, const meao_params *const *prm_of,
-                 int depth_format) const
+                 int depth_format, int32_t width, int32_t height) const
     {
         bool ok = ready.n == n && ready.stream == stream && std::memcmp(ready.depth, depth, sizeof(void *) * n) == 0 &&
-                  (ready.exact || !exact) && ready.depth_pitch == pitch;
+                  (ready.exact || !exact) && ready.depth_pitch == pitch && ready.width == width && ready.height == height;
         for (int f = 0; ok && f < n; ++f) ok = same_zb(ready.zb[f], *prm_of[f], depth_format);
         return ok;
     }
@@ -145,10 +172,13 @@ struct Prefetch {
         if (!matched) set_gen[ds_cur] = fresh_generation();
     }
     uint32_t generation_for_next() { return set_gen[other()] = fresh_generation(); }
-    // The call carried the announced pass: the announcement becomes the ready set.
-    void promote(hipStream_t stream, bool exact, const meao_params &ctx_prm)
+    // The call carried the announced pass: the announcement becomes the ready set.  width x height: the context's size, which
+    // an announcement that is not sized was made for.
+    void promote(hipStream_t stream, bool exact, const meao_params &ctx_prm, int32_t width, int32_t height)
     {
         ready.n = next.n; ready.set = other(); ready.stream = stream; ready.exact = exact; ready.depth_pitch = next.depth_pitch;
+        ready.sized = next.sized;
+        ready.width = next.sized ? next.width : width; ready.height = next.sized ? next.height : height;
         std::memcpy(ready.depth, next.depth, sizeof ready.depth);
         for (int f = 0; f < next.n; ++f) {
             const meao_params &q = next.per_frame ? next.prm[f] : ctx_prm;
@@ -176,6 +206,7 @@ struct TableRing {
     // (reuse waits for it), or, if even that fails, a synchronised stream.
     struct Lease {
         TableRing *ring = nullptr;
+        meao_ctx *ctx = nullptr;
         int slot = 0;
         hipStream_t stream = nullptr;
         bool armed = false;
@@ -192,6 +223,7 @@ struct TableRing {
                 ring->pending[slot] = true;
             } else {
                 (void)hipGetLastError();
+                note_sync(ctx);
                 (void)hipStreamSynchronize(stream);
             }
         }
@@ -219,10 +251,11 @@ struct TableRing {
         const int slot = pos;
         pos = (pos + 1) % N;
         if (pending[slot]) {
+            note_sync(ctx);
             MEAO_HIP(ctx, hipEventSynchronize(ev[slot]));
             pending[slot] = false;
         }
-        lease->ring = this; lease->slot = slot; lease->stream = stream;
+        lease->ring = this; lease->ctx = ctx; lease->slot = slot; lease->stream = stream;
         return MEAO_OK;
     }
 };
@@ -268,6 +301,7 @@ struct Profiler {
     int pass_samples[MEAO_NUM_PASSES] = {};      // executes that ran pass k
     int executes_profiled = 0;
     hipEvent_t *cur = nullptr;                   // the event set of the call under way, null = it runs bare
+    meao_ctx *owner = nullptr;                   // whose synchronising calls fold() makes (note_sync)
 
     hipEvent_t *begin_call()
     {
@@ -314,6 +348,10 @@ struct meao_ctx {
     char *arena = nullptr;
     meao::SlotLayout lay;
     bool two_ds_sets = false;
+    // meao_reserve: the size the slots are laid out and the arena is allocated for; (0, 0) = none, they fit cfg exactly.
+    // A meao_resize inside it changes cfg and the plan only.
+    int32_t cap_w = 0, cap_h = 0;
+    bool within_reservation(int32_t w, int32_t h) const { return cap_w > 0 && w <= cap_w && h <= cap_h; }
     // Hostile-depth flags (meao_dev_downsample.hpp nice_denominator): [set][frame] words the downsample pass
     // stamps with its generation when a frame's levels hold texels outside the exact-division range.
     uint32_t *hostile = nullptr;
@@ -346,6 +384,8 @@ struct meao_ctx {
 #if MEAO_TESTING
     int debug_fail_allocs = 0;         // meao_test_fail_next_allocs: arena allocations still to fail (testhooks variant only)
 #endif
+    // meao_test_counters (exported by the testhooks variant only): arena allocations attempted, synchronising HIP calls made
+    uint64_t arena_allocs = 0, sync_calls = 0;
 
     meao::Profiler profiler;
     meao::Tracer tracer;
@@ -403,21 +443,27 @@ struct CompositeTargets {
 // ---- meao_api.cpp
 int use_device(meao_ctx *ctx);
 bool exact_rcp_div_applicable(const meao_config &c, const Plan &plan);
-// (Re)plans for cfg/two_ds_sets and replaces the arena; on failure the context is untouched.
-int reallocate(meao_ctx *ctx, const meao_config &cfg, bool two_ds_sets);
+// (Re)plans for cfg/two_ds_sets and replaces the arena, laid out for cap_w x cap_h (0, 0: for cfg's size, and the context then
+// holds no reservation); on failure the context is untouched.
+int reallocate(meao_ctx *ctx, const meao_config &cfg, bool two_ds_sets, int32_t cap_w, int32_t cap_h);
+// What config_valid says of a frame size.
+bool size_valid(int32_t width, int32_t height);
 
 // ---- meao_execute.cpp
 // Every params[f] valid (as meao_set_params checks it); else the status, with the frame named in the context's error.
 int validate_frame_params(meao_ctx *ctx, int32_t n, const meao_params *params, const char *what);
 // A row pitch (bytes, 0 = tightly packed) -> the row stride in texels; `what` names the argument in the error.
 int pitch_texels(meao_ctx *ctx, uint64_t pitch, uint64_t elem, const char *what, int32_t *out);
+// The same for frames of width x height instead of the context's size (meao_prefetch_batch_sized).
+int pitch_texels_of(meao_ctx *ctx, int32_t width, int32_t height, uint64_t pitch, uint64_t elem, const char *what, int32_t *out);
 // Every check of an execute call, before anything is enqueued; the row strides in texels on success.
 int validate_execute_batch(meao_ctx *ctx, const FrameSet &fs, int32_t *depth_rows, int32_t *out_rows);
 // For meao_pool.cpp too: meao_execute_batch*; wait_for_host = false (pool members only) leaves the staged copies of a HOST
 // call in flight on `stream` -- the caller synchronises the stream before it touches the host buffers.
 int execute_batch_internal(meao_ctx *ctx, const FrameSet &fs, meao_stream stream, bool wait_for_host);
 // For meao_pool.cpp too: meao_prefetch_batch* without the checks of params[] (the caller made them): fs.n, depth, depth_pitch, params.
-int prefetch_batch_internal(meao_ctx *ctx, const FrameSet &fs);
+// width x height: the announced frames' size (meao_prefetch_batch_sized), 0 x 0 = the context's.
+int prefetch_batch_internal(meao_ctx *ctx, const FrameSet &fs, int32_t width = 0, int32_t height = 0);
 // For meao_pool.cpp: what a member that is dealt no frame of a pool call does instead of that call.
 // ready_too = false (a pool announcement passed it by): an announcement it still holds is withdrawn, as a newer one would
 // replace it.  ready_too = true (a pool execute passed it by): a ready prefetched set goes as well -- the pool-level "call

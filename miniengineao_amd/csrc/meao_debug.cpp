@@ -107,6 +107,7 @@ int32_t meao_get_intermediate(meao_ctx *ctx, int32_t frame, int32_t debug_id, vo
     if (rc != MEAO_OK) return rc;
     MEAO_HIP(ctx, hipMemcpyAsync(dst, src, d.bytes,
                                  dst_loc == MEAO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+    note_sync(ctx);
     MEAO_HIP(ctx, hipStreamSynchronize(s));
     return MEAO_OK;
 }
@@ -142,6 +143,7 @@ int32_t meao_debug_view(meao_ctx *ctx, int32_t frame, int32_t debug_id, void *ou
     MEAO_HIP(ctx, launch_debug_view(dv, ctx->cfg.ao_format, s));
     if (out_loc == MEAO_MEM_HOST) {
         MEAO_HIP(ctx, hipMemcpyAsync(out, dev_out, out_bytes, hipMemcpyDeviceToHost, s));
+        note_sync(ctx);
         MEAO_HIP(ctx, hipStreamSynchronize(s));
     }
     return MEAO_OK;

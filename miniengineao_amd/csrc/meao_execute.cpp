@@ -7,6 +7,8 @@
 #include <string>
 
 #include "meao_ctx.hpp"
+#define MEAO_LAUNCH_RULES_ONLY      // carried_in_last_kernel: the rules of the launch layer without its device headers
+#include "meao_launch.hpp"
 
 using namespace meao;
 
@@ -302,6 +304,12 @@ struct Call {
     bool next_per_frame, per_frame;       // the announced batch has its own constants / the call reads a FrameArgs table
     BatchShape shape;
 
+    // The constants the announced batch's pass is built from where it brought none of its own: the context's plan, or the plan
+    // of the announced size (meao_prefetch_batch_sized).
+    static const Plan *next_shared_plan(const meao_ctx *ctx)
+    {
+        return ctx->prefetch.next.sized ? &ctx->prefetch.next.shared_plan : &ctx->plan;
+    }
     ArgBuilder builder(const meao_ctx *ctx, const Plan *plan, const meao_params *prm) const
     {
         return ArgBuilder{ctx, n, depth_dev, out_dev, ctx->hostile_of(ctx->prefetch.ds_cur), ctx->prefetch.generation(), plan, prm, exact,
@@ -346,16 +354,17 @@ int settle_composite(meao_ctx *ctx, Call *call)
 
 // Step 4.  The announced next batch: its pass rides in this call's last kernel where the fused form applies (f32 depth, 16-byte
 // loads, a workgroup per carried tile), else it runs as a launch of its own behind it.  Either way the next call finds it done.
+// `next`: the builder of the announced pass -- its plan has the announced frames' size, which need not be this call's
+// (meao_prefetch_batch_sized); the rule is carried_in_last_kernel (meao_launch.hpp).
 // (Inside the render launch instead -- CarriedMips in the texel loop, round 6 -- it costs the same 56-60 us per 16 4K frames:
 // profiles/r06_ab_next_downsample_in_render_vs_final_vs_own_launch.jsonl, r06_scripts/r06_downsample_in_render.patch.)
-void decide_announced_pass(meao_ctx *ctx, const ArgBuilder &args, Call *call)
+void decide_announced_pass(meao_ctx *ctx, const ArgBuilder &args, const ArgBuilder &next, Call *call)
 {
     Prefetch &pre = ctx->prefetch;
     if (pre.next.n == 0) return;
     const uint32_t gen = pre.generation_for_next();
-    const DownsampleArgs lean = args.downsample(pre.next.n, pre.next.depth, pre.next.depth_pitch, pre.other(), gen, true, false);
-    call->shape.next =
-        !ctx->tuning.next_ds_own_launch && fused_downsample_applicable(args.upsample(0, true), args.hi_depth(), lean, call->n) ? 1 : 2;
+    const DownsampleArgs lean = next.downsample(pre.next.n, pre.next.depth, pre.next.depth_pitch, pre.other(), gen, true, false);
+    call->shape.next = carried_in_last_kernel(args.upsample(0, true), args.hi_depth(), lean, call->n, ctx->tuning.next_ds_own_launch) ? 1 : 2;
 }
 
 // Step 6, per-frame half.  Frame f's blocks (and the announced batch's frame f for the carried pass) into the leased ring slot,
@@ -370,7 +379,7 @@ int build_frame_table(meao_ctx *ctx, const Call &call, const LaunchList &list, T
     for (int f = 0; f < count; ++f) {
         const ArgBuilder fa = call.builder(ctx, f < call.n ? call.plan_of[f] : &ctx->plan, f < call.n ? call.prm_of[f] : &ctx->prm);
         const bool own_next = call.next_per_frame && f < pre.next.n;
-        const ArgBuilder fb = call.builder(ctx, own_next ? &pre.next.plan[f] : &ctx->plan, own_next ? &pre.next.prm[f] : &ctx->prm);
+        const ArgBuilder fb = call.builder(ctx, own_next ? &pre.next.plan[f] : Call::next_shared_plan(ctx), own_next ? &pre.next.prm[f] : &ctx->prm);
         build_call_args(fa, fb, call.shape, list, &stage[f]);
     }
     lease->arm();      // from here on every exit of this call hands the slot back guarded
@@ -466,17 +475,19 @@ int run_batch(meao_ctx *ctx, Call &call)
     // A previous call may already have downsampled exactly these frames (meao_prefetch_batch): the ready set is consumed either way.
     call.shape = BatchShape{};
     call.shape.frames = call.n;
-    call.shape.prefetched = pre.matches(call.n, call.depth_dev, call.stream, call.depth_pitch, call.exact != 0, call.prm_of, ctx->cfg.depth_format);
+    call.shape.prefetched = pre.matches(call.n, call.depth_dev, call.stream, call.depth_pitch, call.exact != 0, call.prm_of, ctx->cfg.depth_format,
+                                        ctx->cfg.width, ctx->cfg.height);
     pre.begin_call(call.shape.prefetched);
     int rc = settle_composite(ctx, &call);
     if (rc != MEAO_OK) return rc;
 
     const ArgBuilder args = call.builder(ctx, &ctx->plan, &ctx->prm);
-    decide_announced_pass(ctx, args, &call);
+    const ArgBuilder next = call.builder(ctx, Call::next_shared_plan(ctx), &ctx->prm);
+    decide_announced_pass(ctx, args, next, &call);
     const LaunchList list = plan_launches(ctx->cfg, ctx->plan, ctx->tuning, call.shape);
 
     FrameArgs shared{};
-    build_call_args(args, args, call.shape, list, &shared);
+    build_call_args(args, next, call.shape, list, &shared);
     const FrameArgs *pf = nullptr;
     TableRing<FrameArgs, 8>::Lease lease;
     if (call.per_frame && (rc = build_frame_table(ctx, call, list, &lease, &pf)) != MEAO_OK) return rc;
@@ -484,19 +495,22 @@ int run_batch(meao_ctx *ctx, Call &call)
     rc = submit_launches(ctx, list, shared, pf, call.n, call.stream);
     if (rc != MEAO_OK) return rc;
 
-    if (call.shape.next != 0) pre.promote(call.stream, call.exact != 0, ctx->prm);
+    if (call.shape.next != 0) pre.promote(call.stream, call.exact != 0, ctx->prm, ctx->cfg.width, ctx->cfg.height);
     record_last_call(ctx, call);
     return MEAO_OK;
 }
 
-// meao_prefetch_batch_params / _pitched: params[] checked where n is in range (an n out of range is refused by the announcement itself)
+// meao_prefetch_batch_params / _pitched / _sized: params[] checked where n is in range (an n out of range is refused by the announcement itself)
+int fs_params_checked(meao_ctx *ctx, const char *fn, int32_t n, const meao_params *params)
+{
+    if (params && n >= 1 && n <= ctx->cfg.max_batch) return validate_frame_params(ctx, n, params, fn);
+    return MEAO_OK;
+}
+
 int checked_prefetch(meao_ctx *ctx, const char *fn, const FrameSet &fs)
 {
-    if (fs.params && fs.n >= 1 && fs.n <= ctx->cfg.max_batch) {
-        const int rc = validate_frame_params(ctx, fs.n, fs.params, fn);
-        if (rc != MEAO_OK) return rc;
-    }
-    return prefetch_batch_internal(ctx, fs);
+    const int rc = fs_params_checked(ctx, fn, fs.n, fs.params);
+    return rc != MEAO_OK ? rc : prefetch_batch_internal(ctx, fs);
 }
 
 }  // namespace
@@ -517,8 +531,13 @@ int meao::validate_frame_params(meao_ctx *ctx, int32_t n, const meao_params *par
 // offset (the frame's last texel ends at most 2^32 - 1 bytes after its origin).
 int meao::pitch_texels(meao_ctx *ctx, uint64_t pitch, uint64_t elem, const char *what, int32_t *out)
 {
-    const uint64_t w = static_cast<uint64_t>(ctx->cfg.width), h = static_cast<uint64_t>(ctx->cfg.height);
-    if (pitch == 0) { *out = ctx->cfg.width; return MEAO_OK; }
+    return pitch_texels_of(ctx, ctx->cfg.width, ctx->cfg.height, pitch, elem, what, out);
+}
+
+int meao::pitch_texels_of(meao_ctx *ctx, int32_t width, int32_t height, uint64_t pitch, uint64_t elem, const char *what, int32_t *out)
+{
+    const uint64_t w = static_cast<uint64_t>(width), h = static_cast<uint64_t>(height);
+    if (pitch == 0) { *out = width; return MEAO_OK; }
     if (pitch < w * elem) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(what) + ": smaller than a row (width x element size)");
     if (pitch % elem != 0) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(what) + ": not a multiple of the element size");
     if (pitch / elem >= (1ull << 24)) return fail(ctx, MEAO_ERR_UNSUPPORTED, std::string(what) + ": 2^24 texels or more");
@@ -604,29 +623,38 @@ int meao::execute_batch_internal(meao_ctx *ctx, const FrameSet &fs, meao_stream 
             if (out_packed) MEAO_HIP(ctx, hipMemcpyAsync(fs.out[f], out_dev[f], out_bytes, hipMemcpyDeviceToHost, stream));
             else MEAO_HIP(ctx, hipMemcpy2DAsync(fs.out[f], fs.out_pitch, out_dev[f], out_row, out_row, c.height, hipMemcpyDeviceToHost, stream));
         }
-    if (wait_for_host && (fs.out_loc == MEAO_MEM_HOST || fs.depth_loc == MEAO_MEM_HOST)) MEAO_HIP(ctx, hipStreamSynchronize(stream));
+    if (wait_for_host && (fs.out_loc == MEAO_MEM_HOST || fs.depth_loc == MEAO_MEM_HOST)) {
+        note_sync(ctx);
+        MEAO_HIP(ctx, hipStreamSynchronize(stream));
+    }
     return MEAO_OK;
 }
 
-int meao::prefetch_batch_internal(meao_ctx *ctx, const FrameSet &fs)
+int meao::prefetch_batch_internal(meao_ctx *ctx, const FrameSet &fs, int32_t width, int32_t height)
 {
     if (!ctx || !fs.depth) return MEAO_ERR_INVALID_ARGUMENT;
+    const bool sized = (width != 0 || height != 0) && !(width == ctx->cfg.width && height == ctx->cfg.height);
+    if (sized && !(width >= 1 && height >= 1 && ctx->within_reservation(width, height)))
+        return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_prefetch_batch_sized: width/height: not inside the context's reservation (meao_reserve)");
+    if (!sized) { width = ctx->cfg.width; height = ctx->cfg.height; }
     if (fs.n < 1 || fs.n > ctx->cfg.max_batch) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_prefetch_batch: n must be 1..max_batch");
     for (int f = 0; f < fs.n; ++f)
         if (!fs.depth[f]) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_prefetch_batch: null frame pointer");
     int32_t rows = 0;
-    int rc = pitch_texels(ctx, fs.depth_pitch, depth_elem(ctx->cfg.depth_format), "meao_prefetch_batch_pitched: depth_pitch", &rows);
+    int rc = pitch_texels_of(ctx, width, height, fs.depth_pitch, depth_elem(ctx->cfg.depth_format),
+                             sized ? "meao_prefetch_batch_sized: depth_pitch" : "meao_prefetch_batch_pitched: depth_pitch", &rows);
     if (rc != MEAO_OK) return rc;
     rc = use_device(ctx);
     if (rc != MEAO_OK) return rc;
     if (!ctx->two_ds_sets) {
         // Created without cfg.pipelined: the first announcement re-lays the slots out with a second
         // downsample set (device-wide synchronisation + allocation, once).  On failure the context is unchanged.
+        note_sync(ctx);
         MEAO_HIP(ctx, hipDeviceSynchronize());
-        rc = reallocate(ctx, ctx->cfg, true);
+        rc = reallocate(ctx, ctx->cfg, true, ctx->cap_w, ctx->cap_h);
         if (rc != MEAO_OK) return rc;
     }
-    ctx->prefetch.announce(ctx->cfg, fs.n, fs.depth, rows, fs.params);
+    ctx->prefetch.announce(ctx->cfg, width, height, sized, ctx->prm, fs.n, fs.depth, rows, fs.params);
     return MEAO_OK;
 }
 
@@ -675,6 +703,16 @@ int32_t meao_prefetch_batch_pitched(meao_ctx *ctx, int32_t n, const void *const 
 {
     if (!ctx || !depth) return MEAO_ERR_INVALID_ARGUMENT;
     return checked_prefetch(ctx, "meao_prefetch_batch_pitched", FrameSet{n, depth, depth_pitch, MEAO_MEM_DEVICE, nullptr, 0, MEAO_MEM_DEVICE, params});
+}
+
+int32_t meao_prefetch_batch_sized(meao_ctx *ctx, int32_t width, int32_t height, int32_t n, const void *const *depth, uint64_t depth_pitch,
+                                  const meao_params *params)
+{
+    if (!ctx || !depth) return MEAO_ERR_INVALID_ARGUMENT;
+    if (width < 1 || height < 1) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_prefetch_batch_sized: width/height must be at least 1");
+    const int rc = fs_params_checked(ctx, "meao_prefetch_batch_sized", n, params);
+    if (rc != MEAO_OK) return rc;
+    return prefetch_batch_internal(ctx, FrameSet{n, depth, depth_pitch, MEAO_MEM_DEVICE, nullptr, 0, MEAO_MEM_DEVICE, params}, width, height);
 }
 
 }  // extern "C"

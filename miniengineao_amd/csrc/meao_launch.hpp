@@ -3,7 +3,13 @@
 // exist to keep the device code of the kernel families apart; every selection rule is written here, once.
 #pragma once
 
+// A host unit of the C ABI layer (meao_execute.cpp) defines MEAO_LAUNCH_RULES_ONLY in front of this header: it gets the rules
+// that are plain functions of the argument blocks and none of the device headers (its translation unit holds no device code).
+#ifdef MEAO_LAUNCH_RULES_ONLY
+#include "meao_kernels.hpp"
+#else
 #include "meao_dev.hpp"
+#endif
 
 namespace meao {
 
@@ -58,6 +64,17 @@ hipError_t launch_upsample_final_with_downsample_linear(const UpsampleArgs &a, c
                                                         const DownsampleArgs *pf_d);
 hipError_t launch_linear_depth_view(const LinearDepthArgs &a, hipStream_t s);     // LinearDepth (debug id 1) of the linear formats
 
+// The announced next batch's downsample pass (meao_prefetch_batch*): inside the last kernel of the carrying call, or as a launch
+// of its own behind it.  `d` is the pass tiled for the lean tile, with the extents of the ANNOUNCED frames, which need not be
+// those of the call (meao_prefetch_batch_sized): the carrying kernel takes the pass's geometry from `d` alone, so all it needs
+// is f32 depth on both sides, the 16-byte loads (width % 8 == 0, aligned frames and pitch) and a workgroup of `a`'s grid for every
+// tile of `d` -- a pass of a larger size than the call's does not fit and runs as its own launch.  own_launch:
+// MEAO_DEBUG_NEXT_DOWNSAMPLE_OWN_LAUNCH.
+inline bool carried_in_last_kernel(const UpsampleArgs &a, const HiDepthArgs &hi, const DownsampleArgs &d, int frames, bool own_launch)
+{
+    return !own_launch && fused_downsample_applicable(a, hi, d, frames);
+}
+
 // ---------------------------------------------------------------------------------------
 // Argument checks (a launcher that fails one returns hipErrorInvalidValue and launches nothing)
 
@@ -68,6 +85,7 @@ inline bool final_strides_set(const UpsampleArgs &a) { return a.pitch.depth >= a
 // the per-frame sources of a launch with several argument blocks: all of them, or none
 inline bool all_or_none(const void *pf, const void *pf_hi, const void *pf_d) { return (pf && pf_hi && pf_d) || !(pf || pf_hi || pf_d); }
 
+#ifndef MEAO_LAUNCH_RULES_ONLY
 namespace {
 
 // ---------------------------------------------------------------------------------------
@@ -143,4 +161,5 @@ void for_final_variant(const UpsampleArgs &a, const HiDepthArgs &hi, Launch &&la
 }
 
 }  // namespace
+#endif  // MEAO_LAUNCH_RULES_ONLY
 }  // namespace meao

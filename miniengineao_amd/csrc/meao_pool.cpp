@@ -447,8 +447,9 @@ int32_t meao_pool_execute_batch_pitched(meao_pool *p, int32_t n, const void *con
     return pool_execute_batch(p, meao::FrameSet{n, depth, depth_pitch, depth_loc, ao_out, ao_pitch, out_loc, params});
 }
 
-// fs: n, depth, depth_pitch and params of the announcement (params[] already checked).
-static int32_t pool_prefetch_batch(meao_pool *p, const meao::FrameSet &fs)
+// fs: n, depth, depth_pitch and params of the announcement (params[] already checked).  width x height: the announced frames'
+// size (meao_pool_prefetch_batch_sized), 0 x 0 = the members'.
+static int32_t pool_prefetch_batch(meao_pool *p, const meao::FrameSet &fs, int32_t width = 0, int32_t height = 0)
 {
     if (!p || !fs.depth) return MEAO_ERR_INVALID_ARGUMENT;
     const int32_t G = static_cast<int32_t>(p->ctx.size()), n = fs.n;
@@ -464,7 +465,7 @@ static int32_t pool_prefetch_batch(meao_pool *p, const meao::FrameSet &fs)
         const meao::FrameSet share = fs.share(m, G, &mine);
         if (share.n == 0) return MEAO_OK;
         if (hipSetDevice(p->device[m]) != hipSuccess) { (void)hipGetLastError(); set_device_failed = true; return MEAO_ERR_HIP; }
-        return meao::prefetch_batch_internal(p->ctx[m], share);
+        return meao::prefetch_batch_internal(p->ctx[m], share, width, height);
     }, false, &failed);
     if (status != MEAO_OK)       // (a failed hipSetDevice never reached the context: its last error would name an older failure)
         return pool_fail(p, status, std::string("meao_pool_prefetch_batch: member ") + std::to_string(failed) + ": " +
@@ -494,6 +495,51 @@ int32_t meao_pool_prefetch_batch_pitched(meao_pool *p, int32_t n, const void *co
     const int32_t rc = pool_check_call(p, "meao_pool_prefetch_batch_pitched", n, params);
     if (rc != MEAO_OK) return rc;
     return pool_prefetch_batch(p, meao::FrameSet{n, depth, depth_pitch, MEAO_MEM_DEVICE, nullptr, 0, MEAO_MEM_DEVICE, params});
+}
+
+int32_t meao_pool_prefetch_batch_sized(meao_pool *p, int32_t width, int32_t height, int32_t n, const void *const *depth, uint64_t depth_pitch,
+                                       const meao_params *params)
+{
+    if (!p || !depth) return MEAO_ERR_INVALID_ARGUMENT;
+    if (width < 1 || height < 1) return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, "meao_pool_prefetch_batch_sized: width/height must be at least 1");
+    const int32_t rc = pool_check_call(p, "meao_pool_prefetch_batch_sized", n, params);
+    if (rc != MEAO_OK) return rc;
+    return pool_prefetch_batch(p, meao::FrameSet{n, depth, depth_pitch, MEAO_MEM_DEVICE, nullptr, 0, MEAO_MEM_DEVICE, params}, width, height);
+}
+
+// Member by member, on the calling thread (every worker has handed its context back: a pool call returns only after all of
+// them have).  A member that fails keeps what it had; the members before it keep the larger reservation, which changes no result.
+int32_t meao_pool_reserve(meao_pool *p, int32_t max_width, int32_t max_height)
+{
+    if (!p) return MEAO_ERR_INVALID_ARGUMENT;
+    DeviceGuard guard;
+    for (size_t m = 0; m < p->ctx.size(); ++m) {
+        const int32_t rc = meao_reserve(p->ctx[m], max_width, max_height);
+        if (rc != MEAO_OK)
+            return pool_fail(p, rc, std::string("meao_pool_reserve: member ") + std::to_string(m) + ": " + meao_last_error(p->ctx[m]));
+    }
+    return MEAO_OK;
+}
+
+// Only for sizes every member's reservation covers, checked for all of them first: then no member's meao_resize allocates,
+// synchronises or can fail half-way through the pool.  The workers are idle here -- every pool call waits on the host for its
+// workers to finish ENQUEUING (for_each_member), which is no device synchronisation.
+int32_t meao_pool_resize(meao_pool *p, int32_t width, int32_t height)
+{
+    if (!p) return MEAO_ERR_INVALID_ARGUMENT;
+    if (!meao::size_valid(width, height)) return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, "meao_pool_resize: width/height out of range [1, 32768]");
+    for (size_t m = 0; m < p->ctx.size(); ++m)
+        if (!p->ctx[m]->within_reservation(width, height))
+            return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, std::string("meao_pool_resize: member ") + std::to_string(m) +
+                                                               ": width/height not inside its reservation (meao_pool_reserve)");
+    DeviceGuard guard;
+    for (size_t m = 0; m < p->ctx.size(); ++m) {
+        const int32_t rc = meao_resize(p->ctx[m], width, height);
+        if (rc != MEAO_OK)       // (only a waiting composite batch launches anything here, and only a failed launch fails)
+            return pool_fail(p, rc, std::string("meao_pool_resize: member ") + std::to_string(m) + ": " + meao_last_error(p->ctx[m]));
+    }
+    p->out_bytes = static_cast<uint64_t>(width) * height * meao::ao_elem(p->ctx[0]->cfg);
+    return MEAO_OK;
 }
 
 // Every member's share is validated (both halves) before any member enqueues; then each member that is dealt frames runs its
