@@ -228,7 +228,8 @@ MEAO_API int32_t meao_resize(meao_ctx *ctx, int32_t width, int32_t height);
  * meao_reserve sizes the context's intermediates for max_width x max_height -- the arena for max_batch slots, with the second
  * downsample set where the context has one.  It may allocate and synchronises the device once, like meao_resize; it changes no
  * result.  The reservation must cover the current size in both dimensions (else MEAO_ERR_INVALID_ARGUMENT); (0, 0) drops it and
- * returns the context to the exact fit.  On success a ready prefetched set and an announcement are dropped (the buffers moved);
+ * returns the context to the exact fit.  On success a ready prefetched set and an announcement are dropped (the buffers moved)
+ * and the debug state of the last call is gone as after a resize -- also when the reservation asked for is the one it has;
  * on failure the context is exactly as it was: geometry, buffers, reservation, a ready prefetch; a waiting composite batch stays
  * waiting either way.  meao_get_capacity reports the reservation, (0, 0) = none.  meao_reserve_bytes is host-plan only, like
  * meao_describe_buffer (cfg.width / height are validated but not used): the device memory a reservation of that size costs,
@@ -345,9 +346,11 @@ MEAO_API int32_t meao_prefetch_batch_pitched(meao_ctx *ctx, int32_t n, const voi
  * tiles fit that kernel's grid (ceil(w / 128) x ceil(h / 32) announced against ceil(W / 64) x ceil(H / 64) current tiles), else
  * as one more launch behind it; host code decides, no kernel knows.  meao_resize(width, height) KEEPS an announcement or a ready
  * set made by this call for exactly the new size and drops any other -- also every one made by the other meao_prefetch_batch*
- * calls, as ever.  The consuming execute matches on the size as well: a host that announces one size and executes at another
- * gets a correct result from a pass of its own.  With width x height equal to the current size the call IS
- * meao_prefetch_batch_pitched.  The frame loop of a host that scales its resolution:
+ * calls, as ever.  What it keeps is from then on an ordinary announcement or ready set of the context's size: the next resize,
+ * also one to the same size, drops it.  The consuming execute matches on the size as well (where the sizes differ the pitches
+ * are not compared): a host that announces one size and executes at another gets a correct result from a pass of its own.
+ * With width x height equal to the current size the call IS meao_prefetch_batch_pitched.  The frame loop of a host that scales
+ * its resolution:
  *   meao_prefetch_batch_sized(B, frames k+1) -> meao_execute*(frames k, at A) -> meao_resize(B) -> meao_execute*(frames k+1)
  * never leaves the pipelined form. */
 MEAO_API int32_t meao_prefetch_batch_sized(meao_ctx *ctx, int32_t width, int32_t height, int32_t n, const void *const *depth,
@@ -592,7 +595,7 @@ MEAO_API int32_t meao_pool_prefetch_batch_pitched(meao_pool *pool, int32_t n, co
  * checked for every member before any member is touched.  It waits on the host until each worker has finished enqueuing the jobs
  * it was handed (no device synchronisation) and then resizes every member inside its reservation: no allocation, no
  * synchronisation.  meao_pool_gather_to_device copies frames of the new size afterwards.  meao_pool_prefetch_batch_sized: the sized
- * announcement, dealt frame f -> member f mod G like every pool call. */
+ * announcement, dealt frame f -> member f mod G like every pool call; meao_pool_resize keeps or drops it in every member alike. */
 MEAO_API int32_t meao_pool_reserve(meao_pool *pool, int32_t max_width, int32_t max_height);
 MEAO_API int32_t meao_pool_resize(meao_pool *pool, int32_t width, int32_t height);
 MEAO_API int32_t meao_pool_prefetch_batch_sized(meao_pool *pool, int32_t width, int32_t height, int32_t n, const void *const *depth,

@@ -15,6 +15,14 @@ What the header leaves to interpretation and this model fixes (DESIGN.md section
     params[], or one that carries an announcement made with params[].
   * "plain composite launches" are one launch per frame, as meao_composite is.
   * A HOST depth call is staged into context memory, so it never matches a ready set (another pointer); it still carries.
+  * meao_reserve, when it succeeds, leaves nothing "as left by the last execute": the buffers moved, so meao_get_intermediate
+    refuses until the next execute, as after a resize -- also when the reservation is the one the context had, or (0, 0) drops none.
+  * The size is a component of the reuse key, and where it differs the pitch is not compared: a row stride of another width says
+    nothing.  (Pitch option 3 gives two sizes one stride, so that the size is then the ONLY difference.)
+  * What a resize keeps is from then on an ordinary announcement / ready set of the context's size: a second resize drops it, also
+    one to the size the context has.  A resize to the current size is a resize like any other: it keeps nothing, since a sized
+    announcement is by definition for another size.
+  * A pool's announcement (announced_n) lives exactly as long as its members' shares: meao_pool_resize keeps or drops it whole.
 """
 from __future__ import annotations
 
@@ -26,8 +34,16 @@ from typing import Dict, List, Optional, Tuple
 
 RING = 8                                           # meao.h: "a ring of 8 slots"
 OK, ERR_INVALID_ARGUMENT = 0, -1
-KEY_COMPONENTS = ("pointer", "n", "stream", "pitch", "zb", "exact")
+KEY_COMPONENTS = ("size", "pointer", "n", "stream", "pitch", "zb", "exact")
 PITCH_EXTRA = (0, 8, 5)                            # pitch option -> texels beyond the row: packed, 4-texel vectors possible, scalar only
+PITCH_FIXED = 408                                  # pitch option 3: this row stride whatever the width (a viewport of changing size in
+#                                                    one allocation): a frame announced at one size and asked for at another then
+#                                                    differs from the ready set in its size ALONE
+
+
+def row_texels(option: int, width: int) -> int:
+    """Row stride in texels of a surface of `width` under a pitch option."""
+    return PITCH_FIXED if option == 3 else width + PITCH_EXTRA[option]
 
 
 def f32(x: float) -> float:
@@ -55,6 +71,8 @@ class Announcement:
     bufs: Tuple[int, ...]
     pitch: int                                  # row stride in texels (packed = width)
     params: Optional[Tuple[Param, ...]]         # None: the context's parameters at the time of the carrying call
+    sized: bool = False                         # meao_prefetch_batch_sized for another size than the context's
+    size: Tuple[int, int] = (0, 0)              # of the announced frames
 
 
 @dataclass(frozen=True)
@@ -64,6 +82,9 @@ class ReadySet:
     pitch: int
     zb: Tuple[tuple, ...]
     exact: bool                                 # the carrying call divided exactly (it stamped the hostile flags)
+    sized: bool = False                         # it came from a sized announcement: a resize to its size keeps it
+    size: Tuple[int, int] = (0, 0)              # of the frames its levels were built from
+    kept: bool = False                          # a resize kept it
 
 
 @dataclass(frozen=True)
@@ -93,7 +114,9 @@ class LastCall:
 
 @dataclass
 class Op:
-    """One host action.  kind: prefetch | execute | set_params | resize | comp_enqueue | comp_flush | debug_set | refill | invalid."""
+    """One host action.  kind: prefetch | execute | set_params | resize | reserve | comp_enqueue | comp_flush | debug_set | refill |
+    invalid.  `size` is the new size of a resize, the reservation of a reserve ((0, 0) drops it), the announced size of a prefetch
+    (None: the context's, the ordinary announcement) and the size of the frames a refill lays out (None: the context's)."""
     kind: str
     bufs: Tuple[int, ...] = ()
     outs: Tuple[int, ...] = ()
@@ -104,14 +127,14 @@ class Op:
     out_host: bool = False
     stream: int = 0
     param: Optional[Param] = None               # set_params
-    size: Optional[Tuple[int, int]] = None      # resize
+    size: Optional[Tuple[int, int]] = None      # resize, reserve, prefetch, refill (see above)
     mode: int = 0                               # comp_enqueue
     colors: Tuple[int, ...] = ()
     key: int = 0                                # debug_set
     value: int = 0
     contents: Tuple[tuple, ...] = ()            # refill: one content key per buffer of bufs
-    what: str = ""                              # invalid: bad_pitch | n_zero | n_over | bad_params | null_pointer
-    on: str = ""                                # invalid: execute | prefetch
+    what: str = ""                              # invalid: bad_pitch | n_zero | n_over | bad_params | null_pointer | SIZED_INVALID
+    on: str = ""                                # invalid: execute | prefetch | reserve | resize
     read_debug: bool = False                    # stepped mode: compare debug buffers after this execute
 
 
@@ -134,11 +157,19 @@ class Expect:
     events: List[str] = field(default_factory=list)   # coverage classes (tests/test_call_model.py)
 
 
+# the invalid calls of dynamic resolution (Op.what); Op.on says which call makes them
+SIZED_INVALID = ("sized_outside_reservation", "sized_without_reservation", "sized_bad_pitch", "reserve_below_current",
+                 "pool_resize_uncovered")
+
+
 class ContextModel:
-    def __init__(self, width, height, max_batch, param: Param, *, linear=False, rtz=True, pipelined=True, exhaustive=False):
+    def __init__(self, width, height, max_batch, param: Param, *, linear=False, rtz=True, pipelined=True, exhaustive=False,
+                 cap=(0, 0)):
         self.width, self.height, self.max_batch = width, height, max_batch
         self.param, self.linear, self.rtz, self.exhaustive = param, linear, rtz, exhaustive
         self.two_sets = pipelined
+        self.cap: Tuple[int, int] = tuple(cap)      # the reservation (meao_get_capacity); (0, 0): none
+        self.dropped: Optional[ReadySet] = None     # coverage only: the ready set a resize dropped since the last call
         self.ann: Optional[Announcement] = None
         self.ready: Optional[ReadySet] = None
         self.comp: Optional[Composite] = None
@@ -147,11 +178,16 @@ class ContextModel:
         self.last_intact = False                    # the depth frames of the last call have not been refilled since
         self.contents: Dict[int, tuple] = {}        # the host's side of the contract: what each depth buffer holds
         self.fresh: set = set()                     # buffers refilled since a call last read them
-        self.totals = {"own": 0, "carried": 0, "reused": 0, "comp_carried_launches": 0, "comp_plain_launches": 0, "per_frame": 0, "carried_more": 0}
+        self.totals = {"own": 0, "carried": 0, "reused": 0, "comp_carried_launches": 0, "comp_plain_launches": 0, "per_frame": 0, "carried_more": 0,
+                       "carried_sized": 0, "kept_by_resize": 0}
 
     # ---- helpers
-    def pitch_texels(self, option: int) -> int:
-        return self.width + PITCH_EXTRA[option]
+    def pitch_texels(self, option: int, width=None) -> int:
+        return row_texels(option, self.width if width is None else width)
+
+    def within(self, w, h) -> bool:
+        """'a size inside the reservation (both dimensions)'; without a reservation nothing is."""
+        return self.cap != (0, 0) and w <= self.cap[0] and h <= self.cap[1]
 
     def _exact(self, params) -> bool:
         return self.rtz and all(p.exact for p in params)
@@ -196,6 +232,21 @@ class ContextModel:
         """The documented status, nothing launched, state unchanged."""
         status = ERR_INVALID_ARGUMENT
         e = self._expect(status=status)
+        if op.what in SIZED_INVALID:                 # the generator's claim that the call is invalid, held to the rule it names
+            cur = (self.width, self.height)
+            if op.what == "sized_without_reservation":
+                assert self.cap == (0, 0) and tuple(op.size) != cur, op
+            elif op.what == "sized_outside_reservation":
+                assert self.cap != (0, 0) and not self.within(*op.size), op
+            elif op.what == "sized_bad_pitch":       # the pitch is the only thing wrong with it
+                assert self.within(*op.size) and tuple(op.size) != cur, op
+            elif op.what == "reserve_below_current":
+                assert self.reserve(*op.size).status == ERR_INVALID_ARGUMENT, op
+            elif op.what == "pool_resize_uncovered":
+                assert not self.within(*op.size), op
+            e.events.append("invalid_" + op.what)
+            if self.ann is not None and self.ann.sized:
+                e.events.append("invalid_while_sized_announced")
         if self.ann is not None:
             e.events.append("invalid_while_announced")
         if self.comp is not None:
@@ -204,17 +255,39 @@ class ContextModel:
             e.events.append("debug_read_after_invalid")
         return e
 
-    def prefetch(self, bufs, params=None, pitch=0) -> Expect:
+    def prefetch(self, bufs, params=None, pitch=0, size=None, pitch_texels=None) -> Expect:
+        """size: meao_prefetch_batch_sized.  pitch_texels: a row stride given outright instead of a pitch option (the model's own
+        tests; the sequences name their one illegal stride by Op.what)."""
+        cur = (self.width, self.height)
+        sized = size is not None and tuple(size) != cur      # "with width x height equal to the current size the call IS ..._pitched"
+        w, h = tuple(size) if sized else cur
+        if sized and not self.within(w, h):
+            return self._expect(status=ERR_INVALID_ARGUMENT)
+        rows = self.pitch_texels(pitch, w) if pitch_texels is None else pitch_texels
+        if rows < w:                                  # "depth_pitch is validated against the ANNOUNCED size"
+            return self._expect(status=ERR_INVALID_ARGUMENT)
         e = Expect()
         if not self.two_sets:
             self.two_sets = True                 # re-allocates: geometry unchanged, everything "as left by the last execute" gone
-            e.reallocated = True
+            e.reallocated = True                 # (and the reservation unchanged: self.cap is not touched)
             e.events.append("first_announcement_reallocates")
+            if sized:
+                e.events.append("sized_first_announcement_reallocates")
             self.last = None
             self.ready = None
         if self.ann is not None:
             e.events.append("announcement_replaced")
-        self.ann = Announcement(tuple(bufs), self.pitch_texels(pitch), None if params is None else tuple(params))
+        if sized:
+            e.events.append("sized_announcement")
+            if params is not None:
+                e.events.append("sized_per_frame")
+            if rows != w:
+                e.events.append("sized_pitched")
+            if rows < self.width:
+                e.events.append("sized_pitch_below_current_width")
+            if self.comp is not None:
+                e.events.append("sized_announced_while_composite")
+        self.ann = Announcement(tuple(bufs), rows, None if params is None else tuple(params), sized, (w, h))
         e.comp_pending = len(self.comp.ao) if self.comp else 0
         e.last_valid = self.last is not None
         return e
@@ -225,6 +298,7 @@ class ContextModel:
         prm = tuple(params) if params is not None else (self.param,) * n
         exact = self._exact(prm)
         depth_pitch = self.width if depth_host else self.pitch_texels(pitch)      # HOST frames are staged packed
+        assert depth_pitch >= self.width, "illegal sequence: a row stride below the width"
         e = Expect(launched=True, exact=exact)
         for b in bufs:
             if b in self.fresh:
@@ -232,26 +306,40 @@ class ContextModel:
                 break
 
         # own pass iff the ready set does not match in EVERY key component; the ready set is gone either way
-        r = self.ready
-        if r is not None:
+        def differs(r):
             m = min(n, len(r.bufs))
             diff = []
+            other_size = r.size != (self.width, self.height)
+            if other_size:                          # "the consuming execute matches on the size as well"
+                diff.append("size")
             if depth_host or tuple(bufs[:m]) != r.bufs[:m]:
                 diff.append("pointer")
             if n != len(r.bufs):
                 diff.append("n")
             if stream != r.stream:
                 diff.append("stream")
-            if depth_pitch != r.pitch:
+            if depth_pitch != r.pitch and not other_size:      # (a row stride of another width says nothing: "size" stands for it)
                 diff.append("pitch")
             if tuple(p.zb(self.linear) for p in prm[:m]) != r.zb[:m]:
                 diff.append("zb")
             if exact and not r.exact:
                 diff.append("exact")
+            return diff, other_size
+
+        r = self.ready
+        if r is None and self.dropped is not None and not differs(self.dropped)[0]:
+            e.events.append("asked_for_what_a_resize_dropped")      # exactly what a ready set that outlived the resize would serve
+        self.dropped = None
+        if r is not None:
+            diff, other_size = differs(r)
             e.refused = tuple(diff)
             e.reused = not diff
+            if other_size and depth_pitch == r.pitch:
+                e.events.append("other_size_same_stride")
             if e.reused:
                 e.events.append("reuse")
+                if r.kept:
+                    e.events.append("reuse_of_kept_sized_ready" if self.ann is None else "reuse_of_kept_sized_ready_while_carrying")
             elif len(diff) == 1:
                 e.events.append("refused_" + diff[0])
         elif (self.last is not None and self.last.had_ready and not depth_host and not self.last.depth_host
@@ -266,11 +354,18 @@ class ContextModel:
         if a is not None:
             e.carried = a
             aprm = a.params if a.params is not None else (self.param,) * len(a.bufs)
-            self.ready = ReadySet(a.bufs, stream, a.pitch, tuple(p.zb(self.linear) for p in aprm), exact)
+            # (an announcement that is not sized is for the context's size, whatever that was when it was made: no resize keeps it)
+            self.ready = ReadySet(a.bufs, stream, a.pitch, tuple(p.zb(self.linear) for p in aprm), exact, a.sized,
+                                  a.size if a.sized else (self.width, self.height))
             self.ann = None
+            if a.sized:
+                self.totals["carried_sized"] += 1
+                e.events.append("sized_carried")
             if len(a.bufs) > n:
                 self.totals["carried_more"] += 1
                 e.events.append("announced_more_than_carrier")
+                if a.sized:
+                    e.events.append("sized_announced_more_than_carrier")
             elif len(a.bufs) < n:
                 e.events.append("announced_fewer_than_carrier")
         if e.per_frame:
@@ -306,7 +401,7 @@ class ContextModel:
             e.events.append("ready_dropped_by_set_params")
         if self.readable() and self.last.shared and param != self.param:
             e.events.append("debug_read_after_set_params")     # the last call's parameters are no longer the context's
-        self.param, self.ann, self.ready = param, None, None
+        self.param, self.ann, self.ready, self.dropped = param, None, None, None
         e.comp_pending = len(self.comp.ao) if self.comp else 0
         e.last_valid = self.last is not None
         return e
@@ -315,12 +410,58 @@ class ContextModel:
         e = Expect()
         if self.comp is not None:
             self._run_comp_plain(e, "resize")       # at the old size, on the stream that produced its AO
-        if self.ann is not None:
-            e.events.append("announcement_dropped_by_resize")
-        if self.ready is not None:
-            e.events.append("ready_dropped_by_resize")
+        inside = self.within(width, height)
+        if (width, height) == (self.width, self.height) and (self.ann is not None or self.ready is not None):
+            e.events.append("resize_to_current_size")          # a resize like any other: nothing can have been made for it
+        keep = lambda x: inside and x is not None and x.sized and x.size == (width, height)       # noqa: E731
+        for what, x in (("announcement", self.ann), ("ready", self.ready)):
+            if x is None:
+                continue
+            if keep(x):
+                e.events.append("sized_%s_kept_by_resize" % what)
+                self.totals["kept_by_resize"] += 1
+                if e.comp_plain:
+                    e.events.append("comp_flushed_and_sized_kept")
+                continue
+            e.events.append(what + "_dropped_by_resize")
+            if inside:
+                e.events.append(("sized_%s_dropped_other_size" if x.sized else "unsized_%s_dropped_by_resize_inside") % what)
+                if not x.sized:
+                    e.events.append("unsized_dropped_by_resize_inside")
+            elif x.sized:
+                e.events.append("sized_dropped_by_resize_outside")
+        if self.ready is not None and not keep(self.ready) and self.dropped is None:
+            self.dropped = self.ready
+        # a kept one is from now on an ordinary one for the context's size
+        self.ann = dataclasses.replace(self.ann, sized=False) if keep(self.ann) else None
+        self.ready = dataclasses.replace(self.ready, sized=False, kept=True) if keep(self.ready) else None
+        if self.cap != (0, 0) and not inside:       # "the reservation grows to the component-wise maximum"
+            self.cap = (max(self.cap[0], width), max(self.cap[1], height))
+            e.events.append("resize_grows_reservation")
         self.width, self.height = width, height
-        self.ann = self.ready = self.last = None
+        self.last = None
+        e.comp_pending = 0
+        return e
+
+    def reserve(self, width, height) -> Expect:
+        """meao_reserve.  (0, 0) drops the reservation; anything else must cover the current size."""
+        drop = (width, height) == (0, 0)
+        if not drop and (width < self.width or height < self.height):
+            return self._expect(status=ERR_INVALID_ARGUMENT)
+        e = Expect()
+        if self.ann is not None:
+            e.events.append("reserve_drops_announcement")
+        if self.ready is not None:
+            e.events.append("reserve_drops_ready")
+        if self.comp is not None:
+            e.events.append("reserve_keeps_composite")
+        if drop and self.cap != (0, 0):
+            e.events.append("reservation_dropped")
+            if self.ready is not None and self.ready.sized:
+                e.events.append("reservation_dropped_with_sized_ready")
+        self.cap = (width, height)
+        self.ann = self.ready = self.last = self.dropped = None     # the buffers moved: nothing "as left by the last execute" is left
+        e.comp_pending = len(self.comp.ao) if self.comp else 0
         return e
 
     def comp_enqueue(self, mode, ao, colors) -> Expect:
@@ -356,13 +497,19 @@ class ContextModel:
         if k == "refill":
             return self.refill(op.bufs, op.contents, op.pitch)
         if k == "prefetch":
-            return self.prefetch(op.bufs, op.params, op.pitch)
+            e = self.prefetch(op.bufs, op.params, op.pitch, op.size)
+            assert e.status == OK, ("illegal sequence: an announcement the library refuses", op)
+            return e
         if k == "execute":
             return self.execute(op.bufs, op.outs, op.params, op.pitch, op.out_pitch, op.depth_host, op.out_host, op.stream)
         if k == "set_params":
             return self.set_params(op.param)
         if k == "resize":
             return self.resize(*op.size)
+        if k == "reserve":
+            e = self.reserve(*op.size)
+            assert e.status == OK, ("illegal sequence: a reservation the library refuses", op)
+            return e
         if k == "comp_enqueue":
             return self.comp_enqueue(op.mode, op.bufs, op.colors)
         if k == "comp_flush":
@@ -427,8 +574,11 @@ class PoolModel:
             return [c._expect() for c in self.members]
         if k == "execute":
             n = len(op.bufs)
+            idle_sized = [c for c in self.members[n:] if (c.ann is not None and c.ann.sized) or (c.ready is not None and c.ready.sized)]
             out = self._deal(op, lambda c: c.drop_announcement(True))
             ev = out[0].events
+            if idle_sized:
+                ev.append("pool_idle_member_drops_sized")
             if any(b in self.fresh for b in op.bufs):
                 ev.append("refilled_before_call")
             self.fresh.difference_update(op.bufs)
@@ -450,9 +600,19 @@ class PoolModel:
             for e in out[1:]:
                 e.events = [x for x in e.events if x not in out[0].events]      # a coverage class counts once per pool call
             return out
-        if k == "set_params":
+        if k == "set_params" or k == "reserve":          # (a reservation covers every member's size or none's: they are one size)
             self.announced_n = None
-        return [c.apply(op) for c in self.members]      # set_params, comp_flush: every member
+        if k == "resize":
+            # "for sizes that EVERY member's reservation covers; anything else is MEAO_ERR_INVALID_ARGUMENT, checked for every
+            # member before any member is touched"
+            assert all(c.within(*op.size) for c in self.members), ("illegal sequence: a pool resize the library refuses", op)
+            out = [c.apply(op) for c in self.members]
+            if not any(c.ann is not None for c in self.members):
+                self.announced_n = None                   # the pool's announcement lives exactly as long as its members' shares
+            for e in out[1:]:
+                e.events = [x for x in e.events if x not in out[0].events]
+            return out
+        return [c.apply(op) for c in self.members]      # set_params, reserve, comp_flush: every member
 
 
 # ---- the generator -------------------------------------------------------------------------------------------------------------
@@ -490,10 +650,22 @@ class Profile:
     p_again: float = 0.2
     p_set_params_after: float = 0.1    # a shared call is followed by other parameters: debug reads must still show the call's
     p_inexact_carrier: float = 0.3     # a carrying call gets a parameter set outside the exact-division range
-
+    # dynamic resolution; the defaults draw nothing of it (and no random number for it: the older sequences stay as they are)
+    reserve: Optional[Tuple[int, int]] = None    # the reservation: the first operation of a stepped sequence, the state a
+    #                                              free-running one starts in (meao_reserve synchronises)
+    w_reserve: float = 0.0             # meao_reserve in mid-sequence: the same again, larger, (0, 0), or one below the current size
+    p_sized: float = 0.0               # share of announcements made for another size inside the reservation
+    p_sized_then_resize: float = 0.0   # a sized announcement is followed by execute and a resize to its size (the header's frame
+    #                                    loop), or by that resize at once
+    outside_sizes: Tuple[Tuple[int, int], ...] = ()   # sizes no reservation of the sequence covers at first: stepped resizes go there
 
 N_CONTENTS = 12                        # content keys are ("synth" | "hostile" | "hostile_level", seed < N_CONTENTS)
 DEBUG_KEYS = ((0, (0, 1)), (1, (0, 1024)), (2, (0, 256)), (3, (0, 2048)), (4, (0, 640)), (5, (0, 1, 4096)))   # meao_debug_key -> values
+
+
+def initial_cap(profile: Profile) -> Tuple[int, int]:
+    """The reservation a sequence of this profile starts under: a free-running one is reserved before its first operation."""
+    return tuple(profile.reserve) if profile.reserve and profile.free_running else (0, 0)
 
 
 def generate(seed: int, profile: Profile, palette: List[Param], start_param: Param, *, linear=False, rtz=True, pipelined=True):
@@ -510,10 +682,13 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
     bad = [p for p in palette if not p.valid]
     cap = P.max_batch * (G or 1)
     w, h = P.sizes[0]
-    kw = dict(linear=linear, rtz=rtz, pipelined=pipelined)
+    kw = dict(linear=linear, rtz=rtz, pipelined=pipelined, cap=initial_cap(P))
     model = PoolModel(G, w, h, P.max_batch, start_param, **kw) if G else ContextModel(w, h, P.max_batch, start_param, **kw)
+    one = model.members[0] if G else model         # the members of a pool are one size and hold one reservation
     ops: List[Op] = []
-    st = {"stream": 0, "next_out": 0, "promised": None, "announced": None, "last_exec": None, "flip": False}
+    st = {"stream": 0, "next_out": 0, "promised": None, "announced": None, "last_exec": None, "flip": False, "loop": None,
+          "uncovered": False}
+    laid: Dict[int, tuple] = {}                    # depth buffer -> (size, pitch option) of the frame it holds
 
     def emit(op):
         ops.append(op)
@@ -523,6 +698,12 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
         free = [b for b in range(P.n_depth) if b not in avoid]
         rng.shuffle(free)
         return tuple(free[:k])
+
+    def cur_size():
+        return (model.width, model.height)
+
+    def inside_sizes(other_than=None):
+        return [s for s in P.sizes if s != other_than and one.within(*s)]
 
     def draw_outs(k):
         if P.free_running:
@@ -540,16 +721,63 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
         kind = "hostile_level" if r < P.p_hostile * 0.6 else "hostile" if r < P.p_hostile else "synth"
         return (kind, rng.randrange(N_CONTENTS))
 
-    def maybe_refill(bufs, pitch):
-        sel = tuple(b for b in bufs if not model.referenced(b) and (b not in model.contents or rng.random() < P.p_refill))
+    def maybe_refill(bufs, pitch, size=None):
+        """size: the frames are announced at that size, and a buffer that does not hold a frame of it under this pitch gets one."""
+        sel = tuple(b for b in bufs if not model.referenced(b) and
+                    (b not in model.contents or (size is not None and laid.get(b) != (size, pitch)) or rng.random() < P.p_refill))
+        for b in sel:
+            laid[b] = (size or cur_size(), pitch)
         if sel:
-            emit(Op("refill", bufs=sel, contents=tuple(content() for _ in sel), pitch=pitch))   # laid out for the call it is for
+            emit(Op("refill", bufs=sel, contents=tuple(content() for _ in sel), pitch=pitch, size=size))   # laid out for the call it is for
 
     def pitch_option():
         return rng.choice((1, 2)) if rng.random() < P.p_pitched else 0
 
+    def sized_depth(k, size, pitch):
+        """Buffers that hold a frame of `size` under `pitch`, or may be given one now (the free-running pool fills a buffer once)."""
+        once = bool(G) and P.free_running
+        ok = [b for b in range(P.n_depth) if laid.get(b) == (size, pitch) or
+              (not model.referenced(b) and not (once and b in model.contents))]
+        rng.shuffle(ok)
+        return tuple(ok[:k])
+
+    def do_sized_prefetch(k):
+        """meao_prefetch_batch_sized for another size inside the reservation; False: there is none (or no buffer for it)."""
+        sizes = inside_sizes(other_than=cur_size())
+        if not sizes:
+            if one.cap == (0, 0):
+                if P.w_reserve and rng.random() < 0.5:
+                    do_reserve()
+                else:
+                    do_invalid("sized_without_reservation")
+            return False
+        size, pitch = rng.choice(sizes), pitch_option()
+        if rng.random() < 0.3 and max(size[0], model.width) <= PITCH_FIXED:
+            pitch = 3                                # one stride for both sizes
+        bufs = sized_depth(k, size, pitch)
+        if not bufs:
+            return False
+        maybe_refill(bufs, pitch, size)
+        prm = draw_params(len(bufs)) if rng.random() < P.p_per_frame else None
+        op = Op("prefetch", bufs=bufs, params=prm, pitch=pitch, size=size)
+        emit(op)
+        st["announced"] = op
+        r = rng.random()
+        if r < P.p_sized_then_resize:
+            if rng.random() < 0.35:
+                do_resize(to=size)                   # at once: the announcement itself is kept, and carried at its own size
+            else:
+                if rng.random() < 0.3:
+                    do_invalid()                     # an invalid call in between changes nothing
+                st["loop"] = size                    # the header's frame loop: execute at the old size, then the resize
+        elif r < P.p_sized_then_resize + P.p_ann_disturbed:
+            rng.choice((do_invalid, do_set_params, do_resize) + ((do_reserve,) if P.w_reserve else ()))()
+        return True
+
     def do_prefetch():
         k = rng.randint(1, cap)
+        if P.p_sized and rng.random() < P.p_sized and do_sized_prefetch(k):
+            return
         bufs = legal_depth(k)
         pitch = pitch_option()
         maybe_refill(bufs, pitch)
@@ -592,8 +820,12 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
         host_d = host_o = False
         promised = st["promised"]
         r = rng.random()
+        if st.pop("honour", False):
+            r = 0.0
         if promised is not None and r < P.p_honour + P.p_vary_one:
             bufs, prm, pitch = promised.bufs, promised.params, promised.pitch
+            if pitch == 3 and model.width > PITCH_FIXED:
+                pitch = 0
             if r >= P.p_honour:
                 bufs, prm, pitch, stream = vary_one(bufs, prm, pitch, stream)
         else:
@@ -624,6 +856,22 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
                 depth_host=host_d, out_host=host_o, stream=stream, read_debug=not P.free_running)
         emit(op)
         st.update(stream=stream, promised=st["announced"], announced=None, last_exec=op)
+        loop, st["loop"] = st["loop"], None
+        if loop is not None and any(c.ready is not None and c.ready.sized and c.ready.size == loop for c in (model.members if G else [model])):
+            if not op.out_host and op.out_pitch == 0 and rng.random() < 0.3:
+                do_comp_enqueue(1)                   # a composite waits across the resize: it runs plain, at the old size
+            others = inside_sizes(other_than=cur_size())
+            if len(others) > 1 and rng.random() < 0.12:
+                loop = rng.choice([s for s in others if s != loop])      # the host changed its mind: the set is for another size
+            do_resize(to=loop)                       # else the ready set the call left is for exactly this size: it stays
+            if st["promised"] is not None and rng.random() < 0.7:
+                st["honour"] = True
+                do_execute()                         # the frames of the new size, as announced: the loop is closed
+            return
+        if P.reserve and st["promised"] is not None and st["promised"].size is None and one.cap != (0, 0) and rng.random() < 0.3:
+            return do_resize()                       # an ordinary ready set and a resize: often one that ends at its size
+        if P.w_reserve and not G and model.ready is not None and model.ready.sized and rng.random() < 0.2:
+            return do_reserve(drop=True)             # (0, 0) while a sized ready set exists
         if prm is None and rng.random() < P.p_set_params_after:
             do_set_params(other_than=model.param)    # "as left by the last execute" is then not what the context holds
 
@@ -641,10 +889,36 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
         r = rng.random()                             # what ends a wait other than the next call
         if depth == 0 and r < P.p_comp_ended_early:
             ender = rng.choice([lambda: emit(Op("comp_flush")), lambda: do_comp_enqueue(1), do_invalid, do_invalid] +
-                               ([do_resize] if not G and not P.free_running else []))
+                               ([do_resize] if (not G and not P.free_running) or P.reserve else []) +
+                               ([do_reserve] if P.w_reserve else []))
             ender()
 
-    def do_invalid():
+    def sized_invalid(what):
+        """The invalid calls of dynamic resolution that the state allows now; None: `what` is not among them."""
+        cur, reserved = cur_size(), one.cap != (0, 0)
+        beyond = [s for s in P.outside_sizes + ((one.cap[0] + 16, cur[1]),) if not one.within(*s)]
+        inside = inside_sizes(other_than=cur)
+        k = rng.randint(1, cap)
+        if what == "sized_without_reservation" and not reserved:
+            return Op("invalid", what=what, on="prefetch", bufs=legal_depth(k), size=rng.choice([s for s in P.sizes if s != cur]))
+        if what == "sized_outside_reservation" and reserved:
+            return Op("invalid", what=what, on="prefetch", bufs=legal_depth(k), size=rng.choice(beyond))
+        if what == "sized_bad_pitch" and inside:
+            return Op("invalid", what=what, on="prefetch", bufs=legal_depth(k), size=rng.choice(inside))
+        if what == "reserve_below_current" and not P.free_running:     # (refused before anything synchronises, but keep the rule plain)
+            return Op("invalid", what=what, on="reserve", size=rng.choice(((cur[0] - 8, cur[1]), (cur[0], cur[1] - 2), (8, 8))))
+        if what == "pool_resize_uncovered" and G:
+            st["uncovered"] = True
+            return Op("invalid", what=what, on="resize", size=rng.choice(beyond))
+        return None
+
+    def do_invalid(what=None):
+        if what is None and P.reserve and rng.random() < 0.5:
+            what = rng.choice(SIZED_INVALID)
+        if what is not None:
+            op = sized_invalid(what)
+            if op is not None:
+                return emit(op)
         on = rng.choice(("execute", "prefetch"))
         kinds = ("n_zero", "n_over") + (("bad_params",) if bad else ())
         if not G:
@@ -658,10 +932,51 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
         emit(Op("set_params", param=rng.choice([p for p in valid if p != other_than])))
         st.update(promised=None, announced=None)
 
-    def do_resize():
+    def held(what):
+        return any(getattr(c, what) is not None for c in (model.members if G else [model]))
+
+    def do_resize(to=None):
         cur = (model.width, model.height)
-        emit(Op("resize", size=rng.choice([s for s in P.sizes if s != cur] or [cur])))
-        st.update(promised=None, announced=None, last_exec=None)
+        # an ordinary ready set waits for its call: the resizes that end at the size it was made for are the ones that count
+        waits = st["promised"] is not None and st["promised"].size is None
+        if to is None:
+            if G or P.free_running:                  # only inside the reservation: the pool refuses others, and they synchronise
+                sizes = inside_sizes(other_than=cur)
+                if not sizes:
+                    return
+                to = rng.choice(sizes)
+            else:
+                to = rng.choice([s for s in P.sizes + P.outside_sizes if s != cur] or [cur])
+            if P.reserve and one.within(*cur) and rng.random() < (0.3 if waits else 0.12):
+                to = cur                             # a resize to the current size is a resize: it drops everything
+        back = None
+        if P.reserve and to != cur and one.within(*to) and one.within(*cur) and rng.random() < (0.4 if waits else 0.15):
+            back = cur                               # there and back with no call in between: nothing survives it either
+        emit(Op("resize", size=to))
+        if back is not None:
+            emit(Op("resize", size=back))
+        # (what a resize keeps is still announced / promised: the next call is usually the one it was made for)
+        stale = st["promised"] if to == cur or back is not None else None
+        st.update(promised=st["promised"] if held("ready") else None, announced=st["announced"] if held("ann") else None,
+                  last_exec=None, loop=None)
+        if stale is not None and st["promised"] is None and rng.random() < 0.7:
+            st.update(promised=stale, honour=True)   # the host asks for what it was promised all the same: a pass of its own
+            do_execute()
+
+    def do_reserve(drop=False):
+        cur, c = cur_size(), one.cap
+        grown = (max(P.reserve[0], c[0], cur[0]), max(P.reserve[1], c[1], cur[1]))
+        if drop:
+            size = (0, 0)
+        elif c == (0, 0):
+            size = grown
+        else:
+            r = rng.random()
+            if r < 0.25:
+                return do_invalid("reserve_below_current")
+            size = (0, 0) if r < 0.6 else grown if r < 0.85 else (grown[0] + 16, grown[1] + 8)
+        emit(Op("reserve", size=size))
+        st.update(promised=None, announced=None, loop=None)
 
     def do_debug_set():
         key, values = rng.choice(DEBUG_KEYS)
@@ -673,8 +988,16 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
         table.append((P.w_debug_set, do_debug_set))
         if not P.free_running:
             table.append((P.w_resize, do_resize))
+    if P.reserve:
+        if G or P.free_running:
+            table.append((P.w_resize, do_resize))    # inside the reservation it synchronises nothing
+        if not P.free_running:
+            table.append((P.w_reserve, do_reserve))
+            emit(Op("reserve", size=P.reserve))      # (a free-running sequence starts reserved: initial_cap)
     weights = [t[0] for t in table]
     while sum(op.kind != "refill" for op in ops) < P.length:
+        if G and P.reserve and not st["uncovered"] and len(ops) >= P.length // 2:
+            do_invalid("pool_resize_uncovered")      # once per sequence at the least
         if (st["announced"] is not None or st["promised"] is not None) and rng.random() < P.p_follow_up:
             do_execute()                             # an announcement is usually carried, a carried pass usually asked for
         else:
@@ -743,24 +1066,74 @@ POOL = dict(length=40, max_batch=2, sizes=((384, 256),), p_host=0.0, p_other_str
             n_out=14)
 
 
-def case_sequence(kind: str, name: str):
-    """(ops, fresh model) of a committed case: kind = stepped | free | pool_stepped | pool_free."""
-    if kind.startswith("pool"):
-        c = POOL_CASES[name]
+# Dynamic resolution (tests/test_dynamic_resolution_sequences_gpu.py): the reservation, four sizes inside it -- W % 8 == 0; one
+# whose carried pass fits under the first; W % 8 != 0, the scalar forms; the reservation's own size -- and one outside that is
+# wider but shorter, so that the reservation must grow to 416 x 272 and not to 416 x 200.
+DYN_RESERVE = (400, 272)
+DYN_SIZES = ((384, 256), (200, 120), (380, 250), (400, 272))
+DYN_OUTSIDE = ((416, 200),)
+DYN_STEPPED = Profile(sizes=DYN_SIZES, reserve=DYN_RESERVE, outside_sizes=DYN_OUTSIDE, w_resize=3.0, w_reserve=1.6, w_prefetch=8,
+                      p_sized=0.6, p_sized_then_resize=0.6, p_ann_disturbed=0.3)
+DYN_FREE = Profile(free_running=True, length=48, sizes=DYN_SIZES, reserve=DYN_RESERVE, p_host=0.0, w_resize=2.0, w_prefetch=8,
+                   p_sized=0.6, p_sized_then_resize=0.7)
+DYN_POOL = dict(POOL, sizes=DYN_SIZES[:3], reserve=DYN_RESERVE, outside_sizes=DYN_OUTSIDE, w_resize=2.5, w_prefetch=8, p_sized=0.6,
+                p_sized_then_resize=0.65, n_depth=16)
+DYN_CASES = {
+    "r8_rtz_f32": dict(seed=4083),
+    "f16_rtne_unorm16": dict(seed=3852, ao="f16", rtz=False, depth="unorm16"),
+    "r8_rtz_linear_f32": dict(seed=4046, depth="linear_f32", linear=True),
+    "r8_rtz_hq2": dict(seed=1024, hq_levels=2),
+    "r8_rtz_not_pipelined": dict(seed=1111, pipelined=False),
+}
+DYN_FREE_CASES = {"r8_rtz_f32": dict(seed=2056), "r8_rtz_linear_f32": dict(seed=1939, depth="linear_f32", linear=True),
+                  "f16_rtne_unorm16": dict(seed=2098, ao="f16", rtz=False, depth="unorm16")}
+DYN_POOL_CASES = {"pool2": dict(seed=1068, members=2), "pool3": dict(seed=1046, members=3)}
+DYN_POOL_FREE_SEEDS = {"pool2": 2387, "pool3": 1352}
+
+
+def case_profile(kind: str, name: str):
+    """(config, profile, seed) of a committed case: kind = stepped | free | pool_stepped | pool_free, or dyn_ + one of them."""
+    dyn, base = kind.startswith("dyn_"), kind[4:] if kind.startswith("dyn_") else kind
+    if base.startswith("pool"):
+        c = (DYN_POOL_CASES if dyn else POOL_CASES)[name]
         # (free-running: a buffer is filled once, before its first use -- the pool's streams are its own, so a refill cannot be
         # ordered behind a member's work without the host synchronisation this mode is there to avoid)
-        prof = Profile(pool=c["members"], free_running=kind == "pool_free", p_refill=0.0 if kind == "pool_free" else 0.7, **POOL)
-        seed = c["seed"] + (50 if kind == "pool_free" else 0)
+        shape = dict(DYN_POOL, n_depth=48) if dyn and base == "pool_free" else DYN_POOL if dyn else POOL
+        prof = Profile(pool=c["members"], free_running=base == "pool_free", p_refill=0.0 if base == "pool_free" else 0.7, **shape)
+        seed = c["seed"] + (50 if base == "pool_free" else 0)
+        if dyn and base == "pool_free":
+            seed = DYN_POOL_FREE_SEEDS[name] + 50
+    elif dyn:
+        c = (DYN_CASES if base == "stepped" else DYN_FREE_CASES)[name]
+        prof, seed = (DYN_STEPPED if base == "stepped" else DYN_FREE), c["seed"]
     else:
-        c = (CASES if kind == "stepped" else FREE_CASES)[name]
-        prof, seed = (STEPPED if kind == "stepped" else FREE_RUNNING), c["seed"]
+        c = (CASES if base == "stepped" else FREE_CASES)[name]
+        prof, seed = (STEPPED if base == "stepped" else FREE_RUNNING), c["seed"]
+    return c, prof, seed
+
+
+def fresh_model(prof: Profile, cfg: dict):
+    linear, rtz, pipelined = cfg.get("linear", False), cfg.get("rtz", True), cfg.get("pipelined", True)
+    w, h = prof.sizes[0]
+    pal = palette(linear)
+    kw = dict(linear=linear, rtz=rtz, pipelined=pipelined, cap=initial_cap(prof))
+    return PoolModel(prof.pool, w, h, prof.max_batch, pal[0], **kw) if prof.pool else ContextModel(w, h, prof.max_batch, pal[0], **kw)
+
+
+def case_sequence(kind: str, name: str):
+    """(ops, fresh model) of a committed case (kinds: case_profile)."""
+    c, prof, seed = case_profile(kind, name)
     linear, rtz, pipelined = c.get("linear", False), c.get("rtz", True), c.get("pipelined", True)
     pal = palette(linear)
     ops = generate(seed, prof, pal, pal[0], linear=linear, rtz=rtz, pipelined=pipelined)
-    w, h = prof.sizes[0]
-    kw = dict(linear=linear, rtz=rtz, pipelined=pipelined)
-    model = PoolModel(prof.pool, w, h, prof.max_batch, pal[0], **kw) if prof.pool else ContextModel(w, h, prof.max_batch, pal[0], **kw)
-    return ops, model
+    return ops, fresh_model(prof, c)
+
+
+def dynamic_sequences():
+    """Every (kind, name) tests/test_dynamic_resolution_sequences_gpu.py adds."""
+    out = [("dyn_stepped", n) for n in DYN_CASES] + [("dyn_free", n) for n in DYN_FREE_CASES]
+    out += [(k, n) for k in ("dyn_pool_stepped", "dyn_pool_free") for n in DYN_POOL_CASES]
+    return out
 
 
 def committed_sequences():

@@ -87,8 +87,9 @@ class Driver:
         self.ao_dt = np.uint16 if self.ao_fmt == L.AO_F16 else np.uint8
         self.rounding = L.F16_RTZ_CLAMP if cfg.get("rtz", True) else L.F16_RTNE
         self.hq = cfg.get("hq_levels", 0)
-        wmax, hmax = max(s[0] for s in profile.sizes), max(s[1] for s in profile.sizes)
-        self.cap = hmax * (wmax + max(M.PITCH_EXTRA))                 # texels of every surface
+        frames = profile.sizes + profile.outside_sizes      # every size a frame of the sequence can have
+        wmax, hmax = max(s[0] for s in frames), max(s[1] for s in frames)
+        self.cap = hmax * max(wmax + max(M.PITCH_EXTRA), M.PITCH_FIXED)      # texels of every surface
         self.lib = L.load()
         self.ctx_fields = fields_of(0, self.w, self.h)
         base = self.settings(self.ctx_fields)
@@ -222,21 +223,27 @@ class Driver:
         """Free-running: everything the sequence will copy into its buffers goes to the device first."""
         if self.stepped or self.G:
             return
+        size = (self.w, self.h)                                       # the context's, as the sequence will have made it by then
         for op in ops:
             if op.kind == "refill":
                 for c in op.contents:
-                    key = (c, op.pitch)
+                    key = (c, op.pitch, op.size or size)
                     if key not in self.library:
+                        w, h = key[2]
                         img = self.background()[0].copy()
-                        self.lay_out(img, self.frame(c, self.w, self.h)[0], self.w + M.PITCH_EXTRA[op.pitch])
+                        self.lay_out(img, self.frame(c, w, h)[0], M.row_texels(op.pitch, w))
                         self.library[key] = self.torch.from_numpy(img).to(self.dev)
+            elif op.kind == "resize":
+                size = op.size
             elif op.kind == "comp_enqueue":
                 for c in op.colors:
-                    if ("color", c) not in self.library:
+                    if c not in self.colors:
                         s = self.surface(self.colors, c, self.cap * 8, 0)
-                        base = self.color0(c)
-                        s.mirror[:base.nbytes] = base.reshape(-1).view(np.uint8)
-                        self.library[("color", c)] = self.torch.from_numpy(s.mirror.copy()).to(self.dev)
+                    if ("color", c, size) not in self.library:
+                        base = self.color0(c, *size)
+                        img = np.zeros(self.cap * 8, np.uint8)
+                        img[:base.nbytes] = base.reshape(-1).view(np.uint8)
+                        self.library[("color", c, size)] = self.torch.from_numpy(img).to(self.dev)
         self.torch.cuda.synchronize(self.dev)
 
     def lay_out(self, raw, frame, pitch):
@@ -244,25 +251,27 @@ class Driver:
         Surface.view(raw, frame.dtype, pitch, w, h)[:] = frame
 
     def refill(self, op):
-        pitch = self.w + M.PITCH_EXTRA[op.pitch]
+        w, h = op.size or (self.w, self.h)                             # a frame of the size it will be announced at
+        pitch = M.row_texels(op.pitch, w)
         for b, c in zip(op.bufs, op.contents):
             s = self.depth_surface(b)
-            dev_frame, oracle_frame = self.frame(c, self.w, self.h)
+            dev_frame, oracle_frame = self.frame(c, w, h)
             if not self.stepped and not self.G:                        # the library image is the whole surface
                 s.mirror[:] = self.background()[0]
                 if self.linear:
                     s.oracle_bytes[:] = self.background()[1]
-            self.laid[b] = (c, (pitch, self.w, self.h))
+            self.laid[b] = (c, (pitch, w, h))
             self.lay_out(s.mirror, dev_frame, pitch)
             if self.linear:
                 self.lay_out(s.oracle_bytes, oracle_frame, pitch)
-            self.upload(s, (c, op.pitch))
+            self.upload(s, (c, op.pitch, (w, h)))
 
-    def color0(self, i):
-        key = (i, self.w, self.h)
+    def color0(self, i, w=None, h=None):
+        w, h = w or self.w, h or self.h
+        key = (i, w, h)
         if key not in self.color_lib:
             rng = np.random.default_rng(1000 + i)
-            self.color_lib[key] = (rng.random((self.h, self.w, 4)) * 2.0).astype(np.float16).view(np.uint16)
+            self.color_lib[key] = (rng.random((h, w, 4)) * 2.0).astype(np.float16).view(np.uint16)
         return self.color_lib[key]
 
     # ---- the oracle
@@ -321,8 +330,8 @@ class Driver:
         """meao_execute_batch / _params / _pitched (or the pool's) as the operation asks; returns the status."""
         n_real = len(op.bufs)
         de, ae = np.dtype(self.depth_dt).itemsize, np.dtype(self.ao_dt).itemsize
-        dp = (self.w + M.PITCH_EXTRA[op.pitch]) * de if op.pitch else 0
-        opitch = (self.w + M.PITCH_EXTRA[op.out_pitch]) * ae if op.out_pitch else 0
+        dp = (M.row_texels(op.pitch, self.w)) * de if op.pitch else 0
+        opitch = (M.row_texels(op.out_pitch, self.w)) * ae if op.out_pitch else 0
         self.host_out = []
         din, dout = [], []
         for b in op.bufs:
@@ -366,10 +375,18 @@ class Driver:
 
     def call_prefetch(self, op, bad=None):
         de = np.dtype(self.depth_dt).itemsize
-        dp = (self.w + M.PITCH_EXTRA[op.pitch]) * de if op.pitch else 0
+        w = op.size[0] if op.size else self.w                         # the pitch of a sized announcement: texels of ITS width
+        dp = (M.row_texels(op.pitch, w)) * de if op.pitch else 0
         din = [self.depth_surface(b).ptr() for b in op.bufs]
         n = len(din)
         prm = None if op.params is None else self.params_ctypes(op.params)
+        if bad == "sized_bad_pitch":
+            dp = w * de - de                                          # below the announced row
+        if op.size:
+            pin = (C.c_void_p * n)(*din)
+            if self.G:
+                return self.lib.meao_pool_prefetch_batch_sized(self.ao._pool, op.size[0], op.size[1], n, pin, dp, prm)
+            return self.lib.meao_prefetch_batch_sized(self.ao._ctx, op.size[0], op.size[1], n, pin, dp, prm)
         if bad == "bad_pitch":
             dp = self.w * de - de
         if bad == "null_pointer":
@@ -393,7 +410,7 @@ class Driver:
     def frame_inputs(self, op):
         """[(oracle frame, fields)] of an execute, from the bytes the call is given under the pitch it is given."""
         out = []
-        pitch = self.w if op.depth_host else self.w + M.PITCH_EXTRA[op.pitch]
+        pitch = self.w if op.depth_host else M.row_texels(op.pitch, self.w)
         for f, b in enumerate(op.bufs):
             s = self.depth[b]
             frame = Surface.view(s.oracle_bytes, np.float32 if self.linear else self.depth_dt, pitch, self.w, self.h)
@@ -418,7 +435,7 @@ class Driver:
         inputs = self.frame_inputs(op)
         status = self.call_execute(op)
         assert status == L.OK, (op, status, self.lib.meao_last_error(self.members[0]))
-        opitch = self.w if op.out_host else self.w + M.PITCH_EXTRA[op.out_pitch]
+        opitch = self.w if op.out_host else M.row_texels(op.out_pitch, self.w)
         host_want = []
         for f, (frame, fields) in enumerate(inputs):
             want = self.want(frame, fields)["result"]
@@ -474,7 +491,7 @@ class Driver:
         """Known by construction only: inside the exact range, a frame with hostile level texels has its bit, a clean one has not."""
         if self.fmt == L.DEPTH_UNORM16:
             return
-        view = (self.w if op.depth_host else self.w + M.PITCH_EXTRA[op.pitch], self.w, self.h)
+        view = (self.w if op.depth_host else M.row_texels(op.pitch, self.w), self.w, self.h)
         for m, e in enumerate(expects):
             if e is None or not e.exact:
                 continue
@@ -543,9 +560,23 @@ class Driver:
         self.check_debug(op, inputs, why=why, view=True)
 
     def assert_refuses_debug(self, op):
-        with pytest.raises(L.MeaoError) as err:
-            self.ao.debug_buffer(2, frame=0)
-        assert err.value.status == L.ERR_INVALID_ARGUMENT, (op, err.value)
+        """'As left by the last execute' is gone: every member refuses meao_get_intermediate."""
+        for c in self.members:
+            d = L.Desc()
+            L.check(self.lib.meao_get_intermediate(c, 0, 2, None, 0, L.MEM_HOST, C.byref(d)), c)      # the description alone
+            out = np.empty(d.bytes, np.uint8)
+            status = self.lib.meao_get_intermediate(c, 0, 2, out.ctypes.data, out.nbytes, L.MEM_HOST, C.byref(d))
+            assert status == L.ERR_INVALID_ARGUMENT, (op, status)
+
+    def check_geometry(self, op):
+        """Every member has the model's size and the model's reservation (meao_get_config, meao_get_capacity)."""
+        models = self.model.members if self.G else [self.model]
+        for m, c in enumerate(self.members):
+            cfg, cw, ch = L.Config(), C.c_int32(), C.c_int32()
+            L.check(self.lib.meao_get_config(c, C.byref(cfg)), c)
+            L.check(self.lib.meao_get_capacity(c, C.byref(cw), C.byref(ch)), c)
+            assert (cfg.width, cfg.height) == (models[m].width, models[m].height), (op, m, "size", cfg.width, cfg.height)
+            assert (cw.value, ch.value) == models[m].cap, (op, m, "capacity", cw.value, ch.value, models[m].cap)
 
     def comp_enqueue(self, op, expect):
         expects = self.member_expects(expect)
@@ -559,7 +590,7 @@ class Driver:
                 s.dev.copy_(self.torch.from_numpy(s.mirror))
             else:
                 with self.on_stream():
-                    s.dev.copy_(self.library[("color", c)], non_blocking=True)                   # put there by prepare()
+                    s.dev.copy_(self.library[("color", c, (self.w, self.h))], non_blocking=True)   # put there by prepare()
             ao = Surface.view(self.outs[o].mirror, self.ao_dt, self.w, self.w, self.h).copy()
             want = base.copy()
             self.O.composite(ao, want, op.mode, self.ao_fmt)
@@ -573,12 +604,22 @@ class Driver:
     def invalid(self, op, expect):
         expects = self.member_expects(expect)
         before = self.pending()
-        status = self.call_execute(op, bad=op.what) if op.on == "execute" else self.call_prefetch(op, bad=op.what)
+        if op.on == "reserve":
+            status = (self.lib.meao_pool_reserve(self.ao._pool, *op.size) if self.G else self.lib.meao_reserve(self.ao._ctx, *op.size))
+        elif op.on == "resize":
+            status = (self.lib.meao_pool_resize(self.ao._pool, *op.size) if self.G else self.lib.meao_resize(self.ao._ctx, *op.size))
+        else:
+            status = self.call_execute(op, bad=op.what) if op.on == "execute" else self.call_prefetch(op, bad=op.what)
         assert status == expects[0].status, (op, status)
         assert self.pending() == before, (op, "an invalid call must leave a waiting composite waiting")
+        if op.what in M.SIZED_INVALID:
+            self.check_geometry(op)
 
     def run(self, ops, model):
         self.model = model
+        if M.initial_cap(self.P) != (0, 0):                          # a free-running sequence starts reserved
+            self.ao.reserve(*self.P.reserve)
+            self.check_geometry("the reservation before the first operation")
         self.prepare(ops)
         for op in ops:
             expect = model.apply(op)
@@ -592,15 +633,24 @@ class Driver:
                 assert self.call_prefetch(op) == L.OK, op
                 if self.stepped and not self.G and self.member_expects(expect)[0].reallocated:
                     self.assert_refuses_debug(op)
+                    self.check_geometry(op)                          # the reservation survives the re-allocation
             elif k == "set_params":
                 self.apply_params(self.fields_for(op.param))
                 self.reread("after set_params")
             elif k == "resize":
                 self.ao.resize(*op.size)
-                self.check_composites(op, [expect])                  # it ran at the old size
+                self.check_composites(op, self.member_expects(expect))      # it ran at the old size
                 self.w, self.h = op.size
                 self.last_read = None
+                self.check_geometry(op)
+                if self.stepped:
+                    self.assert_refuses_debug(op)
+            elif k == "reserve":
+                self.ao.reserve(*op.size)
+                self.last_read = None
+                self.check_geometry(op)
                 self.assert_refuses_debug(op)
+                self.check_composites(op, self.member_expects(expect))      # none ran: a waiting batch stays waiting
             elif k == "comp_enqueue":
                 self.comp_enqueue(op, expect)
             elif k == "comp_flush":
@@ -895,15 +945,11 @@ kind, name, own_launch = sys.argv[1], sys.argv[2], int(sys.argv[3])
 O.build()
 ops, model = M.case_sequence(kind, name)
 lin_c = None
-if kind == "free":
-    cfg, prof = M.FREE_CASES[name], M.FREE_RUNNING
-    if cfg.get("linear"):
-        import tempfile
-        from tests.test_linear_depth_gpu import build_linearize
-        lin_c = build_linearize(tempfile.mkdtemp())
-else:
-    cfg = M.POOL_CASES[name]
-    prof = M.Profile(pool=cfg["members"], free_running=True, **M.POOL)
+cfg, prof, _ = M.case_profile(kind, name)
+if cfg.get("linear"):
+    import tempfile
+    from tests.test_linear_depth_gpu import build_linearize
+    lin_c = build_linearize(tempfile.mkdtemp())
 d = T.Driver(O, cfg, prof, own_launch, lin_c, stepped=False)
 try:
     d.run(ops, model)

@@ -17,7 +17,8 @@ from tests import helpers as H  # noqa: E402
 
 def run_sequences(count, seed0):
     """The generator and model of tests/call_model.py with fresh seeds, driven by the stepped Driver of
-    tests/test_call_sequences_gpu.py: every case of the suite's stepped and pool modes in turn, both forms of the carried pass."""
+    tests/test_call_sequences_gpu.py: every case of the suite's stepped and pool modes in turn -- those that draw reservations, resizes
+    and sized announcements (tests/test_dynamic_resolution_sequences_gpu.py) included -- and both forms of the carried pass."""
     import tempfile
     import pytest
     from miniengineao_amd import _lib as L
@@ -27,21 +28,16 @@ def run_sequences(count, seed0):
     O.build()
     lin_c = build_linearize(tempfile.mkdtemp())
     cases = [("stepped", n) for n in sorted(M.CASES)] + [("pool_stepped", n) for n in sorted(M.POOL_CASES)]
+    cases += [("dyn_stepped", n) for n in sorted(M.DYN_CASES)] + [("dyn_pool_stepped", n) for n in sorted(M.DYN_POOL_CASES)]
     bad = 0
     for k in range(count):
         kind, name = cases[k % len(cases)]
         seed, own_launch = seed0 + k, (k // len(cases)) % 2
-        if kind == "stepped":
-            cfg, prof = M.CASES[name], M.STEPPED
-        else:
-            cfg = M.POOL_CASES[name]
-            prof = M.Profile(pool=cfg["members"], **M.POOL)
+        cfg, prof, _ = M.case_profile(kind, name)
         kw = dict(linear=cfg.get("linear", False), rtz=cfg.get("rtz", True), pipelined=cfg.get("pipelined", True))
         pal = M.palette(kw["linear"])
         ops = M.generate(seed, prof, pal, pal[0], **kw)
-        w, h = prof.sizes[0]
-        model = (M.PoolModel(prof.pool, w, h, prof.max_batch, pal[0], **kw) if prof.pool
-                 else M.ContextModel(w, h, prof.max_batch, pal[0], **kw))
+        model = M.fresh_model(prof, cfg)
         d = Driver(O, cfg, prof, own_launch, lin_c, stepped=True, seed=seed)
         try:
             d.run(ops, model)
