@@ -73,6 +73,16 @@ namespace MiniEngineAO.Native
         public ulong bytes;
     }
 
+    // one frame's size and row pitches (bytes, 0 = packed for its own width) in meao_execute_batch_extents
+    [StructLayout(LayoutKind.Sequential)]
+    public struct MeaoExtent
+    {
+        public int width;
+        public int height;
+        public ulong depth_pitch;
+        public ulong ao_pitch;
+    }
+
     [StructLayout(LayoutKind.Sequential)]
     public struct MeaoRenderConstants
     {
@@ -138,6 +148,8 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_prefetch_batch_pitched(IntPtr ctx, int n, IntPtr[] depth, ulong depth_pitch, [In] MeaoParams[] prm);
         // the announcement for frames of another size inside the reservation: it survives meao_resize to exactly that size
         [DllImport(Lib)] public static extern int meao_prefetch_batch_sized(IntPtr ctx, int width, int height, int n, IntPtr[] depth, ulong depth_pitch, [In] MeaoParams[] prm);
+        // a mixed-size batch: extents[f] = frame f's size and pitches, inside the reservation (else the context's size); DEVICE surfaces
+        [DllImport(Lib)] public static extern int meao_execute_batch_extents(IntPtr ctx, int n, IntPtr[] depth, IntPtr[] ao_out, [In] MeaoExtent[] extents, [In] MeaoParams[] prm, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_synchronize(IntPtr ctx, IntPtr stream);
 
         [DllImport(Lib)] public static extern int meao_get_intermediate(IntPtr ctx, int frame, int debug_id, IntPtr dst, ulong dst_capacity, int dst_loc, out MeaoDesc desc);
@@ -169,6 +181,7 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_pool_prefetch_batch_params(IntPtr pool, int n, IntPtr[] depth, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_pool_execute_batch_pitched(IntPtr pool, int n, IntPtr[] depth, ulong depth_pitch, int depth_loc, IntPtr[] ao_out, ulong ao_pitch, int out_loc, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_pool_prefetch_batch_pitched(IntPtr pool, int n, IntPtr[] depth, ulong depth_pitch, [In] MeaoParams[] prm);
+        [DllImport(Lib)] public static extern int meao_pool_execute_batch_extents(IntPtr pool, int n, IntPtr[] depth, IntPtr[] ao_out, [In] MeaoExtent[] extents, [In] MeaoParams[] prm);
         [DllImport(Lib)] public static extern int meao_pool_reserve(IntPtr pool, int max_width, int max_height);
         [DllImport(Lib)] public static extern int meao_pool_resize(IntPtr pool, int width, int height);
         [DllImport(Lib)] public static extern int meao_pool_prefetch_batch_sized(IntPtr pool, int width, int height, int n, IntPtr[] depth, ulong depth_pitch, [In] MeaoParams[] prm);

@@ -355,6 +355,34 @@ MEAO_API int32_t meao_prefetch_batch_pitched(meao_ctx *ctx, int32_t n, const voi
  * never leaves the pipelined form. */
 MEAO_API int32_t meao_prefetch_batch_sized(meao_ctx *ctx, int32_t width, int32_t height, int32_t n, const void *const *depth,
                                            uint64_t depth_pitch, const meao_params *params);
+/* Mixed-size batches: one size per frame inside the context's capacity (a 4K main view plus a handful of 256 x 256 probes in
+ * one batched launch sequence).  DEVICE surfaces only.  extents[f] gives frame f its own width, height and row pitches (bytes;
+ * 0 = tightly packed for THAT frame's width).  The capacity is the reservation (meao_reserve) where the context holds one, else
+ * the context's size; every frame needs 1 <= width <= capacity width and 1 <= height <= capacity height, which suffices because
+ * ceil(w / 2^k) is monotone (the argument meao_reserve makes for resizes): frame f's intermediates are packed for its own
+ * extents inside slot f.  Frame f's AO and every intermediate are bit for bit what a context of size extents[f] gives for that
+ * frame with params[f] (NULL: the context's parameters), in every configuration a context can have.  The context's size,
+ * parameters and reservation are neither read for the results nor changed.
+ * Validation, before anything is enqueued (a refused call launches nothing and leaves an announcement, a ready set and a waiting
+ * composite as they were; meao_last_error names the call, the frame and the argument): n, the pointers and params[] as in
+ * meao_execute_batch_params; MEAO_ERR_INVALID_ARGUMENT for a size outside the capacity or outside [1, 32768]; each pitch by the
+ * rules of meao_execute_batch_pitched against its own frame's size.
+ * When every extent equals the context's size and all frames share their pitches the call IS meao_execute_batch_pitched.  Every
+ * other call is a "mixed call", a per-frame call (it reads its argument blocks from the table ring) also with params == NULL,
+ * under the contracts of meao_execute_batch_params -- no allocation, no host synchronisation, asynchronous on `stream`, the ring
+ * of 8 tables -- and: a waiting composite batch is run first as plain launches; a ready prefetched set is consumed unmatched (the
+ * call runs its own downsample pass); an announcement (meao_prefetch_batch*, sized or not) is carried as a launch of its own
+ * behind the last kernel and promoted as usual (there is no announcement form for mixed batches).  Launch shapes are chosen for
+ * the call as a whole: the tile-count thresholds compare the sum over the frames, the 4-texel vector forms need every frame
+ * eligible by its own width, pitches and pointers, and each launch has the grid of its largest frame -- workgroups beyond a
+ * smaller frame's own tile count return at once.  Afterwards meao_get_intermediate / meao_debug_view (dst / out not NULL)
+ * describe and return frame f's buffers at frame f's size. */
+typedef struct meao_extent {
+    int32_t width, height;
+    uint64_t depth_pitch, ao_pitch;
+} meao_extent;
+MEAO_API int32_t meao_execute_batch_extents(meao_ctx *ctx, int32_t n, const void *const *depth, void *const *ao_out,
+                                            const meao_extent *extents, const meao_params *params, meao_stream stream);
 /* Waits for `stream`; NULL = the stream of the last meao_execute* of this context.  meao_composite /
  * meao_composite_flush do not change what NULL means: a composite issued on another stream is waited for
  * by naming that stream here (or by synchronising it directly). */
@@ -589,6 +617,11 @@ MEAO_API int32_t meao_pool_execute_batch_pitched(meao_pool *pool, int32_t n, con
                                                  const meao_params *params);
 MEAO_API int32_t meao_pool_prefetch_batch_pitched(meao_pool *pool, int32_t n, const void *const *depth, uint64_t depth_pitch,
                                                   const meao_params *params);
+/* meao_execute_batch_extents for the pool: frame f, extents[f] and params[f] (if given) go to member f mod G.  Every member's
+ * share is validated against that member's capacity before any member enqueues; members dealt nothing do what they do for
+ * meao_pool_execute_batch_pitched. */
+MEAO_API int32_t meao_pool_execute_batch_extents(meao_pool *pool, int32_t n, const void *const *depth, void *const *ao_out,
+                                                 const meao_extent *extents, const meao_params *params);
 /* Dynamic resolution for the pool.  meao_pool_reserve: meao_reserve member by member; if member k fails, the members before it
  * keep the larger reservation (a reservation changes no result), no member's size changes, and meao_pool_last_error names the
  * member.  meao_pool_resize is for sizes that EVERY member's reservation covers; anything else is MEAO_ERR_INVALID_ARGUMENT,

@@ -156,6 +156,19 @@ public:
         check(meao_execute_batch_pitched(ctx_, static_cast<int32_t>(deviceDepth.size()), deviceDepth.data(), depthPitch, MEAO_MEM_DEVICE,
                                          deviceAo.data(), aoPitch, MEAO_MEM_DEVICE, params.empty() ? nullptr : params.data(), stream));
     }
+    // A mixed-size batch of device surfaces (meao_execute_batch_extents): extents[f] = frame f's own width, height and row
+    // pitches (bytes, 0 = packed for that width), every size inside the reservation, else inside this instance's size; params
+    // empty = the instance's parameters, else one per frame.
+    void RenderBatchExtents(const std::vector<const void *> &deviceDepth, const std::vector<void *> &deviceAo,
+                            const std::vector<meao_extent> &extents, const std::vector<meao_params> &params = {}, meao_stream stream = nullptr)
+    {
+        if (extents.size() != deviceDepth.size() || deviceAo.size() != deviceDepth.size())
+            throw std::invalid_argument("meao: one AO surface and one meao_extent per frame");
+        if (!params.empty() && params.size() != deviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        sync();
+        check(meao_execute_batch_extents(ctx_, static_cast<int32_t>(deviceDepth.size()), deviceDepth.data(), deviceAo.data(), extents.data(),
+                                         params.empty() ? nullptr : params.data(), stream));
+    }
     void PrefetchBatchPitched(const std::vector<const void *> &nextDeviceDepth, uint64_t depthPitch,
                               const std::vector<meao_params> &params = {})
     {
@@ -405,6 +418,16 @@ public:
         check(meao_pool_execute_batch_pitched(pool_, static_cast<int32_t>(deviceDepth.size()), deviceDepth.data(), depthPitch,
                                               MEAO_MEM_DEVICE, deviceAo.data(), aoPitch, MEAO_MEM_DEVICE,
                                               params.empty() ? nullptr : params.data()));
+    }
+    // a mixed-size batch (meao_pool_execute_batch_extents): extents[f] goes with frame f to member f mod G
+    void RenderDeviceBatchExtents(const std::vector<const void *> &deviceDepth, const std::vector<void *> &deviceAo,
+                                  const std::vector<meao_extent> &extents, const std::vector<meao_params> &params = {})
+    {
+        if (extents.size() != deviceDepth.size() || deviceAo.size() != deviceDepth.size())
+            throw std::invalid_argument("meao: one AO surface and one meao_extent per frame");
+        if (!params.empty() && params.size() != deviceDepth.size()) throw std::invalid_argument("meao: one meao_params per frame");
+        check(meao_pool_execute_batch_extents(pool_, static_cast<int32_t>(deviceDepth.size()), deviceDepth.data(), deviceAo.data(),
+                                              extents.data(), params.empty() ? nullptr : params.data()));
     }
     void PrefetchBatchPitched(const std::vector<const void *> &nextDeviceDepth, uint64_t depthPitch,
                               const std::vector<meao_params> &params = {})

@@ -74,6 +74,11 @@ class Desc(C.Structure):
                 ("slices", C.c_int32), ("format", C.c_int32), ("bytes", C.c_uint64)]
 
 
+class Extent(C.Structure):
+    """meao_extent: one frame's size and row pitches (bytes, 0 = packed for its own width) in meao_execute_batch_extents."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("depth_pitch", C.c_uint64), ("ao_pitch", C.c_uint64)]
+
+
 class RenderConstants(C.Structure):
     _fields_ = [("inv_thickness_table", C.c_float * 12), ("sample_weight_table", C.c_float * 12),
                 ("inv_slice_dimension", C.c_float * 2), ("reject_fadeoff", C.c_float),
@@ -122,6 +127,10 @@ SIGNATURES = {
     "meao_prefetch_batch_pitched": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(Params)]),
     "meao_prefetch_batch_sized": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64,
                                               C.POINTER(Params)]),
+    "meao_execute_batch_extents": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(Extent),
+                                               C.POINTER(Params), C.c_void_p]),
+    "meao_pool_execute_batch_extents": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(Extent),
+                                                    C.POINTER(Params)]),
     "meao_synchronize": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "meao_get_intermediate": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64,
                                           C.c_int32, C.POINTER(Desc)]),

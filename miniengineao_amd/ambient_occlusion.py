@@ -35,6 +35,20 @@ DEBUG_BUFFER_NAMES = {
 HQ_BUFFER_NAMES = {18: "OcclusionHQ1", 19: "OcclusionHQ2", 20: "OcclusionHQ3", 21: "OcclusionHQ4"}
 
 
+def extents_array(extents: Sequence[tuple], n: int):
+    """[(width, height[, depth_pitch, ao_pitch]), ...] -> the meao_extent array of meao_execute_batch_extents (pitches in bytes,
+    0 or absent = packed for that frame's width)."""
+    if len(extents) != n:
+        raise ValueError(f"{len(extents)} extents for {n} frames")
+    arr = (L.Extent * n)()
+    for f, e in enumerate(extents):
+        if len(e) not in (2, 4):
+            raise ValueError(f"extents[{f}]: expected (width, height) or (width, height, depth_pitch, ao_pitch)")
+        arr[f].width, arr[f].height = int(e[0]), int(e[1])
+        arr[f].depth_pitch, arr[f].ao_pitch = (int(e[2]), int(e[3])) if len(e) == 4 else (0, 0)
+    return arr
+
+
 class AmbientOcclusion:
     """depth in -> AO texture out, on one MI355X.  One instance per device."""
 
@@ -69,6 +83,7 @@ class AmbientOcclusion:
         self._ambient_only = True          # AO.cs:68; composite-only flag, kept for surface parity
         self._debug = 0                    # AO.cs:60
         self._dirty = True
+        self._last_sizes = None            # [(width, height)] of the frames of the last call where it was a mixed-size batch
         self._ctx = C.c_void_p()
         L.check(self._lib.meao_create(C.byref(cfg), C.byref(self._ctx)))
 
@@ -119,6 +134,7 @@ class AmbientOcclusion:
         """Screen-size change (AO.cs:338-341).  Inside a reservation (reserve()) it neither allocates nor synchronises."""
         L.check(self._lib.meao_resize(self._ctx, width, height), self._ctx)
         self._cfg.width, self._cfg.height = width, height
+        self._last_sizes = None
 
     def reserve(self, max_width: int, max_height: int) -> None:
         """Dynamic resolution (meao_reserve): size the intermediates for max_width x max_height once -- it may allocate and
@@ -153,6 +169,7 @@ class AmbientOcclusion:
         """params: one FrameParams per frame (meao_execute_batch_params; unset fields = this instance's values), or None."""
         n = len(depths)
         self._sync_params()
+        self._last_sizes = None
         prm = None if params is None else params_array(params, n, self._prm)
         dt = DEPTH_NUMPY[self._cfg.depth_format]
         ins = [np.ascontiguousarray(d, dtype=dt) for d in depths]
@@ -169,15 +186,26 @@ class AmbientOcclusion:
         return outs
 
     def execute_device(self, depth_ptrs: Sequence[int], out_ptrs: Sequence[int], stream: int = 0,
-                       params: Optional[Sequence[Optional[FrameParams]]] = None, *, depth_pitch: int = 0, out_pitch: int = 0) -> None:
+                       params: Optional[Sequence[Optional[FrameParams]]] = None, *, depth_pitch: int = 0, out_pitch: int = 0,
+                       extents: Optional[Sequence[tuple]] = None) -> None:
         """Device-resident frames (raw device addresses, e.g. torch ``data_ptr()``); asynchronous.  params: as in render_batch.
-        depth_pitch / out_pitch: bytes between consecutive rows of the surfaces (meao_execute_batch_pitched); 0 = tightly packed."""
+        depth_pitch / out_pitch: bytes between consecutive rows of the surfaces (meao_execute_batch_pitched); 0 = tightly packed.
+        extents: one (width, height[, depth_pitch, ao_pitch]) per frame -- a mixed-size batch (meao_execute_batch_extents): every
+        size inside the reservation, else inside this context's size; the pitches (bytes, 0 = packed for that frame's width) then
+        come from the extents, not from depth_pitch / out_pitch.  debug_buffer / debug_view afterwards have the frame's size."""
         n = len(depth_ptrs)
         self._sync_params()
         pin = (C.c_void_p * n)(*depth_ptrs)
         pout = (C.c_void_p * n)(*out_ptrs)
         s = C.c_void_p(stream) if stream else None
-        if depth_pitch or out_pitch:
+        self._last_sizes = None
+        if extents is not None:
+            if depth_pitch or out_pitch:
+                raise ValueError("execute_device: with extents the pitches are given per frame, inside the extents")
+            prm = None if params is None else params_array(params, n, self._prm)
+            L.check(self._lib.meao_execute_batch_extents(self._ctx, n, pin, pout, extents_array(extents, n), prm, s), self._ctx)
+            self._last_sizes = [(int(e[0]), int(e[1])) for e in extents]
+        elif depth_pitch or out_pitch:
             prm = None if params is None else params_array(params, n, self._prm)
             L.check(self._lib.meao_execute_batch_pitched(self._ctx, n, pin, depth_pitch, L.MEM_DEVICE, pout, out_pitch, L.MEM_DEVICE,
                                                          prm, s), self._ctx)
@@ -198,6 +226,7 @@ class AmbientOcclusion:
         if len(out_ptrs) != n or len(color_ptrs) != n or (gbuffer0_ptrs and len(gbuffer0_ptrs) != n):
             raise ValueError("execute_shaded_device: one AO, one colour (and one GBuffer0) surface per depth frame")
         self._sync_params()
+        self._last_sizes = None
         prm = None if params is None else params_array(params, n, self._prm)
         g = (C.c_void_p * n)(*gbuffer0_ptrs) if gbuffer0_ptrs else None
         L.check(self._lib.meao_execute_batch_shaded(self._ctx, n, (C.c_void_p * n)(*depth_ptrs), depth_pitch, (C.c_void_p * n)(*out_ptrs),
@@ -241,6 +270,10 @@ class AmbientOcclusion:
         ao_dt = torch.uint8 if self._cfg.ao_format == L.AO_R8 else torch.float16
         dev = torch.device("cuda", self._cfg.device)        # every frame of depth and out must be on the context's device
         frames = list(depth) if not hasattr(depth, "dim") else depth
+        if isinstance(frames, list) and any(tuple(t.shape) != (self.height, self.width) for t in frames):
+            if color is not None or gbuffer0 is not None:
+                raise ValueError("execute_tensors: a mixed-size batch has no shaded form")
+            return self._execute_mixed_tensors(frames, out, params, depth_dt, ao_dt, dev)
         d_ptrs, d_pitch = frame_pointers(frames, self.height, self.width, depth_dt, "depth", device=dev)
         n = len(d_ptrs)
         first = frames[0]
@@ -266,6 +299,29 @@ class AmbientOcclusion:
         self.execute_device(d_ptrs, o_ptrs, stream=stream, params=params,
                             depth_pitch=packed_pitch(d_pitch, self.width, first.element_size()),
                             out_pitch=packed_pitch(o_pitch, self.width, o_frames[0].element_size()))
+        return out
+
+    def _execute_mixed_tensors(self, frames, out, params, depth_dt, ao_dt, dev):
+        """execute_tensors for a list of (H_f, W_f) tensors of different shapes (meao_execute_batch_extents): every frame's own
+        row stride becomes its pitch.  out: a list of (H_f, W_f) tensors, or None: allocated packed.  Returns the list."""
+        import torch
+        from .surfaces import frame_pointers, packed_pitch
+        if out is None:
+            out = [torch.empty(tuple(t.shape), dtype=ao_dt, device=dev) for t in frames]
+        out = list(out)
+        if len(out) != len(frames):
+            raise ValueError(f"out has {len(out)} frames, depth {len(frames)}")
+        d_ptrs, o_ptrs, extents = [], [], []
+        for f, (d, o) in enumerate(zip(frames, out)):
+            if d.dim() != 2 or tuple(o.shape) != tuple(d.shape):
+                raise ValueError(f"frame {f}: depth {tuple(d.shape)} and out {tuple(o.shape)} must be the same (H, W)")
+            h, w = d.shape
+            (dp,), d_pitch = frame_pointers([d], h, w, depth_dt, f"depth[{f}]", device=dev)
+            (op,), o_pitch = frame_pointers([o], h, w, ao_dt, f"out[{f}]", device=dev)
+            d_ptrs.append(dp)
+            o_ptrs.append(op)
+            extents.append((w, h, packed_pitch(d_pitch, w, d.element_size()), packed_pitch(o_pitch, w, o.element_size())))
+        self.execute_device(d_ptrs, o_ptrs, stream=torch.cuda.current_stream(dev).cuda_stream, params=params, extents=extents)
         return out
 
     def synchronize(self, stream: int = 0) -> None:
@@ -390,8 +446,14 @@ class AmbientOcclusion:
 
     # ---- observability (the _debug views, AO.cs:787-820) -------------------------------
     def debug_buffer(self, debug_id: int, frame: int = 0) -> np.ndarray:
+        """Debug buffer ``debug_id`` of frame ``frame`` of the last call -- at that frame's own size after a mixed-size batch."""
         d = L.Desc()
-        L.check(self._lib.meao_get_intermediate(self._ctx, frame, debug_id, None, 0, L.MEM_HOST, C.byref(d)), self._ctx)
+        if self._last_sizes is not None and 0 <= frame < len(self._last_sizes):
+            cfg = L.Config.from_buffer_copy(self._cfg)
+            cfg.width, cfg.height = self._last_sizes[frame]
+            L.check(self._lib.meao_describe_buffer(C.byref(cfg), debug_id, C.byref(d)))
+        else:
+            L.check(self._lib.meao_get_intermediate(self._ctx, frame, debug_id, None, 0, L.MEM_HOST, C.byref(d)), self._ctx)
         shape = (d.slices, d.height, d.width) if d.slices > 1 else (d.height, d.width)
         out = np.empty(shape, _NP_OF_FMT[d.format])
         L.check(self._lib.meao_get_intermediate(self._ctx, frame, debug_id, out.ctypes.data, out.nbytes,
@@ -400,7 +462,10 @@ class AmbientOcclusion:
 
     def debug_view(self, debug_id: int, frame: int = 0) -> np.ndarray:
         """What `_debug = debug_id` shows (AO.cs:787-820): the buffer blitted into the AO target."""
-        out = np.empty((self.height, self.width), self.ao_dtype)
+        w, h = self.width, self.height
+        if self._last_sizes is not None and 0 <= frame < len(self._last_sizes):
+            w, h = self._last_sizes[frame]       # a mixed-size batch: the view has the frame's own size
+        out = np.empty((h, w), self.ao_dtype)
         L.check(self._lib.meao_debug_view(self._ctx, frame, debug_id, out.ctypes.data, L.MEM_HOST, None), self._ctx)
         return out
 
@@ -525,12 +590,19 @@ class AmbientOcclusionPool:
         return outs
 
     def execute_device(self, depth_ptrs: Sequence[int], out_ptrs: Sequence[int],
-                       params: Optional[Sequence[Optional[FrameParams]]] = None, *, depth_pitch: int = 0, out_pitch: int = 0) -> None:
+                       params: Optional[Sequence[Optional[FrameParams]]] = None, *, depth_pitch: int = 0, out_pitch: int = 0,
+                       extents: Optional[Sequence[tuple]] = None) -> None:
         """Frame f resident on device_of_frame(f); asynchronous (synchronize()).  depth_pitch / out_pitch: row pitches in bytes of
-        every frame's surfaces (meao_pool_execute_batch_pitched); 0 = tightly packed."""
+        every frame's surfaces (meao_pool_execute_batch_pitched); 0 = tightly packed.  extents: a mixed-size batch, as
+        AmbientOcclusion.execute_device takes it (meao_pool_execute_batch_extents); extents[f] goes with frame f to its member."""
         n = len(depth_ptrs)
         pin, pout = (C.c_void_p * n)(*depth_ptrs), (C.c_void_p * n)(*out_ptrs)
-        if depth_pitch or out_pitch:
+        if extents is not None:
+            if depth_pitch or out_pitch:
+                raise ValueError("execute_device: with extents the pitches are given per frame, inside the extents")
+            prm = None if params is None else params_array(params, n, self._prm)
+            self._check(self._lib.meao_pool_execute_batch_extents(self._pool, n, pin, pout, extents_array(extents, n), prm))
+        elif depth_pitch or out_pitch:
             prm = None if params is None else params_array(params, n, self._prm)
             self._check(self._lib.meao_pool_execute_batch_pitched(self._pool, n, pin, depth_pitch, L.MEM_DEVICE, pout, out_pitch,
                                                                   L.MEM_DEVICE, prm))

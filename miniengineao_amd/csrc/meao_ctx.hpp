@@ -251,8 +251,15 @@ struct TableRing {
         const int slot = pos;
         pos = (pos + 1) % N;
         if (pending[slot]) {
-            note_sync(ctx);
-            MEAO_HIP(ctx, hipEventSynchronize(ev[slot]));
+            // (a host that stays fewer than N calls ahead finds that call completed and makes no synchronising call at all)
+            const hipError_t done = hipEventQuery(ev[slot]);
+            if (done == hipErrorNotReady) {
+                (void)hipGetLastError();
+                note_sync(ctx);
+                MEAO_HIP(ctx, hipEventSynchronize(ev[slot]));
+            } else if (done != hipSuccess) {
+                return fail_hip(ctx, done, "hipEventQuery (per-frame table ring)");
+            }
             pending[slot] = false;
         }
         lease->ring = this; lease->ctx = ctx; lease->slot = slot; lease->stream = stream;
@@ -280,12 +287,14 @@ struct DeviceBuffer {
 struct LastCall {
     int frames = 0;
     hipStream_t stream = nullptr;
-    uint64_t depth_pitch = 0, out_pitch = 0;     // of the device frames, in bytes; 0 = packed (debug ids 1 and 17 pack them first)
+    bool mixed = false;                          // a mixed call (meao_execute_batch_extents): every frame has its own size
     struct Frame {
         const void *depth, *out;                 // device addresses of the raw depth frame (debug id 1) and of the result (17)
         float zp[2];                             // the parameters the call used for this frame
         int32_t reversed_z;
         float pad[4];
+        int32_t width, height;                   // the frame's size: the context's at the time of the call, or its own (mixed)
+        uint64_t depth_pitch, out_pitch;         // of the device frame, in bytes; 0 = packed (debug ids 1 and 17 pack it first)
     } frame[MEAO_MAX_BATCH] = {};
 };
 
@@ -352,6 +361,8 @@ struct meao_ctx {
     // A meao_resize inside it changes cfg and the plan only.
     int32_t cap_w = 0, cap_h = 0;
     bool within_reservation(int32_t w, int32_t h) const { return cap_w > 0 && w <= cap_w && h <= cap_h; }
+    // What bounds the frames of a mixed call (meao_execute_batch_extents): the reservation, else the context's size
+    bool within_capacity(int32_t w, int32_t h) const { return cap_w > 0 ? (w <= cap_w && h <= cap_h) : (w <= cfg.width && h <= cfg.height); }
     // Hostile-depth flags (meao_dev_downsample.hpp nice_denominator): [set][frame] words the downsample pass
     // stamps with its generation when a frame's levels hold texels outside the exact-division range.
     uint32_t *hostile = nullptr;
@@ -401,9 +412,12 @@ struct FrameSet {
     const void *const *depth; uint64_t depth_pitch; int32_t depth_loc;
     void *const *out; uint64_t out_pitch; int32_t out_loc;
     const meao_params *params;
+    // meao_execute_batch_extents: frame f's own size and pitches (depth_pitch / out_pitch above are then unused); null = every
+    // frame has the context's size
+    const meao_extent *extents = nullptr;
 
-    // Member m's frames of a pool of G (frame f -> member f mod G), pointers and parameters, in the caller's `storage`.
-    struct Storage { const void *depth[MEAO_MAX_BATCH]; void *out[MEAO_MAX_BATCH]; meao_params prm[MEAO_MAX_BATCH]; };
+    // Member m's frames of a pool of G (frame f -> member f mod G), pointers, parameters and extents, in the caller's `storage`.
+    struct Storage { const void *depth[MEAO_MAX_BATCH]; void *out[MEAO_MAX_BATCH]; meao_params prm[MEAO_MAX_BATCH]; meao_extent ext[MEAO_MAX_BATCH]; };
     FrameSet share(int32_t m, int32_t G, Storage *s) const
     {
         FrameSet mine = *this;
@@ -412,8 +426,10 @@ struct FrameSet {
             s->depth[k] = depth[f];
             if (out) s->out[k] = out[f];
             if (params) s->prm[k] = params[f];
+            if (extents) s->ext[k] = extents[f];
         }
         mine.n = k; mine.depth = s->depth; mine.out = out ? s->out : nullptr; mine.params = params ? s->prm : nullptr;
+        mine.extents = extents ? s->ext : nullptr;
         return mine;
     }
 };
@@ -458,7 +474,11 @@ int pitch_texels(meao_ctx *ctx, uint64_t pitch, uint64_t elem, const char *what,
 int pitch_texels_of(meao_ctx *ctx, int32_t width, int32_t height, uint64_t pitch, uint64_t elem, const char *what, int32_t *out);
 // Every check of an execute call, before anything is enqueued; the row strides in texels on success.
 int validate_execute_batch(meao_ctx *ctx, const FrameSet &fs, int32_t *depth_rows, int32_t *out_rows);
-// For meao_pool.cpp too: meao_execute_batch*; wait_for_host = false (pool members only) leaves the staged copies of a HOST
+// Every check of meao_execute_batch_extents (fs.extents set, DEVICE surfaces), before anything is enqueued; on success each
+// frame's row strides in texels.  *uniform: every extent is the context's size and all frames share their pitches -- the call is
+// meao_execute_batch_pitched with extents[0]'s.
+int validate_execute_batch_extents(meao_ctx *ctx, const FrameSet &fs, int32_t *depth_rows, int32_t *out_rows, bool *uniform);
+// For meao_pool.cpp too: meao_execute_batch* (fs.extents set: meao_execute_batch_extents); wait_for_host = false (pool members only) leaves the staged copies of a HOST
 // call in flight on `stream` -- the caller synchronises the stream before it touches the host buffers.
 int execute_batch_internal(meao_ctx *ctx, const FrameSet &fs, meao_stream stream, bool wait_for_host);
 // For meao_pool.cpp too: meao_prefetch_batch* without the checks of params[] (the caller made them): fs.n, depth, depth_pitch, params.

@@ -9,12 +9,12 @@ namespace {
 
 // A pitched device frame of the last call (debug ids 1 and 17) packed into the context's scratch first (not a hot path);
 // *frame = the packed copy.
-int pack_last_frame(meao_ctx *ctx, const void **frame, uint64_t pitch, uint64_t elem, hipStream_t s)
+int pack_last_frame(meao_ctx *ctx, const LastCall::Frame &last, const void **frame, uint64_t pitch, uint64_t elem, hipStream_t s)
 {
-    const uint64_t row = static_cast<uint64_t>(ctx->cfg.width) * elem;
-    const int rc = ctx->pack_scratch.reserve(ctx, row * ctx->cfg.height, "hipMalloc (packed copy of a pitched frame)");
+    const uint64_t row = static_cast<uint64_t>(last.width) * elem;
+    const int rc = ctx->pack_scratch.reserve(ctx, row * last.height, "hipMalloc (packed copy of a pitched frame)");
     if (rc != MEAO_OK) return rc;
-    MEAO_HIP(ctx, hipMemcpy2DAsync(ctx->pack_scratch.ptr, row, *frame, pitch, row, ctx->cfg.height, hipMemcpyDeviceToDevice, s));
+    MEAO_HIP(ctx, hipMemcpy2DAsync(ctx->pack_scratch.ptr, row, *frame, pitch, row, last.height, hipMemcpyDeviceToDevice, s));
     *frame = ctx->pack_scratch.ptr;
     return MEAO_OK;
 }
@@ -34,8 +34,8 @@ int locate_debug_buffer(meao_ctx *ctx, int32_t frame, int32_t debug_id, const me
         if (rc != MEAO_OK) return rc;
         LinearDepthArgs la{};
         la.depth = last.depth;
-        if (ctx->last.depth_pitch != 0) {
-            rc = pack_last_frame(ctx, &la.depth, ctx->last.depth_pitch, depth_elem(ctx->cfg.depth_format), s);
+        if (last.depth_pitch != 0) {
+            rc = pack_last_frame(ctx, last, &la.depth, last.depth_pitch, depth_elem(ctx->cfg.depth_format), s);
             if (rc != MEAO_OK) return rc;
         }
         la.dst = reinterpret_cast<uint16_t *>(ctx->atlas_scratch.ptr);
@@ -57,7 +57,8 @@ int locate_debug_buffer(meao_ctx *ctx, int32_t frame, int32_t debug_id, const me
         TileAtlasArgs ta{};
         ta.src = reinterpret_cast<const float *>(slot + lay.off_low_of(ds_cur, level - 1));
         ta.dst = reinterpret_cast<uint16_t *>(ctx->atlas_scratch.ptr);
-        ta.lw = ctx->plan.mip[level].w; ta.lh = ctx->plan.mip[level].h;
+        const Dims lv = level_dims(last.width, last.height, level);     // (the frame's own size after a mixed call)
+        ta.lw = lv.w; ta.lh = lv.h;
         ta.sw = d.width; ta.sh = d.height;
         ta.pad_value = last.pad[level - 1];
         ta.f16_rtne = ctx->cfg.f16_rounding == MEAO_F16_RTNE;
@@ -71,7 +72,7 @@ int locate_debug_buffer(meao_ctx *ctx, int32_t frame, int32_t debug_id, const me
         *out_src = slot + lay.off_comb[debug_id - 14];
     } else if (debug_id == 17) {
         *out_src = last.out;
-        if (ctx->last.out_pitch != 0) return pack_last_frame(ctx, out_src, ctx->last.out_pitch, ao_elem(ctx->cfg), s);
+        if (last.out_pitch != 0) return pack_last_frame(ctx, last, out_src, last.out_pitch, ao_elem(ctx->cfg), s);
     } else {
         const int level = debug_id - MEAO_DEBUG_OCCLUSION_HQ1 + 1;
         if (!level_has_hq(nl, ctx->cfg.hq_levels, level))
@@ -97,6 +98,10 @@ int32_t meao_get_intermediate(meao_ctx *ctx, int32_t frame, int32_t debug_id, vo
     if (!ctx->arena) return fail(ctx, MEAO_ERR_OUT_OF_MEMORY, "meao_get_intermediate: the context has no intermediates");
     if (frame < 0 || frame >= ctx->last.frames)
         return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_get_intermediate: frame not produced by the last execute");
+    if (ctx->last.mixed) {      // the buffers of a mixed call's frame have that frame's size
+        describe_buffer(ctx->last.frame[frame].width, ctx->last.frame[frame].height, ctx->cfg.ao_format, debug_id, &d);
+        if (out_desc) *out_desc = d;
+    }
     if (dst_capacity < d.bytes) return fail(ctx, MEAO_ERR_BUFFER_TOO_SMALL, "meao_get_intermediate: dst_capacity < desc.bytes");
     if (dst_loc != MEAO_MEM_HOST && dst_loc != MEAO_MEM_DEVICE) return MEAO_ERR_INVALID_ARGUMENT;
     int rc = use_device(ctx);
@@ -121,6 +126,10 @@ int32_t meao_debug_view(meao_ctx *ctx, int32_t frame, int32_t debug_id, void *ou
     if (!ctx->arena) return fail(ctx, MEAO_ERR_OUT_OF_MEMORY, "meao_debug_view: the context has no intermediates");
     if (frame < 0 || frame >= ctx->last.frames)
         return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_debug_view: frame not produced by the last execute");
+    // (after a mixed call: the frame's own size, for the buffer and for the view)
+    const int32_t view_w = ctx->last.mixed ? ctx->last.frame[frame].width : ctx->cfg.width;
+    const int32_t view_h = ctx->last.mixed ? ctx->last.frame[frame].height : ctx->cfg.height;
+    if (ctx->last.mixed) describe_buffer(view_w, view_h, ctx->cfg.ao_format, debug_id, &d);
     if (out_loc != MEAO_MEM_HOST && out_loc != MEAO_MEM_DEVICE) return MEAO_ERR_INVALID_ARGUMENT;
     int rc = use_device(ctx);
     if (rc != MEAO_OK) return rc;
@@ -128,7 +137,7 @@ int32_t meao_debug_view(meao_ctx *ctx, int32_t frame, int32_t debug_id, void *ou
     const void *src = nullptr;
     rc = locate_debug_buffer(ctx, frame, debug_id, d, s, &src);
     if (rc != MEAO_OK) return rc;
-    const uint64_t out_bytes = static_cast<uint64_t>(ctx->cfg.width) * ctx->cfg.height * ao_elem(ctx->cfg);
+    const uint64_t out_bytes = static_cast<uint64_t>(view_w) * view_h * ao_elem(ctx->cfg);
     void *dev_out = out;
     if (out_loc == MEAO_MEM_HOST) {   // own staging buffer: stage_out may hold the results (debug id 17)
         rc = ctx->stage_view.reserve(ctx, align_up(out_bytes), "hipMalloc (debug view staging)");
@@ -138,7 +147,7 @@ int32_t meao_debug_view(meao_ctx *ctx, int32_t frame, int32_t debug_id, void *ou
     DebugViewArgs dv{};
     dv.src = src; dv.dst = dev_out;
     dv.sw = d.width; dv.sh = d.height; dv.slices = d.slices; dv.src_format = d.format;
-    dv.w = ctx->cfg.width; dv.h = ctx->cfg.height;
+    dv.w = view_w; dv.h = view_h;
     dv.f16_rtne = ctx->cfg.f16_rounding == MEAO_F16_RTNE;
     MEAO_HIP(ctx, launch_debug_view(dv, ctx->cfg.ao_format, s));
     if (out_loc == MEAO_MEM_HOST) {

@@ -320,6 +320,11 @@ __device__ __forceinline__ const T &frame_block(const T *first, int frame)
     return *(const T *)p;
 }
 
+// A mixed-size call (meao_execute_batch_extents) launches every pass with the grid of its largest frame: a workgroup whose tile /
+// block index is not below its own frame's count (a field of the frame's block: a scalar load) has nothing to do and returns.
+// Workgroup-uniform, so the per-frame kernels test it before their first LDS access and barrier; equal sizes never take it.
+__device__ __forceinline__ bool beyond_frame(int index, int count) { return index >= count; }
+
 // True when the downsample pass that produced this frame's depth mips saw a texel outside the
 // verified operand range of the exact v_rcp_f32 sequences (see nice_denominator).
 __device__ __forceinline__ bool frame_is_hostile(const uint32_t *hostile, uint32_t generation, int frame)

@@ -60,7 +60,23 @@ struct BatchShape {           // what the structure of a call depends on
     int next;                 // 0 = nothing announced; the announced pass 1 = rides in the final kernel, 2 = runs as its own launch
 };
 
-LaunchList plan_launches(const meao_config &c, const Plan &p, const Tuning &t, const BatchShape &b)
+// The launch shape of one call, decided once over all its frames before any argument block is built (decide_call_shape): a
+// launch runs one kernel instantiation with one tiling, so nothing that selects them may differ between the blocks of a table.
+// The tile counts the thresholds compare are summed over the frames -- n x tiles where the frames have one size -- and a vector
+// form needs every frame eligible by its own width, strides and pointers (a mixed call, meao_execute_batch_extents).
+struct CallShape {
+    int ds_rows_per_lane;         // stand-alone downsample pass: kMipRowsPerLane, or 1 (ds_small_max_tiles)
+    int render_tile_h;            // interleaved checker-set render: kRenTileH, or kRenTileHSmall (render_small_max_tiles)
+    int final_tile_h;             // the plain final pass: ups_tile_h(true), or kUpsTileHSmall (final_small_max_tiles)
+    int blend1_tile_h;            // L2 -> L1: ups_tile_h(false), or kUpsTileHTall (blend_tall_min_tiles)
+    int64_t l1_tiles;             // 64 x 32 tiles of L2 -> L1 (nested_max_tiles)
+    bool ds_vec, final_vec;       // the 4-texel forms of the downsample pass and of the final pass
+    int ds_rep, final_rep;        // a frame whose block selects the call's kernel: the first with a pitched depth row / a pitched
+                                  // depth or result row, else frame 0
+};
+
+// l1_tiles: the call's L2 -> L1 tiles (CallShape)
+LaunchList plan_launches(const meao_config &c, int64_t l1_tiles, const Tuning &t, const BatchShape &b)
 {
     static const char *const kBlendRange[4] = {nullptr, "meao:upsample_L2_to_L1", "meao:upsample_L3_to_L2", "meao:upsample_L4_to_L3"};
     LaunchList l;
@@ -69,8 +85,7 @@ LaunchList plan_launches(const meao_config &c, const Plan &p, const Tuning &t, c
     else l.add(Step::Render, MEAO_PASS_RENDER, 0, "meao:render");
     if (c.hq_levels > 0) l.add(Step::RenderHq, MEAO_PASS_RENDER_HQ, 0, "meao:render_hq");
     const bool nestable = t.fuse_coarse_blend && c.num_levels == 4 && c.hq_levels == 0;
-    const int l1_tiles = ((p.mip[1].w + kUpsTileW - 1) / kUpsTileW) * ((p.mip[1].h + ups_tile_h(false) - 1) / ups_tile_h(false));
-    if (nestable && b.frames * l1_tiles <= t.nested_max_tiles) {
+    if (nestable && l1_tiles <= t.nested_max_tiles) {
         // a small frame or two per call (at most two workgroups per CU): all three blend passes in one launch -- their latency
         // chains, not their arithmetic, are what such a call waits for (1080p: 39.2 -> 36.9 us per frame; at 4K, 1020 tiles, it
         // is a wash).  Combined3 and Combined2 are still written
@@ -99,7 +114,9 @@ struct ArgBuilder {
     const Plan *plan;             // the constants: the context's, or one frame's (meao_execute_batch_params)
     const meao_params *prm;
     int exact_rcp_div;            // of the call (over all its frames)
-    int32_t depth_pitch, out_pitch;   // row strides of the call's depth / result frames in texels (cfg.width = packed)
+    int32_t depth_pitch, out_pitch;   // row strides of the depth / result frames in texels (the frames' width = packed): the call's,
+                                      // or one frame's (a mixed call)
+    const CallShape *shape;           // of the call
 
     const Plan &p() const { return *plan; }
     const meao_config &c() const { return ctx->cfg; }
@@ -113,8 +130,10 @@ struct ArgBuilder {
     uintptr_t out_align() const { return 4 * ao_elem(ctx->cfg); }
 
     // ---- PushDownsampleCommands (AO.cs:604-658).  lean: tiled for the tile the final kernel carries (kLeanMipW x kLeanMipRows),
-    // else for the stand-alone pass (small_ok: calls with few tiles use the one-row-per-lane tile)
-    DownsampleArgs downsample(int frames, const void *const *depth, int32_t pitch, int set, uint32_t gen, bool lean, bool small_ok) const
+    // else for the stand-alone pass (small_ok: calls with few tiles use the one-row-per-lane tile).  own: the pass of this call's
+    // own frames, whose vector form and tile come from the call's shape; null = the announced batch's pass (frames of one size)
+    DownsampleArgs downsample(int frames, const void *const *depth, int32_t pitch, int set, uint32_t gen, bool lean, bool small_ok,
+                              const CallShape *own = nullptr) const
     {
         DownsampleArgs ds{};
         bool aligned = (p().mip[0].w & 7) == 0 && (pitch & 3) == 0;     // (a packed row: W % 8 == 0 says it all)
@@ -123,7 +142,7 @@ struct ArgBuilder {
             ds.depth[f] = depth[f];
             aligned = aligned && aligned_to(depth[f], depth_align());
         }
-        ds.vec_ok = aligned;
+        ds.vec_ok = own ? own->ds_vec : aligned;
         ds.frames = frames;
         ds.depth_format = c().depth_format;
         for (int k = 0; k < 4; ++k) ds.low[k] = ctx->slot_ptr<float>(lay().off_low_of(set, k));
@@ -144,7 +163,7 @@ struct ArgBuilder {
             ds.rows_per_lane = kMipRowsPerLane;
             ds.tiles_x = (ds.w[1] + kMipTileW - 1) / kMipTileW;
             ds.tiles_y = (ds.h[1] + kMipRowsPerPass * kMipRowsPerLane - 1) / (kMipRowsPerPass * kMipRowsPerLane);
-            if (small_ok && frames * ds.tiles_x * ds.tiles_y <= ctx->tuning.ds_small_max_tiles) {
+            if (own ? own->ds_rows_per_lane == 1 : small_ok && frames * ds.tiles_x * ds.tiles_y <= ctx->tuning.ds_small_max_tiles) {
                 ds.rows_per_lane = 1;
                 ds.tiles_y = (ds.h[1] + kMipRowsPerPass - 1) / kMipRowsPerPass;
             }
@@ -160,13 +179,7 @@ struct ArgBuilder {
         RenderArgs rn{};
         int blocks = 0, count = 0;
         // few tiles (a 1080p frame or two): 128 x 8 tiles instead of 128 x 32 (render_small_kernel)
-        int tile_h = kRenTileH;
-        if (allow_small && !wide && c().sample_set != MEAO_SAMPLES_EXHAUSTIVE) {
-            int tiles32 = 0;
-            for (int l = first; l <= last; ++l)
-                tiles32 += ((p().mip[l].w + ren_tile_w(false) - 1) / ren_tile_w(false)) * ((p().mip[l].h + kRenTileH - 1) / kRenTileH);
-            if (n * tiles32 <= ctx->tuning.render_small_max_tiles) tile_h = kRenTileHSmall;
-        }
+        const int tile_h = allow_small && !wide && c().sample_set != MEAO_SAMPLES_EXHAUSTIVE ? shape->render_tile_h : kRenTileH;
         rn.tile_h = tile_h;
         for (int l = first; l <= last; ++l) {
             if (wide && !level_has_hq(c().num_levels, c().hq_levels, l)) continue;
@@ -218,12 +231,9 @@ struct ArgBuilder {
         up.tiles_x = (up.hw + kUpsTileW - 1) / kUpsTileW;
         up.tile_h = ups_tile_h(hi == 0);
         // few tiles (one 1080p frame): the plain final pass runs 64 x 32 tiles (upsample_final_small_kernel)
-        if (hi == 0 && !carrying && n * up.tiles_x * ((up.hh + up.tile_h - 1) / up.tile_h) <= ctx->tuning.final_small_max_tiles)
-            up.tile_h = kUpsTileHSmall;
+        if (hi == 0 && !carrying) up.tile_h = shape->final_tile_h;
         // L2 -> L1 of a large batch: 64 x 64 tiles like the full-resolution pass (upsample_blend_tall_kernel)
-        if (hi == 1 && (c().ao_format == MEAO_AO_R8 || ctx->tuning.blend_tall_forced) &&
-            static_cast<int64_t>(n) * up.tiles_x * ((up.hh + up.tile_h - 1) / up.tile_h) >= ctx->tuning.blend_tall_min_tiles)
-            up.tile_h = kUpsTileHTall;
+        if (hi == 1) up.tile_h = shape->blend1_tile_h;
         up.tiles_y = (up.hh + up.tile_h - 1) / up.tile_h;
         up.noise_filter_strength = k.noise_filter_strength;
         up.step_size = k.step_size;
@@ -242,11 +252,8 @@ struct ArgBuilder {
             up.hi_ao = nullptr;
             up.pitch.depth = depth_pitch;      // (in place of hi_depth, which the final pass does not read)
             up.pitch.dst = out_pitch;
-            vec_ok = vec_ok && (depth_pitch & 3) == 0 && (out_pitch & 3) == 0;     // (packed rows: hw % 4 == 0 says it all)
-            for (int f = 0; f < n; ++f) {
-                up.dst[f] = out_dev[f];
-                vec_ok = vec_ok && aligned_to(out_dev[f], out_align()) && aligned_to(depth_dev[f], depth_align());
-            }
+            vec_ok = shape->final_vec;
+            for (int f = 0; f < n; ++f) up.dst[f] = out_dev[f];
         }
         up.vec_ok = vec_ok;
         return up;
@@ -275,7 +282,7 @@ void build_call_args(const ArgBuilder &args, const ArgBuilder &nb, const BatchSh
     const meao_config &c = ctx->cfg;
     const Prefetch &pre = ctx->prefetch;
     const int n = args.n;
-    if (!b.prefetched) out->ds = args.downsample(n, args.depth_dev, args.depth_pitch, pre.ds_cur, pre.generation(), false, true);
+    if (!b.prefetched) out->ds = args.downsample(n, args.depth_dev, args.depth_pitch, pre.ds_cur, pre.generation(), false, true, args.shape);
     out->render = args.render(1, c.num_levels, false, !b.carry_composite);
     if (c.hq_levels > 0) out->render_hq = args.render(1, c.num_levels, true, false);
     for (int hi = 1; hi < c.num_levels; ++hi) out->up[hi] = args.upsample(hi);
@@ -298,11 +305,20 @@ struct Call {
     hipStream_t stream;
     const meao_params *fp;                // per-frame parameters (meao_execute_batch_params), nullptr = the context's
     int32_t depth_pitch, out_pitch;       // row strides of the device frames in texels (cfg.width = tightly packed)
+    // A mixed call (meao_execute_batch_extents): frame f's own size, and its row strides in texels (depth_pitch / out_pitch
+    // above are then unused).  null = every frame has the context's size.
+    const meao_extent *extents = nullptr;
+    const int32_t *depth_pitch_of = nullptr, *out_pitch_of = nullptr;
     const Plan *plan_of[MEAO_MAX_BATCH];
     const meao_params *prm_of[MEAO_MAX_BATCH];
     int exact;
     bool next_per_frame, per_frame;       // the announced batch has its own constants / the call reads a FrameArgs table
     BatchShape shape;
+    CallShape launch;                     // decide_call_shape
+
+    bool mixed() const { return extents != nullptr; }
+    int32_t depth_rows(int f) const { return mixed() ? depth_pitch_of[f] : depth_pitch; }
+    int32_t out_rows(int f) const { return mixed() ? out_pitch_of[f] : out_pitch; }
 
     // The constants the announced batch's pass is built from where it brought none of its own: the context's plan, or the plan
     // of the announced size (meao_prefetch_batch_sized).
@@ -313,7 +329,15 @@ struct Call {
     ArgBuilder builder(const meao_ctx *ctx, const Plan *plan, const meao_params *prm) const
     {
         return ArgBuilder{ctx, n, depth_dev, out_dev, ctx->hostile_of(ctx->prefetch.ds_cur), ctx->prefetch.generation(), plan, prm, exact,
-                          depth_pitch, out_pitch};
+                          depth_pitch, out_pitch, &launch};
+    }
+    // The builder of frame f's blocks: its constants and, in a mixed call, its size (the plan's) and row strides.
+    ArgBuilder frame_builder(const meao_ctx *ctx, int f) const
+    {
+        ArgBuilder b = builder(ctx, plan_of[f], prm_of[f]);
+        b.depth_pitch = depth_rows(f);
+        b.out_pitch = out_rows(f);
+        return b;
     }
 };
 
@@ -323,19 +347,55 @@ void resolve_constants(meao_ctx *ctx, Call *call)
 {
     const meao_config &c = ctx->cfg;
     call->exact = ctx->exact_rcp_div;
-    if (call->fp) {
+    if (call->fp || call->mixed()) {      // (a mixed call: the plan of each frame's own size, the context's plan is not read)
         call->exact = 1;
         for (int f = 0; f < call->n; ++f) {
-            build_plan(c.width, c.height, c.num_levels, c.sample_set, call->fp[f], &ctx->frame_plan[f]);
+            call->prm_of[f] = call->fp ? &call->fp[f] : &ctx->prm;
+            build_plan(call->mixed() ? call->extents[f].width : c.width, call->mixed() ? call->extents[f].height : c.height, c.num_levels,
+                       c.sample_set, *call->prm_of[f], &ctx->frame_plan[f]);
             call->plan_of[f] = &ctx->frame_plan[f];
-            call->prm_of[f] = &call->fp[f];
             if (!exact_rcp_div_applicable(c, ctx->frame_plan[f])) call->exact = 0;
         }
     } else {
         for (int f = 0; f < call->n; ++f) { call->plan_of[f] = &ctx->plan; call->prm_of[f] = &ctx->prm; }
     }
     call->next_per_frame = ctx->prefetch.next.n > 0 && ctx->prefetch.next.per_frame;
-    call->per_frame = call->fp != nullptr || call->next_per_frame;
+    call->per_frame = call->fp != nullptr || call->next_per_frame || call->mixed();
+}
+
+// Step 2.  The launch shape, once for the call (CallShape).  Frames of one size sum to n x tiles: what such calls always chose.
+void decide_call_shape(const meao_ctx *ctx, Call *call)
+{
+    const meao_config &c = ctx->cfg;
+    const Tuning &t = ctx->tuning;
+    const uintptr_t depth_align = 4 * depth_elem(c.depth_format), out_align = 4 * ao_elem(c);
+    auto tiles = [](const Dims &d, int tw, int th) { return static_cast<int64_t>((d.w + tw - 1) / tw) * ((d.h + th - 1) / th); };
+    int64_t ds_tiles = 0, render_tiles = 0, final_tiles = 0, l1_tiles = 0;
+    CallShape &s = call->launch;
+    s.ds_vec = s.final_vec = true;
+    s.ds_rep = s.final_rep = -1;
+    for (int f = 0; f < call->n; ++f) {
+        const Plan &p = *call->plan_of[f];
+        const int32_t w = p.mip[0].w, depth_rows = call->depth_rows(f), out_rows = call->out_rows(f);
+        ds_tiles += tiles(p.mip[1], kMipTileW, kMipRowsPerPass * kMipRowsPerLane);
+        for (int l = 1; l <= c.num_levels; ++l) render_tiles += tiles(p.mip[l], ren_tile_w(false), kRenTileH);
+        final_tiles += tiles(p.mip[0], kUpsTileW, ups_tile_h(true));
+        l1_tiles += tiles(p.mip[1], kUpsTileW, ups_tile_h(false));
+        // 4-texel loads / stores (ArgBuilder::depth_align): width % 8 (downsample: a lane takes 8 raw texels) or % 4, strides
+        // that are multiples of 4 texels (a packed row: the width says it all), aligned frames
+        const bool depth_ok = (depth_rows & 3) == 0 && aligned_to(call->depth_dev[f], depth_align);
+        s.ds_vec = s.ds_vec && (w & 7) == 0 && depth_ok;
+        s.final_vec = s.final_vec && (w & 3) == 0 && depth_ok && (out_rows & 3) == 0 && aligned_to(call->out_dev[f], out_align);
+        if (s.ds_rep < 0 && depth_rows != w) s.ds_rep = f;
+        if (s.final_rep < 0 && (depth_rows != w || out_rows != w)) s.final_rep = f;
+    }
+    s.ds_rep = std::max(s.ds_rep, 0);
+    s.final_rep = std::max(s.final_rep, 0);
+    s.ds_rows_per_lane = ds_tiles <= t.ds_small_max_tiles ? 1 : kMipRowsPerLane;
+    s.render_tile_h = render_tiles <= t.render_small_max_tiles ? kRenTileHSmall : kRenTileH;
+    s.final_tile_h = final_tiles <= t.final_small_max_tiles ? kUpsTileHSmall : ups_tile_h(true);
+    s.blend1_tile_h = (c.ao_format == MEAO_AO_R8 || t.blend_tall_forced) && l1_tiles >= t.blend_tall_min_tiles ? kUpsTileHTall : ups_tile_h(false);
+    s.l1_tiles = l1_tiles;
 }
 
 // Step 3.  A waiting composite rides in this call's render launch, or runs now as plain launches: the 68-sample render kernel
@@ -363,6 +423,7 @@ void decide_announced_pass(meao_ctx *ctx, const ArgBuilder &args, const ArgBuild
     Prefetch &pre = ctx->prefetch;
     if (pre.next.n == 0) return;
     const uint32_t gen = pre.generation_for_next();
+    if (call->mixed()) { call->shape.next = 2; return; }      // the carrying kernel has one size: a mixed call never uses it
     const DownsampleArgs lean = next.downsample(pre.next.n, pre.next.depth, pre.next.depth_pitch, pre.other(), gen, true, false);
     call->shape.next = carried_in_last_kernel(args.upsample(0, true), args.hi_depth(), lean, call->n, ctx->tuning.next_ds_own_launch) ? 1 : 2;
 }
@@ -377,7 +438,7 @@ int build_frame_table(meao_ctx *ctx, const Call &call, const LaunchList &list, T
     FrameArgs *stage = lease->host();
     const int count = std::max(call.n, call.shape.next != 0 ? pre.next.n : 0);
     for (int f = 0; f < count; ++f) {
-        const ArgBuilder fa = call.builder(ctx, f < call.n ? call.plan_of[f] : &ctx->plan, f < call.n ? call.prm_of[f] : &ctx->prm);
+        const ArgBuilder fa = f < call.n ? call.frame_builder(ctx, f) : call.builder(ctx, &ctx->plan, &ctx->prm);
         const bool own_next = call.next_per_frame && f < pre.next.n;
         const ArgBuilder fb = call.builder(ctx, own_next ? &pre.next.plan[f] : Call::next_shared_plan(ctx), own_next ? &pre.next.prm[f] : &ctx->prm);
         build_call_args(fa, fb, call.shape, list, &stage[f]);
@@ -386,6 +447,29 @@ int build_frame_table(meao_ctx *ctx, const Call &call, const LaunchList &list, T
     MEAO_HIP(ctx, hipMemcpyAsync(lease->device(), stage, sizeof(FrameArgs) * count, hipMemcpyHostToDevice, call.stream));
     *pf = lease->device();
     return MEAO_OK;
+}
+
+// Step 6, mixed half.  The shared blocks of a mixed call select each launch's kernel and give its grid, nothing else (no kernel
+// reads them): the blocks of a frame that takes the call's kernel (CallShape::ds_rep / final_rep), with the largest frame's tile
+// or block count as the grid -- never frame 0's, never the context's plan's.
+void grid_blocks_of_table(const Call &call, const FrameArgs *table, FrameArgs *shared)
+{
+    *shared = table[0];
+    shared->ds = table[call.launch.ds_rep].ds;
+    shared->up[0] = table[call.launch.final_rep].up[0];
+    shared->hi = table[call.launch.final_rep].hi;
+    int32_t ds = 0, render = 0, render_hq = 0, up[4] = {0, 0, 0, 0};
+    for (int f = 0; f < call.n; ++f) {
+        const FrameArgs &t = table[f];
+        ds = std::max(ds, t.ds.tiles_x * t.ds.tiles_y);
+        render = std::max(render, t.render.blocks_per_frame);
+        render_hq = std::max(render_hq, t.render_hq.blocks_per_frame);
+        for (int hi = 0; hi < 4; ++hi) up[hi] = std::max(up[hi], t.up[hi].tiles_x * t.up[hi].tiles_y);
+    }
+    shared->ds.tiles_x = ds; shared->ds.tiles_y = 1;
+    shared->render.blocks_per_frame = render;
+    shared->render_hq.blocks_per_frame = render_hq;
+    for (int hi = 0; hi < 4; ++hi) { shared->up[hi].tiles_x = up[hi]; shared->up[hi].tiles_y = 1; }
 }
 
 // Step 7.  Issues the list: `shared` holds the kernarg copies, pf (or null) the call's table of per-frame blocks.
@@ -458,10 +542,13 @@ void record_last_call(meao_ctx *ctx, const Call &call)
         depth_decode_constants(c.depth_format, call.plan_of[f]->zbuffer_params, *call.prm_of[f], lf.zp);
         lf.reversed_z = call.prm_of[f]->reversed_z != 0;
         for (int k = 0; k < 4; ++k) lf.pad[k] = call.plan_of[f]->render[k].pad_value;
+        lf.width = call.plan_of[f]->mip[0].w;
+        lf.height = call.plan_of[f]->mip[0].h;
+        lf.depth_pitch = call.depth_rows(f) == lf.width ? 0 : static_cast<uint64_t>(call.depth_rows(f)) * depth_elem(c.depth_format);
+        lf.out_pitch = call.out_rows(f) == lf.width ? 0 : static_cast<uint64_t>(call.out_rows(f)) * ao_elem(c);
     }
     last.frames = call.n;
-    last.depth_pitch = call.depth_pitch == c.width ? 0 : static_cast<uint64_t>(call.depth_pitch) * depth_elem(c.depth_format);
-    last.out_pitch = call.out_pitch == c.width ? 0 : static_cast<uint64_t>(call.out_pitch) * ao_elem(c);
+    last.mixed = call.mixed();
     last.stream = call.stream;
 }
 
@@ -475,22 +562,25 @@ int run_batch(meao_ctx *ctx, Call &call)
     // A previous call may already have downsampled exactly these frames (meao_prefetch_batch): the ready set is consumed either way.
     call.shape = BatchShape{};
     call.shape.frames = call.n;
-    call.shape.prefetched = pre.matches(call.n, call.depth_dev, call.stream, call.depth_pitch, call.exact != 0, call.prm_of, ctx->cfg.depth_format,
-                                        ctx->cfg.width, ctx->cfg.height);
+    // (a mixed call consumes it unmatched: a ready set holds frames of one size)
+    call.shape.prefetched = !call.mixed() && pre.matches(call.n, call.depth_dev, call.stream, call.depth_pitch, call.exact != 0, call.prm_of,
+                                                         ctx->cfg.depth_format, ctx->cfg.width, ctx->cfg.height);
     pre.begin_call(call.shape.prefetched);
     int rc = settle_composite(ctx, &call);
     if (rc != MEAO_OK) return rc;
+    decide_call_shape(ctx, &call);
 
     const ArgBuilder args = call.builder(ctx, &ctx->plan, &ctx->prm);
     const ArgBuilder next = call.builder(ctx, Call::next_shared_plan(ctx), &ctx->prm);
     decide_announced_pass(ctx, args, next, &call);
-    const LaunchList list = plan_launches(ctx->cfg, ctx->plan, ctx->tuning, call.shape);
+    const LaunchList list = plan_launches(ctx->cfg, call.launch.l1_tiles, ctx->tuning, call.shape);
 
     FrameArgs shared{};
-    build_call_args(args, next, call.shape, list, &shared);
+    if (!call.mixed()) build_call_args(args, next, call.shape, list, &shared);
     const FrameArgs *pf = nullptr;
     TableRing<FrameArgs, 8>::Lease lease;
     if (call.per_frame && (rc = build_frame_table(ctx, call, list, &lease, &pf)) != MEAO_OK) return rc;
+    if (call.mixed()) grid_blocks_of_table(call, lease.host(), &shared);
 
     rc = submit_launches(ctx, list, shared, pf, call.n, call.stream);
     if (rc != MEAO_OK) return rc;
@@ -570,8 +660,65 @@ int meao::validate_execute_batch(meao_ctx *ctx, const FrameSet &fs, int32_t *dep
     return vr;
 }
 
+int meao::validate_execute_batch_extents(meao_ctx *ctx, const FrameSet &fs, int32_t *depth_rows, int32_t *out_rows, bool *uniform)
+{
+    static const char fn[] = "meao_execute_batch_extents";
+    if (!ctx || !fs.depth || !fs.out || !fs.extents) return MEAO_ERR_INVALID_ARGUMENT;
+    if (fs.n < 1 || fs.n > ctx->cfg.max_batch) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": n must be 1..max_batch");
+    if (fs.depth_loc != MEAO_MEM_DEVICE || fs.out_loc != MEAO_MEM_DEVICE)
+        return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": DEVICE surfaces only");
+    for (int f = 0; f < fs.n; ++f)
+        if (!fs.depth[f] || !fs.out[f])
+            return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": frame " + std::to_string(f) + ": null frame pointer");
+    if (!ctx->arena) return fail(ctx, MEAO_ERR_OUT_OF_MEMORY, std::string(fn) + ": the context has no intermediates");
+    if (fs.params) {
+        const int vr = validate_frame_params(ctx, fs.n, fs.params, fn);
+        if (vr != MEAO_OK) return vr;
+    }
+    *uniform = true;
+    for (int f = 0; f < fs.n; ++f) {
+        const meao_extent &e = fs.extents[f];
+        const std::string at = std::string(fn) + ": extents[" + std::to_string(f) + "]";
+        if (!size_valid(e.width, e.height)) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, at + ".width/height out of range [1, 32768]");
+        if (!ctx->within_capacity(e.width, e.height))
+            return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, at + ".width/height: not inside the context's capacity (its reservation, else its size)");
+        int vr = pitch_texels_of(ctx, e.width, e.height, e.depth_pitch, depth_elem(ctx->cfg.depth_format), (at + ".depth_pitch").c_str(), &depth_rows[f]);
+        if (vr == MEAO_OK) vr = pitch_texels_of(ctx, e.width, e.height, e.ao_pitch, ao_elem(ctx->cfg), (at + ".ao_pitch").c_str(), &out_rows[f]);
+        if (vr != MEAO_OK) return vr;
+        *uniform = *uniform && e.width == ctx->cfg.width && e.height == ctx->cfg.height && depth_rows[f] == depth_rows[0] && out_rows[f] == out_rows[0];
+    }
+    return MEAO_OK;
+}
+
+namespace {
+
+// meao_execute_batch_extents, validated: the mixed call
+int execute_mixed_batch(meao_ctx *ctx, const FrameSet &fs, const int32_t *depth_rows, const int32_t *out_rows, meao_stream stream_)
+{
+    const int rc = use_device(ctx);
+    if (rc != MEAO_OK) return rc;
+    Call call;
+    call.n = fs.n; call.depth_dev = fs.depth; call.out_dev = fs.out; call.fp = fs.params;
+    call.stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->own_stream;
+    call.depth_pitch = call.out_pitch = ctx->cfg.width;     // (of the blocks no launch of a mixed call reads)
+    call.extents = fs.extents; call.depth_pitch_of = depth_rows; call.out_pitch_of = out_rows;
+    return run_batch(ctx, call);
+}
+
+}  // namespace
+
 int meao::execute_batch_internal(meao_ctx *ctx, const FrameSet &fs, meao_stream stream_, bool wait_for_host)
 {
+    if (fs.extents) {
+        int32_t rows_d[MEAO_MAX_BATCH], rows_o[MEAO_MAX_BATCH];
+        bool uniform = false;
+        const int vr = validate_execute_batch_extents(ctx, fs, rows_d, rows_o, &uniform);
+        if (vr != MEAO_OK) return vr;
+        if (!uniform) return execute_mixed_batch(ctx, fs, rows_d, rows_o, stream_);
+        FrameSet same = fs;       // every frame at the context's size with one pair of pitches: meao_execute_batch_pitched
+        same.extents = nullptr; same.depth_pitch = fs.extents[0].depth_pitch; same.out_pitch = fs.extents[0].ao_pitch;
+        return execute_batch_internal(ctx, same, stream_, wait_for_host);
+    }
     int32_t depth_rows = 0, out_rows = 0;     // row strides in texels
     {
         const int vr = validate_execute_batch(ctx, fs, &depth_rows, &out_rows);
@@ -678,6 +825,16 @@ int32_t meao_execute_batch_pitched(meao_ctx *ctx, int32_t n, const void *const *
                                    void *const *ao_out, uint64_t ao_pitch, int32_t out_loc, const meao_params *params, meao_stream stream_)
 {
     return execute_batch_internal(ctx, FrameSet{n, depth, depth_pitch, depth_loc, ao_out, ao_pitch, out_loc, params}, stream_, true);
+}
+
+int32_t meao_execute_batch_extents(meao_ctx *ctx, int32_t n, const void *const *depth, void *const *ao_out, const meao_extent *extents,
+                                   const meao_params *params, meao_stream stream_)
+{
+    if (!ctx) return MEAO_ERR_INVALID_ARGUMENT;
+    if (!depth || !ao_out || !extents) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, "meao_execute_batch_extents: depth, ao_out or extents is null");
+    FrameSet fs{n, depth, 0, MEAO_MEM_DEVICE, ao_out, 0, MEAO_MEM_DEVICE, params};
+    fs.extents = extents;
+    return execute_batch_internal(ctx, fs, stream_, true);
 }
 
 int32_t meao_execute(meao_ctx *ctx, const void *depth, int32_t depth_loc, void *ao_out, int32_t out_loc,

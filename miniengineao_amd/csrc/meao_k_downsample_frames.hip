@@ -9,7 +9,9 @@ namespace {
 template <bool VEC, int DIV, int ROWS>
 __global__ __launch_bounds__(kThreads) void downsample_frames_kernel(const DownsampleArgs *t)
 {
-    downsample_tile<VEC, DIV, ROWS>(frame_block(t, blockIdx.z), blockIdx.x, blockIdx.z);
+    const DownsampleArgs &a = frame_block(t, blockIdx.z);
+    if (beyond_frame(blockIdx.x, a.tiles_x * a.tiles_y)) return;
+    downsample_tile<VEC, DIV, ROWS>(a, blockIdx.x, blockIdx.z);
 }
 
 }  // namespace

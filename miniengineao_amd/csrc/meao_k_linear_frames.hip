@@ -10,25 +10,31 @@ namespace {
 template <bool VEC, int DIV, int ROWS>
 __global__ __launch_bounds__(kThreads) void downsample_linear_frames_kernel(const DownsampleArgs *t)
 {
-    downsample_tile<VEC, DIV, ROWS, true, true>(frame_block(t, blockIdx.z), blockIdx.x, blockIdx.z);
+    const DownsampleArgs &a = frame_block(t, blockIdx.z);
+    if (beyond_frame(blockIdx.x, a.tiles_x * a.tiles_y)) return;
+    downsample_tile<VEC, DIV, ROWS, true, true>(a, blockIdx.x, blockIdx.z);
 }
 
 template <int AOFMT, bool RTNE, int DIV, bool F32>
 __global__ __launch_bounds__(kThreads, 7) void upsample_final_linear_frames_kernel(const UpsampleArgs *t, const HiDepthArgs *th)
 {
     __shared__ __attribute__((aligned(16))) float smem[UpsLds<true>::kFloats];
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, ups_tile_h(true), F32, true, true>(frame_block(t, blockIdx.z), smem,
-                                                                                          xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z,
-                                                                                          NoHook(), &frame_block(th, blockIdx.z));
+    const UpsampleArgs &a = frame_block(t, blockIdx.z);
+    const int tile = xcd_contiguous(blockIdx.x, gridDim.x);
+    if (beyond_frame(tile, a.tiles_x * a.tiles_y)) return;
+    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, ups_tile_h(true), F32, true, true>(a, smem, tile, blockIdx.z, NoHook(),
+                                                                                          &frame_block(th, blockIdx.z));
 }
 
 template <int AOFMT, bool RTNE, int DIV, bool F32>
 __global__ __launch_bounds__(kThreads) void upsample_final_small_linear_frames_kernel(const UpsampleArgs *t, const HiDepthArgs *th)
 {
     __shared__ __attribute__((aligned(16))) float smem[UpsLds<true, kUpsTileHSmall>::kFloats];
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, kUpsTileHSmall, F32, true, true>(frame_block(t, blockIdx.z), smem,
-                                                                                        xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z,
-                                                                                        NoHook(), &frame_block(th, blockIdx.z));
+    const UpsampleArgs &a = frame_block(t, blockIdx.z);
+    const int tile = xcd_contiguous(blockIdx.x, gridDim.x);
+    if (beyond_frame(tile, a.tiles_x * a.tiles_y)) return;
+    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, kUpsTileHSmall, F32, true, true>(a, smem, tile, blockIdx.z, NoHook(),
+                                                                                        &frame_block(th, blockIdx.z));
 }
 
 }  // namespace

@@ -13,6 +13,7 @@ __global__ __launch_bounds__(ren_tile_w(EXH) * 4, EXH ? 1 : 8) void render_frame
     __shared__ __attribute__((aligned(16))) float tile[kRenLdsH * (ren_tile_w(EXH) + 2 * kRenApron)];
     const int frame = blockIdx.y, block = xcd_contiguous(blockIdx.x, gridDim.x);
     const RenderArgs &a = frame_block(t, frame);
+    if (beyond_frame(block, a.blocks_per_frame)) return;
     if constexpr (DIV == DIV_EXACT_RCP) {
         if (frame_is_hostile(a.hostile, a.generation, frame)) {
             render_tile<AOFMT, RTNE, DIV_IEEE, EXH>(a, tile, frame, block);
@@ -28,6 +29,7 @@ __global__ __launch_bounds__(ren_tile_w(false) * 4, 6) void render_small_frames_
     __shared__ __attribute__((aligned(16))) float tile[(kRenTileHSmall + 2 * kRenApron) * (ren_tile_w(false) + 2 * kRenApron)];
     const int frame = blockIdx.y, block = xcd_contiguous(blockIdx.x, gridDim.x);
     const RenderArgs &a = frame_block(t, frame);
+    if (beyond_frame(block, a.blocks_per_frame)) return;
     if constexpr (DIV == DIV_EXACT_RCP) {
         if (frame_is_hostile(a.hostile, a.generation, frame)) {
             render_tile<AOFMT, RTNE, DIV_IEEE, false, NoRenderHook, kRenTileHSmall>(a, tile, frame, block);
@@ -43,6 +45,7 @@ __global__ __launch_bounds__(kThreads) void render_wide_frames_kernel(const Rend
     __shared__ __attribute__((aligned(16))) float tile[kWideLdsH * kWideLdsW];
     const int frame = blockIdx.y, block = xcd_contiguous(blockIdx.x, gridDim.x);
     const RenderArgs &a = frame_block(t, frame);
+    if (beyond_frame(block, a.blocks_per_frame)) return;
     if constexpr (DIV == DIV_EXACT_RCP) {
         if (frame_is_hostile(a.hostile, a.generation, frame)) {
             render_wide_tile<AOFMT, RTNE, DIV_IEEE, EXH>(a, tile, frame, block);

@@ -12,6 +12,7 @@ __global__ __launch_bounds__(kThreads, 8) void upsample_two_level_frames_kernel(
     __shared__ __attribute__((aligned(16))) float smem[UpsLds<false>::kFloats];
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x), frame = blockIdx.z;
     const UpsampleArgs &outer = frame_block(t_outer, frame), &inner = frame_block(t_inner, frame);
+    if (beyond_frame(tile, outer.tiles_x * outer.tiles_y)) return;
     if constexpr (DIV == DIV_EXACT_RCP) {
         if (frame_is_hostile(outer.hostile, outer.generation, frame)) {
             upsample_two_level_tile<AOFMT, RTNE, DIV_IEEE>(outer, inner, smem, tile, frame);
@@ -28,6 +29,7 @@ __global__ __launch_bounds__(kThreads) void upsample_three_level_frames_kernel(c
     __shared__ __attribute__((aligned(16))) float smem[UpsLds<false>::kFloats + kNestScratch];
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x), frame = blockIdx.z;
     const UpsampleArgs &outer = frame_block(t_outer, frame), &mid = frame_block(t_mid, frame), &inner = frame_block(t_inner, frame);
+    if (beyond_frame(tile, outer.tiles_x * outer.tiles_y)) return;
     if constexpr (DIV == DIV_EXACT_RCP) {
         if (frame_is_hostile(outer.hostile, outer.generation, frame)) {
             upsample_three_level_tile<AOFMT, RTNE, DIV_IEEE>(outer, mid, inner, smem, tile, frame);

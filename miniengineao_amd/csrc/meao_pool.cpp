@@ -447,6 +447,28 @@ int32_t meao_pool_execute_batch_pitched(meao_pool *p, int32_t n, const void *con
     return pool_execute_batch(p, meao::FrameSet{n, depth, depth_pitch, depth_loc, ao_out, ao_pitch, out_loc, params});
 }
 
+int32_t meao_pool_execute_batch_extents(meao_pool *p, int32_t n, const void *const *depth, void *const *ao_out, const meao_extent *extents,
+                                        const meao_params *params)
+{
+    if (!p || !depth || !ao_out || !extents) return MEAO_ERR_INVALID_ARGUMENT;
+    const int32_t G = static_cast<int32_t>(p->ctx.size());
+    if (n < 1 || n > p->max_batch * G)
+        return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, "meao_pool_execute_batch_extents: n must be 1..max_batch * members");
+    meao::FrameSet fs{n, depth, 0, MEAO_MEM_DEVICE, ao_out, 0, MEAO_MEM_DEVICE, params};
+    fs.extents = extents;
+    // every member's share against that member's capacity, before any member enqueues (no device is touched)
+    for (int32_t m = 0; m < G && m < n; ++m) {
+        meao::FrameSet::Storage mine;
+        int32_t depth_rows[MEAO_MAX_BATCH], out_rows[MEAO_MAX_BATCH];
+        bool uniform = false;
+        const int32_t rc = meao::validate_execute_batch_extents(p->ctx[m], fs.share(m, G, &mine), depth_rows, out_rows, &uniform);
+        if (rc != MEAO_OK)
+            return pool_fail(p, rc, std::string("meao_pool_execute_batch_extents: member ") + std::to_string(m) + " (frame k of its share is frame " +
+                                        std::to_string(m) + " + k x " + std::to_string(G) + "): " + meao_last_error(p->ctx[m]));
+    }
+    return pool_execute_batch(p, fs);
+}
+
 // fs: n, depth, depth_pitch and params of the announcement (params[] already checked).  width x height: the announced frames'
 // size (meao_pool_prefetch_batch_sized), 0 x 0 = the members'.
 static int32_t pool_prefetch_batch(meao_pool *p, const meao::FrameSet &fs, int32_t width = 0, int32_t height = 0)
