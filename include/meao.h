@@ -376,7 +376,21 @@ MEAO_API int32_t meao_prefetch_batch_sized(meao_ctx *ctx, int32_t width, int32_t
  * the call as a whole: the tile-count thresholds compare the sum over the frames, the 4-texel vector forms need every frame
  * eligible by its own width, pitches and pointers, and each launch has the grid of its largest frame -- workgroups beyond a
  * smaller frame's own tile count return at once.  Afterwards meao_get_intermediate / meao_debug_view (dst / out not NULL)
- * describe and return frame f's buffers at frame f's size. */
+ * describe and return frame f's buffers at frame f's size; a frame index >= n is refused (MEAO_ERR_INVALID_ARGUMENT), as after
+ * every call, and meao_reserve, meao_resize and a re-allocation take the per-frame sizes away with everything else "as left by
+ * the last execute".
+ * What the rules above imply, spelt out (tests/call_model.py models exactly this):
+ *   - "all frames share their pitches" compares row strides in texels: 0 and the packed row in bytes are the same stride.  A call
+ *     whose frames all have the context's size but two different strides is a mixed call.
+ *   - A mixed call chooses exact division as every per-frame call does: for the call, and only if every frame's parameters
+ *     (params[f], or the context's) are inside the exact range.  The ready set it promotes is stamped with that choice.
+ *   - meao_hostile_frames afterwards has one bit per frame, in frame order, as after every call.
+ *   - The ready set is consumed unmatched also when every component of its key would have matched this call (same pointers, n,
+ *     stream, strides, Z-buffer parameters): the key is not compared.
+ *   - The ready set a mixed call promotes is an ordinary one: it has the announcement's size if that was sized, else the
+ *     context's; its stride; this call's stream; it is matched, kept by meao_resize or dropped by meao_set_params like any other.
+ *   - The AO surfaces a mixed call wrote may be named by a later meao_composite_enqueue*, which reads them as it reads every AO
+ *     surface: at the CONTEXT's size under the pitch it is given.  Only frames of that size are meaningful input to it. */
 typedef struct meao_extent {
     int32_t width, height;
     uint64_t depth_pitch, ao_pitch;
@@ -618,8 +632,10 @@ MEAO_API int32_t meao_pool_execute_batch_pitched(meao_pool *pool, int32_t n, con
 MEAO_API int32_t meao_pool_prefetch_batch_pitched(meao_pool *pool, int32_t n, const void *const *depth, uint64_t depth_pitch,
                                                   const meao_params *params);
 /* meao_execute_batch_extents for the pool: frame f, extents[f] and params[f] (if given) go to member f mod G.  Every member's
- * share is validated against that member's capacity before any member enqueues; members dealt nothing do what they do for
- * meao_pool_execute_batch_pitched. */
+ * share is validated against that member's capacity before any member enqueues (one share that is refused refuses the call: no
+ * member launches and none changes); members dealt nothing do what they do for meao_pool_execute_batch_pitched (they drop the
+ * announcement and the ready set they hold).  Each member classifies ITS OWN share: a member whose share is uniform at its size
+ * makes the pitched call -- it may reuse a ready set and carry inside its last kernel -- while another member's share is mixed. */
 MEAO_API int32_t meao_pool_execute_batch_extents(meao_pool *pool, int32_t n, const void *const *depth, void *const *ao_out,
                                                  const meao_extent *extents, const meao_params *params);
 /* Dynamic resolution for the pool.  meao_pool_reserve: meao_reserve member by member; if member k fails, the members before it

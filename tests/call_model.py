@@ -23,6 +23,19 @@ What the header leaves to interpretation and this model fixes (DESIGN.md section
     one to the size the context has.  A resize to the current size is a resize like any other: it keeps nothing, since a sized
     announcement is by definition for another size.
   * A pool's announcement (announced_n) lives exactly as long as its members' shares: meao_pool_resize keeps or drops it whole.
+Mixed-size batches (meao_execute_batch_extents; Op.extents) -- what the header left open and this model fixes:
+  * `exact` of a mixed call is "every frame exact", as for every per-frame call: the context's parameters stand in for a frame
+    without params[], the frames' sizes play no part.  The ready set the call promotes carries that `exact`.
+  * The hostile mask after a mixed call has one bit per frame, in frame order, as after every call.
+  * A ready set that a mixed call consumes is reported as refused for the one reason "mixed", also when every component of its key
+    would have matched: the key is not compared.  ("mixed" is the last of KEY_COMPONENTS.)
+  * meao_get_intermediate for a frame index >= n after a mixed call is refused, as after a uniform call.
+  * A later meao_composite_enqueue* may name the outputs of a mixed call; the composite reads them tightly packed at the
+    CONTEXT's size.  The generator therefore draws only AO buffers whose last writer was a frame of the context's size with packed
+    rows (after a mixed call: the frames that happen to have the context's size and AO pitch option 0).
+  * A pool member classifies ITS OWN share: a share whose extents all equal the member's size with one pair of strides is the
+    pitched call for that member (it may reuse and carry inside its last kernel) while another member's share is mixed.
+  * Uniform extents compare strides in texels: 0 and the packed row in bytes are the same stride.
 """
 from __future__ import annotations
 
@@ -34,7 +47,8 @@ from typing import Dict, List, Optional, Tuple
 
 RING = 8                                           # meao.h: "a ring of 8 slots"
 OK, ERR_INVALID_ARGUMENT = 0, -1
-KEY_COMPONENTS = ("size", "pointer", "n", "stream", "pitch", "zb", "exact")
+KEY_COMPONENTS = ("size", "pointer", "n", "stream", "pitch", "zb", "exact", "mixed")    # "mixed": consumed by a mixed call, key not compared
+MAX_EXTENT = 32768                                 # meao.h: "outside [1, 32768]"
 PITCH_EXTRA = (0, 8, 5)                            # pitch option -> texels beyond the row: packed, 4-texel vectors possible, scalar only
 PITCH_FIXED = 408                                  # pitch option 3: this row stride whatever the width (a viewport of changing size in
 #                                                    one allocation): a frame announced at one size and asked for at another then
@@ -85,6 +99,7 @@ class ReadySet:
     sized: bool = False                         # it came from a sized announcement: a resize to its size keeps it
     size: Tuple[int, int] = (0, 0)              # of the frames its levels were built from
     kept: bool = False                          # a resize kept it
+    from_mixed: bool = False                    # coverage only: a mixed call carried it
 
 
 @dataclass(frozen=True)
@@ -110,6 +125,9 @@ class LastCall:
     reused: bool
     had_ready: bool = False                     # a ready set existed when the call was made (it is gone after it)
     shared: bool = True                         # the call used the context's parameters (no params[])
+    mixed: bool = False                         # a mixed call: every frame has its own size and row strides
+    sizes: Tuple[Tuple[int, int], ...] = ()     # per frame (the context's size at the time for every other call)
+    rows: Tuple[Tuple[int, int], ...] = ()      # per frame: (depth, AO) row stride in texels
 
 
 @dataclass
@@ -136,6 +154,16 @@ class Op:
     what: str = ""                              # invalid: bad_pitch | n_zero | n_over | bad_params | null_pointer | SIZED_INVALID
     on: str = ""                                # invalid: execute | prefetch | reserve | resize
     read_debug: bool = False                    # stepped mode: compare debug buffers after this execute
+    # execute: meao_execute_batch_extents -- one (width, height, depth pitch option, AO pitch option) per frame, the options taken
+    # at THAT frame's width; DEVICE / DEVICE.  invalid (MIXED_INVALID): the extents as the refused call passes them.
+    # (In the repr only where it is set -- see below: the digests of the older sequences are taken over repr(ops).)
+    extents: Optional[Tuple[Tuple[int, int, int, int], ...]] = field(default=None, repr=False)
+
+
+# repr(Op) is what it was before Op.extents for every operation without extents (the pinned digests), and ends in the extents for
+# an operation that has them, so that an assertion that prints a mixed call shows its sizes and pitch options.
+_op_repr = Op.__repr__
+Op.__repr__ = lambda self: _op_repr(self) if self.extents is None else "%s, extents=%r)" % (_op_repr(self)[:-1], self.extents)
 
 
 @dataclass
@@ -162,6 +190,12 @@ SIZED_INVALID = ("sized_outside_reservation", "sized_without_reservation", "size
                  "pool_resize_uncovered")
 
 
+# the invalid calls of mixed-size batches: each leaves announcement, ready set, waiting composite and last call as they were.
+# extent_pitch_below_row: Op.key says which stride (0 depth, 1 AO), Op.value which frame.
+MIXED_INVALID = ("extent_outside_capacity", "extent_zero", "extent_pitch_below_row", "extent_bad_params", "extent_n_over",
+                 "extent_outside_on_one_member")
+
+
 class ContextModel:
     def __init__(self, width, height, max_batch, param: Param, *, linear=False, rtz=True, pipelined=True, exhaustive=False,
                  cap=(0, 0)):
@@ -179,7 +213,9 @@ class ContextModel:
         self.contents: Dict[int, tuple] = {}        # the host's side of the contract: what each depth buffer holds
         self.fresh: set = set()                     # buffers refilled since a call last read them
         self.totals = {"own": 0, "carried": 0, "reused": 0, "comp_carried_launches": 0, "comp_plain_launches": 0, "per_frame": 0, "carried_more": 0,
-                       "carried_sized": 0, "kept_by_resize": 0}
+                       "carried_sized": 0, "kept_by_resize": 0, "mixed": 0, "carried_by_mixed": 0, "uniform_extents": 0}
+        self.invalidated = False                    # coverage only: a reserve or resize took the last call away since it was made
+        self.prev_stream = 0                        # coverage only: of the last execute, whatever happened since
 
     # ---- helpers
     def pitch_texels(self, option: int, width=None) -> int:
@@ -228,7 +264,7 @@ class ContextModel:
         """Everything "as left by the last execute" can be read back and compared: there was one, and its frames are unchanged."""
         return self.last is not None and self.last_intact
 
-    def invalid(self, op: Op) -> Expect:
+    def invalid(self, op: Op, pool_checked=False) -> Expect:
         """The documented status, nothing launched, state unchanged."""
         status = ERR_INVALID_ARGUMENT
         e = self._expect(status=status)
@@ -247,13 +283,44 @@ class ContextModel:
             e.events.append("invalid_" + op.what)
             if self.ann is not None and self.ann.sized:
                 e.events.append("invalid_while_sized_announced")
+        if op.what in MIXED_INVALID:
+            if not pool_checked:                     # (the pool holds the call to its rule itself: n and the shares are the pool's)
+                assert self._mixed_invalid_claim(op), ("illegal sequence: a mixed call claimed invalid that the library accepts", op)
+            e.events.append("invalid_" + op.what)
+            for what, x in (("announcement", self.ann), ("ready", self.ready), ("composite", self.comp)):
+                if x is not None:
+                    e.events.append("mixed_refused_keeps_" + what)
         if self.ann is not None:
             e.events.append("invalid_while_announced")
         if self.comp is not None:
             e.events.append("invalid_while_composite")
         if self.readable():
             e.events.append("debug_read_after_invalid")
+            if self.last.mixed:
+                e.events.append("mixed_then_debug_read")
         return e
+
+    def _mixed_invalid_claim(self, op: Op, limit=None) -> bool:
+        """The generator's claim that a mixed call is invalid, held to the rule it names: that rule refuses it, and nothing before
+        it in the validation order does."""
+        n, ext = len(op.bufs), op.extents
+        ok_n = 1 <= n <= (self.max_batch if limit is None else limit)
+        rows = None
+        if op.what == "extent_n_over":
+            return not ok_n
+        if op.what == "extent_pitch_below_row":      # the driver passes one stride of width - 1 texels: frame op.value, kind op.key
+            rows = [list(r) for r in self.extent_rows(ext)]
+            rows[op.value][op.key] = ext[op.value][0] - 1
+            ext_ok = self.check_extents(n, ext, op.params, None, limit) == OK
+            return ok_n and ext_ok and self.check_extents(n, ext, op.params, rows, limit) != OK
+        if op.what == "extent_bad_params":
+            return ok_n and op.params is not None and self.check_extents(n, ext, None, None, limit) == OK and \
+                self.check_extents(n, ext, op.params, None, limit) != OK
+        cw, ch = self.capacity()
+        bad = [(w, h) for w, h, _, _ in ext if not (1 <= w <= cw and 1 <= h <= ch)]
+        if op.what == "extent_zero":
+            return ok_n and len(bad) == 1 and 0 in bad[0]
+        return ok_n and len(bad) == 1 and min(bad[0]) >= 1       # extent_outside_capacity (for the pool: on one member)
 
     def prefetch(self, bufs, params=None, pitch=0, size=None, pitch_texels=None) -> Expect:
         """size: meao_prefetch_batch_sized.  pitch_texels: a row stride given outright instead of a pitch option (the model's own
@@ -292,12 +359,119 @@ class ContextModel:
         e.last_valid = self.last is not None
         return e
 
+    def capacity(self) -> Tuple[int, int]:
+        """'The capacity is the reservation (meao_reserve) where the context holds one, else the context's size'"""
+        return self.cap if self.cap != (0, 0) else (self.width, self.height)
+
+    def extent_rows(self, extents, rows=None):
+        """Per frame (depth, AO) row strides in texels: given outright (the model's own tests, the one illegal stride of a
+        sequence) or from the pitch options at each frame's own width."""
+        return tuple(rows) if rows is not None else tuple((row_texels(dp, w), row_texels(ap, w)) for w, h, dp, ap in extents)
+
+    def check_extents(self, n, extents, params=None, rows=None, limit=None) -> int:
+        """The validation of meao_execute_batch_extents, in the header's order: n and params[] as meao_execute_batch_params checks
+        them, then every frame's size against [1, 32768] and the capacity, then each pitch against its own frame."""
+        if not 1 <= n <= (self.max_batch if limit is None else limit) or len(extents) != n:
+            return ERR_INVALID_ARGUMENT
+        if params is not None and not all(p.valid for p in params):
+            return ERR_INVALID_ARGUMENT
+        cw, ch = self.capacity()
+        for (w, h, _, _), (drow, arow) in zip(extents, self.extent_rows(extents, rows)):
+            if not (1 <= w <= MAX_EXTENT and 1 <= h <= MAX_EXTENT) or w > cw or h > ch:
+                return ERR_INVALID_ARGUMENT
+            if drow < w or arow < w:
+                return ERR_INVALID_ARGUMENT
+        return OK
+
+    def extents_uniform(self, extents, rows=None) -> bool:
+        """'every extent equals the context's size and all frames share their pitches' (strides compared in texels)"""
+        r = self.extent_rows(extents, rows)
+        return all((w, h) == (self.width, self.height) for w, h, _, _ in extents) and len(set(r)) == 1
+
+    def execute_extents(self, bufs, outs, extents, params=None, stream=0, rows=None) -> Expect:
+        """meao_execute_batch_extents.  A refused call changes nothing; uniform extents ARE the pitched call; every other call is
+        a mixed call."""
+        n = len(bufs)
+        if len(outs) != n or self.check_extents(n, extents, params, rows) != OK:
+            return self._expect(status=ERR_INVALID_ARGUMENT)
+        r = self.extent_rows(extents, rows)
+        if self.extents_uniform(extents, rows):
+            had_ready, had_ann = self.ready is not None, self.ann is not None
+            e = self._execute(bufs, outs, params, stream=stream, depth_rows=r[0][0], out_rows=r[0][1])
+            self.totals["uniform_extents"] += 1
+            e.events.append("uniform_extents")
+            if e.reused:
+                e.events.append("uniform_extents_reuses")
+            if had_ann:
+                e.events.append("uniform_extents_carries")
+            return e
+        prm = tuple(params) if params is not None else (self.param,) * n
+        exact = self._exact(prm)                    # "every frame exact", as for every per-frame call
+        e = Expect(launched=True, exact=exact, own_pass=True, per_frame=True)
+        e.events.append("mixed_call")
+        if any(b in self.fresh for b in bufs):
+            e.events.append("refilled_before_call")
+        if self.last is None and self.invalidated:
+            e.events.append("mixed_after_invalidation")
+        if stream != self.prev_stream:
+            e.events.append("mixed_on_other_stream")
+        # a waiting composite runs first as plain launches, also when the call has no params[]
+        if self.comp is not None:
+            self._run_comp_plain(e, "mixed_call")
+            e.events.append("mixed_flushes_composite")
+        # a ready set is consumed unmatched: its key is not compared
+        had_ready = self.ready is not None
+        if had_ready:
+            e.refused = ("mixed",)
+            e.events.append("mixed_consumes_ready")
+            if tuple(bufs) == self.ready.bufs and stream == self.ready.stream:
+                e.events.append("mixed_consumes_ready_same_buffers")
+        self.ready = self.dropped = None
+        # an announcement of any kind is carried, as a launch of its own, and promoted as usual
+        a = self.ann
+        if a is not None:
+            e.carried = a
+            aprm = a.params if a.params is not None else (self.param,) * len(a.bufs)
+            self.ready = ReadySet(a.bufs, stream, a.pitch, tuple(p.zb(self.linear) for p in aprm), exact, a.sized,
+                                  a.size if a.sized else (self.width, self.height), from_mixed=True)
+            self.ann = None
+            self.totals["carried_by_mixed"] += 1
+            kinds = [k for k, is_k in (("sized", a.sized), ("per_frame", a.params is not None), ("pitched", a.pitch != a.size[0])) if is_k]
+            e.events += ["mixed_carries_" + k for k in kinds or ["plain"]]
+            if a.sized:
+                self.totals["carried_sized"] += 1
+                e.events.append("sized_carried")
+            if len(a.bufs) > n:
+                self.totals["carried_more"] += 1
+                e.events.append("mixed_carries_more_frames_than_n")
+        if params is None and (a is None or a.params is None):
+            e.events.append("mixed_shared_params_takes_ring_slot")
+        self.ring = (self.ring + 1) % RING
+        self.totals["per_frame"] += 1
+        for b in bufs:
+            self.fresh.discard(b)
+        self.last = LastCall(n, prm, tuple(bufs), tuple(outs), -1, -1, False, False, stream, exact, False, had_ready, params is None,
+                             True, tuple((w, h) for w, h, _, _ in extents), r)
+        self.last_intact, self.invalidated, self.prev_stream = True, False, stream
+        self.totals["own"] += 1
+        self.totals["mixed"] += 1
+        self.totals["carried"] += a is not None
+        e.last_valid = True
+        return e
+
     def execute(self, bufs, outs, params=None, pitch=0, out_pitch=0, depth_host=False, out_host=False, stream=0) -> Expect:
+        return self._execute(bufs, outs, params, pitch, out_pitch, depth_host, out_host, stream)
+
+    def _execute(self, bufs, outs, params=None, pitch=0, out_pitch=0, depth_host=False, out_host=False, stream=0, depth_rows=None,
+                 out_rows=None) -> Expect:
+        """depth_rows / out_rows: the row strides in texels given outright (uniform extents), instead of the pitch options."""
         n = len(bufs)
         assert 1 <= n <= self.max_batch and len(outs) == n
         prm = tuple(params) if params is not None else (self.param,) * n
         exact = self._exact(prm)
         depth_pitch = self.width if depth_host else self.pitch_texels(pitch)      # HOST frames are staged packed
+        if depth_rows is not None:
+            depth_pitch = depth_rows
         assert depth_pitch >= self.width, "illegal sequence: a row stride below the width"
         e = Expect(launched=True, exact=exact)
         for b in bufs:
@@ -384,9 +558,10 @@ class ContextModel:
 
         for b in bufs:
             self.fresh.discard(b)
-        self.last = LastCall(n, prm, tuple(bufs), tuple(outs), depth_pitch, self.width if out_host else self.pitch_texels(out_pitch),
-                             depth_host, out_host, stream, exact, e.reused, r is not None, params is None)
-        self.last_intact = True
+        out_texels = self.width if out_host else self.pitch_texels(out_pitch) if out_rows is None else out_rows
+        self.last = LastCall(n, prm, tuple(bufs), tuple(outs), depth_pitch, out_texels, depth_host, out_host, stream, exact, e.reused,
+                             r is not None, params is None, False, ((self.width, self.height),) * n, ((depth_pitch, out_texels),) * n)
+        self.last_intact, self.invalidated, self.prev_stream = True, False, stream
         self.totals["own"] += e.own_pass
         self.totals["reused"] += e.reused
         self.totals["carried"] += e.carried is not None
@@ -401,6 +576,8 @@ class ContextModel:
             e.events.append("ready_dropped_by_set_params")
         if self.readable() and self.last.shared and param != self.param:
             e.events.append("debug_read_after_set_params")     # the last call's parameters are no longer the context's
+            if self.last.mixed:
+                e.events.append("mixed_then_debug_read")
         self.param, self.ann, self.ready, self.dropped = param, None, None, None
         e.comp_pending = len(self.comp.ao) if self.comp else 0
         e.last_valid = self.last is not None
@@ -419,6 +596,8 @@ class ContextModel:
                 continue
             if keep(x):
                 e.events.append("sized_%s_kept_by_resize" % what)
+                if what == "ready" and x.from_mixed:
+                    e.events.append("sized_ready_from_mixed_kept_by_resize")
                 self.totals["kept_by_resize"] += 1
                 if e.comp_plain:
                     e.events.append("comp_flushed_and_sized_kept")
@@ -439,9 +618,17 @@ class ContextModel:
             self.cap = (max(self.cap[0], width), max(self.cap[1], height))
             e.events.append("resize_grows_reservation")
         self.width, self.height = width, height
-        self.last = None
+        self._invalidate_last(e)
         e.comp_pending = 0
         return e
+
+    def _invalidate_last(self, e: Expect) -> None:
+        """A reserve or a resize: nothing "as left by the last execute" is left, per-frame sizes included."""
+        if self.last is not None:
+            self.invalidated = True
+            if self.last.mixed:
+                e.events.append("mixed_then_reserve_invalidates")
+        self.last = None
 
     def reserve(self, width, height) -> Expect:
         """meao_reserve.  (0, 0) drops the reservation; anything else must cover the current size."""
@@ -460,7 +647,8 @@ class ContextModel:
             if self.ready is not None and self.ready.sized:
                 e.events.append("reservation_dropped_with_sized_ready")
         self.cap = (width, height)
-        self.ann = self.ready = self.last = self.dropped = None     # the buffers moved: nothing "as left by the last execute" is left
+        self.ann = self.ready = self.dropped = None                 # the buffers moved: nothing "as left by the last execute" is left
+        self._invalidate_last(e)
         e.comp_pending = len(self.comp.ao) if self.comp else 0
         return e
 
@@ -484,6 +672,8 @@ class ContextModel:
         e = self._expect()                          # a launch-structure key: no change of any result
         if self.readable():
             e.events.append("debug_read_after_debug_set")
+            if self.last.mixed:
+                e.events.append("mixed_then_debug_read")
         return e
 
     def drop_announcement(self, ready_too: bool) -> None:
@@ -499,6 +689,12 @@ class ContextModel:
         if k == "prefetch":
             e = self.prefetch(op.bufs, op.params, op.pitch, op.size)
             assert e.status == OK, ("illegal sequence: an announcement the library refuses", op)
+            return e
+        if k == "execute" and op.extents is not None:
+            e = self.execute_extents(op.bufs, op.outs, op.extents, op.params, op.stream)
+            assert e.status == OK, ("illegal sequence: a mixed call the library refuses", op)
+            if op.read_debug and self.last.mixed:
+                e.events.append("mixed_then_debug_read")
             return e
         if k == "execute":
             return self.execute(op.bufs, op.outs, op.params, op.pitch, op.out_pitch, op.depth_host, op.out_host, op.stream)
@@ -546,6 +742,40 @@ class PoolModel:
     def ao_waiting(self, buf):
         return any(c.ao_waiting(buf) for c in self.members)
 
+    def check_extents(self, op: Op, claimed=False) -> int:
+        """meao_pool_execute_batch_extents: n against max_batch x members, then every member's share by that member's rules, before
+        any member is given work.  claimed: an invalid Op -- the rule it names must be the one that refuses it."""
+        n = len(op.bufs)
+        if claimed and op.what == "extent_n_over":
+            return OK if 1 <= n <= self.max_batch * self.G else ERR_INVALID_ARGUMENT
+        if not 1 <= n <= self.max_batch * self.G:
+            assert not claimed, op
+            return ERR_INVALID_ARGUMENT
+        bad = 0
+        for m, c in enumerate(self.members[:n]):
+            sub = dataclasses.replace(op, bufs=self.share(m, op.bufs), extents=self.share(m, op.extents),
+                                      params=None if op.params is None else self.share(m, op.params))
+            if claimed:
+                if op.what == "extent_pitch_below_row":
+                    mine = op.value % self.G == m
+                    sub.value = op.value // self.G
+                    ok = c._mixed_invalid_claim(sub) if mine else c.check_extents(len(sub.bufs), sub.extents, sub.params) == OK
+                    bad += mine and ok
+                    assert ok, op
+                elif op.what == "extent_bad_params":
+                    bad += c._mixed_invalid_claim(sub)
+                else:
+                    refused = c.check_extents(len(sub.bufs), sub.extents, sub.params) != OK
+                    assert not refused or c._mixed_invalid_claim(sub), op
+                    bad += refused
+            elif c.check_extents(len(sub.bufs), sub.extents, sub.params) != OK:
+                return ERR_INVALID_ARGUMENT
+        if claimed:
+            if op.what == "extent_outside_on_one_member":
+                assert bad == 1, op                   # one member's share is refused, the others' are fine: still nobody runs
+            return ERR_INVALID_ARGUMENT if bad else OK
+        return OK
+
     def _deal(self, op: Op, idle=None) -> List[Optional[Expect]]:
         out = []
         n = len(op.bufs)
@@ -556,7 +786,8 @@ class PoolModel:
                 out.append(None)
                 continue
             sub = dataclasses.replace(op, bufs=self.share(m, op.bufs), outs=self.share(m, op.outs), colors=self.share(m, op.colors),
-                                      params=None if op.params is None else self.share(m, op.params))
+                                      params=None if op.params is None else self.share(m, op.params),
+                                      extents=None if op.extents is None else self.share(m, op.extents))
             out.append(c.apply(sub))
         return out
 
@@ -574,6 +805,11 @@ class PoolModel:
             return [c._expect() for c in self.members]
         if k == "execute":
             n = len(op.bufs)
+            kinds = None
+            if op.extents is not None:
+                # "Every member's share is validated against that member's capacity before any member enqueues"
+                assert self.check_extents(op) == OK, ("illegal sequence: a mixed pool call the library refuses", op)
+                kinds = [c.extents_uniform(self.share(m, op.extents)) for m, c in enumerate(self.members[:n])]
             idle_sized = [c for c in self.members[n:] if (c.ann is not None and c.ann.sized) or (c.ready is not None and c.ready.sized)]
             out = self._deal(op, lambda c: c.drop_announcement(True))
             ev = out[0].events
@@ -589,6 +825,13 @@ class PoolModel:
             if self.announced_n is not None and self.announced_n != n:
                 ev.append("pool_n_differs_from_announced")
             self.announced_n = None
+            if kinds is not None and not all(kinds):
+                if any(kinds):                       # each member classifies its own share
+                    ev.append("pool_member_uniform_while_other_mixed")
+                    if any(u and x.reused for u, x in zip(kinds, out)):
+                        ev.append("pool_member_uniform_reuses_while_other_mixed")
+                if n < self.G:
+                    ev.append("pool_mixed_idle_member")
             return out
         if k == "prefetch":
             self.announced_n = len(op.bufs)
@@ -596,7 +839,11 @@ class PoolModel:
         if k == "comp_enqueue":
             return self._deal(op)
         if k == "invalid":
-            out = [c.invalid(op) for c in self.members]
+            if op.what in MIXED_INVALID:
+                assert self.check_extents(op, claimed=True) != OK, ("illegal sequence: a mixed pool call claimed invalid", op)
+            out = [c.invalid(op, pool_checked=True) for c in self.members]
+            if op.what in MIXED_INVALID:
+                out[0].events.append("pool_mixed_refused_whole")
             for e in out[1:]:
                 e.events = [x for x in e.events if x not in out[0].events]      # a coverage class counts once per pool call
             return out
@@ -658,6 +905,10 @@ class Profile:
     p_sized_then_resize: float = 0.0   # a sized announcement is followed by execute and a resize to its size (the header's frame
     #                                    loop), or by that resize at once
     outside_sizes: Tuple[Tuple[int, int], ...] = ()   # sizes no reservation of the sequence covers at first: stepped resizes go there
+    # mixed-size batches (meao_execute_batch_extents); the defaults draw nothing of them, and no random number for them
+    p_mixed: float = 0.0               # share of executes that are mixed calls
+    p_uniform_extents: float = 0.0     # share of the other DEVICE / DEVICE executes that go through the extents call, all frames alike
+    mixed_sizes: Tuple[Tuple[int, int], ...] = ()     # the sizes a mixed call's frames draw from (those inside the capacity)
 
 N_CONTENTS = 12                        # content keys are ("synth" | "hostile" | "hostile_level", seed < N_CONTENTS)
 DEBUG_KEYS = ((0, (0, 1)), (1, (0, 1024)), (2, (0, 256)), (3, (0, 2048)), (4, (0, 640)), (5, (0, 1, 4096)))   # meao_debug_key -> values
@@ -815,7 +1066,68 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
                 prm = base[:i] + (rng.choice(same_rest),) + base[i + 1:]
         return bufs, prm, pitch, stream
 
+    def fits(size):
+        cw, ch = one.capacity()
+        return size[0] <= cw and size[1] <= ch
+
+    def frame_depth(size, pitch, avoid):
+        """(buffer, fillable) for one frame of a mixed call: one that holds a frame of `size` under `pitch` or may be given one
+        now; failing that any other, read under the frame's own size and stride whatever was laid out in it."""
+        once = bool(G) and P.free_running
+        ok = [b for b in range(P.n_depth) if b not in avoid and
+              (laid.get(b) == (size, pitch) or (not model.referenced(b) and not (once and b in model.contents)))]
+        if ok:
+            return rng.choice(ok), True
+        return rng.choice([b for b in range(P.n_depth) if b not in avoid]), False
+
+    def do_mixed_execute():
+        """meao_execute_batch_extents with frames that are not all the context's size; False: no such sizes fit the capacity."""
+        cur = cur_size()
+        sizes_in = [s for s in P.mixed_sizes if fits(s)]
+        others = [s for s in sizes_in if s != cur]
+        if not others:
+            return False
+        stream, promised = st["stream"], st["promised"]
+        same = promised is not None and held("ready") and rng.random() < 0.4
+        if same:
+            bufs = promised.bufs                     # the ready set's own buffers, so that "mixed" is all that refuses it
+        else:
+            bufs = None
+            if not G and rng.random() < max(P.p_other_stream, 0.25):
+                stream = 1 - stream
+        n = len(bufs) if same else rng.randint(1, cap)
+        ext = [list(rng.choice(sizes_in)) + [pitch_option(), pitch_option()] for _ in range(n)]
+        if G and n > 1 and rng.random() < 0.5:
+            # one member's share alike at the members' size (with the announced stride where the frames are the announced ones):
+            # that member makes the pitched call, and may reuse, while the others make mixed calls
+            m = rng.randrange(min(G, n))
+            for f in range(m, n, G):
+                ext[f] = [cur[0], cur[1], promised.pitch if same and promised.size is None and promised.pitch != 3 else 0, 0]
+        if all(tuple(x[:2]) == cur for x in ext):
+            f = rng.randrange(n)
+            ext[f][:2] = rng.choice(others)
+        if not same:
+            chosen = []
+            for w, h, dp, _ in ext:
+                b, fillable = frame_depth((w, h), dp, chosen)
+                if fillable:
+                    maybe_refill((b,), dp, (w, h))
+                chosen.append(b)
+            bufs = tuple(chosen)
+        prm = draw_params(n) if rng.random() < P.p_per_frame else None
+        outs = draw_outs(n)
+        if len(outs) < n:
+            emit(Op("comp_flush"))
+            outs = draw_outs(n)
+        op = Op("execute", bufs=tuple(bufs), outs=outs, params=prm, stream=stream, read_debug=not P.free_running,
+                extents=tuple(tuple(x) for x in ext))
+        emit(op)
+        after_execute(op, prm, stream)
+        return True
+
     def do_execute():
+        if P.p_mixed and not st.get("honour", False) and rng.random() < P.p_mixed and do_mixed_execute():
+            return
         stream = st["stream"]
         host_d = host_o = False
         promised = st["promised"]
@@ -854,8 +1166,18 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
             outs = draw_outs(len(bufs))
         op = Op("execute", bufs=bufs, outs=outs, params=prm, pitch=pitch, out_pitch=0 if host_o else pitch_option(),
                 depth_host=host_d, out_host=host_o, stream=stream, read_debug=not P.free_running)
+        # (three times as often where the call asks for what it was promised: the extents call must reuse as the pitched call does)
+        if P.p_uniform_extents and not host_d and not host_o and not (pitch == 3 and model.width > PITCH_FIXED) and \
+                rng.random() < P.p_uniform_extents * (3 if promised is not None and r < P.p_honour else 1):
+            # the extents call with every frame alike at the context's size: the pitched call in every respect
+            op.extents = ((model.width, model.height, op.pitch, op.out_pitch),) * len(bufs)
         emit(op)
+        after_execute(op, prm, stream)
+
+    def after_execute(op, prm, stream):
         st.update(stream=stream, promised=st["announced"], announced=None, last_exec=op)
+        if P.p_mixed and st["promised"] is not None and rng.random() < 0.15:
+            do_invalid(rng.choice(MIXED_INVALID))    # a refused mixed call while a ready set waits: it stays
         loop, st["loop"] = st["loop"], None
         if loop is not None and any(c.ready is not None and c.ready.sized and c.ready.size == loop for c in (model.members if G else [model])):
             if not op.out_host and op.out_pitch == 0 and rng.random() < 0.3:
@@ -877,6 +1199,15 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
 
     def do_comp_enqueue(depth=0):
         le = st["last_exec"]
+        if le is not None and le.extents is not None and not one.extents_uniform(le.extents):
+            # after a mixed call: the frames that have the context's size and packed AO rows, in the pool the leading ones (frame
+            # k of the composite goes to member k mod G, which must be the member that produced it)
+            ok = [x[:2] == cur_size() and x[3] == 0 for x in le.extents]
+            lead = ok.index(False) if False in ok else len(ok)
+            elig = tuple(o for o, good in zip(le.outs, ok) if good) if not G else le.outs[:lead]
+            if not elig:
+                return do_execute() if depth == 0 else None
+            le = dataclasses.replace(le, outs=elig)
         if le is None or le.out_host or le.out_pitch != 0:      # composites take tightly packed DEVICE surfaces
             return do_execute()
         waiting = model.comp.color if not G and model.comp else ()
@@ -886,6 +1217,11 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
         colors = tuple(free[:k]) if not G else tuple(range(k) if st["flip"] else range(half, half + k))
         st["flip"] = not st["flip"]
         emit(Op("comp_enqueue", bufs=le.outs[:k], colors=colors, mode=rng.choice((0, 2))))
+        if P.p_mixed and depth == 0 and rng.random() < P.p_mixed:
+            if rng.random() < 0.3:
+                do_invalid(rng.choice(MIXED_INVALID))      # a refused mixed call leaves the batch waiting ...
+            if do_mixed_execute():                   # ... and a mixed call runs it first as plain launches, params[] or not
+                return
         r = rng.random()                             # what ends a wait other than the next call
         if depth == 0 and r < P.p_comp_ended_early:
             ender = rng.choice([lambda: emit(Op("comp_flush")), lambda: do_comp_enqueue(1), do_invalid, do_invalid] +
@@ -912,7 +1248,37 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
             return Op("invalid", what=what, on="resize", size=rng.choice(beyond))
         return None
 
+    def mixed_invalid(what):
+        """A mixed call the library must refuse for the rule `what` names and no other; None: not possible now."""
+        sizes_in = [s for s in P.mixed_sizes if fits(s)]
+        n = cap + 1 if what == "extent_n_over" else rng.randint(1, cap)
+        if not sizes_in or (what == "extent_outside_on_one_member" and (not G or n < 2)) or (what == "extent_bad_params" and not bad):
+            return None
+        cw, ch = one.capacity()
+        ext = [list(rng.choice(sizes_in)) + [pitch_option(), pitch_option()] for _ in range(n)]
+        f = rng.randrange(n)
+        prm, key = None, 0
+        if what in ("extent_outside_capacity", "extent_outside_on_one_member"):
+            ext[f][:2] = rng.choice(((cw + 16, ext[f][1]), (ext[f][0], ch + 8)))
+        elif what == "extent_zero":
+            ext[f][rng.randrange(2)] = 0
+        elif what == "extent_bad_params":
+            prm = tuple(bad[0] if i == f else rng.choice(valid) for i in range(n))
+        elif what == "extent_pitch_below_row":
+            key = rng.randrange(2)                   # the depth stride or the AO stride of frame f: one texel short of its row
+        elif rng.random() < P.p_per_frame:
+            prm = draw_params(n)
+        return Op("invalid", what=what, on="execute", bufs=legal_depth(min(n, P.n_depth)), outs=tuple(range(n)), params=prm,
+                  stream=st["stream"], extents=tuple(tuple(x) for x in ext), key=key, value=f)
+
     def do_invalid(what=None):
+        if what is None and P.p_mixed and rng.random() < 0.5:
+            what = rng.choice(MIXED_INVALID)
+        if what in MIXED_INVALID:
+            op = mixed_invalid(what)
+            if op is not None:
+                return emit(op)
+            what = None
         if what is None and P.reserve and rng.random() < 0.5:
             what = rng.choice(SIZED_INVALID)
         if what is not None:
@@ -1007,6 +1373,30 @@ def generate(seed: int, profile: Profile, palette: List[Param], start_param: Par
     return ops
 
 
+def header_lets_it_ride(a: Announcement, n: int, size, f32_depth: bool) -> bool:
+    """What include/meao.h names as needed for an announced pass to run INSIDE the last kernel of a carrier that is not a mixed
+    call (meao_prefetch_batch, meao_prefetch_batch_sized): f32 depth, the announced width % 8 == 0 under a stride of whole
+    4-texel vectors (aligned frames are the driver's: every surface is), no more frames than the carrier's n, and
+    ceil(w / 128) x ceil(h / 32) announced tiles within the carrier's ceil(W / 64) x ceil(H / 64).  Necessary, not sufficient:
+    "host code decides".  The model predicts nothing from it; the free-running tests bound the fused launches of a trace by it."""
+    (w, h), up = a.size, lambda x, t: -(-x // t)
+    return f32_depth and w % 8 == 0 and a.pitch % 4 == 0 and len(a.bufs) <= n and \
+        up(w, 128) * up(h, 32) <= up(size[0], 64) * up(size[1], 64)
+
+
+def may_ride_count(ops, model, f32_depth=True) -> int:
+    """The carried passes of a sequence that the header lets ride (never one a mixed call carries), over all members."""
+    count = 0
+    for op in ops:
+        e = model.apply(op)
+        if op.kind == "execute":
+            members = model.members if isinstance(e, list) else [model]
+            for m, x in enumerate(e if isinstance(e, list) else [e]):
+                if x is not None and x.carried is not None and "mixed_call" not in x.events:
+                    count += header_lets_it_ride(x.carried, len(op.bufs[m::len(members)]), (members[m].width, members[m].height), f32_depth)
+    return count
+
+
 def replay(ops, model):
     """[(op, expect)] through `model` (a fresh one): what the GPU tests hold the library to, and what the coverage tests count.
     For a PoolModel the expectation is the list of the members'."""
@@ -1091,8 +1481,33 @@ DYN_POOL_CASES = {"pool2": dict(seed=1068, members=2), "pool3": dict(seed=1046, 
 DYN_POOL_FREE_SEEDS = {"pool2": 2387, "pool3": 1352}
 
 
+# Mixed-size batches (tests/test_mixed_size_sequences_gpu.py): the dynamic-resolution profiles, whose executes are now often mixed
+# calls.  The frames draw from the four sizes the context moves between and from four more, the smallest shapes that still have one
+# tile in every pass: an odd width, a frame taller but narrower than another (97 x 61 against 129 x 65 and 257 x 31), one wider but
+# shorter.
+MIX_SIZES = DYN_SIZES + ((33, 17), (97, 61), (129, 65), (257, 31))
+MIX = dict(p_mixed=0.4, p_uniform_extents=0.1, mixed_sizes=MIX_SIZES)
+MIX_STEPPED = dataclasses.replace(DYN_STEPPED, length=44, **MIX)
+MIX_FREE = dataclasses.replace(DYN_FREE, length=44, **MIX)
+MIX_POOL = dict(DYN_POOL, max_batch=4, n_depth=20, n_out=26, **MIX)
+MIX_CASES = {name: dict(c, seed=seed) for (name, c), seed in zip(CASES.items(), (166, 349, 324, 16, 92))}
+MIX_FREE_CASES = {name: dict(c, seed=seed) for (name, c), seed in zip(FREE_CASES.items(), (545, 722, 38))}
+MIX_POOL_CASES = {"pool2": dict(seed=7, members=2), "pool3": dict(seed=90, members=3)}
+MIX_POOL_FREE_SEEDS = {"pool2": 147, "pool3": 333}
+
+
 def case_profile(kind: str, name: str):
-    """(config, profile, seed) of a committed case: kind = stepped | free | pool_stepped | pool_free, or dyn_ + one of them."""
+    """(config, profile, seed) of a committed case: kind = stepped | free | pool_stepped | pool_free, or dyn_ / mix_ + one of them."""
+    if kind.startswith("mix_"):
+        base = kind[4:]
+        if base.startswith("pool"):
+            c = MIX_POOL_CASES[name]
+            free = base == "pool_free"
+            shape = dict(MIX_POOL, n_depth=64) if free else MIX_POOL
+            prof = Profile(pool=c["members"], free_running=free, p_refill=0.0 if free else 0.7, **shape)
+            return c, prof, MIX_POOL_FREE_SEEDS[name] if free else c["seed"]
+        c = (MIX_CASES if base == "stepped" else MIX_FREE_CASES)[name]
+        return c, (MIX_STEPPED if base == "stepped" else MIX_FREE), c["seed"]
     dyn, base = kind.startswith("dyn_"), kind[4:] if kind.startswith("dyn_") else kind
     if base.startswith("pool"):
         c = (DYN_POOL_CASES if dyn else POOL_CASES)[name]
@@ -1133,6 +1548,13 @@ def dynamic_sequences():
     """Every (kind, name) tests/test_dynamic_resolution_sequences_gpu.py adds."""
     out = [("dyn_stepped", n) for n in DYN_CASES] + [("dyn_free", n) for n in DYN_FREE_CASES]
     out += [(k, n) for k in ("dyn_pool_stepped", "dyn_pool_free") for n in DYN_POOL_CASES]
+    return out
+
+
+def mixed_sequences():
+    """Every (kind, name) tests/test_mixed_size_sequences_gpu.py adds."""
+    out = [("mix_stepped", n) for n in MIX_CASES] + [("mix_free", n) for n in MIX_FREE_CASES]
+    out += [(k, n) for k in ("mix_pool_stepped", "mix_pool_free") for n in MIX_POOL_CASES]
     return out
 
 

@@ -1,6 +1,7 @@
 """CPU tests of tests/call_model.py: the committed sequences of tests/test_call_sequences_gpu.py reach the histories they are there
 for, and the model says what include/meao.h says (hand-written sequences, expectations typed in from the header -- so that a model
 bug cannot cancel a library bug of the same shape)."""
+import dataclasses
 from collections import Counter
 
 import pytest
@@ -143,7 +144,10 @@ def test_each_key_component_refuses_on_its_own(component):
         c = ctx(cap=(400, 272))
         c.prefetch((1, 2), params=(P0, P1), pitch=1, size=(380, 250))
         c.execute((5, 6), (0, 1), params=carrier, stream=0)
-    e = c.execute(**call)
+    if component == "mixed":                    # exactly what was announced, through the extents call with one frame smaller
+        e = c.execute_extents(call["bufs"], call["outs"], ((384, 256, 1, 0), (200, 120, 1, 0)), params=call["params"], stream=0)
+    else:
+        e = c.execute(**call)
     assert e.own_pass and e.refused == (component,)
 
 
@@ -341,13 +345,27 @@ PINNED = {
     "reserved/r8_rtz_f32": "db8512aa5f49068b697e0ba2fcd3f6d2945e274f8b005d9329e4782602964d2c",
     "reserved/f16_rtne_unorm16": "5677a0815ae24cf818b5ae6e40e067335d2bfa6c3b0a0cf3422e5480db0dc364",
     "reserved/r8_rtz_hq2": "25f1c508858f58c96de7d4dc78c0461473683d3854e4f70b4ba275d5f17e8653",
+    # the dynamic-resolution sequences, computed with the generator as it was before it learnt mixed-size batches
+    "dyn_stepped/r8_rtz_f32": "b63680cc0e484405e7037df2df784bda30871ad2997fbf5c83283254b4e2c788",
+    "dyn_stepped/f16_rtne_unorm16": "3e546a97d7d5e49f950589833f790541a5ee2542fcde85b033faf4940841e639",
+    "dyn_stepped/r8_rtz_linear_f32": "0cd951a3ab9a3be4474a63759ea5f3cc8e7a91a0785f1221ef178aeca9e85d4f",
+    "dyn_stepped/r8_rtz_hq2": "955dab6ec8347739d9d55f42c7cfbd00df440812212c3694a09e134e9db2d96d",
+    "dyn_stepped/r8_rtz_not_pipelined": "e7893446a622c282a8f75245695d08d80000b38afcd75d2b2439fcff3498beec",
+    "dyn_free/r8_rtz_f32": "e954afdcb26a00b4605d8113188285d7b945199dca6bfd73a80eab27d87742fc",
+    "dyn_free/r8_rtz_linear_f32": "8e6d0206465b78f2c6668dae2c95493c3a35e919791e0e8e1984422c42b98b25",
+    "dyn_free/f16_rtne_unorm16": "91e7cde6e445e9b5dcca9d2e21bc63876183c23dc696ddb71488db04a48fd746",
+    "dyn_pool_stepped/pool2": "36d31b5ac7f3502a8880c44702447a333a531c4c47584ba9eb2fce864070cd4d",
+    "dyn_pool_stepped/pool3": "6b1388b2f47ab1fc1d08a5c70516678ff7dbfb3b102a69f09e13e3d391da4ddd",
+    "dyn_pool_free/pool2": "97730b7be043aae6bf92032434178ebfa602f427a239e6b21940717cdbb02508",
+    "dyn_pool_free/pool3": "f21e9e2ce79627065d0d6fc982787ddf593fbe8c8e567a00c1f7617c08fa40a3",
 }
 
 
 def test_older_sequences_are_what_they_were():
     import hashlib
     from tests import test_dynamic_resolution_sequences_gpu as D
-    got = {"%s/%s" % (kind, name): M.case_sequence(kind, name)[0] for kind, name in M.committed_sequences()}
+    got = {"%s/%s" % (kind, name): M.case_sequence(kind, name)[0] for kind, name in M.committed_sequences() + M.dynamic_sequences()}
+    assert not any(op.extents is not None for ops in got.values() for op in ops)     # (Op.extents is not in the repr)
     got.update({"reserved/" + name: D.sequence(cfg)[0] for name, cfg in D.CASES.items()})
     assert set(got) == set(PINNED)
     for key, ops in got.items():
@@ -757,3 +775,354 @@ def test_a_call_for_what_a_resize_dropped_is_a_coverage_class_of_its_own():
     c.execute((5,), (0,))
     c.resize(200, 120)
     assert "asked_for_what_a_resize_dropped" not in c.execute((1,), (0,)).events      # another size: nothing would have matched
+
+
+# ---- mixed-size batches: the committed seeds of the new cases reach every rule
+
+REQUIRED_MIXED = [
+    "mixed_flushes_composite", "mixed_consumes_ready", "mixed_consumes_ready_same_buffers", "mixed_carries_plain",
+    "mixed_carries_pitched", "mixed_carries_per_frame", "mixed_carries_sized", "mixed_carries_more_frames_than_n",
+    "mixed_shared_params_takes_ring_slot", "sized_ready_from_mixed_kept_by_resize", "uniform_extents_reuses",
+    "uniform_extents_carries", "mixed_refused_keeps_announcement", "mixed_refused_keeps_ready", "mixed_refused_keeps_composite",
+    "mixed_then_debug_read", "mixed_then_reserve_invalidates", "mixed_after_invalidation", "mixed_on_other_stream",
+    "pool_member_uniform_while_other_mixed", "pool_mixed_idle_member", "pool_mixed_refused_whole",
+] + ["invalid_" + what for what in M.MIXED_INVALID]
+
+
+@pytest.fixture(scope="module")
+def mixed():
+    total = Counter()
+    per_case = {}
+    for kind, name in M.mixed_sequences():
+        ops, model = M.case_sequence(kind, name)
+        per_case[(kind, name)] = Counter(M.events_of(ops, model))
+        total += per_case[(kind, name)]
+    return total, per_case
+
+
+@pytest.mark.parametrize("event", REQUIRED_MIXED)
+def test_mixed_sequences_reach(mixed, event):
+    total, _ = mixed
+    assert total[event] >= 2, (event, total[event])       # more than once: no rule rests on a single operation of a single seed
+
+
+def test_every_mixed_case_carries_consumes_and_refuses(mixed):
+    """Each case on its own: mixed calls that carry an announcement, one that consumes a ready set, one that is refused."""
+    _, per_case = mixed
+    for case, ev in per_case.items():
+        assert ev["mixed_call"] >= 8 and ev["mixed_consumes_ready"] and ev["uniform_extents"], (case, ev["mixed_call"])
+        assert sum(ev["mixed_carries_" + k] for k in ("plain", "pitched", "per_frame", "sized")) >= 3, case
+        assert sum(ev["invalid_" + what] for what in M.MIXED_INVALID) >= 1, case
+
+
+def test_mixed_sequences_are_deterministic_and_legal():
+    for kind, name in M.mixed_sequences():
+        a, model = M.case_sequence(kind, name)
+        b, _ = M.case_sequence(kind, name)
+        assert a == b
+        M.replay(a, model)                      # the model asserts legality: refills, refused calls held to the rule they name
+        assert sum(op.kind != "refill" for op in a) >= 40 and sum(op.kind == "execute" for op in a) >= 12, (kind, name)
+        one = M.fresh_model(M.case_profile(kind, name)[1], M.case_profile(kind, name)[0])
+        laid = {}
+        for op in a:
+            c = one.members[0] if kind.startswith("mix_pool") else one
+            cur, cap = (c.width, c.height), c.capacity()
+            if op.kind == "refill":
+                laid.update({x: (op.size or cur, op.pitch) for x in op.bufs})
+            if op.kind == "execute" and op.extents is not None:
+                assert not (op.depth_host or op.out_host) and len(op.extents) == len(op.bufs) == len(op.outs), (kind, name, op)
+                assert all(s[:2] in M.MIX_SIZES and s[0] <= cap[0] and s[1] <= cap[1] for s in op.extents), (kind, name, op)
+                if not c.extents_uniform(op.extents) and not kind.startswith("mix_pool"):
+                    assert any(s[:2] != cur for s in op.extents) or len({s[2:] for s in op.extents}) > 1, (kind, name, op)
+            if op.kind == "comp_enqueue":
+                # a composite reads AO surfaces packed at the context's size: after a mixed call only such frames are named
+                last = [x for x in a[:a.index(op)] if x.kind == "execute"][-1]
+                if last.extents is not None:
+                    for o in op.bufs:
+                        assert last.extents[last.outs.index(o)][:2] == cur and last.extents[last.outs.index(o)][3] == 0, (kind, name, op)
+            one.apply(op)
+
+
+def test_free_running_mixed_sequences_hold_nothing_that_synchronises():
+    for kind, name in M.mixed_sequences():
+        if kind not in ("mix_free", "mix_pool_free"):
+            continue
+        ops, model = M.case_sequence(kind, name)
+        one = model.members[0] if kind == "mix_pool_free" else model
+        assert one.cap == M.DYN_RESERVE
+        for op in ops:
+            assert op.kind != "reserve" and not (op.kind == "invalid" and op.on == "reserve"), (kind, name, op)
+            assert not (op.depth_host or op.out_host or op.read_debug), (kind, name, op)
+            if op.kind == "resize":
+                assert one.within(*op.size) and one.cap == M.DYN_RESERVE, (kind, name, op)
+            model.apply(op)
+
+
+def test_replay_of_a_mixed_sequence_equals_the_generators_own_model():
+    """generate() keeps a model of its own; replay(ops, fresh model) must walk through the same states: same events, same totals."""
+    for kind, name in M.mixed_sequences():
+        a, model = M.case_sequence(kind, name)
+        b, again = M.case_sequence(kind, name)
+        ea = [(op.kind, e if isinstance(e, list) else [e]) for op, e in M.replay(a, model)]
+        eb = [(op.kind, e if isinstance(e, list) else [e]) for op, e in M.replay(b, again)]
+        assert ea == eb
+        assert all(x is None or x.status == (M.ERR_INVALID_ARGUMENT if k == "invalid" else M.OK) for k, e in ea for x in e), (kind, name)
+        members = model.members if kind.startswith("mix_pool") else [model]
+        assert sum(m.totals["mixed"] for m in members) == sum("mixed_call" in x.events for _, e in ea for x in e if x is not None)
+
+
+# ---- mixed-size batches: the model against the header, by hand
+
+MIXED2 = ((384, 256, 0, 0), (200, 120, 0, 0))
+
+
+def test_a_mixed_call_is_a_per_frame_call_also_without_params():
+    """'Every other call is a "mixed call", a per-frame call (it reads its argument blocks from the table ring) also with
+    params == NULL'"""
+    c = ctx()
+    e = c.execute_extents((1, 2), (0, 1), MIXED2)
+    assert e.status == M.OK and e.launched and e.per_frame and e.own_pass and c.ring == 1 and c.totals["per_frame"] == 1
+    assert "mixed_shared_params_takes_ring_slot" in e.events
+    e = c.execute_extents((1, 2), (0, 1), MIXED2, params=(P0, P1))
+    assert e.per_frame and c.ring == 2 and "mixed_shared_params_takes_ring_slot" not in e.events
+
+
+def test_a_mixed_call_runs_a_waiting_composite_first_as_plain_launches():
+    """'a waiting composite batch is run first as plain launches' -- where a shared call of the context's size would carry it"""
+    c = ctx()
+    c.execute((1, 2), (0, 1), stream=1)
+    c.comp_enqueue(0, (0, 1), (0, 1))
+    e = c.execute_extents((3, 4), (2, 3), MIXED2)
+    assert e.comp_plain == 2 and e.comp_carried == 0 and e.comp_pending == 0 and e.comp_ran.stream == 1
+    assert "mixed_flushes_composite" in e.events and c.totals["comp_plain_launches"] == 2 and c.totals["comp_carried_launches"] == 0
+
+
+def test_a_mixed_call_consumes_a_ready_set_unmatched_and_reports_mixed_alone():
+    """'a ready prefetched set is consumed unmatched (the call runs its own downsample pass)'; the model reports "mixed" as the
+    one reason, also when every component of the key would have matched, and also when none would."""
+    c = ctx()
+    c.prefetch((1, 2))
+    c.execute((5, 6), (0, 1))
+    e = c.execute_extents((1, 2), (0, 1), MIXED2)                      # the announced buffers, the same stream
+    assert e.own_pass and not e.reused and e.refused == ("mixed",) and c.ready is None
+    assert {"mixed_consumes_ready", "mixed_consumes_ready_same_buffers"} <= set(e.events)
+    assert c.execute((1, 2), (0, 1)).refused == ()                      # gone after the one call
+    c.prefetch((1, 2))
+    c.execute((5, 6), (0, 1))
+    e = c.execute_extents((7,), (0,), ((200, 120, 1, 2),), params=(P2,), stream=1)      # nothing of the key matches
+    assert e.refused == ("mixed",) and "mixed_consumes_ready_same_buffers" not in e.events
+
+
+@pytest.mark.parametrize("kind", ["plain", "pitched", "per_frame", "sized"])
+def test_a_mixed_call_carries_any_announcement_as_a_launch_of_its_own_and_promotes_it(kind):
+    """'an announcement (meao_prefetch_batch*, sized or not) is carried as a launch of its own behind the last kernel and promoted
+    as usual': the ready set keeps the announcement's own size if sized (else the context's), its pitch, the call's stream and
+    the call's exactness; its Z-buffer inputs are its own params' or the context's."""
+    c = reserved()
+    kw = dict(plain={}, pitched=dict(pitch=1), per_frame=dict(params=(P1, P2, P3)), sized=dict(size=(200, 120), pitch=2))[kind]
+    c.prefetch((1, 2, 3), **kw)
+    e = c.execute_extents((5, 6), (0, 1), MIXED2, params=(PX0, P0), stream=1)
+    assert e.carried.bufs == (1, 2, 3) and e.own_pass and c.ann is None and not e.exact
+    assert "mixed_carries_" + kind in e.events and "mixed_carries_more_frames_than_n" in e.events
+    r = c.ready
+    assert r.bufs == (1, 2, 3) and r.stream == 1 and not r.exact and r.sized == (kind == "sized")
+    assert r.size == ((200, 120) if kind == "sized" else (384, 256))
+    assert r.pitch == {"plain": 384, "pitched": 392, "per_frame": 384, "sized": 205}[kind]
+    assert r.zb == tuple(p.zb(False) for p in ((P1, P2, P3) if kind == "per_frame" else (P0,) * 3))
+    assert c.totals["carried"] == 1 and c.totals["carried_by_mixed"] == 1 and c.totals["own"] == 1
+    # and the announced batch finds it: reused by an inexact call on that stream at that size, refused by an exact one
+    if kind == "sized":
+        assert "sized_ready_from_mixed_kept_by_resize" in c.resize(200, 120).events
+    call = dict(pitch={"pitched": 1, "sized": 2}.get(kind, 0), stream=1)
+    prm = (P1, P2, P3) if kind == "per_frame" else (P0, P0, P0)
+    if kind != "per_frame":                     # (PX0 is P0's camera: frame 0 of the per-frame announcement has P1's)
+        assert c.execute((1, 2, 3), (0, 1, 2), params=(PX0,) + prm[1:], **call).reused
+    else:
+        assert c.execute((1, 2, 3), (0, 1, 2), params=prm, **call).refused == ("exact",)
+    c.prefetch((1, 2, 3), **{k: v for k, v in kw.items() if k != "size"})
+    c.execute_extents((5, 6), (0, 1), ((33, 17, 0, 0), (97, 61, 0, 0)), stream=1)       # an exact carrier
+    assert c.execute((1, 2, 3), (0, 1, 2), params=prm, **call).reused
+
+
+def test_exact_of_a_mixed_call_is_every_frame_exact():
+    c = ctx()
+    assert c.execute_extents((1, 2), (0, 1), MIXED2).exact                               # the context's parameters for every frame
+    assert not c.execute_extents((1, 2), (0, 1), MIXED2, params=(P0, PX2)).exact
+    c.set_params(PX0)
+    assert not c.execute_extents((1, 2), (0, 1), MIXED2).exact
+    assert not ctx(rtz=False).execute_extents((1, 2), (0, 1), MIXED2).exact
+
+
+def test_a_refused_mixed_call_changes_nothing():
+    """'a refused call launches nothing and leaves an announcement, a ready set and a waiting composite as they were'; the
+    validation order: n, params[], then each frame's size against [1, 32768] and the capacity, then each pitch against ITS frame."""
+    c = reserved()
+    c.prefetch((1,))
+    c.execute((5,), (0,))
+    c.comp_enqueue(0, (0,), (0,))
+    c.prefetch((2,))
+    before = (c.ann, c.ready, c.comp, c.last, c.ring, dict(c.totals))
+    bad = [dict(extents=((401, 256, 0, 0),)), dict(extents=((384, 273, 0, 0),)), dict(extents=((0, 256, 0, 0),)),
+           dict(extents=((384, 0, 0, 0),)), dict(extents=((32769, 1, 0, 0),)), dict(extents=((200, 120, 0, 0),), rows=((199, 200),)),
+           dict(extents=((200, 120, 0, 0),), rows=((200, 199),)), dict(extents=((200, 120, 0, 0),), params=(PBAD,)),
+           dict(extents=((200, 120, 0, 0),) * 5, bufs=(1, 2, 3, 4, 5)), dict(extents=(), bufs=())]
+    for kw in bad:
+        bufs = kw.pop("bufs", (7,))
+        e = c.execute_extents(bufs, tuple(range(len(bufs))), kw.pop("extents"), **kw)
+        assert e.status == M.ERR_INVALID_ARGUMENT and not e.launched and e.comp_pending == 1 and e.last_valid, kw
+        assert (c.ann, c.ready, c.comp, c.last, c.ring, dict(c.totals)) == before, kw
+    # a stride that is legal for its own frame although it is below the context's width, and the capacity's own size, are accepted
+    assert c.execute_extents((7, 8), (1, 2), ((200, 120, 0, 0), (400, 272, 0, 0)), rows=((200, 200), (400, 408))).status == M.OK
+    # without a reservation the capacity is the context's size
+    c = ctx()
+    assert c.execute_extents((7,), (1,), ((385, 256, 0, 0),)).status == M.ERR_INVALID_ARGUMENT
+    assert c.execute_extents((7,), (1,), ((383, 256, 0, 0),)).status == M.OK
+
+
+def test_uniform_extents_are_the_pitched_call():
+    """'When every extent equals the context's size and all frames share their pitches the call IS meao_execute_batch_pitched':
+    it reuses, carries as an ordinary call does, takes a ring slot only with per-frame constants, and lets a composite ride."""
+    c = ctx()
+    c.prefetch((1, 2), pitch=1)
+    c.execute((5, 6), (0, 1))
+    c.comp_enqueue(0, (0,), (0,))
+    c.prefetch((3,))
+    e = c.execute_extents((1, 2), (2, 3), ((384, 256, 1, 2),) * 2)
+    assert e.reused and not e.own_pass and not e.per_frame and c.ring == 0 and e.comp_carried == 1 and e.carried.bufs == (3,)
+    assert {"uniform_extents", "uniform_extents_reuses", "uniform_extents_carries"} <= set(e.events) and "mixed_call" not in e.events
+    assert not c.last.mixed and c.last.depth_pitch == 392 and c.last.out_pitch == 389
+    # strides are compared in texels: 0 and the packed row are one stride; two strides make the call mixed at the context's size
+    assert c.extents_uniform(((384, 256, 0, 0),) * 2, rows=((384, 384), (384, 384)))
+    assert not c.extents_uniform(((384, 256, 0, 0), (384, 256, 1, 0)))
+    c.prefetch((1,))
+    c.execute((5,), (0,))
+    e = c.execute_extents((1, 2), (0, 1), ((384, 256, 0, 0), (384, 256, 0, 1)))
+    assert e.refused == ("mixed",) and e.per_frame and c.last.mixed
+    # with params[] it is the per-frame pitched call
+    assert c.execute_extents((1,), (0,), ((384, 256, 0, 0),), params=(P1,)).per_frame
+
+
+def test_last_call_of_a_mixed_call_has_per_frame_sizes_and_is_invalidated_as_ever():
+    """'Afterwards meao_get_intermediate / meao_debug_view describe and return frame f's buffers at frame f's size'; a reserve, a
+    resize and a re-allocation take it away as they take every last call; a refill of one of its frames makes it unreadable."""
+    c = reserved()
+    c.refill((1, 2), (("synth", 0), ("synth", 1)))
+    e = c.execute_extents((1, 2), (0, 1), ((200, 120, 1, 0), (380, 250, 0, 2)), params=(P1, P2))
+    assert c.last.mixed and c.last.n == 2 and c.last.sizes == ((200, 120), (380, 250)) and c.last.rows == ((208, 200), (380, 385))
+    assert c.last.params == (P1, P2) and c.readable() and e.last_valid
+    assert "mixed_then_debug_read" in c.debug_set(0, 1).events
+    assert "mixed_then_debug_read" in c.invalid(M.Op("invalid", what="n_zero", on="execute")).events
+    c.refill((2,), (("synth", 2),))
+    assert not c.readable()
+    c.execute_extents((1, 2), (0, 1), MIXED2)
+    e = c.reserve(400, 272)
+    assert "mixed_then_reserve_invalidates" in e.events and c.last is None and not e.last_valid
+    assert "mixed_after_invalidation" in c.execute_extents((1, 2), (0, 1), MIXED2).events
+    assert "mixed_then_reserve_invalidates" in c.resize(380, 250).events and c.last is None
+    assert c.execute((1,), (0,)).last_valid and c.last.sizes == ((380, 250),) and not c.last.mixed
+    c = ctx(pipelined=False)
+    c.execute_extents((1, 2), (0, 1), MIXED2)
+    assert c.prefetch((3,)).reallocated and c.last is None
+
+
+def test_what_follows_a_mixed_call_obeys_the_existing_rules():
+    """The ready set a mixed call leaves is an ordinary one: set_params drops it, a resize keeps a sized one for exactly its size."""
+    c = reserved()
+    c.prefetch((1,), size=(200, 120))
+    c.execute_extents((5, 6), (0, 1), MIXED2)
+    assert "sized_ready_dropped_other_size" in c.resize(380, 250).events and c.ready is None
+    c.prefetch((1,), size=(200, 120))
+    c.execute_extents((5, 6), (0, 1), MIXED2)
+    assert "ready_dropped_by_set_params" in c.set_params(P1).events and c.ready is None
+    c.prefetch((1,))
+    c.execute_extents((5, 6), (0, 1), MIXED2)
+    assert "unsized_dropped_by_resize_inside" in c.resize(200, 120).events
+
+
+def test_a_mixed_call_on_the_other_stream_leaves_a_ready_set_of_that_stream():
+    c = ctx()
+    c.execute((9,), (0,), stream=0)
+    c.prefetch((1,))
+    e = c.execute_extents((5, 6), (0, 1), MIXED2, stream=1)
+    assert "mixed_on_other_stream" in e.events and c.ready.stream == 1
+    assert c.execute((1,), (0,), stream=0).refused == ("stream",)
+
+
+def mixed_pool(G=3):
+    return reserved_pool(G)
+
+
+def test_pool_deals_extents_with_the_frames_and_each_member_classifies_its_own_share():
+    """'frame f, extents[f] and params[f] (if given) go to member f mod G'; a member whose share is uniform at its size makes the
+    pitched call -- it may reuse -- while the others make mixed calls and consume their ready sets unmatched."""
+    p = mixed_pool()
+    p.apply(M.Op("prefetch", bufs=(10, 11, 12, 13, 14, 15)))
+    p.apply(M.Op("execute", bufs=(1, 2, 3, 4, 5, 6), outs=(0, 1, 2, 3, 4, 5)))
+    ext = ((384, 256, 0, 0), (200, 120, 0, 0), (97, 61, 1, 0), (384, 256, 0, 0), (33, 17, 0, 2), (257, 31, 0, 0))
+    e = p.apply(M.Op("execute", bufs=(10, 11, 12, 13, 14, 15), outs=(0, 1, 2, 3, 4, 5), extents=ext, params=(P0, P1, P2, P0, P4, P5)))
+    assert e[0].reused and e[0].refused == () and "mixed_call" not in e[0].events
+    assert all(x.own_pass and x.refused == ("mixed",) and x.per_frame for x in e[1:])
+    assert {"pool_member_uniform_while_other_mixed", "pool_member_uniform_reuses_while_other_mixed"} <= set(e[0].events)
+    assert p.members[1].last.sizes == ((200, 120), (33, 17)) and p.members[1].last.params == (P1, P4)
+    assert p.members[2].last.rows == ((105, 97), (257, 257))
+
+
+def test_pool_mixed_call_members_dealt_nothing_drop_what_they_hold():
+    """'members dealt nothing do what they do for meao_pool_execute_batch_pitched': they drop announcement and ready set."""
+    p = mixed_pool()
+    p.apply(M.Op("prefetch", bufs=(10, 11, 12)))
+    e = p.apply(M.Op("execute", bufs=(1, 2), outs=(0, 1), extents=((200, 120, 0, 0), (384, 256, 0, 0))))
+    assert e[2] is None and p.members[2].ann is None and "pool_mixed_idle_member" in e[0].events
+    assert e[0].carried.bufs == (10,) and "mixed_call" in e[0].events and "mixed_call" not in e[1].events and e[1].carried.bufs == (11,)
+    assert "pool_member_uniform_while_other_mixed" in e[0].events
+
+
+def test_pool_mixed_call_with_one_bad_share_is_refused_whole():
+    """'Every member's share is validated against that member's capacity before any member enqueues'"""
+    p = mixed_pool()
+    p.apply(M.Op("prefetch", bufs=(10, 11, 12)))
+    bad = M.Op("execute", bufs=(1, 2, 3), outs=(0, 1, 2), extents=((200, 120, 0, 0), (416, 120, 0, 0), (97, 61, 0, 0)))
+    with pytest.raises(AssertionError):
+        p.apply(bad)                                                    # a sequence may not hold it as a valid call
+    assert p.check_extents(bad) == M.ERR_INVALID_ARGUMENT
+    e = p.apply(dataclasses.replace(bad, kind="invalid", what="extent_outside_on_one_member", on="execute"))
+    assert all(x.status == M.ERR_INVALID_ARGUMENT and not x.launched for x in e) and "pool_mixed_refused_whole" in e[0].events
+    assert all(c.ann is not None and c.last is None for c in p.members) and p.announced_n == 3
+    # n is the pool's: max_batch x members
+    assert p.check_extents(M.Op("execute", bufs=tuple(range(7)), extents=((200, 120, 0, 0),) * 7)) == M.ERR_INVALID_ARGUMENT
+    assert p.check_extents(M.Op("execute", bufs=tuple(range(6)), extents=((200, 120, 0, 0),) * 6)) == M.OK
+
+
+def test_the_model_holds_the_generators_mixed_invalid_calls_to_the_rule_they_name():
+    c = reserved()
+    ok = ((200, 120, 0, 0), (97, 61, 1, 2))
+    for op in (M.Op("invalid", what="extent_outside_capacity", on="execute", bufs=(1, 2), extents=ok),
+               M.Op("invalid", what="extent_zero", on="execute", bufs=(1, 2), extents=((416, 120, 0, 0), (97, 61, 0, 0))),
+               M.Op("invalid", what="extent_pitch_below_row", on="execute", bufs=(1, 2), extents=((0, 120, 0, 0), (97, 61, 0, 0)), value=1),
+               M.Op("invalid", what="extent_bad_params", on="execute", bufs=(1, 2), extents=ok, params=(P0, P1)),
+               M.Op("invalid", what="extent_n_over", on="execute", bufs=(1, 2), extents=ok)):
+        with pytest.raises(AssertionError):
+            c.apply(op)
+    for op in (M.Op("invalid", what="extent_outside_capacity", on="execute", bufs=(1, 2), extents=((200, 120, 0, 0), (97, 280, 0, 0))),
+               M.Op("invalid", what="extent_zero", on="execute", bufs=(1, 2), extents=((200, 0, 0, 0), (97, 61, 0, 0))),
+               M.Op("invalid", what="extent_pitch_below_row", on="execute", bufs=(1, 2), extents=ok, key=1, value=1),
+               M.Op("invalid", what="extent_bad_params", on="execute", bufs=(1, 2), extents=ok, params=(P0, PBAD)),
+               M.Op("invalid", what="extent_n_over", on="execute", bufs=(1, 2, 3, 4, 5), extents=ok[:1] * 5)):
+        assert c.apply(op).status == M.ERR_INVALID_ARGUMENT
+
+
+def test_f32_free_running_mixed_cases_hold_carries_the_header_lets_ride():
+    """The free-running tests bound the fused launches of a trace by the carried passes that include/meao.h lets ride inside an
+    ordinary carrier's last kernel (M.header_lets_it_ride).  In the two f32 cases that bound must not be zero, so that the fused
+    form is in play next to the mixed calls, which never use it."""
+    for name in ("r8_rtz_f32", "r8_rtz_linear_f32"):
+        ops, model = M.case_sequence("mix_free", name)
+        assert M.may_ride_count(ops, model) >= 2, name
+    ops, model = M.case_sequence("mix_free", "f16_rtne_unorm16")
+    assert M.may_ride_count(ops, model, f32_depth=False) == 0          # UNORM16 depth: nothing rides
+    a = M.Announcement((1, 2), 384, None, False, (384, 256))
+    assert M.header_lets_it_ride(a, 2, (384, 256), True) and not M.header_lets_it_ride(a, 1, (384, 256), True)
+    assert not M.header_lets_it_ride(M.Announcement((1,), 380, None, False, (380, 250)), 1, (384, 256), True)      # width % 8
+    assert not M.header_lets_it_ride(M.Announcement((1,), 389, None, False, (384, 256)), 1, (384, 256), True)      # stride % 4
+    assert not M.header_lets_it_ride(M.Announcement((1,), 400, None, True, (400, 272)), 1, (200, 120), True)       # tiles do not fit
+    assert M.header_lets_it_ride(M.Announcement((1,), 200, None, True, (200, 120)), 1, (384, 256), True)

@@ -10,6 +10,9 @@ colour targets) is put on the device before the first call and copied from there
 its members' streams are its own, so a buffer is filled (once, before its first use) and a colour target reset by a blocking copy
 from host memory -- which waits for none of the members' non-blocking streams, so nothing the pool has in flight is held up.
 
+An execute has a size, two row strides and oracle settings PER FRAME (Driver.geometry): the context's size under the call's
+pitches for every call but meao_execute_batch_extents (Op.extents; tests/test_mixed_size_sequences_gpu.py draws those).
+
 Every surface of a sequence has the size of the largest frame plus the widest pitch and stays allocated until the sequence has
 ended, so that a call running on stale bookkeeping still reads and writes live memory of the right size.
 """
@@ -87,8 +90,10 @@ class Driver:
         self.ao_dt = np.uint16 if self.ao_fmt == L.AO_F16 else np.uint8
         self.rounding = L.F16_RTZ_CLAMP if cfg.get("rtz", True) else L.F16_RTNE
         self.hq = cfg.get("hq_levels", 0)
-        frames = profile.sizes + profile.outside_sizes      # every size a frame of the sequence can have
+        frames = profile.sizes + profile.outside_sizes + profile.mixed_sizes      # every size a frame of the sequence can have
         wmax, hmax = max(s[0] for s in frames), max(s[1] for s in frames)
+        if profile.mixed_sizes:                              # (and the extents of the mixed calls the library must refuse)
+            wmax, hmax = wmax + 16, hmax + 8
         self.cap = hmax * max(wmax + max(M.PITCH_EXTRA), M.PITCH_FIXED)      # texels of every surface
         self.lib = L.load()
         self.ctx_fields = fields_of(0, self.w, self.h)
@@ -128,6 +133,7 @@ class Driver:
         self.bg = None
         self.last_read = None        # the last execute: (op, [(oracle frame, fields)], expects), for reads some operations later
         self.log = []
+        self.fusable = 0             # carried passes that the header allows inside the carrier's last kernel (see note_fusable)
 
     # ---- settings, parameters
     def settings(self, fields, w=None, h=None):
@@ -195,6 +201,11 @@ class Driver:
             else:
                 from tests.test_param_domain_gpu import hostile_level_texels
                 d = hostile_level_texels(w, h, 80 + seed)
+                if w * h < 200 * 120:
+                    # a few hundred texels (the small frames of a mixed call): the sprinkled ones may miss the texels the levels
+                    # are made of, so one of every hostile kind is planted there (y and x even) -- the bit is known again
+                    for i, v in enumerate(H.hostile_values().values()):
+                        d[2 * (i // 4), 2 * (i % 4)] = v
             d = np.ascontiguousarray(d, np.float32)
             if self.fmt == L.DEPTH_UNORM16:
                 d = np.round(np.clip(d, 0, 1) * 65535).astype(np.uint16)
@@ -326,8 +337,37 @@ class Driver:
         got = self.colors[c].dev.cpu().numpy()[:want.nbytes].view(np.uint16).reshape(want.shape)
         assert np.array_equal(got, want), (op, "composite of colour %d" % c, H.diff_report("color", got, want))
 
+    def geometry(self, op):
+        """[(width, height, depth row stride, AO row stride)] of an execute's frames, in texels: every frame at the context's
+        size under the call's pitches, or each at its own (Op.extents)."""
+        if op.extents is not None:
+            return [(w, h, M.row_texels(dp, w), M.row_texels(ap, w)) for w, h, dp, ap in op.extents]
+        return [(self.w, self.h, self.w if op.depth_host else M.row_texels(op.pitch, self.w),
+                 self.w if op.out_host else M.row_texels(op.out_pitch, self.w))] * len(op.bufs)
+
+    def is_mixed(self, op):
+        """A mixed call: extents that are not all the context's size under one pair of strides."""
+        geo = self.geometry(op)
+        return op.extents is not None and not (all(g[:2] == (self.w, self.h) for g in geo) and len(set(geo)) == 1)
+
+    def extents_ctypes(self, op, bad=None):
+        """The meao_extent array of an execute.  The packed row is given as 0 for even frames and in bytes for odd ones: the
+        same stride."""
+        de, ae = np.dtype(self.depth_dt).itemsize, np.dtype(self.ao_dt).itemsize
+        ext = (L.Extent * max(1, len(op.extents)))()
+        for f, (w, h, dp, ap) in enumerate(op.extents):
+            ext[f].width, ext[f].height = w, h
+            ext[f].depth_pitch = M.row_texels(dp, w) * de if dp or f % 2 else 0
+            ext[f].ao_pitch = M.row_texels(ap, w) * ae if ap or f % 2 else 0
+        if bad == "extent_pitch_below_row":                           # one texel short of the row of ITS frame
+            if op.key == 0:
+                ext[op.value].depth_pitch = (op.extents[op.value][0] - 1) * de
+            else:
+                ext[op.value].ao_pitch = (op.extents[op.value][0] - 1) * ae
+        return ext
+
     def call_execute(self, op, bad=None):
-        """meao_execute_batch / _params / _pitched (or the pool's) as the operation asks; returns the status."""
+        """meao_execute_batch / _params / _pitched / _extents (or the pool's) as the operation asks; returns the status."""
         n_real = len(op.bufs)
         de, ae = np.dtype(self.depth_dt).itemsize, np.dtype(self.ao_dt).itemsize
         dp = (M.row_texels(op.pitch, self.w)) * de if op.pitch else 0
@@ -356,6 +396,14 @@ class Driver:
             din, dout = (din * n_real)[:n_real], (dout * n_real)[:n_real]
         if bad == "bad_params":
             prm = self.params_ctypes(op.params)
+        if op.extents is not None:
+            n_real = len(op.extents)                                  # (extent_n_over: one more than the limit)
+            din, dout = (din * n_real)[:n_real], (dout * n_real)[:n_real]
+            pin, pout = (C.c_void_p * n_real)(*din), (C.c_void_p * n_real)(*dout)
+            ext = self.extents_ctypes(op, bad)
+            if self.G:
+                return self.lib.meao_pool_execute_batch_extents(self.ao._pool, n_real, pin, pout, ext, prm)
+            return self.lib.meao_execute_batch_extents(self.ao._ctx, n_real, pin, pout, ext, prm, C.c_void_p(self.stream_handle()))
         k = max(1, len(din))
         pin, pout = (C.c_void_p * k)(*din), (C.c_void_p * k)(*dout)
         dl, ol = (L.MEM_HOST if op.depth_host else L.MEM_DEVICE), (L.MEM_HOST if op.out_host else L.MEM_DEVICE)
@@ -410,10 +458,9 @@ class Driver:
     def frame_inputs(self, op):
         """[(oracle frame, fields)] of an execute, from the bytes the call is given under the pitch it is given."""
         out = []
-        pitch = self.w if op.depth_host else M.row_texels(op.pitch, self.w)
-        for f, b in enumerate(op.bufs):
+        for f, (b, (w, h, pitch, _)) in enumerate(zip(op.bufs, self.geometry(op))):
             s = self.depth[b]
-            frame = Surface.view(s.oracle_bytes, np.float32 if self.linear else self.depth_dt, pitch, self.w, self.h)
+            frame = Surface.view(s.oracle_bytes, np.float32 if self.linear else self.depth_dt, pitch, w, h)
             fields = self.ctx_fields if op.params is None else self.fields_for(op.params[f])
             out.append((frame, fields))
         return out
@@ -427,36 +474,50 @@ class Driver:
         L.check(self.lib.meao_get_pass_times(c, C.byref(ms), C.byref(cnt)), c)
         return list(ms), cnt.value
 
+    def note_fusable(self, op, expects):
+        """Counts the carried passes that MAY run inside their carrier's last kernel, by what include/meao.h says of it: never
+        what a mixed call carries, else M.header_lets_it_ride (every surface here is aligned).  An upper bound on the fused launches of a trace, not their number: whether an eligible pass does ride is decided
+        by host code the header leaves free ("host code decides, no kernel knows" -- the tile height of the last kernel)."""
+        G = self.G or 1
+        for m, e in enumerate(expects):
+            if e is None or e.carried is None or "mixed_call" in e.events or self.own_launch:
+                continue
+            self.fusable += M.header_lets_it_ride(e.carried, len(op.bufs[m::G]), (self.w, self.h),
+                                                  self.fmt in (L.DEPTH_F32, L.DEPTH_LINEAR_F32))
+
     def execute(self, op, expect):
         expects = self.member_expects(expect)
+        self.note_fusable(op, expects)
         self.switch_stream(op.stream)
         if self.stepped:
             self.set_profiling()
         inputs = self.frame_inputs(op)
         status = self.call_execute(op)
         assert status == L.OK, (op, status, self.lib.meao_last_error(self.members[0]))
-        opitch = self.w if op.out_host else M.row_texels(op.out_pitch, self.w)
+        geo = self.geometry(op)
         host_want = []
         for f, (frame, fields) in enumerate(inputs):
+            w, h, _, opitch = geo[f]
             want = self.want(frame, fields)["result"]
             if op.out_host:                                           # the device surface of that id is not touched
                 host_want.append(self.outs[op.outs[f]].mirror.copy())
-                Surface.view(host_want[-1], self.ao_dt, opitch, self.w, self.h)[:] = want
+                Surface.view(host_want[-1], self.ao_dt, opitch, w, h)[:] = want
             else:
-                Surface.view(self.outs[op.outs[f]].mirror, self.ao_dt, opitch, self.w, self.h)[:] = want
+                Surface.view(self.outs[op.outs[f]].mirror, self.ao_dt, opitch, w, h)[:] = want
         if not self.stepped:
-            self.checks += [("out", o, opitch, self.w, self.h, op) for o in op.outs]
+            self.checks += [("out", o, g[3], g[0], g[1], op) for o, g in zip(op.outs, geo)]
             self.check_composites(op, expects)
             return
         self.sync()
         for f, o in enumerate(op.outs):
+            view = (geo[f][3], geo[f][0], geo[f][1])
             if op.out_host:
-                self.compare_bytes(self.host_out[f], host_want[f], op, f, "HOST result", opitch)
+                self.compare_bytes(self.host_out[f], host_want[f], op, f, "HOST result", view)
             else:
-                self.compare_surface(self.outs[o], op, f, "result", opitch)
+                self.compare_surface(self.outs[o], op, f, "result", view)
         if not op.depth_host:
             for f, b in enumerate(op.bufs):                         # depth surfaces are read, never written
-                self.compare_surface(self.depth[b], op, f, "depth surface", 0)
+                self.compare_surface(self.depth[b], op, f, "depth surface", None)
         # pass times: what the header gives (see the module docstring of tests/call_model.py)
         for m, e in enumerate(expects):
             ms, cnt = self.pass_times(self.members[m])
@@ -470,36 +531,41 @@ class Driver:
                 assert ms[PASS_DOWNSAMPLE] == 0, (op, m, "a reused pass and nothing announced: no downsample launch", ms)
             elif self.own_launch:
                 assert ms[PASS_DOWNSAMPLE] > 0, (op, m, "the carried pass as a launch of its own", ms)
+            if "mixed_call" in e.events:                             # its own pass, and what it carries behind it, in both modes
+                assert e.own_pass and e.per_frame and ms[PASS_DOWNSAMPLE] > 0, (op, m, "a mixed call runs its own downsample pass", ms)
         self.check_composites(op, expects)
         self.check_hostile(op, expects)
         if op.read_debug:
             self.check_debug(op, inputs)
         self.last_read = (op, [(frame.copy(), fields) for frame, fields in inputs], expects)
 
-    def compare_bytes(self, got, want, op, f, what, pitch):
+    def compare_bytes(self, got, want, op, f, what, view):
+        """Every byte of a surface.  view: (row stride, width, height) of the frame in it, in texels, for the report alone."""
         if not np.array_equal(got, want):
-            frame_g = Surface.view(got, self.ao_dt, pitch, self.w, self.h) if pitch else got
-            frame_w = Surface.view(want, self.ao_dt, pitch, self.w, self.h) if pitch else want
+            frame_g = Surface.view(got, self.ao_dt, *view) if view else got
+            frame_w = Surface.view(want, self.ao_dt, *view) if view else want
             inside = not np.array_equal(frame_g, frame_w)
             raise AssertionError((op, "frame %d" % f, what, "texels differ" if inside else "bytes OUTSIDE the frame changed",
                                   int((got != want).sum()), self.log[-6:]))
 
-    def compare_surface(self, s, op, f, what, pitch):
-        self.compare_bytes(s.dev.cpu().numpy(), s.mirror, op, f, what, pitch)
+    def compare_surface(self, s, op, f, what, view):
+        self.compare_bytes(s.dev.cpu().numpy(), s.mirror, op, f, what, view)
 
     def check_hostile(self, op, expects):
         """Known by construction only: inside the exact range, a frame with hostile level texels has its bit, a clean one has not."""
         if self.fmt == L.DEPTH_UNORM16:
             return
-        view = (self.w if op.depth_host else M.row_texels(op.pitch, self.w), self.w, self.h)
+        geo = self.geometry(op)
+        G = self.G or 1
         for m, e in enumerate(expects):
             if e is None or not e.exact:
                 continue
             mask = C.c_uint64()
             L.check(self.lib.meao_hostile_frames(self.members[m], C.byref(mask)), self.members[m])
-            for i, b in enumerate(op.bufs[m::self.G] if self.G else op.bufs):
-                content, laid = self.laid[b]
-                if laid != view:
+            for i, b in enumerate(op.bufs[m::G]):                   # one bit per frame of the member's share, in frame order
+                content, laid = self.laid.get(b, (("unknown", 0), None))
+                w, h, rows, _ = geo[m + i * G]
+                if laid != (rows, w, h):
                     continue                                        # read under another pitch than it was written: not a known frame
                 bit = mask.value >> i & 1
                 if content[0] == "hostile_level":
@@ -507,11 +573,22 @@ class Driver:
                 elif content[0] == "synth":
                     assert bit == 0, (op, m, i, "clean frame: bit must be clear", hex(mask.value), e.reused)
 
-    def debug_buffer(self, f, debug_id):
-        """meao_get_intermediate of frame f of the last call: slot f // G of member f mod G."""
+    def debug_buffer(self, f, debug_id, size=None):
+        """meao_get_intermediate of frame f of the last call: slot f // G of member f mod G.  size: the frame's own, after a mixed
+        call -- the buffer is then described by the call that returns it, and room is made for the largest the member can hold."""
         G = self.G or 1
         ctx, slot = self.members[f % G], f // G
         d = L.Desc()
+        if size is not None:
+            cfg, cw, ch = L.Config(), C.c_int32(), C.c_int32()
+            L.check(self.lib.meao_get_config(ctx, C.byref(cfg)), ctx)
+            L.check(self.lib.meao_get_capacity(ctx, C.byref(cw), C.byref(ch)), ctx)
+            cfg.width, cfg.height = max(cw.value, cfg.width), max(ch.value, cfg.height)
+            L.check(self.lib.meao_describe_buffer(C.byref(cfg), debug_id, C.byref(d)))
+            raw = np.empty(d.bytes, np.uint8)
+            L.check(self.lib.meao_get_intermediate(ctx, slot, debug_id, raw.ctypes.data, raw.nbytes, L.MEM_HOST, C.byref(d)), ctx)
+            dt = {L.FMT_F32: np.float32, L.FMT_F16: np.uint16, L.FMT_UNORM8: np.uint8}[d.format]
+            return raw[:d.bytes].view(dt).reshape((d.slices, d.height, d.width) if d.slices > 1 else (d.height, d.width))
         L.check(self.lib.meao_get_intermediate(ctx, slot, debug_id, None, 0, L.MEM_HOST, C.byref(d)), ctx)
         out = np.empty((d.slices, d.height, d.width) if d.slices > 1 else (d.height, d.width),
                        {L.FMT_F32: np.float32, L.FMT_F16: np.uint16, L.FMT_UNORM8: np.uint8}[d.format])
@@ -527,8 +604,11 @@ class Driver:
         pick = [self.rng.choice(range(1, 10))] + self.rng.sample(ids, 2)
         frame, fields = inputs[f]
         want = self.want(frame, fields, full=True)
+        mixed = self.is_mixed(op)
         for i in pick:
-            got = self.debug_buffer(f, i)
+            got = self.debug_buffer(f, i, frame.shape[::-1] if mixed else None)
+            # (after a mixed call: frame f's buffers at frame f's size -- the oracle's at that size)
+            assert got.shape == want[H.NAMES[i]].shape, (op, why, "debug id %d of frame %d" % (i, f), got.shape, want[H.NAMES[i]].shape)
             ok, _ = H.nan_aware_equal(got, want[H.NAMES[i]])
             assert ok, (op, why, "debug id %d of frame %d" % (i, f), H.diff_report(H.NAMES[i], got, want[H.NAMES[i]]), self.log[-6:])
         if self.G:
@@ -540,8 +620,9 @@ class Driver:
         if view or not self.viewed:
             self.viewed = True
             i = pick[0]
-            got = self.ao.debug_view(i, frame=f)
-            wantv = self.O.debug_view(want, i, self.settings(fields))
+            got = np.empty(frame.shape, self.ao_dt)                 # meao_debug_view: the frame's own size after a mixed call
+            L.check(self.lib.meao_debug_view(self.ao._ctx, f, i, got.ctypes.data, L.MEM_HOST, None), self.ao._ctx)
+            wantv = self.O.debug_view(want, i, self.settings(fields, frame.shape[1], frame.shape[0]))
             ok, _ = H.nan_aware_equal(got, wantv)
             assert ok, (op, why, "debug view %d of frame %d" % (i, f), H.diff_report("view", got, wantv))
 
@@ -673,7 +754,7 @@ class Driver:
                 _, o, pitch, w, h, op = chk
                 if o not in seen:
                     seen.add(o)
-                    self.compare_surface(self.outs[o], op, 0, "result (buffer %d)" % o, pitch)
+                    self.compare_surface(self.outs[o], op, 0, "result (buffer %d)" % o, (pitch, w, h))
         for c, want in self.final_color.items():
             got = self.colors[c].dev.cpu().numpy()[:want.nbytes].view(np.uint16).reshape(want.shape)
             assert np.array_equal(got, want), ("composite of colour %d" % c, H.diff_report("color", got, want))
@@ -681,7 +762,7 @@ class Driver:
 
     def totals(self):
         models = self.model.members if self.G else [self.model]
-        return {k: sum(m.totals[k] for m in models) for k in models[0].totals}
+        return dict({k: sum(m.totals[k] for m in models) for k in models[0].totals}, fusable=self.fusable)
 
     def close(self):
         self.ao.close(flush_composite=True)

@@ -18,7 +18,8 @@ from tests import helpers as H  # noqa: E402
 def run_sequences(count, seed0):
     """The generator and model of tests/call_model.py with fresh seeds, driven by the stepped Driver of
     tests/test_call_sequences_gpu.py: every case of the suite's stepped and pool modes in turn -- those that draw reservations, resizes
-    and sized announcements (tests/test_dynamic_resolution_sequences_gpu.py) included -- and both forms of the carried pass."""
+    and sized announcements (tests/test_dynamic_resolution_sequences_gpu.py) and those that draw mixed-size batches into them
+    (tests/test_mixed_size_sequences_gpu.py) included -- and both forms of the carried pass."""
     import tempfile
     import pytest
     from miniengineao_amd import _lib as L
@@ -29,6 +30,7 @@ def run_sequences(count, seed0):
     lin_c = build_linearize(tempfile.mkdtemp())
     cases = [("stepped", n) for n in sorted(M.CASES)] + [("pool_stepped", n) for n in sorted(M.POOL_CASES)]
     cases += [("dyn_stepped", n) for n in sorted(M.DYN_CASES)] + [("dyn_pool_stepped", n) for n in sorted(M.DYN_POOL_CASES)]
+    cases += [("mix_stepped", n) for n in sorted(M.MIX_CASES)] + [("mix_pool_stepped", n) for n in sorted(M.MIX_POOL_CASES)]
     bad = 0
     for k in range(count):
         kind, name = cases[k % len(cases)]
