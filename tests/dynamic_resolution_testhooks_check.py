@@ -11,7 +11,7 @@ import torch
 
 from miniengineao_amd import _lib as L
 from oracle import oracle
-from tests import test_dynamic_resolution_gpu as D
+from tests import dynamic_resolution as D
 
 
 def counters(lib, ao):

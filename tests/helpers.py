@@ -2,6 +2,8 @@
 C-ABI library so that every comparison runs on identical inputs and parameters."""
 from __future__ import annotations
 
+import dataclasses
+
 import numpy as np
 
 from miniengineao_amd import synth
@@ -51,6 +53,97 @@ def diff_report(name, got, want):
     first = tuple(bad[0])
     return (f"{name}: {len(bad)} of {got.size} texels differ; first at {first}: "
             f"got {got[first]!r} want {want[first]!r}")
+
+
+def compare(got, want, what):
+    ok, _ = nan_aware_equal(got, want)
+    assert ok, diff_report(what, got, want)
+
+
+def same(got, want, what):
+    assert np.array_equal(got, want), diff_report(what, got, want)
+
+
+# ---- small things the GPU suites share
+
+PASS_DOWNSAMPLE = 0                  # meao_pass launch slot
+DEPTH_FORMATS = {"f32": 0, "unorm16": 1, "unorm24": 2, "f16": 3}
+
+# FrameParams field -> oracle Settings field
+ORACLE_FIELD = {"nearClipPlane": "near_clip", "farClipPlane": "far_clip", "projection00": "proj00",
+                "usesReversedZBuffer": "reversed_z", "singlePassStereoEnabled": "single_pass_stereo",
+                "intensity": "intensity", "thicknessModifier": "thickness_modifier",
+                "noiseFilterTolerance": "noise_filter_tolerance", "blurTolerance": "blur_tolerance",
+                "upsampleTolerance": "upsample_tolerance"}
+
+
+def frame_settings(base, fp):
+    """oracle Settings of one frame: `base` with the fields the FrameParams sets."""
+    return dataclasses.replace(base, **{ORACLE_FIELD[k]: v for k, v in dataclasses.asdict(fp).items() if v is not None})
+
+
+def params_of(s, fields=("intensity", "thicknessModifier", "projection00")):
+    """The FrameParams that sets `fields` to what Settings `s` holds (the inverse of frame_settings)."""
+    from miniengineao_amd import FrameParams
+    return FrameParams(**{k: getattr(s, ORACLE_FIELD[k]) for k in fields})
+
+
+def ao_dtype(ao_format):
+    return np.uint8 if ao_format == 0 else np.uint16          # L.AO_R8, else f16 bits
+
+
+def ptr_array(ptrs):
+    import ctypes as C
+    return (C.c_void_p * len(ptrs))(*ptrs)
+
+
+def colour(w, h, seed):
+    """RGBA16F bits: finite halfs of every sign and size."""
+    rng = np.random.default_rng(seed)
+    return (rng.integers(0, 0x7C00, (h, w, 4)) | (rng.integers(0, 2, (h, w, 4)) << 15)).astype(np.uint16)
+
+
+def encode_depth(d, fmt):
+    """Raw f32 depth in a depth-buffer storage format (L.DEPTH_F32 / _UNORM16 / _UNORM24 / _F16), clipped to [0, 1] for the UNORM
+    ones.  Bit-equal to oracle.encode_depth for F32, UNORM16 and F16 on the suites' frames; its UNORM24 codes are the oracle's
+    without the 0xA5 stencil byte that the oracle plants above them."""
+    if fmt == 0:
+        return d.astype(np.float32)
+    if fmt == 1:
+        return np.round(np.clip(d, 0, 1) * 65535).astype(np.uint16)
+    if fmt == 2:
+        return np.round(np.clip(d, 0, 1).astype(np.float64) * 16777215).astype(np.uint32)
+    return d.astype(np.float16).view(np.uint16)
+
+
+def downsample_ms(ao, call):
+    """The DOWNSAMPLE slot of one call, in a profiling window of its own: 0 = that call launched no downsample pass."""
+    ao.set_profiling(True)
+    call()
+    ms, execs = ao.pass_times_ms()
+    assert execs == 1
+    return ms[PASS_DOWNSAMPLE]
+
+
+_WANT, _AO = {}, {}
+
+
+def want_of(oracle, key, depth, s, result_only=False, **kw):
+    """oracle.run(depth, s), computed once per (frame key, every field of s, result_only) and never modified: the oracle is the
+    slow part of the GPU suites.  `key` names the frame's contents; their checksum keeps suites with like keys apart."""
+    k = (key, checksum(depth), dataclasses.astuple(s), result_only)
+    if k not in _WANT:
+        _WANT[k] = oracle.run(depth, s, result_only=result_only, **kw)
+    return _WANT[k]
+
+
+def oracle_frame(oracle, w, h, ao_format, seed):
+    """(depth, oracle AO) of one synthetic frame; cached."""
+    key = (w, h, ao_format, seed)
+    if key not in _AO:
+        depth = synth.make("S2", w, h, seed=seed)
+        _AO[key] = (depth, oracle.run(depth, settings(oracle, w, h, ao_format=ao_format), result_only=True)["result"])
+    return _AO[key]
 
 
 def checksum(arr: np.ndarray) -> int:
@@ -115,6 +208,24 @@ def hostile_frame(w, h, seed, cam=synth.DEFAULT_CAMERA, density=0.01, kinds=None
     return d
 
 
+def hostile_level_texels(w, h, seed):
+    """S2 with hostile raw texels only where (y, x) are both even: the texels the levels are made of."""
+    clean = synth.make("S2", w, h, seed=seed)
+    d = hostile_frame(w, h, seed, density=0.02)
+    yy, xx = np.mgrid[0:h, 0:w]
+    return np.where(((yy & 1) == 0) & ((xx & 1) == 0), d, clean).astype(np.float32)
+
+
+def flat_sky_frame(w, h, seed, cam=synth.DEFAULT_CAMERA):
+    """S2 with flat regions made of whole 2 x 2-aligned blocks (every level's hi == lo there: |delta| = 0) and sky texels."""
+    d = synth.make("S2", w, h, seed=seed).copy()
+    d[32:96, 64:192] = d[32, 64]
+    d[130:162, 300:364] = d[130, 300]
+    d[64:66, 400:402] = d[64, 400]
+    sky = np.float32(0.0 if cam.reversed_z else 1.0)
+    d[180:232, 100:164] = sky
+    d[7:9, 9:13] = sky
+    return d
 
 
 # ---- the parameter domain (tests/test_abi.py, tests/test_param_domain_gpu.py, tools/fuzz_gpu.py)
@@ -123,6 +234,34 @@ def hostile_frame(w, h, seed, cam=synth.DEFAULT_CAMERA, density=0.01, kinds=None
 # underflow of 10^x, zero and negative thickness / intensity
 FAR_OUTSIDE = {"upsample_tolerance": (-20.0, -40.0, -46.0, 20.0, 39.0), "noise_filter_tolerance": (-46.0, 20.0, 39.0),
                "blur_tolerance": (-46.0, 3.0, 39.0), "thickness_modifier": (-1.0, 1e-30, 1e30), "intensity": (-1.0, 3.0, 1e30)}
+
+
+def f32(x):
+    return float(np.float32(x))
+
+
+def random_params(rng, w, h, n):
+    """n FrameParams with all ten fields drawn from their valid ranges, plus the extremes."""
+    from miniengineao_amd import FrameParams
+    out = []
+    for f in range(n):
+        near = f32(10 ** rng.uniform(-2, 0))
+        far = f32(near * 10 ** rng.uniform(1, 4))
+        fov = rng.uniform(20, 100)
+        out.append(FrameParams(
+            nearClipPlane=near, farClipPlane=far,
+            projection00=synth.Camera(near, far, fov).proj00(w, h),
+            usesReversedZBuffer=bool(rng.integers(0, 2)), singlePassStereoEnabled=bool(rng.integers(0, 2)),
+            intensity=f32(rng.uniform(0, 4)), thicknessModifier=f32(rng.uniform(1, 10)),
+            noiseFilterTolerance=f32(rng.uniform(-8, 0)), blurTolerance=f32(rng.uniform(-8, -1)),
+            upsampleTolerance=f32(rng.uniform(-12, -1))))
+    ext = [dict(nearClipPlane=0.01, farClipPlane=1e5, usesReversedZBuffer=True, upsampleTolerance=-1.0, noiseFilterTolerance=-8.0),
+           dict(nearClipPlane=0.01, farClipPlane=1e5, usesReversedZBuffer=False, upsampleTolerance=-12.0, noiseFilterTolerance=0.0),
+           dict(usesReversedZBuffer=False, upsampleTolerance=-12.0, noiseFilterTolerance=-8.0),
+           dict(usesReversedZBuffer=True, upsampleTolerance=-1.0, noiseFilterTolerance=0.0)]
+    for i, e in enumerate(ext[:n]):
+        out[i] = dataclasses.replace(out[i], **e)
+    return out
 
 
 def upsample_constants(lib, w=516, h=260, level=1, **fields):
@@ -183,6 +322,7 @@ def kernel_trace(tmp_path, script, args=()):
     if prof is None:
         pytest.skip("rocprofv3 is not installed")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    tmp_path.mkdir(parents=True, exist_ok=True)           # a sub-directory of the test's tmp_path: one per trace of a test
     src = tmp_path / "child.py"
     src.write_text(script)
     env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))

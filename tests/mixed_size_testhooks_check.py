@@ -12,7 +12,7 @@ import torch
 
 from miniengineao_amd import _lib as L
 from oracle import oracle
-from tests import test_mixed_size_gpu as M
+from tests import mixed_size as M
 
 
 def counters(lib, ao):

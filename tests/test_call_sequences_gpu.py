@@ -32,10 +32,10 @@ from miniengineao_amd import _lib as L
 from miniengineao_amd.frame_params import params_array, to_params
 from tests import call_model as M
 from tests import helpers as H
+from tests.helpers import PASS_DOWNSAMPLE, downsample_ms
 
 pytestmark = pytest.mark.gpu
 
-PASS_DOWNSAMPLE = 0
 CAM_LINEAR = synth.Camera(near=0.1, far=128.0, reversed_z=True)       # palette entries M.LINEAR_TAGS
 DEPTH_FORMATS = {"f32": (L.DEPTH_F32, np.float32), "unorm16": (L.DEPTH_UNORM16, np.uint16), "linear_f32": (L.DEPTH_LINEAR_F32, np.float32)}
 PATTERN = 0xA5
@@ -186,7 +186,7 @@ class Driver:
         return self.bg
 
     def to_linear(self, d):
-        from tests.test_linear_depth_gpu import to_linear
+        from tests.linear_depth import to_linear
         return to_linear(self.lin_c, d, CAM_LINEAR)
 
     def frame(self, content, w, h):
@@ -199,7 +199,7 @@ class Driver:
             elif kind == "hostile":
                 d = H.hostile_frame(w, h, 60 + seed)
             else:
-                from tests.test_param_domain_gpu import hostile_level_texels
+                from tests.helpers import hostile_level_texels
                 d = hostile_level_texels(w, h, 80 + seed)
                 if w * h < 200 * 120:
                     # a few hundred texels (the small frames of a mixed call): the sprinkled ones may miss the texels the levels
@@ -769,9 +769,9 @@ class Driver:
 
 
 @pytest.fixture(scope="module")
-def lin_c(tmp_path_factory):
-    from tests.test_linear_depth_gpu import build_linearize
-    return build_linearize(str(tmp_path_factory.mktemp("lin")))
+def lin_c():
+    from tests.linear_depth import linearize
+    return linearize()
 
 
 # ---- stepped sequences on one context
@@ -844,15 +844,6 @@ def test_pool_member_that_sat_a_call_out_holds_no_announcement(oracle):
 
 # ---- hand-written histories that must not depend on a seed
 
-def downsample_ms(ao, call):
-    """The DOWNSAMPLE slot of one call, in a profiling window of its own."""
-    ao.set_profiling(True)
-    call()
-    ms, execs = ao.pass_times_ms()
-    assert execs == 1
-    return ms[PASS_DOWNSAMPLE]
-
-
 @pytest.mark.parametrize("how", ["set_params", "resize"])
 def test_announcement_does_not_survive_set_params_or_resize(oracle, how):
     """Announce B, then meao_set_params / meao_resize, execute A, execute B: A carries nothing, so B finds nothing ready and runs
@@ -903,7 +894,7 @@ def test_linear_depth_reuse_key_is_the_far_plane_alone(oracle, lin_c):
     A frame announced with far 128 and asked for with far 64 (and linearised by THAT camera) is refused; announced with far 128
     and asked for with another near plane and Z direction but far 128 is reused.  Both equal the oracle of the asking camera."""
     import torch
-    from tests.test_linear_depth_gpu import to_linear
+    from tests.linear_depth import to_linear
     w, h = 384, 256
     dev = torch.device("cuda", 0)
     ann = fields_of(0, w, h)                                          # near 0.1, far 128, reversed Z
@@ -1020,7 +1011,7 @@ import json
 import sys
 from oracle import oracle as O
 from tests import call_model as M
-from tests import test_call_sequences_gpu as T
+from tests import test_call_sequences_gpu as T          # the child's own parent module: the driver stays in its suite
 
 kind, name, own_launch = sys.argv[1], sys.argv[2], int(sys.argv[3])
 O.build()
@@ -1028,9 +1019,8 @@ ops, model = M.case_sequence(kind, name)
 lin_c = None
 cfg, prof, _ = M.case_profile(kind, name)
 if cfg.get("linear"):
-    import tempfile
-    from tests.test_linear_depth_gpu import build_linearize
-    lin_c = build_linearize(tempfile.mkdtemp())
+    from tests.linear_depth import linearize
+    lin_c = linearize()
 d = T.Driver(O, cfg, prof, own_launch, lin_c, stepped=False)
 try:
     d.run(ops, model)

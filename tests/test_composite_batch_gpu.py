@@ -7,7 +7,6 @@ the same inputs.  Surfaces are the Targets of tests/test_composite_formats_gpu.p
 byte outside a viewport unchanged afterwards (layouts "packed", "vector", "oddbase" = origins one AO texel / 4 colour bytes off:
 the per-texel form for the whole batch)."""
 import ctypes as C
-import dataclasses
 
 import numpy as np
 import pytest
@@ -18,29 +17,18 @@ from miniengineao_amd import synth
 from miniengineao_amd.frame_params import FrameParams, params_array
 from tests import color_formats as CF
 from tests import helpers as H
-from tests.test_composite_formats_gpu import Targets, oracle_frame, ptr_array, raw_of, stream, typed
+from tests.composite_targets import FormatTargets as BatchTargets
+from tests.helpers import encode_depth as encode
+from tests.helpers import frame_settings, oracle_frame, ptr_array
 
 pytestmark = pytest.mark.gpu
 
 ALL_FORMATS = [CF.RGBA16F, CF.RGBA32F, CF.RGBA8, CF.R11G11B10F]
 MODES = ((0, False), (1, True), (2, False))
-_ORACLE = {}
 
 
-class BatchTargets(Targets):
-    """Targets whose RGBA16F expectation is the oracle's composite (the model covers the other formats)."""
-
-    def expected(self, mode, f, with_g=True):
-        if self.fmt != CF.RGBA16F:
-            return super().expected(mode, f, with_g)
-        c, g = typed(self.color0[f], CF.RGBA16F).copy(), self.gbuf0[f].copy()
-        _ORACLE["O"].composite(np.ascontiguousarray(self.want_ao[f]), c, mode, self.ao_format, g if mode == 1 and with_g else None)
-        return raw_of(c, CF.RGBA16F, self.h, self.w), g
-
-
-@pytest.fixture(autouse=True)
-def _oracle(oracle):
-    _ORACLE["O"] = oracle
+def stream():
+    return torch.cuda.current_stream().cuda_stream
 
 
 def batch(ao, T, mode, with_g=True, n=None, stream_=None):
@@ -67,7 +55,7 @@ def same_as_per_frame(ao, T, mode, with_g, seed):
     B = BatchTargets(T.w, T.h, T.fmt, T.ao_format, T.kind, T.want_ao, seed=seed)
     per_frame(ao, B, mode, with_g)
     torch.cuda.synchronize()
-    assert torch.equal(T.color_buf, B.color_buf) and torch.equal(T.g, B.g), (T.kind, T.fmt, mode)
+    assert torch.equal(T.color.dev, B.color.dev) and torch.equal(T.g.dev, B.g.dev), (T.kind, T.fmt, mode)
 
 
 # ---- shapes x layouts x formats x modes x AO formats x n
@@ -236,20 +224,8 @@ def test_launch_counts(tmp_path):
 WS, HS = 96, 64
 
 
-def frame_settings(base, fp):
-    names = {"intensity": "intensity", "thicknessModifier": "thickness_modifier", "upsampleTolerance": "upsample_tolerance",
-             "blurTolerance": "blur_tolerance", "noiseFilterTolerance": "noise_filter_tolerance"}
-    return dataclasses.replace(base, **{names[k]: v for k, v in dataclasses.asdict(fp).items() if v is not None})
-
-
 def own_params(n):
     return [FrameParams(intensity=1.0 + 0.5 * f, thicknessModifier=1.0 + f, blurTolerance=-4.6 + 0.5 * f) for f in range(n)]
-
-
-def encode(depth, fmt):
-    if fmt == L.DEPTH_UNORM16:
-        return np.round(np.clip(depth, 0, 1) * 65535).astype(np.uint16)
-    return depth
 
 
 class Scene:
@@ -327,7 +303,7 @@ def test_execute_batch_shaded(oracle, case):
             assert S.shaded(ao, T, mode, params) == 0, err(ao)
             assert not ao.composite_pending
             S.check_ao()
-            T.check(mode, ao=T.ao_host)
+            T.check(mode, ao=T.ao.host)
     finally:
         ao.close()
 
@@ -352,7 +328,7 @@ def test_execute_batch_shaded_with_an_announcement(oracle):
         assert samples == 1 and ms[0] == 0 and ms[1] > 0, ms   # PASS_DOWNSAMPLE did not run in step 2: step 1 had carried it
         for k in range(3):
             steps[k].check_ao()
-            Ts[k].check(0, ao=Ts[k].ao_host)
+            Ts[k].check(0, ao=Ts[k].ao.host)
     finally:
         ao.close()
 
@@ -371,7 +347,7 @@ def test_execute_batch_shaded_sees_the_redone_lanes(oracle):
             S.out.fill_(0xA5)
             assert S.shaded(ao, T, 2) == 0, err(ao)           # DEBUG: the colour IS the AO
             S.check_ao()
-            T.check(2, ao=T.ao_host)
+            T.check(2, ao=T.ao.host)
     finally:
         ao.close()
 
@@ -392,14 +368,14 @@ def test_a_waiting_batch_is_left_alone_then_carried(oracle):
         other = S.targets(CF.R11G11B10F, "packed", 102)
         assert batch(ao, other, 0) == 0, err(ao)
         assert ao._lib.meao_composite_pending(ao._ctx, C.byref(pending)) == 0 and pending.value == n
-        other.check(0, ao=other.ao_host)
-        W.check(0, frames=(), ao=W.ao_host)                     # still waiting, untouched
+        other.check(0, ao=other.ao.host)
+        W.check(0, frames=(), ao=W.ao.host)                     # still waiting, untouched
         mine = S.targets(CF.RGBA8, "packed", 103)
         assert S.shaded(ao, mine, 0) == 0, err(ao)              # carries W as a plain execute would, and shades its own frames
         assert ao._lib.meao_composite_pending(ao._ctx, C.byref(pending)) == 0 and pending.value == 0
         S.check_ao()
-        W.check(0, ao=W.ao_host)
-        mine.check(0, ao=mine.ao_host)
+        W.check(0, ao=W.ao.host)
+        mine.check(0, ao=mine.ao.host)
     finally:
         ao.close()
 
@@ -450,8 +426,8 @@ def test_refusals(oracle):
         assert "meao_execute_batch_shaded" in err(ao) and "params[2]" in err(ao), err(ao)
         # nothing ran: AO and colours as they were, the batch still waits
         S.check_ao(untouched=True)
-        T.check(0, frames=(), ao=T.ao_host)
-        W.check(0, frames=(), ao=W.ao_host)
+        T.check(0, frames=(), ao=T.ao.host)
+        W.check(0, frames=(), ao=W.ao.host)
         pending = C.c_int32(0)
         assert lib.meao_composite_pending(ctx, C.byref(pending)) == 0 and pending.value == n
         # ... and the announcement is still there: the next call runs the waiting batch and carries the announced frames' downsample
@@ -498,7 +474,7 @@ def test_pool_of_two_members(oracle, tmp_path):
         assert not pool.composite_pending
         pool.synchronize()
         S.check_ao()
-        T.check(1, ao=T.ao_host)
+        T.check(1, ao=T.ao.host)
         with pytest.raises(L.MeaoError, match="meao_pool_execute_batch_shaded"):
             pool.execute_shaded_device(S.depth_ptrs(), S.out_ptrs(), 1, T.color_ptrs(), None, color_format=T.fmt)
     finally:

@@ -19,156 +19,18 @@ import pytest
 import torch
 
 from miniengineao_amd import _lib as L
-from miniengineao_amd import synth
 from tests import color_formats as CF
+from tests import composite_targets
 from tests import helpers as H
+from tests.composite_targets import FormatTargets as Targets
+from tests.composite_targets import random_color, raw_of, typed
+from tests.helpers import oracle_frame, ptr_array
 
 pytestmark = pytest.mark.gpu
 
 FORMATS = [CF.RGBA32F, CF.RGBA8, CF.R11G11B10F]
 SHAPES = [(64, 48), (133, 77), (130, 40), (67, 33), (640, 360)]      # w mod 4 = 0, 1, 2, 3; more groups per lane than one pass
 KINDS = ["packed", "vector", "scalar", "oddbase"]
-Y0 = 2
-_AO = {}
-
-
-def oracle_frame(oracle, w, h, ao_format, seed):
-    key = (w, h, ao_format, seed)
-    if key not in _AO:
-        depth = synth.make("S2", w, h, seed=seed)
-        _AO[key] = (depth, oracle.run(depth, H.settings(oracle, w, h, ao_format=ao_format), result_only=True)["result"])
-    return _AO[key]
-
-
-def up4(x):
-    return (x + 3) // 4 * 4
-
-
-def typed(raw, fmt):
-    """(h, w, texel bytes) uint8 -> the model's view of a colour surface."""
-    raw = np.ascontiguousarray(raw)
-    if fmt == CF.RGBA32F:
-        return raw.view(np.float32)
-    if fmt == CF.RGBA8:
-        return raw
-    if fmt == CF.R11G11B10F:
-        return raw.view(np.uint32)[..., 0]
-    return raw.view(np.uint16)
-
-
-def raw_of(c, fmt, h, w):
-    return np.ascontiguousarray(c).view(np.uint8).reshape(h, w, CF.TEXEL_BYTES[fmt])
-
-
-def random_color(rng, fmt, h, w):
-    """Random texels of `fmt` as (h, w, texel bytes) uint8, with one probe texel of non-finite and edge values."""
-    if fmt == CF.RGBA32F:
-        c = (rng.random((h, w, 4)) * 6.0).astype(np.float32)
-        c[h // 3, w // 2] = [np.inf, -np.inf, 1e-45, -0.0]
-    elif fmt == CF.RGBA8:
-        c = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
-        c[h // 3, w // 2] = [0, 255, 1, 254]
-    elif fmt == CF.R11G11B10F:
-        c = rng.integers(0, 1 << 32, (h, w), dtype=np.uint64).astype(np.uint32)
-        c &= ~np.uint32((0x400 << 0) | (0x400 << 11) | (0x200 << 22))                # exponents below 16: finite values up to 2
-        c[h // 3, w // 2] = 0x7C0 | (0x7FF << 11) | (0x001 << 22)                    # inf, NaN, the smallest subnormal
-    else:
-        c = (rng.random((h, w, 4)) * 6.0).astype(np.float16).view(np.uint16)
-    return raw_of(c, fmt, h, w)
-
-
-class Targets:
-    """n frames of AO (input), colour in `fmt` and RGBA8 GBuffer0 viewports inside larger surfaces filled with 0xA5."""
-
-    def __init__(self, w, h, fmt, ao_format, kind, ao_frames, color_frames=None, seed=1, device="cuda"):
-        self.w, self.h, self.fmt, self.ao_format, self.kind, self.n = w, h, fmt, ao_format, kind, len(ao_frames)
-        self.ae, self.ce = (1 if ao_format == L.AO_R8 else 2), CF.TEXEL_BYTES[fmt]
-        if kind == "vector":
-            (self.ax0, self.ap), (self.cx0, self.cp), (self.gx0, self.gp) = (4, up4(w + 8)), (4, up4(w + 8)), (1, w + 3)
-        elif kind == "scalar":
-            (self.ax0, self.ap), (self.cx0, self.cp), (self.gx0, self.gp) = (1, (w + 4) | 1), (1, (w + 4) | 1), (3, w + 5)
-        elif kind == "oddbase":
-            (self.ax0, self.ap), (self.cx0, self.cp), (self.gx0, self.gp) = (1, up4(w + 8)), (4, up4(w + 8)), (2, w + 2)
-        else:
-            (self.ax0, self.ap), (self.cx0, self.cp), (self.gx0, self.gp) = (0, w), (0, w), (0, w)
-        self.shift = 4 if kind == "oddbase" else 0                      # bytes the whole colour allocation is moved by
-        self.y0 = 0 if kind == "packed" else Y0
-        self.rows = h if kind == "packed" else h + Y0 + 1
-        rng = np.random.default_rng(seed)
-        n = self.n
-        self.want_ao = ao_frames
-        self.color0 = color_frames if color_frames is not None else [random_color(rng, fmt, h, w) for _ in range(n)]
-        self.gbuf0 = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(n)]
-        self.ao_host = np.full((n, self.rows, self.ap, self.ae), 0xA5, np.uint8)
-        self.color_host = np.full((n, self.rows, self.cp, self.ce), 0xA5, np.uint8)
-        self.g_host = np.full((n, self.rows, self.gp, 4), 0xA5, np.uint8)
-        for f in range(n):
-            self.view(self.ao_host, f, self.ax0)[...] = np.ascontiguousarray(ao_frames[f]).view(np.uint8).reshape(h, w, self.ae)
-            self.view(self.color_host, f, self.cx0)[...] = self.color0[f]
-            self.view(self.g_host, f, self.gx0)[...] = self.gbuf0[f]
-        if device is not None:
-            self.ao = torch.from_numpy(self.ao_host.copy()).to(device)
-            self.color_buf = torch.full((self.color_host.size + 16,), 0xA5, dtype=torch.uint8, device=device)
-            self.color = self.color_buf[self.shift:self.shift + self.color_host.size]
-            self.color.copy_(torch.from_numpy(self.color_host.reshape(-1)))
-            self.g = torch.from_numpy(self.g_host.copy()).to(device)
-
-    def view(self, a, f, x0):
-        return a[f, self.y0:self.y0 + self.h, x0:x0 + self.w]
-
-    ao_pitch = property(lambda self: 0 if self.kind == "packed" else self.ap * self.ae)
-    color_pitch = property(lambda self: 0 if self.kind == "packed" else self.cp * self.ce)
-    g_pitch = property(lambda self: 0 if self.kind == "packed" else self.gp * 4)
-
-    def ptrs(self, base, pitch, x0, elem):
-        return [base + ((f * self.rows + self.y0) * pitch + x0) * elem for f in range(self.n)]
-
-    def ao_ptrs(self, base=None):
-        return self.ptrs(self.ao.data_ptr() if base is None else base, self.ap, self.ax0, self.ae)
-
-    def color_ptrs(self, base=None):
-        return self.ptrs(self.color.data_ptr() if base is None else base, self.cp, self.cx0, self.ce)
-
-    def g_ptrs(self, base=None):
-        return self.ptrs(self.g.data_ptr() if base is None else base, self.gp, self.gx0, 4)
-
-    def expected(self, mode, f, with_g=True):
-        c, g = CF.composite(self.want_ao[f], self.ao_format, typed(self.color0[f], self.fmt), self.fmt, mode,
-                            self.gbuf0[f] if mode == 1 and with_g else None)
-        return raw_of(c, self.fmt, self.h, self.w), (g if g is not None else self.gbuf0[f])
-
-    def check(self, mode, frames=None, color=None, g=None, ao=None, nan_limit=4):
-        """Frames `frames` (default: all) composited in `mode`, the others as uploaded; arrays default to the device's.  nan_limit: how
-        many RGBA32F channel values of a frame may fall under the NaN rule (None: the frame is made of such values on purpose)."""
-        torch.cuda.synchronize()
-        if color is None:
-            assert (self.color_buf[:self.shift] == 0xA5).all() and (self.color_buf[self.shift + self.color_host.size:] == 0xA5).all()
-            color = self.color.cpu().numpy().reshape(self.color_host.shape)
-        g = self.g.cpu().numpy() if g is None else g
-        ao = self.ao.cpu().numpy() if ao is None else ao
-        assert np.array_equal(ao, self.ao_host), "the AO surface is an input"
-        frames = range(self.n) if frames is None else frames
-        for f in range(self.n):
-            want_c, want_g = self.expected(mode, f) if f in frames else (self.color0[f], self.gbuf0[f])
-            got_c, got_g = self.view(color, f, self.cx0), self.view(g, f, self.gx0)
-            if self.fmt == CF.RGBA32F:
-                gw, ww = got_c.view(np.uint32).copy(), np.ascontiguousarray(want_c).view(np.uint32).copy()
-                nan = np.isnan(ww.view(np.float32))
-                assert nan_limit is None or int(nan.sum()) <= nan_limit, "at most the probe texel's four channels fall under the NaN rule"
-                assert np.array_equal(np.isnan(gw.view(np.float32)), nan), (self.kind, mode, f, "NaN-ness")
-                gw[nan], ww[nan] = 0, 0
-                assert np.array_equal(gw, ww), (self.kind, self.fmt, mode, f, H.diff_report("color", gw, ww))
-            else:
-                assert np.array_equal(got_c, want_c), (self.kind, self.fmt, mode, f, H.diff_report("color", got_c, want_c))
-            assert np.array_equal(got_g, want_g), (self.kind, self.fmt, mode, f, H.diff_report("gbuffer0", got_g, want_g))
-            for a, x0, what in ((color, self.cx0, "colour"), (g, self.gx0, "GBuffer0")):
-                pad = np.ones(a[f].shape, bool)
-                self.view(pad[None], 0, x0)[...] = False
-                assert (a[f][pad] == 0xA5).all(), (f, what + " bytes outside the viewport changed")
-
-
-def ptr_array(ptrs):
-    return (C.c_void_p * len(ptrs))(*ptrs)
 
 
 def composite_now(ao, T, mode, stream, with_g=True):
@@ -294,23 +156,8 @@ def test_ambient_only_needs_the_gbuffer0_target(oracle):
 W3, H3, N3 = 133, 77, 3
 
 
-class Renders:
-    def __init__(self, oracle, w, h, ao_format, n):
-        frames = [oracle_frame(oracle, w, h, ao_format, 30 + f) for f in range(n)]
-        self.n, self.want = n, [a for _, a in frames]
-        self.depth = [torch.from_numpy(d).cuda() for d, _ in frames]
-        dt = torch.uint8 if ao_format == L.AO_R8 else torch.int16
-        self.out = [torch.zeros((h, w), dtype=dt, device="cuda") for _ in range(n)]
-
-    def execute(self, ao, n=None, params=None):
-        n = self.n if n is None else n
-        ao.execute_device([t.data_ptr() for t in self.depth[:n]], [t.data_ptr() for t in self.out[:n]], stream(), params=params)
-
-    def check(self):
-        torch.cuda.synchronize()
-        for f in range(self.n):
-            got = self.out[f].cpu().numpy().view(self.want[f].dtype)
-            assert np.array_equal(got, self.want[f]), (f, H.diff_report("result", got, self.want[f]))
+def Renders(oracle, w, h, ao_format, n):
+    return composite_targets.Renders([oracle_frame(oracle, w, h, ao_format, 30 + f) for f in range(n)], ao_format)
 
 
 @pytest.mark.parametrize("loc", ["device", "host"])
@@ -325,7 +172,7 @@ def test_standalone(oracle, mode, fmt, loc):
             composite_now(ao, T, mode, stream())
             T.check(mode)
         else:
-            color, g, a = T.color_host.copy(), T.g_host.copy(), T.ao_host.copy()
+            color, g, a = T.color.host.copy(), T.g.host.copy(), T.ao.host.copy()
             for f in range(N3):
                 rc = ao._lib.meao_composite_format(ao._ctx, mode, T.ao_ptrs(a.ctypes.data)[f], T.ao_pitch, T.color_ptrs(color.ctypes.data)[f],
                                                    fmt, T.color_pitch, T.g_ptrs(g.ctypes.data)[f] if mode == 1 else None, T.g_pitch,
@@ -461,13 +308,13 @@ def test_rgba16f_through_the_new_entry_points_is_the_old_call(oracle, mode, kind
             assert rc == 0
         composite_now(ao, B, mode, stream())
         torch.cuda.synchronize()
-        assert torch.equal(A.color, B.color) and torch.equal(A.g, B.g)
+        assert torch.equal(A.color.dev, B.color.dev) and torch.equal(A.g.dev, B.g.dev)
         for f in range(N3):
             want_c, want_g = typed(A.color0[f], CF.RGBA16F).copy(), A.gbuf0[f].copy()
             oracle.composite(R.want[f], want_c, mode, L.AO_R8, want_g if mode == 1 else None)
-            got = A.view(A.color.cpu().numpy().reshape(A.color_host.shape), f, A.cx0)
+            got = A.color.texels(f)
             assert H.nan_aware_equal(typed(got, CF.RGBA16F), want_c)[0]
-            assert np.array_equal(A.view(A.g.cpu().numpy(), f, A.gx0), want_g)
+            assert np.array_equal(A.g.texels(f), want_g)
         # enqueued through the new entry point, an RGBA16F batch is still carried by the render kernel (test_never_carried)
         R.execute(ao)
         assert enqueue(ao, B, mode) == 0

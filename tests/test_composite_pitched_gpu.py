@@ -17,8 +17,11 @@ import pytest
 import torch
 
 from miniengineao_amd import _lib as L
-from miniengineao_amd import synth
+from tests import color_formats as CF
+from tests import composite_targets
 from tests import helpers as H
+from tests.composite_targets import raw_of, typed
+from tests.helpers import oracle_frame, ptr_array
 
 pytestmark = pytest.mark.gpu
 
@@ -34,113 +37,50 @@ def odd(x):
     return x | 1
 
 
-_AO = {}
+def layout(kind, w, h):
+    table = {"vector": ((2, even(w + 6)), (2, even(w + 5)), (1, w + 3)), "scalar": ((1, odd(w + 4)), (1, odd(w + 4)), (3, w + 5)),
+             "oddbase": ((1, even(w + 6)), (1, even(w + 5)), (2, w + 2)), "packed": ((0, w), (0, w), (0, w))}      # "packed": tight rows
+    return table[kind], (0 if kind == "packed" else Y0), (h if kind == "packed" else h + Y0 + 1), 0
 
 
-def oracle_frame(oracle, w, h, ao_format, seed):
-    """(depth, oracle AO) of one synthetic frame; cached, the oracle is the slow part."""
-    key = (w, h, ao_format, seed)
-    if key not in _AO:
-        depth = synth.make("S2", w, h, seed=seed)
-        _AO[key] = (depth, oracle.run(depth, H.settings(oracle, w, h, ao_format=ao_format), result_only=True)["result"])
-    return _AO[key]
+def halfs(raw):
+    return typed(raw, CF.RGBA16F)
 
 
-class Targets:
+def is_nan(x):
+    return (x & 0x7fff) > 0x7c00
+
+
+class Targets(composite_targets.Targets):
     """n frames of AO (input), RGBA16F colour and RGBA8 GBuffer0 viewports at (x0, Y0) of (h + Y0 + 1)-row surfaces."""
 
     def __init__(self, oracle, w, h, n, ao_format, kind, seed, device="cuda"):
-        self.w, self.h, self.n, self.ao_format, self.kind = w, h, n, ao_format, kind
-        self.ae = 1 if ao_format == L.AO_R8 else 2
-        if kind == "vector":
-            (self.ax0, self.ap), (self.cx0, self.cp), (self.gx0, self.gp) = (2, even(w + 6)), (2, even(w + 5)), (1, w + 3)
-        elif kind == "scalar":
-            (self.ax0, self.ap), (self.cx0, self.cp), (self.gx0, self.gp) = (1, odd(w + 4)), (1, odd(w + 4)), (3, w + 5)
-        elif kind == "oddbase":
-            (self.ax0, self.ap), (self.cx0, self.cp), (self.gx0, self.gp) = (1, even(w + 6)), (1, even(w + 5)), (2, w + 2)
-        else:                                                   # "packed": tight rows, no padding rows
-            (self.ax0, self.ap), (self.cx0, self.cp), (self.gx0, self.gp) = (0, w), (0, w), (0, w)
-        self.y0 = 0 if kind == "packed" else Y0
-        self.rows = h if kind == "packed" else h + Y0 + 1
         rng = np.random.default_rng(seed)
         frames = [oracle_frame(oracle, w, h, ao_format, seed + f) for f in range(n)]
         self.depth = [d for d, _ in frames]
-        self.want_ao = [a for _, a in frames]
-        self.color0 = [(rng.random((h, w, 4)) * 6.0).astype(np.float16).view(np.uint16) for _ in range(n)]
-        for c in self.color0:
+        color = [(rng.random((h, w, 4)) * 6.0).astype(np.float16).view(np.uint16) for _ in range(n)]
+        for c in color:
             c[h // 3, w // 2] = [0x7c00, 0xfc00, 0x0001, 0x8000]         # the probe texel: inf, -inf, smallest subnormal, -0
-        self.gbuf0 = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(n)]
-        self.ao_host = np.full((n, self.rows, self.ap), 0xA5A5 if self.ae == 2 else 0xA5, np.uint16 if self.ae == 2 else np.uint8)
-        self.color_host = np.full((n, self.rows, self.cp, 4), 0xA5A5, np.uint16)
-        self.g_host = np.full((n, self.rows, self.gp, 4), 0xA5, np.uint8)
-        for f in range(n):
-            self.ao_view(self.ao_host, f)[...] = self.want_ao[f]
-            self.color_view(self.color_host, f)[...] = self.color0[f]
-            self.g_view(self.g_host, f)[...] = self.gbuf0[f]
-        if device is not None:
-            self.ao = torch.from_numpy(self.ao_host.view(np.uint8).copy()).to(device)
-            self.color = torch.from_numpy(self.color_host.view(np.int16).copy()).to(device)
-            self.g = torch.from_numpy(self.g_host.copy()).to(device)
+        g = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(n)]
+        super().__init__(w, h, CF.RGBA16F, ao_format, kind, layout(kind, w, h), [a for _, a in frames],
+                         [raw_of(c, CF.RGBA16F, h, w) for c in color], g, device)
 
-    def ao_view(self, a, f):
-        return a[f, self.y0:self.y0 + self.h, self.ax0:self.ax0 + self.w]
+    # the pitches as they are, a packed row's included
+    ao_pitch = property(lambda self: self.ao.row_bytes)
+    color_pitch = property(lambda self: self.color.row_bytes)
+    g_pitch = property(lambda self: self.g.row_bytes)
 
-    def color_view(self, a, f):
-        return a[f, self.y0:self.y0 + self.h, self.cx0:self.cx0 + self.w]
-
-    def g_view(self, a, f):
-        return a[f, self.y0:self.y0 + self.h, self.gx0:self.gx0 + self.w]
-
-    ao_pitch = property(lambda self: self.ap * self.ae)
-    color_pitch = property(lambda self: self.cp * 8)
-    g_pitch = property(lambda self: self.gp * 4)
-
-    def ao_ptrs(self, base=None):
-        b = self.ao.data_ptr() if base is None else base
-        return [b + ((f * self.rows + self.y0) * self.ap + self.ax0) * self.ae for f in range(self.n)]
-
-    def color_ptrs(self, base=None):
-        b = self.color.data_ptr() if base is None else base
-        return [b + ((f * self.rows + self.y0) * self.cp + self.cx0) * 8 for f in range(self.n)]
-
-    def g_ptrs(self, base=None):
-        b = self.g.data_ptr() if base is None else base
-        return [b + ((f * self.rows + self.y0) * self.gp + self.gx0) * 4 for f in range(self.n)]
-
-    def expected(self, oracle, mode, f):
-        c, g = self.color0[f].copy(), self.gbuf0[f].copy()
-        oracle.composite(self.want_ao[f], c, mode, self.ao_format, g if mode == 1 else None)
-        return c, g
+    def same_color(self, got, want, nan_limit, what):
+        """Colour values the oracle gives as NaN are compared for NaN-ness only."""
+        got, want = halfs(got), halfs(want)
+        assert int(is_nan(want).sum()) <= 4, "at most the probe texel's four channels fall under the NaN rule"
+        got, want = np.where(is_nan(got), 0x7e00, got), np.where(is_nan(want), 0x7e00, want)
+        assert np.array_equal(got, want), (what, H.diff_report("color", got, want))
 
     def check(self, oracle, mode, frames=None, color=None, g=None, ao=None, untouched=()):
         """Frames `frames` (default: all) composited in `mode`, frames `untouched` as uploaded; arrays default to the device's."""
-        torch.cuda.synchronize()
-        color = self.color.cpu().numpy().view(np.uint16) if color is None else color
-        g = self.g.cpu().numpy() if g is None else g
-        ao = (self.ao.cpu().numpy().view(self.ao_host.dtype).reshape(self.ao_host.shape)) if ao is None else ao
-        assert np.array_equal(ao, self.ao_host), "the AO surface is an input"
-        frames = range(self.n) if frames is None else frames
-        for f in range(self.n):
-            if f in untouched or f not in frames:
-                want_c, want_g = self.color0[f], self.gbuf0[f]
-            else:
-                want_c, want_g = self.expected(oracle, mode, f)
-            got_c, got_g = self.color_view(color, f), self.g_view(g, f)
-            nan = lambda x: (x & 0x7fff) > 0x7c00                # noqa: E731
-            assert int(nan(want_c).sum()) <= 4, "at most the probe texel's four channels fall under the NaN rule"
-            ok = np.array_equal(np.where(nan(got_c), 0x7e00, got_c), np.where(nan(want_c), 0x7e00, want_c))
-            assert ok, (self.kind, mode, f, H.diff_report("color", np.where(nan(got_c), 0x7e00, got_c), np.where(nan(want_c), 0x7e00, want_c)))
-            assert np.array_equal(got_g, want_g), (self.kind, mode, f, H.diff_report("gbuffer0", got_g, want_g))
-            pad = np.ones(color[f].shape, bool)
-            self.color_view(pad[None], 0)[...] = False
-            assert (color[f][pad] == 0xA5A5).all(), (f, "colour bytes outside the viewport changed")
-            pad = np.ones(g[f].shape, bool)
-            self.g_view(pad[None], 0)[...] = False
-            assert (g[f][pad] == 0xA5).all(), (f, "GBuffer0 bytes outside the viewport changed")
-
-
-def ptr_array(ptrs):
-    return (C.c_void_p * len(ptrs))(*ptrs)
+        frames = [f for f in (range(self.n) if frames is None else frames) if f not in untouched]
+        super().check(mode, frames, color, g, ao)
 
 
 def composite_now(ao, T, mode, stream, frames=None):
@@ -161,25 +101,8 @@ def enqueue(ao, T, mode, ao_pitch=None, color_pitch=None, g_pitch=None, with_g=N
         ptr_array(T.g_ptrs()) if with_g else None, T.g_pitch if g_pitch is None else g_pitch)
 
 
-class Renders:
-    """Depth frames on the device and somewhere for the AO of the calls that carry (or push out) a composite batch."""
-
-    def __init__(self, T, n):
-        self.n = n
-        self.depth = [torch.from_numpy(T.depth[f % T.n]).cuda() for f in range(n)]
-        self.want = [T.want_ao[f % T.n] for f in range(n)]
-        dt = torch.uint8 if T.ao_format == L.AO_R8 else torch.int16
-        self.out = [torch.zeros((T.h, T.w), dtype=dt, device="cuda") for _ in range(n)]
-
-    def execute(self, ao, stream, n=None, params=None):
-        n = self.n if n is None else n
-        ao.execute_device([t.data_ptr() for t in self.depth[:n]], [t.data_ptr() for t in self.out[:n]], stream, params=params)
-
-    def check(self, n=None):
-        torch.cuda.synchronize()
-        for f in range(self.n if n is None else n):
-            got = self.out[f].cpu().numpy().view(self.want[f].dtype)
-            assert np.array_equal(got, self.want[f]), (f, H.diff_report("result", got, self.want[f]))
+def Renders(T, n):
+    return composite_targets.Renders([(T.depth[f % T.n], T.want_ao[f % T.n]) for f in range(n)], T.ao_format)
 
 
 def context(oracle, T, max_batch):
@@ -209,7 +132,7 @@ def test_standalone_host(oracle, mode, ao_format, kind):
     T = Targets(oracle, 131, 77, 1, ao_format, kind, seed=13, device=None)
     ao = context(oracle, T, 1)
     try:
-        color, g, a = T.color_host.copy(), T.g_host.copy(), T.ao_host.copy()
+        color, g, a = T.color.host.copy(), T.g.host.copy(), T.ao.host.copy()
         rc = ao._lib.meao_composite_pitched(ao._ctx, mode, T.ao_ptrs(a.ctypes.data)[0], T.ao_pitch, T.color_ptrs(color.ctypes.data)[0],
                                             T.color_pitch, T.g_ptrs(g.ctypes.data)[0] if mode == 1 else None, T.g_pitch,
                                             L.MEM_HOST, None)
@@ -231,11 +154,10 @@ def test_enqueued_and_carried(oracle, mode, ao_format, w, h, kind):
     R = Renders(T, n)
     ao = context(oracle, T, n)
     try:
-        st = torch.cuda.current_stream().cuda_stream
-        R.execute(ao, st)
+        R.execute(ao)
         assert enqueue(ao, T, mode) == 0, ao._lib.meao_last_error(ao._ctx)
         assert ao.composite_pending
-        R.execute(ao, st)                           # carries the batch: in its texel loop for multiply, in front of the tile otherwise
+        R.execute(ao)                           # carries the batch: in its texel loop for multiply, in front of the tile otherwise
         assert not ao.composite_pending
         T.check(oracle, mode)
         R.check()
@@ -248,10 +170,9 @@ def test_oddbase_batch_is_carried_in_the_scalar_form(oracle):
     R = Renders(T, 2)
     ao = context(oracle, T, 2)
     try:
-        st = torch.cuda.current_stream().cuda_stream
-        R.execute(ao, st)
+        R.execute(ao)
         assert enqueue(ao, T, 0) == 0
-        R.execute(ao, st)
+        R.execute(ao)
         T.check(oracle, 0)
     finally:
         ao.close()
@@ -268,10 +189,9 @@ def test_rows_wider_than_a_workgroup_are_carried_in_chunks(oracle, ao_format, w,
     R = Renders(T, n)
     ao = context(oracle, T, n)
     try:
-        st = torch.cuda.current_stream().cuda_stream
-        R.execute(ao, st)
+        R.execute(ao)
         assert enqueue(ao, T, 0) == 0, ao._lib.meao_last_error(ao._ctx)
-        R.execute(ao, st)
+        R.execute(ao)
         assert not ao.composite_pending
         T.check(oracle, 0)
         R.check()
@@ -291,7 +211,7 @@ def test_waiting_batch_runs_with_its_pitches(oracle, way, mode, ao_format, w, h,
     ao = context(oracle, T, 3)
     try:
         st = torch.cuda.current_stream().cuda_stream
-        R.execute(ao, st, n)
+        R.execute(ao, n)
         assert enqueue(ao, T, mode) == 0, ao._lib.meao_last_error(ao._ctx)
         if way == "flush":
             ao.composite_flush(st)
@@ -304,10 +224,10 @@ def test_waiting_batch_runs_with_its_pitches(oracle, way, mode, ao_format, w, h,
             ao.composite_flush(st)
             T2.check(oracle, mode)
         elif way == "other_frame_count":
-            R.execute(ao, st, 3)                        # three render frames, two composite frames: in front of the tiles
+            R.execute(ao, 3)                        # three render frames, two composite frames: in front of the tiles
             R.check(3)
         elif way == "per_frame_call":
-            R.execute(ao, st, n, params=[None] * n)     # a per-frame call carries nothing: it flushes first
+            R.execute(ao, n, params=[None] * n)     # a per-frame call carries nothing: it flushes first
             R.check(n)
         else:
             torch.cuda.synchronize()
@@ -430,20 +350,20 @@ def test_packed_pitch_through_the_pitched_entry_points_is_the_packed_call(oracle
             ao.composite_device(mode, A.ao_ptrs()[f], A.color_ptrs()[f], A.g_ptrs()[f] if mode == 1 else 0, st)
         composite_now(ao, B, mode, st)
         torch.cuda.synchronize()
-        assert torch.equal(A.color, B.color) and torch.equal(A.g, B.g)
+        assert torch.equal(A.color.dev, B.color.dev) and torch.equal(A.g.dev, B.g.dev)
         A.check(oracle, mode)
         # composited twice now, enqueued and carried: still the same bits
-        R.execute(ao, st)
+        R.execute(ao)
         ao.composite_enqueue_device(mode, A.ao_ptrs(), A.color_ptrs(), A.g_ptrs() if mode == 1 else None)
-        R.execute(ao, st)
+        R.execute(ao)
         assert enqueue(ao, B, mode) == 0
-        R.execute(ao, st)
+        R.execute(ao)
         assert enqueue(ao, Z, mode, ao_pitch=0, color_pitch=0, g_pitch=0) == 0
-        R.execute(ao, st)
+        R.execute(ao)
         composite_now(ao, Z, mode, st)
         torch.cuda.synchronize()
-        assert torch.equal(A.color, B.color) and torch.equal(A.g, B.g)
-        assert torch.equal(A.color, Z.color) and torch.equal(A.g, Z.g)
+        assert torch.equal(A.color.dev, B.color.dev) and torch.equal(A.g.dev, B.g.dev)
+        assert torch.equal(A.color.dev, Z.color.dev) and torch.equal(A.g.dev, Z.g.dev)
     finally:
         ao.close()
 
@@ -541,9 +461,9 @@ def test_refusals_launch_nothing_and_leave_a_waiting_batch_alone(oracle):
         pool.synchronize()
         torch.cuda.synchronize()
         # T was composited twice now (the context's batch, then the pool's): AMBIENT_ONLY twice
-        c, g = T.expected(oracle, 1, 0)
-        oracle.composite(T.want_ao[0], c, 1, L.AO_F16, g)
-        assert np.array_equal(T.g_view(T.g.cpu().numpy(), 0), g)
+        c, g = T.expected(1, 0)
+        oracle.composite(T.want_ao[0], halfs(c), 1, L.AO_F16, g)
+        assert np.array_equal(T.g.texels(0), g)
     finally:
         ao.close()
         pool.close()

@@ -7,8 +7,7 @@ import pytest
 
 from miniengineao_amd import synth
 from tests import helpers as H
-
-FORMATS = {"f32": 0, "unorm16": 1, "unorm24": 2, "f16": 3}
+from tests.helpers import DEPTH_FORMATS as FORMATS
 
 
 def test_unorm_decode_is_exact_for_every_code(oracle):

@@ -10,81 +10,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from miniengineao_amd import FrameParams, synth
+from miniengineao_amd import FrameParams
 from miniengineao_amd import _lib as L
 from tests import helpers as H
+from tests.dynamic_resolution import A, B, C3, LADDER, PER_FRAME, RES, Stream, Surfaces, call_frames, want_of
+from tests.helpers import PASS_DOWNSAMPLE, colour
 
 pytestmark = pytest.mark.gpu
-
-RES = (400, 272)
-LADDER = [(384, 256), (200, 120), (380, 250), (97, 61), (33, 17), (400, 272), (200, 120)]
-PASS_DOWNSAMPLE = 0
-PATTERN = 0xA5
-
-_frames, _wants = {}, {}
-
-
-def frame(kind, w, h, seed):
-    """Distinct contents: "S2" = synth.make("S2"), "field" = a sparser synth.occluder_field."""
-    key = (kind, w, h, seed)
-    if key not in _frames:
-        _frames[key] = synth.make("S2", w, h, seed=seed) if kind == "S2" else synth.occluder_field(w, h, seed=seed, n_rects=48, n_discs=24)
-    return _frames[key]
-
-
-def call_frames(k, w, h):
-    """The two frames of call k: an S2 frame and an occluder field, other contents in every call."""
-    return [frame("S2", w, h, 3 + 2 * k), frame("field", w, h, 1000 + 7 * k)]
-
-
-def skey(s):
-    return (s.width, s.height, s.ao_format, s.hq_levels, s.depth_format, s.intensity, s.thickness_modifier, s.proj00)
-
-
-def want_of(oracle, depth, s, key, full=False):
-    """The oracle's buffers for `depth` under `s`, computed once per (frame, settings)."""
-    k = (key, skey(s), full)
-    if k not in _wants:
-        _wants[k] = oracle.run(depth, s) if full else oracle.run(depth, s, result_only=True)
-    return _wants[k]
-
-
-def ao_dtype(fmt):
-    return np.uint8 if fmt == L.AO_R8 else np.uint16
-
-
-class Surfaces:
-    """n device surfaces of sw x sh texels of `dtype`, filled with a pattern, the frames in their top-left w x h viewports."""
-
-    def __init__(self, torch, n, sw, sh, dtype, tail=()):
-        self.torch, self.dtype, self.sw, self.sh, self.tail = torch, np.dtype(dtype), sw, sh, tuple(tail)
-        texels = sh * sw * int(np.prod(self.tail, dtype=np.int64))
-        self.host = [np.full(texels * self.dtype.itemsize, PATTERN, np.uint8).view(self.dtype).reshape((sh, sw) + self.tail)
-                     for _ in range(n)]
-        self.dev = [None] * n
-
-    def put(self, frames):
-        for f, a in enumerate(frames):
-            self.host[f][:a.shape[0], :a.shape[1]] = a
-        self.upload()
-
-    def upload(self):
-        self.dev = [self.torch.from_numpy(h.reshape(-1).view(np.uint8).copy()).cuda() for h in self.host]
-
-    def ptrs(self):
-        return [d.data_ptr() for d in self.dev]
-
-    @property
-    def pitch(self):
-        return self.sw * self.dtype.itemsize * int(np.prod(self.tail, dtype=np.int64))
-
-    def get(self, f, w, h):
-        """(the w x h viewport of surface f, whether every byte outside it still holds what the host put there)"""
-        got = self.dev[f].cpu().numpy().view(self.dtype).reshape((self.sh, self.sw) + self.tail)
-        keep = got.copy()
-        keep[:h, :w] = self.host[f][:h, :w]
-        return got[:h, :w].copy(), np.array_equal(keep.view(np.uint8), self.host[f].view(np.uint8))
-
 
 VARIANTS = {
     # name: (oracle Settings fields, component keywords, how the call is made)
@@ -97,7 +29,6 @@ VARIANTS = {
     "viewport_f16": (dict(ao_format=L.AO_F16), dict(), "viewport"),
     "shaded": (dict(), dict(), "shaded"),
 }
-PER_FRAME = [dict(), dict(intensity=1.5, thickness_modifier=2.0)]       # frame 1 of a per-frame call has parameters of its own
 
 
 def settings_for(oracle, w, h, skw, f=0, how="packed"):
@@ -113,12 +44,6 @@ def frame_params(oracle, w, h, skw):
     return out
 
 
-def colour(w, h, seed):
-    """RGBA16F bits: finite halfs of every sign and size."""
-    rng = np.random.default_rng(seed)
-    return (rng.integers(0, 0x7C00, (h, w, 4)) | (rng.integers(0, 2, (h, w, 4)) << 15)).astype(np.uint16)
-
-
 def run_call(torch, oracle, ao, k, w, h, skw, how):
     """Call k at the context's current size w x h.  Returns (results, full oracle buffers of frame 0 or None); asserts exactness."""
     s0 = settings_for(oracle, w, h, skw)
@@ -126,17 +51,14 @@ def run_call(torch, oracle, ao, k, w, h, skw, how):
     raw = call_frames(k, w, h)
     depth = [oracle.encode_depth(d, skw["depth_format"]) for d in raw] if "depth_format" in skw else raw
     surf = RES if how in ("viewport", "shaded") else (w, h)
-    din = Surfaces(torch, 2, surf[0], surf[1], depth[0].dtype)
-    din.put(depth)
-    out = Surfaces(torch, 2, surf[0], surf[1], ao_dtype(s0.ao_format))
-    out.upload()
+    din = Surfaces(2, surf, (w, h), depth[0].dtype, frames=depth)
+    out = Surfaces(2, surf, (w, h), H.ao_dtype(s0.ao_format))
     dp, op = (din.pitch, out.pitch) if surf != (w, h) else (0, 0)
     params = frame_params(oracle, w, h, skw) if how == "per_frame" else None
     col = None
     if how == "shaded":
-        col = Surfaces(torch, 2, surf[0], surf[1], np.uint16, tail=(4,))
-        col.put([colour(w, h, 50 + 2 * k + f) for f in range(2)])
-        before = [c[:h, :w].copy() for c in col.host]
+        before = [colour(w, h, 50 + 2 * k + f) for f in range(2)]
+        col = Surfaces(2, surf, (w, h), np.uint16, tail=(4,), frames=before)
         ao.execute_shaded_device(din.ptrs(), out.ptrs(), L.COMPOSITE_MULTIPLY, col.ptrs(), depth_pitch=dp, out_pitch=op, color_pitch=col.pitch)
     else:
         ao.execute_device(din.ptrs(), out.ptrs(), params=params, depth_pitch=dp, out_pitch=op)
@@ -145,14 +67,14 @@ def run_call(torch, oracle, ao, k, w, h, skw, how):
     for f in range(2):
         s = settings_for(oracle, w, h, skw, f, how)
         want = want_of(oracle, depth[f], s, (k, f), full=(f == 0))["result"]
-        g, untouched = out.get(f, w, h)
+        g, untouched = out.get(f)
         assert np.array_equal(g, want), (k, (w, h), f, H.diff_report("result", g, want))
         assert untouched, (k, (w, h), f, "texels outside the viewport were written")
         got.append(g)
         if col is not None:
             expect = before[f].copy()
             oracle.composite(want, expect, L.COMPOSITE_MULTIPLY, s.ao_format)
-            c, untouched = col.get(f, w, h)
+            c, untouched = col.get(f)
             assert np.array_equal(c, expect), (k, (w, h), f, "colour")
             assert untouched, (k, (w, h), f, "colour texels outside the viewport were written")
     return got, want_of(oracle, depth[0], s0, (k, 0), full=True), (din, out)
@@ -205,67 +127,6 @@ def test_host_frames_follow_the_resizes(oracle):
 
 
 # ---- the pipelined stream across size changes
-
-class Stream:
-    """A pipelined context with a reservation, fed depth frames in 400 x 272 surfaces or packed.  Shared parameters: the camera
-    does not change with the size (one proj00, the oracle's Settings take it: meao_set_params would drop every announcement);
-    per-frame parameters: every frame brings the proj00 of its size, as H.settings computes it."""
-
-    def __init__(self, torch, oracle, own_launch, per_frame, first):
-        self.torch, self.O, self.per_frame = torch, oracle, per_frame
-        self.proj00 = H.settings(oracle, *first).proj00
-        self.ao = H.component(self.settings(*first), max_batch=2, pipelined=True, debug={L.DEBUG_NEXT_DOWNSAMPLE_OWN_LAUNCH: own_launch})
-        self.ao.reserve(*RES)
-        self.ao.set_profiling(True)
-        self.keep = []
-
-    def settings(self, w, h, f=0):
-        s = H.settings(self.O, w, h, **(PER_FRAME[f] if self.per_frame else {}))
-        if not self.per_frame:
-            s.proj00 = self.proj00
-        return s
-
-    def params(self, w, h):
-        if not self.per_frame:
-            return None
-        return [FrameParams(intensity=s.intensity, thicknessModifier=s.thickness_modifier, projection00=s.proj00)
-                for s in (self.settings(w, h, f) for f in range(2))]
-
-    def batch(self, k, w, h):
-        """Device frames of step k (packed) and the AO surfaces they will be written to."""
-        raw = call_frames(k, w, h)
-        din = Surfaces(self.torch, 2, w, h, np.float32)
-        din.put(raw)
-        out = Surfaces(self.torch, 2, w, h, np.uint8)
-        out.upload()
-        self.keep.append((din, out))
-        return dict(k=k, size=(w, h), raw=raw, din=din, out=out)
-
-    def announce(self, b, sized=True):
-        self.ao.prefetch_device(b["din"].ptrs(), self.params(*b["size"]), size=b["size"] if sized else None)
-
-    def execute(self, b):
-        self.ao.execute_device(b["din"].ptrs(), b["out"].ptrs(), params=self.params(*b["size"]))
-
-    def check(self, b):
-        self.ao.synchronize()
-        w, h = b["size"]
-        for f in range(2):
-            want = want_of(self.O, b["raw"][f], self.settings(w, h, f), (b["k"], f))["result"]
-            got, _ = b["out"].get(f, w, h)
-            assert np.array_equal(got, want), (b["k"], b["size"], f, H.diff_report("result", got, want))
-
-    def downsample_ms(self, b):
-        """The DOWNSAMPLE slot of executing `b` alone: 0 = that call launched no downsample pass."""
-        self.ao.set_profiling(True)                 # restarts the window
-        self.execute(b)
-        ms, n = self.ao.pass_times_ms()
-        assert n == 1
-        self.check(b)
-        return ms[PASS_DOWNSAMPLE]
-
-
-A, B, C3 = (384, 256), (200, 120), (380, 250)
 
 
 @pytest.mark.parametrize("per_frame", [False, True])
@@ -361,9 +222,8 @@ def test_resize_rules_for_announcements_and_composites(oracle):
         b = st.batch(408, *A)
         st.execute(b)
         st.check(b)
-        col = Surfaces(torch, 2, A[0], A[1], np.uint16, tail=(4,))
         before = [colour(A[0], A[1], 60 + f) for f in range(2)]
-        col.put(before)
+        col = Surfaces(2, A, A, np.uint16, tail=(4,), frames=before)
         ao.composite_enqueue_device(L.COMPOSITE_MULTIPLY, b["out"].ptrs(), col.ptrs())
         assert ao.composite_pending
         ao.resize(*B)
@@ -372,8 +232,8 @@ def test_resize_rules_for_announcements_and_composites(oracle):
         torch.cuda.synchronize()
         for f in range(2):
             want = before[f].copy()
-            oracle.composite(b["out"].get(f, *A)[0], want, L.COMPOSITE_MULTIPLY, L.AO_R8)
-            assert np.array_equal(col.get(f, *A)[0], want), f
+            oracle.composite(b["out"].get(f)[0], want, L.COMPOSITE_MULTIPLY, L.AO_R8)
+            assert np.array_equal(col.get(f)[0], want), f
     finally:
         ao.close()
 
@@ -447,10 +307,8 @@ def test_pool_ladder_and_refused_resize(oracle):
             assert member_sizes(pool) == [(w, h)] * 2
             s = H.settings(oracle, w, h)
             raw = call_frames(600 + 2 * k, w, h) + call_frames(601 + 2 * k, w, h)           # four distinct frames
-            din = Surfaces(torch, 4, w, h, np.float32)
-            din.put(raw)
-            out = Surfaces(torch, 4, w, h, np.uint8)
-            out.upload()
+            din = Surfaces(4, (w, h), (w, h), np.float32, frames=raw)
+            out = Surfaces(4, (w, h), (w, h), np.uint8)
             keep.append((din, out))
             # every frame brings the camera of its size (the pool has no set_params between calls here)
             prm = [FrameParams(projection00=s.proj00)] * 4
@@ -458,19 +316,15 @@ def test_pool_ladder_and_refused_resize(oracle):
             pool.synchronize()
             for f in range(4):
                 want = want_of(oracle, raw[f], s, (600 + 2 * k + f // 2, f % 2))["result"]
-                got, _ = out.get(f, w, h)
+                got, _ = out.get(f)
                 assert np.array_equal(got, want), (k, (w, h), f, H.diff_report("result", got, want))
         # sized announcements through the pool: announced at the current size for the next, kept by the pool's resize
         (wa, ha), (wb, hb) = LADDER[3], LADDER[1]
         sa, sb = H.settings(oracle, wa, ha), H.settings(oracle, wb, hb)
         raw_a = call_frames(610, wa, ha) + call_frames(611, wa, ha)
         raw_b = call_frames(612, wb, hb) + call_frames(613, wb, hb)
-        da, db = Surfaces(torch, 4, wa, ha, np.float32), Surfaces(torch, 4, wb, hb, np.float32)
-        da.put(raw_a)
-        db.put(raw_b)
-        oa, ob = Surfaces(torch, 4, wa, ha, np.uint8), Surfaces(torch, 4, wb, hb, np.uint8)
-        oa.upload()
-        ob.upload()
+        da, db = Surfaces(4, (wa, ha), (wa, ha), np.float32, frames=raw_a), Surfaces(4, (wb, hb), (wb, hb), np.float32, frames=raw_b)
+        oa, ob = Surfaces(4, (wa, ha), (wa, ha), np.uint8), Surfaces(4, (wb, hb), (wb, hb), np.uint8)
         pb = [FrameParams(projection00=sb.proj00)] * 4
         pool.prefetch_device(db.ptrs(), pb, size=(wb, hb))
         pool.execute_device(da.ptrs(), oa.ptrs(), params=[FrameParams(projection00=sa.proj00)] * 4)
@@ -484,8 +338,8 @@ def test_pool_ladder_and_refused_resize(oracle):
             L.check(lib.meao_get_pass_times(pool.member_context(m), C.byref(ms), C.byref(n)))
             assert n.value == 1 and ms[PASS_DOWNSAMPLE] == 0, (m, list(ms))
         for f in range(4):
-            assert np.array_equal(oa.get(f, wa, ha)[0], want_of(oracle, raw_a[f], sa, (610 + f // 2, f % 2))["result"]), f
-            assert np.array_equal(ob.get(f, wb, hb)[0], want_of(oracle, raw_b[f], sb, (612 + f // 2, f % 2))["result"]), f
+            assert np.array_equal(oa.get(f)[0], want_of(oracle, raw_a[f], sa, (610 + f // 2, f % 2))["result"]), f
+            assert np.array_equal(ob.get(f)[0], want_of(oracle, raw_b[f], sb, (612 + f // 2, f % 2))["result"]), f
         # a size one member's reservation does not cover is refused before any member is touched
         L.check(lib.meao_reserve(pool.member_context(0), 512, 300))
         before = member_sizes(pool)

@@ -17,7 +17,7 @@ every reserve and resize (and every refused one) it compares every member's size
 import pytest
 
 from tests import call_model as M
-from tests import test_call_sequences_gpu as S
+from tests import test_call_sequences_gpu as S          # the call-sequence driver stays in its suite
 
 pytestmark = pytest.mark.gpu
 
@@ -72,9 +72,9 @@ def run_stepped(oracle, lin_c, kind, name, own_launch):
 
 
 @pytest.fixture(scope="module")
-def lin_c(tmp_path_factory):
-    from tests.test_linear_depth_gpu import build_linearize
-    return build_linearize(str(tmp_path_factory.mktemp("lin")))
+def lin_c():
+    from tests.linear_depth import linearize
+    return linearize()
 
 
 @pytest.mark.parametrize("own_launch", [0, 1])

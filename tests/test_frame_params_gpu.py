@@ -14,51 +14,11 @@ from miniengineao_amd import FrameParams
 from miniengineao_amd import _lib as L
 from miniengineao_amd import synth
 from tests import helpers as H
+from tests.helpers import encode_depth, f32, frame_settings, random_params
 
 pytestmark = pytest.mark.gpu
 
 PASS_DOWNSAMPLE, PASS_UPSAMPLE_3, PASS_UPSAMPLE_2 = 0, 2, 3      # meao_pass launch slots
-
-# FrameParams field -> oracle Settings field
-ORACLE_FIELD = {"nearClipPlane": "near_clip", "farClipPlane": "far_clip", "projection00": "proj00",
-                "usesReversedZBuffer": "reversed_z", "singlePassStereoEnabled": "single_pass_stereo",
-                "intensity": "intensity", "thicknessModifier": "thickness_modifier",
-                "noiseFilterTolerance": "noise_filter_tolerance", "blurTolerance": "blur_tolerance",
-                "upsampleTolerance": "upsample_tolerance"}
-
-
-def f32(x):
-    return float(np.float32(x))
-
-
-def random_params(rng, w, h, n):
-    """n FrameParams with all ten fields drawn from their valid ranges, plus the extremes."""
-    out = []
-    for f in range(n):
-        near = f32(10 ** rng.uniform(-2, 0))
-        far = f32(near * 10 ** rng.uniform(1, 4))
-        fov = rng.uniform(20, 100)
-        out.append(FrameParams(
-            nearClipPlane=near, farClipPlane=far,
-            projection00=synth.Camera(near, far, fov).proj00(w, h),
-            usesReversedZBuffer=bool(rng.integers(0, 2)), singlePassStereoEnabled=bool(rng.integers(0, 2)),
-            intensity=f32(rng.uniform(0, 4)), thicknessModifier=f32(rng.uniform(1, 10)),
-            noiseFilterTolerance=f32(rng.uniform(-8, 0)), blurTolerance=f32(rng.uniform(-8, -1)),
-            upsampleTolerance=f32(rng.uniform(-12, -1))))
-    ext = [dict(nearClipPlane=0.01, farClipPlane=1e5, usesReversedZBuffer=True, upsampleTolerance=-1.0, noiseFilterTolerance=-8.0),
-           dict(nearClipPlane=0.01, farClipPlane=1e5, usesReversedZBuffer=False, upsampleTolerance=-12.0, noiseFilterTolerance=0.0),
-           dict(usesReversedZBuffer=False, upsampleTolerance=-12.0, noiseFilterTolerance=-8.0),
-           dict(usesReversedZBuffer=True, upsampleTolerance=-1.0, noiseFilterTolerance=0.0)]
-    for i, e in enumerate(ext[:n]):
-        out[i] = dataclasses.replace(out[i], **e)
-    return out
-
-
-def frame_settings(oracle, base, fp):
-    """oracle Settings of one frame: `base` with the fields the FrameParams sets."""
-    kw = {ORACLE_FIELD[k]: v for k, v in dataclasses.asdict(fp).items() if v is not None}
-    return dataclasses.replace(base, **kw)
-
 
 def frame_depth(s, seed):
     """An S2 frame seen by the frame's own camera (its near / far / reversed_z)."""
@@ -67,14 +27,6 @@ def frame_depth(s, seed):
     if s.depth_format == L.DEPTH_F32:
         return d
     return encode_depth(d, s.depth_format)
-
-
-def encode_depth(d, fmt):
-    if fmt == L.DEPTH_UNORM16:
-        return np.round(np.clip(d, 0, 1) * 65535).astype(np.uint16)
-    if fmt == L.DEPTH_UNORM24:
-        return np.round(np.clip(d, 0, 1).astype(np.float64) * 16777215).astype(np.uint32)
-    return d.astype(np.float16).view(np.uint16)
 
 
 def assert_frame(ao, oracle, depth, s, f, got=None, ids=None):
@@ -90,7 +42,7 @@ def assert_frame(ao, oracle, depth, s, f, got=None, ids=None):
 
 def run_host(oracle, base, params, seeds, max_batch=None, debug=None, ids=None, **kw):
     n = len(params)
-    sets = [frame_settings(oracle, base, p) for p in params]
+    sets = [frame_settings(base, p) for p in params]
     depths = [frame_depth(s, seed) for s, seed in zip(sets, seeds)]
     ao = H.component(base, max_batch=max_batch or n, debug=debug, depth_format=base.depth_format, **kw)
     try:
@@ -106,7 +58,7 @@ def test_mixed_cameras_every_buffer(oracle):
     base = H.settings(oracle, w, h)
     params = random_params(np.random.default_rng(20261015), w, h, n)
     # the instance's own parameters are neither read nor changed: give it something no frame uses
-    sets = [frame_settings(oracle, base, p) for p in params]
+    sets = [frame_settings(base, p) for p in params]
     depths = [frame_depth(s, 100 + f) for f, s in enumerate(sets)]
     ao = H.component(base, max_batch=n)
     try:
@@ -158,7 +110,7 @@ def test_launch_structures(oracle, name):
     w, h = (1920, 1080) if n <= 2 else (256, 160)
     base = H.settings(oracle, w, h)
     params = random_params(np.random.default_rng(n * 7 + mb), w, h, n)
-    sets = [frame_settings(oracle, base, p) for p in params]
+    sets = [frame_settings(base, p) for p in params]
     depths = [frame_depth(s, 900 + f % 8) for f, s in enumerate(sets)]
     ao = H.component(base, max_batch=mb, debug=debug)
     try:
@@ -201,7 +153,7 @@ def test_pipelined_stream_changing_cameras(oracle, own_launch):
     base = H.settings(oracle, w, h)
     rng = np.random.default_rng(77)
     params = [random_params(rng, w, h, B) for _ in range(steps)]
-    sets = [[frame_settings(oracle, base, p) for p in ps] for ps in params]
+    sets = [[frame_settings(base, p) for p in ps] for ps in params]
     depths = [[frame_depth(s, 300 + 10 * k + f) for f, s in enumerate(ss)] for k, ss in enumerate(sets)]
     depths[1][1] = H.hostile_frame(w, h, 5, kinds=["nan", "neg", "huge"], density=0.002)     # odd texels only
     depths[1][1][0::2, 0::2] = frame_depth(sets[1][1], 5)[0::2, 0::2]
@@ -246,7 +198,7 @@ def test_pool_deals_params_with_frames(oracle):
     w, h, n = 256, 144, 5
     base = H.settings(oracle, w, h)
     params = random_params(np.random.default_rng(9), w, h, n)
-    sets = [frame_settings(oracle, base, p) for p in params]
+    sets = [frame_settings(base, p) for p in params]
     depths = [frame_depth(s, 40 + f) for f, s in enumerate(sets)]
     pool = AmbientOcclusionPool(w, h, [0, 0], max_batch=3, near_clip=base.near_clip, far_clip=base.far_clip,
                                 projection00=base.proj00, reversed_z=base.reversed_z)
@@ -265,7 +217,7 @@ def test_pending_composite_applied_before_per_frame_call(oracle):
     base = H.settings(oracle, w, h)
     dev = torch.device("cuda", 0)
     params = random_params(np.random.default_rng(3), w, h, n)
-    sets = [frame_settings(oracle, base, p) for p in params]
+    sets = [frame_settings(base, p) for p in params]
     depths = [frame_depth(s, 60 + f) for f, s in enumerate(sets)]
     dd = [torch.from_numpy(d).to(dev) for d in depths]
     out = [torch.zeros((h, w), dtype=torch.uint8, device=dev) for _ in range(n)]
@@ -338,7 +290,7 @@ from oracle import oracle as O
 from miniengineao_amd import _lib as L
 from miniengineao_amd import synth
 from tests import helpers as H
-from tests.test_frame_params_gpu import random_params
+from tests.helpers import random_params
 
 
 def run(w, h, n, debug=None, **cfg):
@@ -364,7 +316,7 @@ from oracle import oracle as O
 from miniengineao_amd import _lib as L
 from miniengineao_amd import synth
 from tests import helpers as H
-from tests.test_frame_params_gpu import random_params
+from tests.helpers import random_params
 
 w, h, B = 384, 256, 4
 ao = H.component(H.settings(O, w, h), max_batch=B, pipelined=True)

@@ -87,14 +87,13 @@ def test_exact_and_partial_last_tile_rows(oracle, w, h, debug):
 
 @pytest.mark.parametrize("fmt", ["unorm16", "unorm24", "f16"])
 def test_depth_formats_through_tall_from_raw_tiles(oracle, fmt):
-    from tests.test_depth_formats import FORMATS
     w, h = 320, 192
     raw = synth.occluder_field(w, h, seed=35).copy()
     raw[100:140, 150:] = 0.0                                          # sky (reversed Z), across tile borders
-    depth = oracle.encode_depth(raw, FORMATS[fmt])
-    s = H.settings(oracle, w, h, depth_format=FORMATS[fmt])
+    depth = oracle.encode_depth(raw, H.DEPTH_FORMATS[fmt])
+    s = H.settings(oracle, w, h, depth_format=H.DEPTH_FORMATS[fmt])
     want = oracle.run(depth, s)
-    ao = H.component(s, debug=TALL, depth_format=FORMATS[fmt])
+    ao = H.component(s, debug=TALL, depth_format=H.DEPTH_FORMATS[fmt])
     try:
         assert np.array_equal(ao.render(depth), want["result"])
         for i in (1, 2):

@@ -36,7 +36,6 @@ EXCLUDED = {
 CHILD = r"""
 import dataclasses
 import sys
-import tempfile
 import time
 
 import numpy as np
@@ -45,15 +44,16 @@ import torch
 from oracle import oracle as O
 from miniengineao_amd import FrameParams, synth
 from miniengineao_amd import _lib as L
+from tests import gpu_kit
 from tests import helpers as H
-from tests.test_kernel_coverage_gpu import COLUMNS
-from tests.test_linear_depth_gpu import build_linearize, to_linear
+from tests.test_kernel_coverage_gpu import COLUMNS          # the child's own parent module, for this data table alone
+from tests.linear_depth import linearize, to_linear
 
 t0 = time.time()
 O.build()
 CAM = synth.Camera(near=0.1, far=128.0, reversed_z=True)      # far a power of two: linear z = dist * far exactly
 DEV = torch.device("cuda", 0)
-LIN = build_linearize(tempfile.mkdtemp())
+LIN = linearize()
 BIG = 1 << 20
 F32, U16, LF32, LF16 = L.DEPTH_F32, L.DEPTH_UNORM16, L.DEPTH_LINEAR_F32, L.DEPTH_LINEAR_F16
 NP_DEPTH = {F32: np.float32, U16: np.uint16, LF32: np.float32, LF16: np.float16}
@@ -104,19 +104,18 @@ def expected(s, fmt, oracle_frames, inputs, params, sets, debug):
         ref.close()
 
 
-def device_frames(arrs, pitch, extra=0):
-    # one byte tensor holding the frames as surfaces of `pitch` elements per row (+ `extra` bytes in front); element pointers
-    n, (h, w) = len(arrs), arrs[0].shape
-    surf = np.zeros((n, h, pitch), arrs[0].dtype)
-    surf[:, :, :w] = np.stack(arrs)
-    raw = np.concatenate([np.zeros(extra, np.uint8), surf.view(np.uint8).ravel()])
-    t = torch.from_numpy(raw).to(DEV)
-    step = h * pitch * surf.itemsize
-    return t, [t.data_ptr() + extra + f * step for f in range(n)], pitch * surf.itemsize
+def device_frames(arrs, pitch):
+    # one allocation holding the frames as surfaces of `pitch` elements per row, the padding zero: (surface, pointers, pitch in bytes)
+    (h, w) = arrs[0].shape
+    s = gpu_kit.Surface(w, h, arrs[0].dtype, n=len(arrs), pitch=pitch, fill=0, content=arrs, device=DEV)
+    return s, s.ptrs(), s.row_bytes
 
 
-def read_frames(t, n, h, pitch, dtype, w):
-    return [a[:, :w].copy() for a in t.cpu().numpy().view(dtype).reshape(n, h, pitch)]
+def read_frames(what, s):
+    raw = s.download()
+    if not s.intact(raw):
+        sys.exit("MISMATCH %s: row padding was written" % what)
+    return [s.texels(f, raw) for f in range(s.n)]
 
 
 def check(what, ao, s, outs, want):
@@ -160,7 +159,7 @@ def run(w, h, n, fmt=F32, debug=None, per_frame=False, pitch=0, steps=0, composi
             ao.execute_device(dev_in[k][1], dev_out[k][1], st, params=params, **pitches)
         torch.cuda.synchronize(DEV)
         for k, (oracle_frames, inputs, params, sets) in enumerate(calls):
-            outs = read_frames(dev_out[k][0], n, h, dp, ao_dt, w)
+            outs = read_frames(what, dev_out[k][0])
             want = expected(s, fmt, oracle_frames, inputs, params, sets, debug) if k + 1 == len(calls) else \
                 [{"result": r["result"]} for r in expected(s, fmt, oracle_frames, inputs, params, sets, debug)]
             if k + 1 == len(calls):
@@ -169,7 +168,7 @@ def run(w, h, n, fmt=F32, debug=None, per_frame=False, pitch=0, steps=0, composi
                 for f, o in enumerate(outs):
                     compare("%s call %d frame %d result" % (what, k, f), o, want[f]["result"])
         if composite:
-            first = read_frames(dev_out[0][0], n, h, dp, ao_dt, w)
+            first = read_frames(what, dev_out[0][0])
             for f in range(n):
                 want_col = colors[f].copy()
                 O.composite(np.ascontiguousarray(first[f]), want_col, 0, ao_format=s.ao_format)
@@ -225,7 +224,6 @@ INDEPENDENT_CHILD = r"""
 import sys
 import time
 
-import tempfile
 
 import numpy as np
 
@@ -233,11 +231,11 @@ from oracle import oracle as O
 from miniengineao_amd import synth
 from miniengineao_amd import _lib as L
 from tests import helpers as H
-from tests.test_linear_depth_gpu import build_linearize, to_linear
+from tests.linear_depth import linearize, to_linear
 
 t0 = time.time()
 O.build()
-LIN = build_linearize(tempfile.mkdtemp())
+LIN = linearize()
 w, h = 96, 64
 for ao_format in (L.AO_R8, L.AO_F16):
     for rounding in (L.F16_RTZ_CLAMP, L.F16_RTNE):

@@ -9,6 +9,8 @@ import sys
 
 import pytest
 
+from tests.kernel_inventory import HOT
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -29,18 +31,6 @@ def test_no_kernel_spills_or_uses_scratch(rows):
     bad = [n for n, r in rows.items()
            if int(r["ScratchSize [bytes/lane]"]) or int(r["VGPRs Spill"]) or r["Dynamic Stack"] != "False"]
     assert not bad, bad
-
-
-# kernel (R8, RTZ, exact division = what bench.py times): (waves per SIMD, max VGPRs, max LDS bytes per workgroup)
-HOT = {
-    "render_kernel<0, false, 0, false>": (8, 64, 40960),                                   # 4 workgroups of 8 waves per CU
-    "render_with_composite_kernel<0, false, 0>": (8, 64, 40960),
-    "upsample_final_kernel<0, false, 0, true>": (7, 72, 163840 // 7),                       # seven 256-thread workgroups per CU
-    "upsample_final_with_next_downsample_kernel<0, false, 0>": (7, 72, 163840 // 7),
-    "upsample_kernel<0, false, 0>": (8, 64, 163840 // 8),
-    "upsample_two_level_kernel<0, false, 0>": (8, 64, 163840 // 8),                       # compiled for 8 waves per SIMD: 4080 workgroups = 1.99 rounds of the slots
-    "downsample_kernel<true, 0, 2>": (8, 64, 0),
-}
 
 
 @pytest.mark.parametrize("name", sorted(HOT))

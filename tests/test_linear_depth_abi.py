@@ -13,7 +13,7 @@ import pytest
 
 from miniengineao_amd import _lib as L
 from miniengineao_amd.ambient_occlusion import DEPTH_NUMPY, DEPTH_TORCH
-from tests.test_kernel_resources import HOT
+from tests.kernel_inventory import HOT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "meao.h")).read()

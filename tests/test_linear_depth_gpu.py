@@ -5,10 +5,8 @@ raw frame's results bit for bit.  The reference: a raw frame d and its camera (f
 the oracle evaluates it (1 / fmaf(zp.x, d, zp.y), sky select; fmaf exact, in C); z = dist * far (exact).  A non-sky raw texel whose
 dist is >= 1 is made a sky texel in d first; sky texels become far or +inf, alternating.  Then library(LINEAR, z) == oracle(d).
 """
-import ctypes as C
 import dataclasses
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,62 +15,20 @@ import torch
 from miniengineao_amd import FrameParams, synth
 from miniengineao_amd import _lib as L
 from tests import helpers as H
+from tests import kernel_inventory as K
+from tests.helpers import PASS_DOWNSAMPLE, compare
+from tests.linear_depth import linearize, to_linear
 
 pytestmark = pytest.mark.gpu
 
 CAM_REV = synth.Camera(near=0.1, far=128.0, reversed_z=True)
 CAM_CONV = synth.Camera(near=0.1, far=128.0, reversed_z=False)
-PASS_DOWNSAMPLE = 0
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def build_linearize(directory):
-    """Linearize exactly as the oracle evaluates it (fmaf of the C library: exact whatever the compiler flags)."""
-    src, lib = os.path.join(directory, "lin.c"), os.path.join(directory, "liblin.so")
-    with open(src, "w") as f:
-        f.write(r"""
-#include <math.h>
-#include <stddef.h>
-void linearize(const float *d, float *out, size_t n, float zp0, float zp1, float sky)
-{
-    for (size_t i = 0; i < n; i++) out[i] = d[i] == sky ? 1e5f : 1.0f / fmaf(zp0, d[i], zp1);
-}
-""")
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", lib, "-lm"], check=True)
-    so = C.CDLL(lib)
-    so.linearize.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_float]
-    return so
-
-
 @pytest.fixture(scope="session")
-def linearize_c(tmp_path_factory):
-    return build_linearize(str(tmp_path_factory.mktemp("lin")))
-
-
-def to_linear(lin_c, d, cam, far=None):
-    """(d with far-plane-or-beyond texels made sky, z) for raw f32 frame d of camera cam; z in the units of `far`."""
-    far = np.float32(cam.far if far is None else far)
-    fpn = np.float32(cam.far) / np.float32(cam.near)
-    zp0, zp1 = ((fpn - np.float32(1), np.float32(1)) if cam.reversed_z else (np.float32(1) - fpn, fpn))
-    sky = np.float32(0.0 if cam.reversed_z else 1.0)
-    d = np.ascontiguousarray(d, np.float32).copy()
-    dist = np.empty_like(d)
-    lin_c.linearize(d.ctypes.data, dist.ctypes.data, d.size, float(zp0), float(zp1), float(sky))
-    with np.errstate(invalid="ignore"):
-        beyond = (dist >= 1) & (d != sky)
-    d[beyond] = sky
-    is_sky = d == sky
-    with np.errstate(over="ignore", invalid="ignore"):
-        z = dist * far
-    alt = (np.arange(d.size).reshape(d.shape) & 1) == 1
-    z[is_sky & alt] = np.inf
-    z[is_sky & ~alt] = far
-    return d, z.astype(np.float32)
-
-
-def compare(got, want, what):
-    ok, _ = H.nan_aware_equal(got, want)
-    assert ok, H.diff_report(what, got, want)
+def linearize_c():
+    return linearize()
 
 
 def check_ids(ao, want, ids, frame=0, checksums=False):
@@ -342,29 +298,8 @@ ao.close()
 
 
 def kernel_trace(tmp_path, fmt):
-    import csv
-    import glob
-    import shutil
-    import sys
-    prof = shutil.which("rocprofv3") or ("/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else None)
-    if prof is None:
-        pytest.skip("rocprofv3 is not installed")
-    d = tmp_path / str(fmt)
-    d.mkdir()
-    src = d / "child.py"
-    src.write_text(TRACE.replace("FMT", str(fmt)))
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run([prof, "--kernel-trace", "--output-format", "csv", "-d", str(d / "kt"), "-o", "kt", "--",
-                        sys.executable, str(src)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    rows = []
-    for f in glob.glob(str(d / "kt" / "**" / "*kernel_trace.csv"), recursive=True):
-        with open(f) as fh:
-            rows += [(int(row.get("Start_Timestamp") or 0), row["Kernel_Name"]) for row in csv.DictReader(fh)]
-    import re
-    names = [nm for _, nm in sorted(rows) if "meao::" in nm or "4meao" in nm]
-    # the template's name, demangled ("::name<") or mangled ("<length>nameI")
-    return [re.search(r"(?:::|\d)([a-z_]+_kernel)", nm).group(1) for nm in names]
+    """The child's meao kernels in start order, by template name."""
+    return [K.split(n)[0] for n in H.kernel_trace(tmp_path / str(fmt), TRACE.replace("FMT", str(fmt))).short]
 
 
 def test_kernel_trace_4k_pipelined_same_structure_as_raw_f32(tmp_path):

@@ -12,214 +12,14 @@ import dataclasses
 import numpy as np
 import pytest
 
-from miniengineao_amd import FrameParams, synth
 from miniengineao_amd import _lib as L
 from tests import helpers as H
+from tests.helpers import colour, want_of
+from tests.mixed_size import (
+    COLUMNS, CTX, EDGES, F32, FAMILIES, FUSED, MAX_BATCH, MixedCall, ORDER, ORDERINGS, SENTINEL, VARIANTS, base_settings,
+    context, frame, frame_settings, run_variant)
 
 pytestmark = pytest.mark.gpu
-
-CTX = (400, 272)
-MAX_BATCH = 8
-ORDER = [(33, 17), (400, 272), (200, 120), (97, 61)]
-ORDERINGS = {"small_first": ORDER, "reversed": ORDER[::-1], "largest_last": [(33, 17), (200, 120), (97, 61), (400, 272)]}
-EDGES = [(64, 64), (65, 33), (128, 32), (129, 65), (256, 64), (257, 31)]
-ALIGNED = [(64, 64), (128, 32), (256, 64), (400, 272)]        # every width % 8 == 0
-SENTINEL = 0xA5
-GUARD = 256                                                    # bytes in front of and behind every output surface
-BIG = 1 << 20
-PASS_DOWNSAMPLE = 0
-F32, U16, LF32 = L.DEPTH_F32, L.DEPTH_UNORM16, L.DEPTH_LINEAR_F32
-CAM = synth.Camera(near=0.1, far=128.0, reversed_z=True)       # far a power of two: linear z = distance x far exactly
-
-# (AOFMT, RTNE, DIV) columns: the settings that select each (tests/test_kernel_coverage_gpu.py)
-COLUMNS = {
-    "r8_rtz_exact": dict(),
-    "r8_rtz_ieee": dict(upsample_tolerance=-14.0),
-    "r8_rtne": dict(f16_rounding=1),
-    "f16_rtz_exact": dict(ao_format=1),
-    "f16_rtz_ieee": dict(ao_format=1, upsample_tolerance=-14.0),
-    "f16_rtne": dict(ao_format=1, f16_rounding=1),
-}
-
-# Launch structures and configurations under mixed sizes, in the R8 / RTZ / exact column: name -> (meao_debug_set overrides,
-# oracle Settings fields, depth format, pitched, hostile frame, the per-frame kernel templates the call must launch)
-VARIANTS = {
-    "defaults": ({}, {}, F32, False, None,
-                 ["downsample_frames_kernel", "render_small_frames_kernel", "upsample_three_level_frames_kernel",
-                  "upsample_final_small_frames_kernel"]),
-    "nested_0": ({L.DEBUG_NESTED_MAX_TILES: 0}, {}, F32, False, None, ["upsample_two_level_frames_kernel", "upsample_frames_kernel"]),
-    "nested_large": ({L.DEBUG_NESTED_MAX_TILES: BIG}, {}, F32, False, None, ["upsample_three_level_frames_kernel"]),
-    "separate_blends": ({L.DEBUG_FUSE_COARSE_BLEND: 0}, {}, F32, False, None, ["upsample_frames_kernel"]),
-    "no_small_tiles": ({L.DEBUG_RENDER_SMALL_MAX_TILES: 0, L.DEBUG_FINAL_SMALL_MAX_TILES: 0, L.DEBUG_DS_SMALL_MAX_TILES: 0}, {}, F32,
-                       False, None, ["downsample_frames_kernel", "render_frames_kernel", "upsample_final_frames_kernel"]),
-    "small_tiles": ({L.DEBUG_RENDER_SMALL_MAX_TILES: BIG, L.DEBUG_FINAL_SMALL_MAX_TILES: BIG, L.DEBUG_DS_SMALL_MAX_TILES: BIG}, {}, F32,
-                    False, None, ["downsample_frames_kernel", "render_small_frames_kernel", "upsample_final_small_frames_kernel"]),
-    "blend_tall": ({L.DEBUG_NESTED_MAX_TILES: 0, L.DEBUG_BLEND_TALL_MIN_TILES: 1}, {}, F32, False, None,
-                   ["upsample_two_level_frames_kernel", "upsample_blend_tall_frames_kernel"]),
-    "hq_levels_2": ({}, dict(hq_levels=2), F32, False, None, ["render_wide_frames_kernel"]),
-    "exhaustive": ({}, dict(sample_set=L.SAMPLES_EXHAUSTIVE), F32, False, None, ["render_frames_kernel"]),
-    "pitched_small": ({L.DEBUG_FINAL_SMALL_MAX_TILES: BIG, L.DEBUG_DS_SMALL_MAX_TILES: BIG}, {}, F32, True, None,
-                      ["downsample_pitched_frames_kernel", "upsample_final_small_pitched_frames_kernel"]),
-    "pitched_large": ({L.DEBUG_FINAL_SMALL_MAX_TILES: 0, L.DEBUG_DS_SMALL_MAX_TILES: 0}, {}, F32, True, None,
-                      ["downsample_pitched_frames_kernel", "upsample_final_pitched_frames_kernel"]),
-    "linear_small": ({L.DEBUG_FINAL_SMALL_MAX_TILES: BIG}, {}, LF32, False, None,
-                     ["downsample_linear_frames_kernel", "upsample_final_small_linear_frames_kernel"]),
-    "linear_large": ({L.DEBUG_FINAL_SMALL_MAX_TILES: 0}, {}, LF32, True, None,
-                     ["downsample_linear_frames_kernel", "upsample_final_linear_frames_kernel"]),
-    "unorm16": ({}, dict(depth_format=U16), U16, False, None, ["downsample_frames_kernel", "upsample_final_small_frames_kernel"]),
-    "hostile_neighbour": ({}, {}, F32, False, 2, ["render_small_frames_kernel"]),
-}
-FAMILIES = sorted({k for v in VARIANTS.values() for k in v[5]})
-FUSED = "upsample_final_with_next_downsample_frames_kernel"
-
-_frames, _wants, _lin = {}, {}, []
-
-
-def base_settings(oracle, **kw):
-    """The oracle Settings of the 400 x 272 context (proj00 of that aspect)."""
-    return H.settings(oracle, *CTX, cam=CAM, **kw)
-
-
-def frame_settings(base, w, h, f=None, own_camera=False):
-    """Frame f's Settings at its own size: the context's parameters, or (f given) parameters of its own."""
-    s = dataclasses.replace(base, width=w, height=h)
-    if f is not None:
-        s = dataclasses.replace(s, intensity=1.0 + 0.25 * f, thickness_modifier=1.0 + 0.5 * f, proj00=CAM.proj00(w, h))
-    return s
-
-
-def params_of(s):
-    return FrameParams(intensity=s.intensity, thicknessModifier=s.thickness_modifier, projection00=s.proj00)
-
-
-def linearize():
-    if not _lin:
-        import tempfile
-        from tests.test_linear_depth_gpu import build_linearize
-        _lin.append(build_linearize(tempfile.mkdtemp()))
-    return _lin[0]
-
-
-def frame(oracle, w, h, fmt=F32, hostile=False, seed=0):
-    """-> (the oracle's input frame, the library's input frame); one frame per size, format and seed."""
-    key = (w, h, fmt, hostile, seed)
-    if key not in _frames:
-        raw = H.hostile_frame(w, h, 7 + seed, cam=CAM) if hostile else synth.occluder_field(w, h, seed=w * 1000 + h + seed, cam=CAM)
-        if fmt == U16:
-            enc = oracle.encode_depth(raw, U16)
-            _frames[key] = (enc, enc)
-        elif fmt == LF32:
-            from tests.test_linear_depth_gpu import to_linear
-            _frames[key] = to_linear(linearize(), raw, CAM)
-        else:
-            _frames[key] = (raw, raw)
-    return _frames[key]
-
-
-def want_of(oracle, key, depth, s):
-    k = (key, dataclasses.astuple(s))
-    if k not in _wants:
-        _wants[k] = oracle.run(depth, s, nthreads=8)
-    return _wants[k]
-
-
-def ao_dtype(s):
-    return np.uint8 if s.ao_format == L.AO_R8 else np.uint16
-
-
-class Surface:
-    """One frame's device surface of `pitch` texels per row inside an allocation with GUARD bytes of SENTINEL on both sides; the
-    row padding holds SENTINEL bytes too.  intact(): every byte outside the w x h texels is still what was uploaded."""
-
-    def __init__(self, torch, w, h, dtype, pitch, content=None):
-        self.w, self.h, self.dtype, self.pitch = w, h, np.dtype(dtype), pitch
-        body = np.full(h * pitch * self.dtype.itemsize, SENTINEL, np.uint8).view(self.dtype).reshape(h, pitch)
-        if content is not None:
-            body[:, :w] = content
-        guard = np.full(GUARD, SENTINEL, np.uint8)
-        self.host = np.concatenate([guard, body.view(np.uint8).ravel(), guard])
-        self.dev = torch.from_numpy(self.host.copy()).cuda()
-
-    @property
-    def ptr(self):
-        return self.dev.data_ptr() + GUARD
-
-    @property
-    def pitch_bytes(self):
-        return 0 if self.pitch == self.w else self.pitch * self.dtype.itemsize
-
-    def read(self):
-        got = self.dev.cpu().numpy()
-        body = got[GUARD:len(got) - GUARD].view(self.dtype).reshape(self.h, self.pitch)
-        texels = body[:, :self.w].copy()
-        rest = got.copy()
-        rest[GUARD:len(got) - GUARD].view(self.dtype).reshape(self.h, self.pitch)[:, :self.w] = \
-            self.host[GUARD:len(got) - GUARD].view(self.dtype).reshape(self.h, self.pitch)[:, :self.w]
-        return texels, np.array_equal(rest, self.host)
-
-
-class MixedCall:
-    """The surfaces, extents and expectations of one mixed call on a context configured like `base`."""
-
-    def __init__(self, torch, oracle, base, sizes, fmt=F32, per_frame=False, pitched=False, hostile=None, seed=0):
-        self.oracle, self.base, self.sizes = oracle, base, list(sizes)
-        self.settings, self.depth, self.out, self.keys, self.oracle_in = [], [], [], [], []
-        for f, (w, h) in enumerate(self.sizes):
-            s = frame_settings(base, w, h, f if per_frame else None)
-            fseed = seed + 1000 * self.sizes[:f].count((w, h))           # frames of one size in one call differ
-            want_in, lib_in = frame(oracle, w, h, fmt, hostile == f, fseed)
-            # pitched: odd and even paddings, so that some frames lose the 4-texel forms and the call with them
-            dpitch, opitch = (w + 3 + 4 * f, w + 8 + f) if pitched else (w, w)
-            self.settings.append(s)
-            self.oracle_in.append(want_in)
-            self.keys.append((w, h, fmt, hostile == f, fseed))
-            self.depth.append(Surface(torch, w, h, lib_in.dtype, dpitch, lib_in))
-            self.out.append(Surface(torch, w, h, ao_dtype(s), opitch))
-        self.params = [params_of(s) for s in self.settings] if per_frame else None
-        self.extents = [(w, h, d.pitch_bytes, o.pitch_bytes) for (w, h), d, o in zip(self.sizes, self.depth, self.out)]
-
-    def execute(self, ao):
-        ao.execute_device([d.ptr for d in self.depth], [o.ptr for o in self.out], params=self.params, extents=self.extents)
-
-    def want(self, f):
-        return want_of(self.oracle, self.keys[f], self.oracle_in[f], self.settings[f])
-
-    def check(self, ao, debug_buffers=True, what=""):
-        ao.synchronize()
-        for f, (w, h) in enumerate(self.sizes):
-            want = self.want(f)
-            got, intact = self.out[f].read()
-            ok, _ = H.nan_aware_equal(got, want["result"])
-            assert ok, (what, f, (w, h), H.diff_report("result", got, want["result"]))
-            assert intact, (what, f, (w, h), "bytes outside the frame's texels were written")
-        if debug_buffers:
-            s0 = self.settings[0]
-            for f, (w, h) in enumerate(self.sizes):
-                want = self.want(f)
-                for i in H.valid_debug_ids(s0.num_levels, s0.hq_levels):
-                    got = ao.debug_buffer(i, frame=f)
-                    assert got.shape == want[H.NAMES[i]].shape, (what, f, (w, h), H.NAMES[i], got.shape, want[H.NAMES[i]].shape)
-                    ok, _ = H.nan_aware_equal(got, want[H.NAMES[i]])
-                    assert ok, (what, f, (w, h), H.diff_report(H.NAMES[i], got, want[H.NAMES[i]]))
-
-
-def context(base, fmt=F32, debug=None, **kw):
-    return H.component(base, max_batch=MAX_BATCH, depth_format=fmt, debug=debug, **kw)
-
-
-def run_variant(torch, oracle, name, sizes=ORDER, column="r8_rtz_exact", debug_buffers=True):
-    debug, skw, fmt, pitched, hostile, _ = VARIANTS[name]
-    base = base_settings(oracle, **{**COLUMNS[column], **skw})
-    ao = context(base, fmt, debug)
-    try:
-        call = MixedCall(torch, oracle, base, sizes, fmt=fmt, per_frame=(name != "hostile_neighbour"), pitched=pitched, hostile=hostile)
-        call.execute(ao)
-        call.check(ao, debug_buffers, what=name)
-        if hostile is not None:
-            assert ao.hostile_frames() >> hostile & 1          # that frame ran the IEEE-division bodies, next to clean ones
-    finally:
-        ao.close()
-
 
 # ---- orderings, tile edges, capacity
 
@@ -293,7 +93,7 @@ TRACE_CHILD = r"""
 import sys
 import torch
 from oracle import oracle as O
-from tests import test_mixed_size_gpu as M
+from tests import mixed_size as M
 O.build()
 for name in sorted(M.VARIANTS):
     M.run_variant(torch, O, name, debug_buffers=False)
@@ -330,7 +130,7 @@ import sys
 import torch
 from oracle import oracle as O
 from miniengineao_amd import _lib as L
-from tests import test_mixed_size_gpu as M
+from tests import mixed_size as M
 O.build()
 base = M.base_settings(O)
 for limit in (int(sys.argv[1]), int(sys.argv[1]) - 1):
@@ -355,7 +155,7 @@ def test_thresholds_compare_the_sum_over_the_frames(tmp_path):
 VECTOR_CHILD = r"""
 import torch
 from oracle import oracle as O
-from tests import test_mixed_size_gpu as M
+from tests import mixed_size as M
 O.build()
 base = M.base_settings(O)
 ao = M.context(base)
@@ -386,20 +186,6 @@ def execute_uniform(ao, b):
     ao.execute_device([d.ptr for d in b.depth], [o.ptr for o in b.out])
 
 
-def downsample_ms(ao, b):
-    """The DOWNSAMPLE slot of executing the uniform batch `b` alone: 0 = that call launched no downsample pass."""
-    ao.set_profiling(True)
-    execute_uniform(ao, b)
-    ms, n = ao.pass_times_ms()
-    assert n == 1
-    return ms[PASS_DOWNSAMPLE]
-
-
-def colour(w, h, seed):
-    rng = np.random.default_rng(seed)
-    return (rng.integers(0, 0x7C00, (h, w, 4)) | (rng.integers(0, 2, (h, w, 4)) << 15)).astype(np.uint16)
-
-
 def test_uniform_call_after_a_mixed_call(oracle):
     import torch
     base = base_settings(oracle)
@@ -426,7 +212,7 @@ def test_announcement_is_carried_as_its_own_launch(oracle):
         ao.prefetch_device([d.ptr for d in nxt.depth])
         call = MixedCall(torch, oracle, base, ORDER)
         call.execute(ao)
-        assert downsample_ms(ao, nxt) == 0             # the mixed call carried the announced pass and promoted it
+        assert H.downsample_ms(ao, lambda: execute_uniform(ao, nxt)) == 0      # the mixed call carried the announced pass and promoted it
         nxt.check(ao, debug_buffers=False, what="announced batch")
         call.check(ao, debug_buffers=False, what="carrying mixed call")
         # a ready set is consumed unmatched by a mixed call: the batch it was made for runs its own pass afterwards
@@ -434,7 +220,7 @@ def test_announcement_is_carried_as_its_own_launch(oracle):
         ao.prefetch_device([d.ptr for d in again.depth])
         execute_uniform(ao, nxt)
         call.execute(ao)
-        assert downsample_ms(ao, again) > 0
+        assert H.downsample_ms(ao, lambda: execute_uniform(ao, again)) > 0
         again.check(ao, debug_buffers=False, what="after the consumed set")
     finally:
         ao.close()
@@ -498,7 +284,7 @@ def test_refused_call_leaves_the_state_untouched(oracle):
         ao.prefetch_device([d.ptr for d in ready.depth])
         execute_uniform(ao, first)
         refuse_all()
-        assert downsample_ms(ao, ready) == 0                         # it was still there: no downsample launch
+        assert H.downsample_ms(ao, lambda: execute_uniform(ao, ready)) == 0      # it was still there: no downsample launch
         # an announcement and a waiting composite
         ao.prefetch_device([d.ptr for d in announced.depth])
         before = [colour(*CTX, 80 + f) for f in range(2)]
@@ -508,7 +294,7 @@ def test_refused_call_leaves_the_state_untouched(oracle):
         assert ao.composite_pending                                  # the composite still waits
         execute_uniform(ao, filler)                                  # carries the announced pass; the composite rides in its render kernel
         assert not ao.composite_pending
-        assert downsample_ms(ao, announced) == 0                     # the announcement was still there
+        assert H.downsample_ms(ao, lambda: execute_uniform(ao, announced)) == 0      # the announcement was still there
         ao.synchronize()
         for o in call.out:
             assert o.read()[1] and np.all(o.read()[0].view(np.uint8) == SENTINEL)      # no refused call launched anything
@@ -583,7 +369,7 @@ def test_tensors_of_different_shapes(oracle):
         torch.cuda.synchronize()
         for f, (w, h) in enumerate(ORDER):
             s = frame_settings(base, w, h)
-            want = want_of(oracle, (w, h, F32, False, 0), frame(oracle, w, h)[0], s)["result"]
+            want = want_of(oracle, (w, h, F32, False, 0), frame(oracle, w, h)[0], s, nthreads=8)["result"]
             assert tuple(outs[f].shape) == (h, w) and np.array_equal(outs[f].cpu().numpy(), want), f
     finally:
         ao.close()

@@ -24,15 +24,15 @@ from miniengineao_amd import synth
 from miniengineao_amd import _lib as L
 from tests import call_model as M
 from tests import helpers as H
-from tests import test_call_sequences_gpu as S
+from tests import test_call_sequences_gpu as S          # the call-sequence driver stays in its suite
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def lin_c(tmp_path_factory):
-    from tests.test_linear_depth_gpu import build_linearize
-    return build_linearize(str(tmp_path_factory.mktemp("lin")))
+def lin_c():
+    from tests.linear_depth import linearize
+    return linearize()
 
 
 def run_stepped(oracle, lin_c, kind, name, own_launch):
@@ -319,8 +319,8 @@ import torch
 from oracle import oracle as O
 from miniengineao_amd import synth
 from tests import helpers as H
-from tests import test_call_sequences_gpu as S
-from tests import test_mixed_size_sequences_gpu as T
+from tests import test_call_sequences_gpu as S          # the call-sequence driver stays in its suite
+from tests import test_mixed_size_sequences_gpu as T          # the child's own parent module: sizes and the flat-buffer helpers
 
 how = sys.argv[1]
 O.build()

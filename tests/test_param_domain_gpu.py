@@ -5,7 +5,6 @@ range those were verified for (meao_api.cpp exact_rcp_div_applicable); any other
 runs the IEEE-division bodies (DIV = 1), with a clamped, finite sky.  Each frame must equal the CPU oracle under its own
 parameters in every buffer (NaN-aware), on both sides of each edge, far outside, in per-frame calls that mix the two, and
 across the prefetch reuse key that depends on the column (ready_exact)."""
-import dataclasses
 import os
 
 import numpy as np
@@ -15,38 +14,18 @@ from miniengineao_amd import FrameParams, synth
 from miniengineao_amd import _lib as L
 from tests import helpers as H
 from tests import kernel_inventory as K
+from tests.helpers import PASS_DOWNSAMPLE, flat_sky_frame, frame_settings, hostile_level_texels
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PASS_DOWNSAMPLE = 0
 W, HT = 516, 260
 COLUMNS = {"r8_rtz": dict(), "r8_rtne": dict(f16_rounding=L.F16_RTNE), "f16_rtz": dict(ao_format=L.AO_F16),
            "f16_rtne": dict(ao_format=L.AO_F16, f16_rounding=L.F16_RTNE)}
 
 
-def flat_sky_frame(w, h, seed, cam=synth.DEFAULT_CAMERA):
-    """S2 with flat regions made of whole 2 x 2-aligned blocks (every level's hi == lo there: |delta| = 0) and sky texels."""
-    d = synth.make("S2", w, h, seed=seed).copy()
-    d[32:96, 64:192] = d[32, 64]
-    d[130:162, 300:364] = d[130, 300]
-    d[64:66, 400:402] = d[64, 400]
-    sky = np.float32(0.0 if cam.reversed_z else 1.0)
-    d[180:232, 100:164] = sky
-    d[7:9, 9:13] = sky
-    return d
-
-
 def hostile_fixture():
     return np.load(os.path.join(ROOT, "tests", "golden", "ref_s2h_516x260_hostile_r8.npz"))["depth"]
-
-
-def hostile_level_texels(w, h, seed):
-    """S2 with hostile raw texels only where (y, x) are both even: the texels the levels are made of."""
-    clean = synth.make("S2", w, h, seed=seed)
-    d = H.hostile_frame(w, h, seed, density=0.02)
-    yy, xx = np.mgrid[0:h, 0:w]
-    return np.where(((yy & 1) == 0) & ((xx & 1) == 0), d, clean).astype(np.float32)
 
 
 def check_frames(oracle, ao, depths, sets, ids=True):
@@ -68,7 +47,8 @@ from oracle import oracle as O
 from miniengineao_amd import _lib as L
 from miniengineao_amd import synth
 from tests import helpers as H
-from tests.test_param_domain_gpu import W, HT, flat_sky_frame
+from tests.helpers import flat_sky_frame
+from tests.test_param_domain_gpu import W, HT          # the child's own parent module, for these two constants alone
 
 side = sys.argv[1]
 lib = L.load()
@@ -123,14 +103,13 @@ def test_far_outside_every_column_every_buffer(oracle, field, value):
 MIXED_CHILD = r"""
 import dataclasses
 import sys
-import tempfile
 import numpy as np
 import torch
 from oracle import oracle as O
 from miniengineao_amd import FrameParams, synth
 from miniengineao_amd import _lib as L
 from tests import helpers as H
-from tests.test_linear_depth_gpu import build_linearize, to_linear
+from tests.linear_depth import linearize, to_linear
 
 O.build()
 CAM = synth.Camera(near=0.1, far=128.0, reversed_z=True)
@@ -172,7 +151,7 @@ for ao_format in (L.AO_R8, L.AO_F16):
     o = out[:, 1:1 + h, 4:4 + w].cpu().numpy()
     check(ao, [o[f].view(np.uint8 if ao_format == L.AO_R8 else np.uint16) for f in range(4)], raws, "pitched")
     ao.close()
-    lin_c = build_linearize(tempfile.mkdtemp())               # linear view-space depth
+    lin_c = linearize()               # linear view-space depth
     pairs = [to_linear(lin_c, r, CAM) for r in raws]
     ao = H.component(s, max_batch=4, depth_format=L.DEPTH_LINEAR_F32)
     check(ao, ao.render_batch([z for _, z in pairs], params=params), [d for d, _ in pairs], "linear")
@@ -229,11 +208,6 @@ def pipelined_calls(oracle, steps, w=384, h=256, n=2):
     finally:
         ao.close()
     return ds_ms, hostile
-
-
-def frame_settings(base, fp):
-    from tests.test_frame_params_gpu import ORACLE_FIELD
-    return dataclasses.replace(base, **{ORACLE_FIELD[k]: v for k, v in dataclasses.asdict(fp).items() if v is not None})
 
 
 IEEE = [FrameParams(upsampleTolerance=-14.0), FrameParams(upsampleTolerance=-14.0, intensity=2.0)]

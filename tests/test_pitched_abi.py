@@ -14,7 +14,7 @@ import torch
 
 from miniengineao_amd import _lib as L
 from miniengineao_amd.surfaces import frame_pointers, packed_pitch
-from tests.test_kernel_resources import HOT
+from tests.kernel_inventory import HOT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "meao.h")).read()

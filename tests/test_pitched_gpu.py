@@ -5,7 +5,6 @@ surface is pre-filled with 0xA5.  The viewport's AO must be bit-equal to the ora
 of the AO surface outside the viewport may change -- in every launch structure a packed call can reach.
 """
 import ctypes as C
-import dataclasses
 
 import numpy as np
 import pytest
@@ -15,24 +14,15 @@ from miniengineao_amd import FrameParams
 from miniengineao_amd import _lib as L
 from miniengineao_amd import synth
 from miniengineao_amd.frame_params import params_array
+from tests import gpu_kit
 from tests import helpers as H
+from tests.helpers import PASS_DOWNSAMPLE, encode_depth, frame_settings
 
 pytestmark = pytest.mark.gpu
 
-DEPTH_ELEM = {L.DEPTH_F32: 4, L.DEPTH_UNORM16: 2, L.DEPTH_UNORM24: 4, L.DEPTH_F16: 2}
 DEPTH_NP = {L.DEPTH_F32: np.float32, L.DEPTH_UNORM16: np.uint16, L.DEPTH_UNORM24: np.uint32, L.DEPTH_F16: np.uint16}
-PAD_WORD = {L.DEPTH_F32: 0x7fc00000, L.DEPTH_UNORM16: 0xffff, L.DEPTH_UNORM24: 0xffffffff, L.DEPTH_F16: 0x7e00}
-PASS_DOWNSAMPLE = 0
-
-
-def encode_depth(d, fmt):
-    if fmt == L.DEPTH_F32:
-        return d.astype(np.float32)
-    if fmt == L.DEPTH_UNORM16:
-        return np.round(np.clip(d, 0, 1) * 65535).astype(np.uint16)
-    if fmt == L.DEPTH_UNORM24:
-        return np.round(np.clip(d, 0, 1).astype(np.float64) * 16777215).astype(np.uint32)
-    return d.astype(np.float16).view(np.uint16)
+PAD_WORD = gpu_kit.DEPTH_PAD_WORD
+GUARD = 256                                             # sentinel bytes in front of and behind both allocations
 
 
 def pitch_texels(kind, w, x0, elem):
@@ -48,45 +38,22 @@ def pitch_texels(kind, w, x0, elem):
     return 2 * w + x0                                   # "2w"
 
 
+def surface(w, h, n, dtype, kind, x0, **kw):
+    """n frames of (h + 2) x pitch texels each, viewport at (x0, 1), adjacent in one allocation; "packed": tight, no rows around."""
+    x0, y0 = (0, 0) if kind == "packed" else (x0, 1)
+    return gpu_kit.Surface(w, h, dtype, n=n, pitch=pitch_texels(kind, w, x0, np.dtype(dtype).itemsize), x0=x0, y0=y0, rows=h + 2 * y0,
+                           guard=GUARD, **kw)
+
+
 class Surfaces:
-    """n frames of (h + 2) x pitch texels each, viewport at (x0, 1); depth and AO surfaces in one torch allocation each."""
+    """The depth surfaces (padding: PAD_WORD of the format) and the AO surfaces (0xA5) of n frames."""
 
-    def __init__(self, w, h, n, fmt, ao_format, depth_kind, out_kind, x0, seed, device="cuda"):
-        self.w, self.h, self.n, self.x0, self.y0 = w, h, n, x0, 1
-        de, ae = DEPTH_ELEM[fmt], (1 if ao_format == L.AO_R8 else 2)
-        self.de, self.ae = de, ae
-        self.dp = pitch_texels(depth_kind, w, x0 if depth_kind != "packed" else 0, de)
-        self.op = pitch_texels(out_kind, w, x0 if out_kind != "packed" else 0, ae)
-        self.dx0 = 0 if depth_kind == "packed" else x0
-        self.ox0 = 0 if out_kind == "packed" else x0
-        self.dy0 = 0 if depth_kind == "packed" else 1
-        self.oy0 = 0 if out_kind == "packed" else 1
-        rows_d, rows_o = h + 2 * self.dy0, h + 2 * self.oy0
+    def __init__(self, w, h, n, fmt, ao_format, depth_kind, out_kind, x0, seed):
+        self.n = n
         self.views = [encode_depth(synth.occluder_field(w, h, seed + f), fmt) for f in range(n)]
-        host = np.full((n, rows_d, self.dp), PAD_WORD[fmt], dtype=np.uint32 if de == 4 else np.uint16).view(DEPTH_NP[fmt])
-        for f in range(n):
-            host[f, self.dy0:self.dy0 + h, self.dx0:self.dx0 + w] = self.views[f]
-        self.depth_host = host
-        self.depth = torch.from_numpy(host.view(np.uint8).copy()).to(device)
-        self.out = torch.full((n, rows_o, self.op * ae), 0xA5, dtype=torch.uint8, device=device)
-        self.out_rows = rows_o
-
-    def depth_ptrs(self):
-        b, fs = self.depth.data_ptr(), self.depth[0].numel()
-        return [b + f * fs + self.dy0 * self.dp * self.de + self.dx0 * self.de for f in range(self.n)]
-
-    def out_ptrs(self):
-        b, fs = self.out.data_ptr(), self.out[0].numel()
-        return [b + f * fs + self.oy0 * self.op * self.ae + self.ox0 * self.ae for f in range(self.n)]
-
-    def result(self, f):
-        """(viewport AO in the oracle's dtype, whether every byte outside it is still 0xA5)"""
-        o = self.out[f].cpu().numpy()
-        x0b, wb = self.ox0 * self.ae, self.w * self.ae
-        view = np.ascontiguousarray(o[self.oy0:self.oy0 + self.h, x0b:x0b + wb])
-        mask = np.ones(o.shape, bool)
-        mask[self.oy0:self.oy0 + self.h, x0b:x0b + wb] = False
-        return (view if self.ae == 1 else view.view(np.uint16)), bool((o[mask] == 0xA5).all())
+        self.depth = surface(w, h, n, DEPTH_NP[fmt], depth_kind, x0, pad_word=PAD_WORD[fmt], content=self.views)
+        self.out = surface(w, h, n, H.ao_dtype(ao_format), out_kind, x0)
+        self.dpitch, self.opitch = self.depth.row_bytes, self.out.row_bytes      # passed as given, a packed one included
 
 
 def pitched_call(ao, n, dptrs, dpitch, optrs, opitch, params=None, stream=None, prefetch=False):
@@ -106,7 +73,7 @@ def check(ao, oracle, s, surf, ids=None):
     torch.cuda.synchronize()
     for f in range(surf.n):
         want = oracle.run(surf.views[f], s[f] if isinstance(s, list) else s, result_only=not ids)
-        got, untouched = surf.result(f)
+        got, untouched = surf.out.read(f)
         assert untouched, f"frame {f}: bytes outside the viewport changed"
         ok, _ = H.nan_aware_equal(got, want["result"])
         assert ok, (f, H.diff_report("result", got, want["result"]))
@@ -123,7 +90,7 @@ def run_case(oracle, w, h, n, fmt=L.DEPTH_F32, ao_format=L.AO_R8, rtne=0, depth_
     try:
         surf = Surfaces(w, h, n, fmt, ao_format, depth_kind, out_kind, x0, seed)
         torch.cuda.synchronize()
-        rc = pitched_call(ao, n, surf.depth_ptrs(), surf.dp * surf.de, surf.out_ptrs(), surf.op * surf.ae)
+        rc = pitched_call(ao, n, surf.depth.ptrs(), surf.dpitch, surf.out.ptrs(), surf.opitch)
         assert rc == 0, ao._lib.meao_last_error(ao._ctx)
         check(ao, oracle, s, surf, ids)
     finally:
@@ -163,10 +130,6 @@ def test_max_batch_64(oracle):
     run_case(oracle, 132, 40, 64, depth_kind="256", out_kind="256", x0=0, max_batch=64)
 
 
-def frame_settings(base, fp):
-    return dataclasses.replace(base, intensity=np.float32(fp.intensity), near_clip=np.float32(fp.nearClipPlane))
-
-
 def per_frame_params(n, seed=0):
     return [FrameParams(intensity=0.5 + 0.5 * ((f + seed) % 3), nearClipPlane=0.1 * (1 + (f + seed) % 4)) for f in range(n)]
 
@@ -181,7 +144,7 @@ def test_per_frame_params(oracle, w, h, depth_kind, out_kind, x0):
     try:
         surf = Surfaces(w, h, n, L.DEPTH_F32, L.AO_R8, depth_kind, out_kind, x0, 40)
         torch.cuda.synchronize()
-        assert pitched_call(ao, n, surf.depth_ptrs(), surf.dp * 4, surf.out_ptrs(), surf.op, params=fps) == 0
+        assert pitched_call(ao, n, surf.depth.ptrs(), surf.dpitch, surf.out.ptrs(), surf.opitch, params=fps) == 0
         check(ao, oracle, [frame_settings(base, fp) for fp in fps], surf)
     finally:
         ao.close()
@@ -197,19 +160,19 @@ def run_stream(oracle, kinds, own_launch, per_frame=False, w=640, h=360, n=2):
     try:
         steps = [Surfaces(w, h, n, L.DEPTH_F32, L.AO_R8, dk, ok, 0, 100 + 10 * k) for k, (dk, ok) in enumerate(kinds)]
         fps = [per_frame_params(n, seed=k) if per_frame else None for k in range(3)]
-        dpitch = [0 if dk == "packed" else st.dp * 4 for (dk, _), st in zip(kinds, steps)]
-        opitch = [0 if ok == "packed" else st.op for (_, ok), st in zip(kinds, steps)]
+        dpitch = [0 if dk == "packed" else st.dpitch for (dk, _), st in zip(kinds, steps)]
+        opitch = [0 if ok == "packed" else st.opitch for (_, ok), st in zip(kinds, steps)]
         torch.cuda.synchronize()
         stream = torch.cuda.current_stream().cuda_stream
         for k in range(3):
             if k == 1:
                 ao.set_profiling(True)
             if k + 1 < 3:
-                ao.prefetch_device(steps[k + 1].depth_ptrs(), fps[k + 1], depth_pitch=dpitch[k + 1])
-            ao.execute_device(steps[k].depth_ptrs(), steps[k].out_ptrs(), stream=stream, params=fps[k],
+                ao.prefetch_device(steps[k + 1].depth.ptrs(), fps[k + 1], depth_pitch=dpitch[k + 1])
+            ao.execute_device(steps[k].depth.ptrs(), steps[k].out.ptrs(), stream=stream, params=fps[k],
                               depth_pitch=dpitch[k], out_pitch=opitch[k])
         ms, samples = ao.pass_times_ms()
-        fused = not own_launch and (steps[2].dp * 4) % 16 == 0 and w % 8 == 0
+        fused = not own_launch and (steps[2].dpitch) % 16 == 0 and w % 8 == 0
         assert samples == 2 and (ms[PASS_DOWNSAMPLE] == 0) == fused, (ms, fused)
         for k in range(3):
             sets = base if fps[k] is None else [frame_settings(base, fp) for fp in fps[k]]
@@ -245,10 +208,10 @@ def test_prefetch_with_another_pitch_reruns_the_pass(oracle):
         b = Surfaces(w, h, 1, L.DEPTH_F32, L.AO_R8, "2w", "256", 0, 6)       # same pointer announced with another pitch
         torch.cuda.synchronize()
         stream = torch.cuda.current_stream().cuda_stream
-        assert pitched_call(ao, 1, b.depth_ptrs(), a.dp * 4, None, 0, prefetch=True) == 0     # announce pitch P
-        assert pitched_call(ao, 1, a.depth_ptrs(), a.dp * 4, a.out_ptrs(), a.op, stream=stream) == 0
+        assert pitched_call(ao, 1, b.depth.ptrs(), a.dpitch, None, 0, prefetch=True) == 0     # announce pitch P
+        assert pitched_call(ao, 1, a.depth.ptrs(), a.dpitch, a.out.ptrs(), a.opitch, stream=stream) == 0
         ao.set_profiling(True)
-        assert pitched_call(ao, 1, b.depth_ptrs(), b.dp * 4, b.out_ptrs(), b.op, stream=stream) == 0   # consume with P' != P
+        assert pitched_call(ao, 1, b.depth.ptrs(), b.dpitch, b.out.ptrs(), b.opitch, stream=stream) == 0   # consume with P' != P
         ms, samples = ao.pass_times_ms()
         assert samples >= 1 and ms[PASS_DOWNSAMPLE] > 0, ms
         check(ao, oracle, s, a)
@@ -266,11 +229,11 @@ def test_pool_two_members(oracle):
     try:
         surf = Surfaces(w, h, n, L.DEPTH_F32, L.AO_R8, "+3", "256", 1, 60)
         torch.cuda.synchronize()
-        pool.execute_device(surf.depth_ptrs(), surf.out_ptrs(), depth_pitch=surf.dp * 4, out_pitch=surf.op)
+        pool.execute_device(surf.depth.ptrs(), surf.out.ptrs(), depth_pitch=surf.dpitch, out_pitch=surf.opitch)
         pool.synchronize()
         for f in range(n):
             want = oracle.run(surf.views[f], s, result_only=True)["result"]
-            got, untouched = surf.result(f)
+            got, untouched = surf.out.read(f)
             assert untouched and np.array_equal(got, want), (f, H.diff_report("result", got, want))
     finally:
         pool.close()
@@ -354,8 +317,8 @@ def test_invalid_pitches_launch_nothing(oracle):
     try:
         surf = Surfaces(w, h, 1, L.DEPTH_F32, L.AO_F16, "256", "256", 0, 3)
         torch.cuda.synchronize()
-        d, o = surf.depth_ptrs(), surf.out_ptrs()
-        before = surf.out.clone()
+        d, o = surf.depth.ptrs(), surf.out.ptrs()
+        before = surf.out.dev.clone()
         cases = [((w - 1) * 4, 0, L.ERR_INVALID_ARGUMENT), (w * 4 + 2, 0, L.ERR_INVALID_ARGUMENT),
                  (0, w * 2 - 2, L.ERR_INVALID_ARGUMENT), (0, w * 2 + 1, L.ERR_INVALID_ARGUMENT),
                  ((1 << 24) * 4, 0, L.ERR_UNSUPPORTED), (((1 << 24) - 4) * 4, 0, L.ERR_UNSUPPORTED)]     # 2^24 texels; > 2^32 bytes
@@ -365,7 +328,7 @@ def test_invalid_pitches_launch_nothing(oracle):
             assert ("depth_pitch" if dp else "ao_pitch") in msg, msg
         assert pitched_call(ao, 1, d, (w - 1) * 4, None, 0, prefetch=True) == L.ERR_INVALID_ARGUMENT
         torch.cuda.synchronize()
-        assert torch.equal(surf.out, before)
+        assert torch.equal(surf.out.dev, before)
     finally:
         ao.close()
 
@@ -412,60 +375,35 @@ ao.close()
 
 
 def kernel_trace(tmp_path, mode):
-    """Kernel names of the child's launches in start order (rocprofv3 --kernel-trace), from its first meao kernel on: what the
-    context creation and the tensors' setup launched before that is left out."""
-    import csv
-    import glob
-    import os
-    import shutil
-    import subprocess
-    import sys
-    prof = shutil.which("rocprofv3") or ("/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else None)
-    if prof is None:
-        pytest.skip("rocprofv3 is not installed")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = tmp_path / "child.py"
-    src.write_text(TRACE.replace("MODE", repr(mode)))
-    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run([prof, "--kernel-trace", "--output-format", "csv", "-d", str(tmp_path / "kt"), "-o", "kt", "--",
-                        sys.executable, str(src)], cwd=root, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    files = glob.glob(str(tmp_path / "kt" / "**" / "*kernel_trace.csv"), recursive=True)
-    assert files, r.stdout[-2000:]
-    rows = []
-    for f in files:
-        with open(f) as fh:
-            rows += [(int(row.get("Start_Timestamp") or 0), row["Kernel_Name"]) for row in csv.DictReader(fh)]
-    names = [n for _, n in sorted(rows, key=lambda t: t[0])]
-    first = next(i for i, n in enumerate(names) if "meao::" in n or "4meao" in n)
-    return names[first:]
-
-
-def launches(names, kernel):
-    return sum(1 for k in names if "::%s<" % kernel in k or "%d%sI" % (len(kernel), kernel) in k)
+    """The child's launches (H.kernel_trace) from its first meao kernel on: what the context creation and the tensors' setup
+    launched before that is left out of .names."""
+    k = H.kernel_trace(tmp_path, TRACE.replace("MODE", repr(mode)))
+    first = next(i for i, n in enumerate(k.names) if "meao::" in n or "4meao" in n)
+    k.names[:first] = []                               # in place: the counts k[...] are taken over .names
+    return k
 
 
 def test_kernel_trace_pitched_calls(tmp_path):
-    names = kernel_trace(tmp_path, "pitched")
+    k = kernel_trace(tmp_path, "pitched")
     for kernel in ("downsample_pitched_kernel", "upsample_final_pitched_kernel", "upsample_final_small_pitched_kernel",
                    "upsample_final_with_next_downsample_pitched_kernel"):
-        assert launches(names, kernel) > 0, (kernel, names)
-    assert launches(names, "downsample_pitched_kernel") == 4, names       # calls 1, 2 and 4; the own launch of call 4
+        assert k[kernel] > 0, (kernel, k.names)
+    assert k["downsample_pitched_kernel"] == 4, k.names       # calls 1, 2 and 4; the own launch of call 4
     for packed in ("downsample_kernel", "upsample_final_kernel", "upsample_final_small_kernel",
                    "upsample_final_with_next_downsample_kernel"):
-        assert launches(names, packed) == 0, (packed, names)
-    assert not [n for n in names if "rocclr" in n or "copy" in n.lower()], names      # read and written in place
+        assert k[packed] == 0, (packed, k.names)
+    assert not [n for n in k.names if "rocclr" in n or "copy" in n.lower()], k.names      # read and written in place
 
 
 def test_kernel_trace_per_frame_pitched_calls(tmp_path):
-    names = kernel_trace(tmp_path, "frames")
+    k = kernel_trace(tmp_path, "frames")
     for kernel in ("downsample_pitched_frames_kernel", "upsample_final_small_pitched_frames_kernel",
                    "upsample_final_pitched_frames_kernel", "upsample_final_with_next_downsample_pitched_frames_kernel"):
-        assert launches(names, kernel) > 0, (kernel, names)
-    assert not [n for n in names if "pitched" not in n and ("final" in n or "downsample" in n)], names
+        assert k[kernel] > 0, (kernel, k.names)
+    assert not [n for n in k.names if "pitched" not in n and ("final" in n or "downsample" in n)], k.names
 
 
 def test_kernel_trace_packed_pitches_launch_the_shared_kernels(tmp_path):
-    names = kernel_trace(tmp_path, "packed")
-    assert launches(names, "downsample_kernel") == 2 and launches(names, "upsample_final_small_kernel") == 2, names
-    assert not [n for n in names if "pitched" in n], names
+    k = kernel_trace(tmp_path, "packed")
+    assert k["downsample_kernel"] == 2 and k["upsample_final_small_kernel"] == 2, k.names
+    assert not [n for n in k.names if "pitched" in n], k.names

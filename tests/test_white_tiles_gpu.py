@@ -17,7 +17,6 @@ the radial gradient, UNORM16 and linear f32 / f16 depth, both sides of the edges
 thickness, 1 and 2 levels, hq_levels, the exhaustive sample set, single-pass stereo, per-frame parameter batches inside the exact
 column and with one frame outside it, pitched surfaces with a vector pitch and with pitch 389, 380 x 320, 400 x 330, 384 x 312 and the
 shaded call.  The window, wave and lane tests are in tests/test_white_tiles_window_gpu.py."""
-import dataclasses
 import os
 import subprocess
 import sys
@@ -29,6 +28,7 @@ from miniengineao_amd import FrameParams, synth
 from miniengineao_amd import _lib as L
 from tests import helpers as H
 from tests import white_tiles as WT
+from tests.helpers import frame_settings, same, want_of
 
 pytestmark = pytest.mark.gpu
 
@@ -49,10 +49,6 @@ def cases(oracle):
         d.setflags(write=False)
         out[name] = (d, oracle.run(d, s))
     return s, out
-
-
-def same(got, want, what):
-    assert np.array_equal(got, want), H.diff_report(what, got, want)
 
 
 def test_the_oracle_sees_the_tiles_the_frames_are_built_for(cases):
@@ -227,19 +223,9 @@ def test_variant_libraries(variant):
 # oracle for 64 x 64 and 64 x 32 tiles; the oracle must find white tiles in the frame, so that no case passes because the shortcut
 # never fires (which path DOES fire is read from the phase stamps: tests/white_tiles_clocks_check.py).
 
-CONV = dataclasses.replace(synth.DEFAULT_CAMERA, reversed_z=False)
 CAM128 = synth.Camera(near=0.1, far=128.0, reversed_z=True)
 RAW_Z2 = np.float32(63.0 / 1279.0)       # with CAM128: 1279 d + 1 rounds to 64, dist = 1 / 64, z = 2.0 -- exact in f16
 TILE_IDS = ["tiles64x64", "tiles64x32"]
-_WANT = {}
-
-
-def want_of(oracle, key, depth, s):
-    """Oracle outputs, computed once per (case, Settings) and shared by the tile heights; never modified."""
-    key = (key, tuple(sorted(vars(s).items())), depth.shape, str(depth.dtype))
-    if key not in _WANT:
-        _WANT[key] = oracle.run(depth, s)
-    return _WANT[key]
 
 
 def check_class(oracle, key, s, depth, debug, lib_depth=None, white=True, **kw):
@@ -256,25 +242,17 @@ def check_class(oracle, key, s, depth, debug, lib_depth=None, white=True, **kw):
     return want
 
 
-def field_frame(name):
-    cam = CONV if name.endswith("_convz") else synth.DEFAULT_CAMERA
-    kind = name.replace("_convz", "")
-    d = {"sky": lambda: WT.sky_frame(cam.reversed_z), "half_sky": lambda: WT.half_sky_frame(cam), "flat": WT.flat_frame,
-         "radial": lambda: synth.radial_gradient(WT.W, WT.H, cam)}[kind]()
-    return cam, d
-
-
 @pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
 @pytest.mark.parametrize("name", ["sky", "sky_convz", "half_sky", "half_sky_convz", "radial"])
 def test_field_frames(oracle, name, debug):
-    cam, d = field_frame(name)
+    cam, d = WT.field_frame(name)
     check_class(oracle, name, H.settings(oracle, WT.W, WT.H, cam=cam), d, debug)
 
 
 @pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
 @pytest.mark.parametrize("name", ["flat", "half_sky"])
 def test_unorm16_depth(oracle, name, debug):
-    _, d = field_frame(name)
+    _, d = WT.field_frame(name)
     s = H.settings(oracle, WT.W, WT.H, depth_format=oracle.DEPTH_UNORM16)
     check_class(oracle, "u16_" + name, s, oracle.encode_depth(d, oracle.DEPTH_UNORM16), debug, depth_format=L.DEPTH_UNORM16)
 
@@ -310,14 +288,14 @@ def test_exact_range_edges_on_white_frames(oracle, meao_lib, side, debug):
         v = inside if side == "inside" else outside
         assert H.in_exact_range(meao_lib, **{field: v}) == (side == "inside")
         for name in ("flat", "half_sky", "radial"):
-            cam, d = field_frame(name)
+            cam, d = WT.field_frame(name)
             s = H.settings(oracle, WT.W, WT.H, cam=cam, **{field: v})
             check_class(oracle, (edge, side, name), s, d, debug)
 
 
 @pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
 def test_far_outside_intensity_and_thickness(oracle, meao_lib, debug):
-    _, d = field_frame("half_sky")
+    _, d = WT.field_frame("half_sky")
     for field in ("intensity", "thickness_modifier"):
         for v in H.FAR_OUTSIDE[field]:
             assert H.in_exact_range(meao_lib, **{field: v})              # these leave the exact range untouched
@@ -330,7 +308,7 @@ def test_far_outside_intensity_and_thickness(oracle, meao_lib, debug):
 @pytest.mark.parametrize("kw", [dict(num_levels=1), dict(num_levels=2), dict(hq_levels=2), dict(single_pass_stereo=True)],
                          ids=["levels1", "levels2", "hq2", "stereo"])
 def test_level_counts_and_variants(oracle, kw, debug):
-    _, d = field_frame("half_sky")
+    _, d = WT.field_frame("half_sky")
     s = H.settings(oracle, WT.W, WT.H, **kw)
     want = want_of(oracle, str(kw), d, s)
     check_class(oracle, str(kw), s, d, debug, white=bool(WT.white_tiles_h(WT.low_ao(want, s), WT.W, WT.H)))
@@ -338,16 +316,10 @@ def test_level_counts_and_variants(oracle, kw, debug):
 
 @pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
 def test_exhaustive_sample_set(oracle, debug):
-    _, d = field_frame("half_sky")
+    _, d = WT.field_frame("half_sky")
     s = H.settings(oracle, WT.W, WT.H, sample_set=oracle.SAMPLES_EXHAUSTIVE)
     want = want_of(oracle, "exhaustive", d, s)
     check_class(oracle, "exhaustive", s, d, debug, white=bool(WT.white_tiles_h(want["combined1"], WT.W, WT.H)))
-
-
-def frame_settings(base, p):
-    names = {"intensity": "intensity", "blurTolerance": "blur_tolerance", "upsampleTolerance": "upsample_tolerance",
-             "noiseFilterTolerance": "noise_filter_tolerance", "thicknessModifier": "thickness_modifier"}
-    return dataclasses.replace(base, **{names[k]: v for k, v in dataclasses.asdict(p).items() if v is not None})
 
 
 @pytest.mark.parametrize("debug", [TALL, None], ids=TILE_IDS)
@@ -360,7 +332,7 @@ def test_per_frame_parameter_batches(oracle, meao_lib, mixed, debug):
               FrameParams(noiseFilterTolerance=edges["noise_high"][1]), FrameParams(upsampleTolerance=edges["upsample_low"][1])]
     if mixed:
         params[3] = FrameParams(upsampleTolerance=edges["upsample_high"][2])
-    depths = [field_frame(n)[1] for n in ("flat", "half_sky", "radial", "half_sky", "flat")]
+    depths = [WT.field_frame(n)[1] for n in ("flat", "half_sky", "radial", "half_sky", "flat")]
     base = H.settings(oracle, WT.W, WT.H)
     ao = H.component(base, max_batch=len(depths), debug=debug)
     try:
@@ -382,7 +354,7 @@ def test_per_frame_parameter_batches(oracle, meao_lib, mixed, debug):
 def test_pitched_surfaces_of_field_frames(oracle, name, pitch):
     """Pitch 389: rows are not 16-byte aligned (vec_ok false), the shortcut stands down and the normal path stores the same 255s."""
     torch = pytest.importorskip("torch")
-    _, d = field_frame(name)
+    _, d = WT.field_frame(name)
     s = H.settings(oracle, WT.W, WT.H)
     want = want_of(oracle, name, d, s)
     dev = torch.device("cuda", 0)
@@ -426,7 +398,7 @@ def test_frame_sizes_with_partial_tiles(oracle, w, h, debug):
 def test_shaded_batch_on_half_sky(oracle):
     """meao_execute_batch_shaded: the AO of the white path composited by the same call, against oracle.composite of the oracle's AO."""
     torch = pytest.importorskip("torch")
-    _, d = field_frame("half_sky")
+    _, d = WT.field_frame("half_sky")
     s = H.settings(oracle, WT.W, WT.H)
     want = want_of(oracle, "half_sky", d, s)
     rng = np.random.default_rng(5)
@@ -454,13 +426,12 @@ from oracle import oracle as O
 from miniengineao_amd import _lib as L
 from tests import helpers as H
 from tests import white_tiles as WT
-from tests.test_white_tiles_gpu import field_frame
 
 side = sys.argv[1]
 O.build()
 for edge, (field, inside, outside) in sorted(H.exact_range_edges(L.load()).items()):
     for name in ("flat", "half_sky", "radial"):
-        cam, d = field_frame(name)
+        cam, d = WT.field_frame(name)
         s = H.settings(O, WT.W, WT.H, cam=cam, **{field: inside if side == "inside" else outside})
         for debug in ({L.DEBUG_FINAL_SMALL_MAX_TILES: 0}, None):
             ao = H.component(s, debug=debug)

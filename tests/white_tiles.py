@@ -4,6 +4,8 @@ tile"), shared by tests/test_white_tile_rule.py (CPU), tests/test_white_tiles_gp
 The rule: a 64 x 64 tile of the result whose low-res AO window -- the 38 x 38 `combined1` texels [32 tx - 3, 32 tx + 34] x
 [32 ty - 3, 32 ty + 34], clamp-addressed -- is all code 255 is all 255 itself, unless a hi-res depth texel of the tile is not
 clean (NaN: the reference stores 0 there)."""
+import dataclasses
+
 import numpy as np
 
 W, H = 384, 320                     # 6 x 5 tiles of 64 x 64; the from-raw tiles are columns 1..4 (meao_dev_upsample.hpp ups_tile_from_raw)
@@ -126,6 +128,16 @@ def half_sky_frame(cam=None, w=W, h=H, lin=0.37):
     d = np.full((h, w), synth.linear01_to_raw(np.float64(lin), cam), np.float32)
     d[:, :w // 2] = SKY[cam.reversed_z]
     return d
+
+
+def field_frame(name):
+    """(camera, frame) of "sky", "half_sky", "flat", "radial"; "_convz": the conventional-Z camera."""
+    from miniengineao_amd import synth
+    cam = dataclasses.replace(synth.DEFAULT_CAMERA, reversed_z=False) if name.endswith("_convz") else synth.DEFAULT_CAMERA
+    kind = name.replace("_convz", "")
+    d = {"sky": lambda: sky_frame(cam.reversed_z), "half_sky": lambda: half_sky_frame(cam), "flat": flat_frame,
+         "radial": lambda: synth.radial_gradient(W, H, cam)}[kind]()
+    return cam, d
 
 
 def sky_and_flat_occluders(cam=None, w=W, h=H, seed=5):

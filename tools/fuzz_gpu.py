@@ -20,14 +20,13 @@ def run_sequences(count, seed0):
     tests/test_call_sequences_gpu.py: every case of the suite's stepped and pool modes in turn -- those that draw reservations, resizes
     and sized announcements (tests/test_dynamic_resolution_sequences_gpu.py) and those that draw mixed-size batches into them
     (tests/test_mixed_size_sequences_gpu.py) included -- and both forms of the carried pass."""
-    import tempfile
     import pytest
     from miniengineao_amd import _lib as L
     from tests import call_model as M
-    from tests.test_call_sequences_gpu import Driver
-    from tests.test_linear_depth_gpu import build_linearize
+    from tests.test_call_sequences_gpu import Driver          # the call-sequence driver stays in its suite
+    from tests.linear_depth import linearize
     O.build()
-    lin_c = build_linearize(tempfile.mkdtemp())
+    lin_c = linearize()
     cases = [("stepped", n) for n in sorted(M.CASES)] + [("pool_stepped", n) for n in sorted(M.POOL_CASES)]
     cases += [("dyn_stepped", n) for n in sorted(M.DYN_CASES)] + [("dyn_pool_stepped", n) for n in sorted(M.DYN_POOL_CASES)]
     cases += [("mix_stepped", n) for n in sorted(M.MIX_CASES)] + [("mix_pool_stepped", n) for n in sorted(M.MIX_POOL_CASES)]
