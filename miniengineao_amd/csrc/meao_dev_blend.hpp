@@ -82,7 +82,7 @@ __device__ __forceinline__ void blend_window_into_lds(const UpsampleArgs &in, fl
     for (int i = threadIdx.x; i < kNestRawW * rh; i += kThreads) {
         const int r = i / kNestRawW, c = i % kNestRawW;
         if (c >= rw) continue;
-        const uint32_t idx = static_cast<uint32_t>(clampi(ry0 + r, 0, lh - 1) * lw + clampi(rx0 + c, 0, lw - 1));   // a level is < 2^30 texels
+        const uint32_t idx = static_cast<uint32_t>(clampi(ry0 + r, 0, lh - 1) * lw + clampi(rx0 + c, 0, lw - 1));   // a level is <= 2^28 texels (16384 x 16384)
         const float d = *at_byte_offset(lo_depth, idx * 4u);
         r_dep[i] = d;
         r_inv[i] = rcp_strict<DIV>(d);                                          // UPS:67

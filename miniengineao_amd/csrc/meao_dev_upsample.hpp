@@ -516,7 +516,9 @@ __device__ __forceinline__ void ups_issue_hoisted(const UpsampleArgs &a, const H
             const int hy = CLAMPED ? min(hy_raw, hh - 1) : hy_raw;
             if constexpr (FINAL && !CLAMPED) L.hraw[pass][f] = uint4v{0x3f000000u, 0x3f000000u, 0x3f000000u, 0x3f000000u};   // texels past the frame: a clean depth, never used
             if (CLAMPED || (hhx0 < hw && hy < hh)) {
-                // texel index in the level (< 2^27): 32-bit byte offsets from the frame's uniform bases (saddr addressing)
+                // texel index in the level or the caller's frame, below 2^32 / texel size: a packed frame or level has at most 2^30
+                // texels (32768 x 32768), a pitched frame's last texel ends at most 2^32 - 1 bytes behind its origin (pitch_texels_of)
+                // -- 32-bit byte offsets from the frame's uniform bases (saddr addressing); tests/test_address_limits_gpu.py
                 const uint32_t hrow = PITCHED ? static_cast<uint32_t>(hy) * static_cast<uint32_t>(a.pitch.depth) + static_cast<uint32_t>(hhx0)
                                               : static_cast<uint32_t>(hy * hw + hhx0);
                 if constexpr (FINAL) {

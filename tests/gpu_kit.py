@@ -7,7 +7,8 @@ a pad word instead (DEPTH_PAD_WORD: a NaN or the all-ones code of the format).  
 intact() compares every byte outside the viewports with it: row padding, rows above and below, guards and slack alike.
 
 A suite that wants one allocation per frame (mixed sizes) makes a list of Surfaces with n = 1.  What a suite's layouts are -- its
-pitch kinds, origins and shifts -- stays with the suite: test data.  tests/test_gpu_kit.py checks the checker on the CPU."""
+pitch kinds, origins and shifts -- stays with the suite: test data.  A SparseSurface is the same guarded frame without the host
+mirror, for allocations of gigabytes (tests/test_address_limits_gpu.py).  tests/test_gpu_kit.py checks both checkers on the CPU."""
 from __future__ import annotations
 
 import numpy as np
@@ -96,3 +97,101 @@ class Surface:
         """(frame f's viewport texels, intact()) from one download."""
         raw = self.download() if raw is None else raw
         return self.texels(f, raw), self.intact(raw)
+
+
+CHUNK = 256 << 20            # bytes of a SparseSurface that one step of intact() examines
+
+
+class SparseSurface:
+    """Surface's device-resident sibling for one frame whose rows lie so far apart that the allocation is gigabytes and the
+    viewport a few KB: no host mirror.  The allocation is guard + (rows - 1) * row_bytes + (x0 + w) * texel_bytes + guard bytes --
+    it ends behind the last row's last viewport texel -- filled with the byte `fill` on the device; the viewport rows are written
+    and read through a strided device view, and intact() compares every other byte with `fill` on the device, CHUNK bytes at a
+    time (its temporaries are one byte per byte examined), so nothing of the surface's size crosses to the host."""
+
+    def __init__(self, w, h, dtype, tail=(), pitch=None, x0=0, y0=0, rows=None, guard=0, fill=SENTINEL, content=None, device="cuda"):
+        import torch
+        self.w, self.h, self.dtype, self.tail, self.n = w, h, np.dtype(dtype), tuple(tail), 1
+        self.x0, self.y0, self.fill = x0, y0, fill
+        self.pitch = x0 + w if pitch is None else pitch
+        self.rows = y0 + h if rows is None else rows
+        assert self.pitch >= x0 + w and self.rows >= y0 + h
+        self.texel_bytes = self.dtype.itemsize * int(np.prod(self.tail, dtype=np.int64))
+        self.row_bytes = self.pitch * self.texel_bytes
+        self.view_bytes = w * self.texel_bytes                       # of one viewport row
+        self.body_bytes = (self.rows - 1) * self.row_bytes + (x0 + w) * self.texel_bytes
+        self.offset = guard                                          # of the body in the allocation
+        self.first = guard + y0 * self.row_bytes + x0 * self.texel_bytes      # of the viewport in the allocation
+        self.nbytes = 2 * guard + self.body_bytes
+        self.device = device
+        self.dev = torch.full((self.nbytes,), fill, dtype=torch.uint8, device=device)
+        if content is not None:
+            self.put(content)
+        self._settle()
+
+    def _settle(self):
+        """The fill and the copies are work torch queues on its stream; a library call on another stream is not ordered behind
+        them, so construction and put() return with that work complete (as Surface's upload does)."""
+        if self.dev.is_cuda:
+            import torch
+            torch.cuda.synchronize(self.dev.device)
+
+    def rows_view(self):
+        """The viewport as an (h, w * texel_bytes) byte tensor over the allocation."""
+        return self.dev.as_strided((self.h, self.view_bytes), (self.row_bytes, 1), self.first)
+
+    def put(self, content):
+        """content: the viewport's texels, or a list holding them (as Surface takes its frames)."""
+        import torch
+        a = content[0] if isinstance(content, (list, tuple)) else content
+        a = np.ascontiguousarray(np.asarray(a).reshape((self.h, self.w) + self.tail)).view(np.uint8)
+        self.rows_view().copy_(torch.from_numpy(a.reshape(self.h, self.view_bytes).copy()))
+        self._settle()
+
+    @property
+    def ptr(self):
+        return self.dev.data_ptr() + self.first
+
+    def ptrs(self):
+        return [self.ptr]
+
+    @property
+    def packed(self):
+        return self.pitch == self.w
+
+    @property
+    def pitch_bytes(self):
+        return 0 if self.packed else self.row_bytes
+
+    def texels(self):
+        """The viewport's texels: the only download."""
+        raw = self.rows_view().cpu().numpy()
+        return np.ascontiguousarray(raw).view(self.dtype).reshape((self.h, self.w) + self.tail)
+
+    def _outside(self):
+        """(start, count, length, stride) of the byte runs that hold no viewport texel: what lies in front of the viewport, the
+        h - 1 runs between the end of one viewport row and the start of the next, what lies behind its last row."""
+        last_end = self.first + (self.h - 1) * self.row_bytes + self.view_bytes
+        return [(0, 1, self.first, 0), (self.first + self.view_bytes, self.h - 1, self.row_bytes - self.view_bytes, self.row_bytes),
+                (last_end, 1, self.nbytes - last_end, 0)]
+
+    def intact(self):
+        """Whether every byte that is no viewport texel still holds `fill`; decided on the device."""
+        for start, count, length, stride in self._outside():
+            if count == 0 or length == 0:
+                continue
+            if count == 1:                                   # one run: CHUNK bytes at a time
+                for at in range(start, start + length, CHUNK):
+                    if not bool((self.dev[at:min(at + CHUNK, start + length)] == self.fill).all()):
+                        return False
+                continue
+            step = max(1, CHUNK // length)                   # runs a stride apart: as many as make CHUNK bytes (a run is shorter than
+            for k in range(0, count, step):                  # a row: one alone is examined whole)
+                runs = self.dev.as_strided((min(step, count - k), length), (stride, 1), start + k * stride)
+                if not bool((runs == self.fill).all()):
+                    return False
+        return True
+
+    def read(self):
+        """(the viewport's texels, intact())."""
+        return self.texels(), self.intact()

@@ -1,5 +1,6 @@
 """The checker of the GPU suites checked on the CPU: tests/gpu_kit.py Surface through its host mirror (device=None).  A byte flipped
-anywhere outside the viewports must make intact() False; a flipped viewport texel must not, and must show in the texels."""
+anywhere outside the viewports must make intact() False; a flipped viewport texel must not, and must show in the texels.  The
+same for SparseSurface, whose tensor lives on the CPU here (device="cpu")."""
 import numpy as np
 import pytest
 
@@ -84,6 +85,88 @@ def test_packed():
     raw = g.host.copy()
     raw[-1] = 0
     assert g.intact(g.host) and not g.intact(raw)
+
+
+# ---- SparseSurface: the same questions, asked of a torch tensor on the CPU
+
+SPARSE = [dict(), dict(x0=X0, y0=Y0, rows=ROWS), dict(rows=H + 1)]         # the allocation ends behind the viewport's last texel or later
+
+
+def sparse(dtype, tail, **kw):
+    rng = np.random.default_rng(2)
+    content = rng.integers(0, 200, (H, W) + tail).astype(dtype)
+    content[0, 0] = content[H - 1, W - 1] = gpu_kit.SENTINEL          # sentinel-valued texels are texels
+    kw = dict(dict(pitch=PITCH + kw.get("x0", 0), guard=GUARD), **kw)
+    return gpu_kit.SparseSurface(W, H, dtype, tail, content=[content], device="cpu", **kw), content
+
+
+def sparse_regions(s):
+    """{region: byte offset in the allocation} of one byte in every kind of place outside the viewport."""
+    tb, vb = s.texel_bytes, s.view_bytes
+    row = lambda y: s.first + y * s.row_bytes                          # noqa: E731  (viewport row y's first texel)
+    out = {"front guard, first byte": 0, "front guard, last byte": GUARD - 1,
+           "back guard, first byte": s.nbytes - GUARD, "back guard, last byte": s.nbytes - 1,
+           "row padding, first byte behind row 0": row(0) + vb, "row padding, last byte in front of row 1": row(1) - 1,
+           "row padding behind the last row but one": row(H - 2) + vb, "row padding in front of the last row": row(H - 1) - 1,
+           "the byte behind the last row's texels": row(H - 1) + vb}
+    if s.x0 or s.y0:
+        out["in front of the first row's texels"] = row(0) - 1
+        out["the body's first byte"] = GUARD
+    if s.rows > s.y0 + H:
+        out["row below, below the viewport"] = row(H) + tb
+        out["the body's last byte"] = s.nbytes - GUARD - 1
+    return out
+
+
+@pytest.mark.parametrize("chunk", [gpu_kit.CHUNK, 64, 7])                  # one step; several runs per step; several steps per run
+@pytest.mark.parametrize("kw", SPARSE)
+@pytest.mark.parametrize("dtype,tail", TEXELS)
+def test_sparse_a_stray_byte_outside_the_viewport_is_seen(monkeypatch, dtype, tail, kw, chunk):
+    monkeypatch.setattr(gpu_kit, "CHUNK", chunk)
+    s, content = sparse(dtype, tail, **kw)
+    assert s.nbytes == 2 * GUARD + (s.rows - 1) * s.row_bytes + (s.x0 + W) * s.texel_bytes == len(s.dev)
+    texels, intact = s.read()
+    assert intact and texels.dtype == np.dtype(dtype) and np.array_equal(texels, content)
+    for region, at in sparse_regions(s).items():
+        assert int(s.dev[at]) == gpu_kit.SENTINEL, (region, at)
+        s.dev[at] ^= 0x01
+        texels, intact = s.read()
+        assert not intact, region
+        assert np.array_equal(texels, content), region
+        s.dev[at] ^= 0x01
+        assert s.intact(), region
+
+
+@pytest.mark.parametrize("kw", SPARSE)
+@pytest.mark.parametrize("dtype,tail", TEXELS)
+def test_sparse_a_changed_viewport_byte_shows_in_the_texels_alone(dtype, tail, kw):
+    s, content = sparse(dtype, tail, **kw)
+    for y, x in [(0, 0), (H - 1, W - 1), (1, 2), (0, W - 1), (H - 1, 0)]:
+        for b in (0, s.texel_bytes - 1):                                  # a texel's first and last byte
+            at = s.first + y * s.row_bytes + x * s.texel_bytes + b
+            s.dev[at] ^= 0x01
+            texels, intact = s.read()
+            bad = np.argwhere((texels != content).reshape(H, W, -1).any(axis=2))
+            assert intact and bad.tolist() == [[y, x]], (y, x, b, bad)
+            s.dev[at] ^= 0x01
+    new = content[::-1, ::-1].copy()
+    s.put(new)                                                            # put() again replaces the viewport, nothing else
+    texels, intact = s.read()
+    assert intact and np.array_equal(texels, new)
+
+
+def test_sparse_addresses_and_pitches():
+    s, _ = sparse(np.uint16, (4,), x0=X0, y0=Y0, rows=ROWS)
+    assert s.row_bytes == s.pitch_bytes == (PITCH + X0) * 8 and not s.packed and s.ptrs() == [s.ptr]
+    assert s.ptr == s.dev.data_ptr() + GUARD + (Y0 * (PITCH + X0) + X0) * 8 == s.rows_view().data_ptr()
+    p = gpu_kit.SparseSurface(W, H, np.uint16, content=np.arange(W * H, dtype=np.uint16), device="cpu")
+    assert p.packed and p.pitch_bytes == 0 and p.row_bytes == 2 * W and p.nbytes == 2 * W * H and p.ptr == p.dev.data_ptr()
+    texels, intact = p.read()
+    assert intact and np.array_equal(texels, np.arange(W * H, dtype=np.uint16).reshape(H, W))
+    f = gpu_kit.SparseSurface(W, H, np.uint8, pitch=PITCH, guard=GUARD, fill=0x00, device="cpu")       # another fill byte
+    assert f.intact() and not f.texels().any()
+    f.dev[GUARD + W] = gpu_kit.SENTINEL
+    assert not f.intact()
 
 
 @pytest.mark.parametrize("fmt,dtype,pattern", [(0, np.float32, [0x00, 0x00, 0xc0, 0x7f]), (1, np.uint16, [0xff, 0xff]),
