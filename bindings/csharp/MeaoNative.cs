@@ -83,6 +83,18 @@ namespace MiniEngineAO.Native
         public ulong ao_pitch;
     }
 
+    // one frame's size and the row pitches of its AO, colour and GBuffer0 surfaces (bytes, 0 = packed for its own width) in
+    // meao_composite_batch_extents
+    [StructLayout(LayoutKind.Sequential)]
+    public struct MeaoTargetExtent
+    {
+        public int width;
+        public int height;
+        public ulong ao_pitch;
+        public ulong color_pitch;
+        public ulong gbuffer0_pitch;
+    }
+
     [StructLayout(LayoutKind.Sequential)]
     public struct MeaoRenderConstants
     {
@@ -164,6 +176,9 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_composite_enqueue_format(IntPtr ctx, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
         [DllImport(Lib)] public static extern int meao_composite_batch(IntPtr ctx, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_execute_batch_shaded(IntPtr ctx, int n, IntPtr[] depth, ulong depth_pitch, IntPtr[] ao_out, ulong ao_pitch, [In] MeaoParams[] prm, int mode, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch, IntPtr stream);
+        // the batched composite and the shaded execute with one size per frame (mixed-size batches); color_pitch / gbuffer0_pitch: one per frame, null = packed
+        [DllImport(Lib)] public static extern int meao_composite_batch_extents(IntPtr ctx, int mode, int n, IntPtr[] ao, IntPtr[] color, int color_format, IntPtr[] gbuffer0_rgba8, [In] MeaoTargetExtent[] extents, IntPtr stream);
+        [DllImport(Lib)] public static extern int meao_execute_batch_extents_shaded(IntPtr ctx, int n, IntPtr[] depth, IntPtr[] ao_out, [In] MeaoExtent[] extents, [In] MeaoParams[] prm, int mode, IntPtr[] color, int color_format, [In] ulong[] color_pitch, IntPtr[] gbuffer0_rgba8, [In] ulong[] gbuffer0_pitch, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_composite_flush(IntPtr ctx, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_composite_pending(IntPtr ctx, out int out_frames);
 
@@ -189,6 +204,7 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue_pitched(IntPtr pool, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color_rgba16f, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
         [DllImport(Lib)] public static extern int meao_pool_composite_enqueue_format(IntPtr pool, int mode, int n, IntPtr[] ao, ulong ao_pitch, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
         [DllImport(Lib)] public static extern int meao_pool_execute_batch_shaded(IntPtr pool, int n, IntPtr[] depth, ulong depth_pitch, IntPtr[] ao_out, ulong ao_pitch, [In] MeaoParams[] prm, int mode, IntPtr[] color, int color_format, ulong color_pitch, IntPtr[] gbuffer0_rgba8, ulong gbuffer0_pitch);
+        [DllImport(Lib)] public static extern int meao_pool_execute_batch_extents_shaded(IntPtr pool, int n, IntPtr[] depth, IntPtr[] ao_out, [In] MeaoExtent[] extents, [In] MeaoParams[] prm, int mode, IntPtr[] color, int color_format, [In] ulong[] color_pitch, IntPtr[] gbuffer0_rgba8, [In] ulong[] gbuffer0_pitch);
         [DllImport(Lib)] public static extern int meao_pool_composite_flush(IntPtr pool);
         [DllImport(Lib)] public static extern int meao_pool_composite_pending(IntPtr pool, out int out_frames);
         [DllImport(Lib)] public static extern int meao_pool_gather_to_device(IntPtr pool, int n, IntPtr[] ao_src, IntPtr[] dst, int dst_device);

@@ -390,7 +390,9 @@ MEAO_API int32_t meao_prefetch_batch_sized(meao_ctx *ctx, int32_t width, int32_t
  *   - The ready set a mixed call promotes is an ordinary one: it has the announcement's size if that was sized, else the
  *     context's; its stride; this call's stream; it is matched, kept by meao_resize or dropped by meao_set_params like any other.
  *   - The AO surfaces a mixed call wrote may be named by a later meao_composite_enqueue*, which reads them as it reads every AO
- *     surface: at the CONTEXT's size under the pitch it is given.  Only frames of that size are meaningful input to it. */
+ *     surface: at the CONTEXT's size under the pitch it is given.  Only frames of that size are meaningful input to it.  Frames
+ *     of their own sizes are composited by meao_composite_batch_extents, or shaded in the same call by
+ *     meao_execute_batch_extents_shaded (below, with the composite calls); there is no enqueued or carried form for them. */
 typedef struct meao_extent {
     int32_t width, height;
     uint64_t depth_pitch, ao_pitch;
@@ -565,6 +567,56 @@ MEAO_API int32_t meao_execute_batch_shaded(meao_ctx *ctx, int32_t n, const void 
                                            int32_t mode, void *const *color, int32_t color_format, uint64_t color_pitch,
                                            void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch, meao_stream stream);
 
+/* Shaded frames from mixed-size batches: the batched composite with one size and one set of pitches per frame.  (The ABI version
+ * is unchanged: hosts probe for these symbols.)
+ * meao_composite_batch_extents: meao_composite_batch where frame f is extents[f].width x extents[f].height texels under
+ * extents[f]'s three pitches (bytes, 0 = tightly packed for THAT frame's width).  DEVICE surfaces only; n in 1..cfg.max_batch; the
+ * modes, colour formats and GBuffer0 rules of meao_composite_format.  Frame f's colour and GBuffer0 bytes are bit for bit what
+ * meao_composite_format on a context of size extents[f] leaves, and bytes outside a frame's width x height texels are neither
+ * read nor written.  The composite uses no intermediates, so the capacity does not bound it: every frame needs width and height
+ * in [1, 32768], nothing more.  The context's size is neither read for the results nor changed; nothing waits afterwards;
+ * meao_composite_pending, a waiting enqueued batch, an announcement and a ready set are untouched.  The n frames run as ONE
+ * composite_kernel launch on `stream` (NULL = the context's own stream): each frame's origins, extent, strides and form travel
+ * in a 64-byte entry of a context-owned table filled by one copy on `stream`, in a ring of 8 slots of its own (meao_create
+ * allocates it: 8 x max_batch x 64 bytes of device memory and as much pinned host memory, next to the 8 x max_batch x 24 bytes
+ * of meao_composite_batch's ring; the back-pressure rule of the per-frame table ring applies to each ring by itself).  Every
+ * frame is dealt row by row, and the vector form is chosen PER FRAME: a frame whose colour base and pitch are multiples of 16
+ * bytes and whose AO base and pitch are multiples of a lane's AO texels takes it whatever its neighbours do, with the same
+ * results either way.  The launch has the workgroups of its largest frame; those beyond a smaller frame's rows touch no memory.
+ * When every extent equals the context's size and all frames share their three strides the call IS meao_composite_batch with
+ * extents[0]'s pitches (strides are compared in texels, 0 equals the packed row, and GBuffer0's stride counts only where GBuffer0
+ * is given -- as in meao_execute_batch_extents); a call whose frames all have the context's size but two different strides is
+ * the sized launch.
+ * meao_execute_batch_extents_shaded: meao_execute_batch_extents followed, on the same stream, by that composite of ao_out[f] (at
+ * extents[f].ao_pitch) into color[f] (at color_pitch[f]; GBuffer0 at gbuffer0_pitch[f]).  color_pitch and gbuffer0_pitch hold one
+ * entry per frame, NULL = every frame tightly packed; gbuffer0_pitch is ignored where gbuffer0_rgba8 is NULL.  The execute half IS
+ * meao_execute_batch_extents: the same classification (uniform = the pitched call, else a mixed call), the same capacity rule, the
+ * same treatment of a waiting composite, a ready set and an announcement, the same "last execute" state and per-frame debug
+ * sizes.  The composite is one launch behind the last AO kernel and never waits.  Each half classifies itself: a call that is
+ * uniform for the execute may be the sized launch for the composite (two colour strides), and the other way round.
+ * Validation, for both calls, before anything is enqueued -- for the shaded call both halves' checks; a refused call launches
+ * nothing and leaves the AO, the colours, an announcement, a ready set and a waiting batch as they were.  n, the mode, the
+ * pointers and the AMBIENT_ONLY / GBuffer0 rule as in meao_composite_batch; an unknown color_format is
+ * MEAO_ERR_INVALID_ARGUMENT; a width or height outside [1, 32768] is MEAO_ERR_INVALID_ARGUMENT; each frame's pitches follow the
+ * rules of meao_composite_format against ITS OWN width: non-zero and smaller than width x element size, or not a multiple of the
+ * element size: MEAO_ERR_INVALID_ARGUMENT; pitch / element size >= 2^24: MEAO_ERR_UNSUPPORTED; (height - 1) x pitch + width x
+ * element size > 2^32 - 1: MEAO_ERR_UNSUPPORTED.  In the sized launch a tightly packed frame is rows of pitch = width, addressed
+ * with 32-bit byte offsets like any row, so that last limit applies to packed frames too -- RGBA16F included, which
+ * meao_composite_batch takes packed at any size.  meao_last_error names the call, extents[f] (for the shaded call color_pitch[f]
+ * / gbuffer0_pitch[f]) and the argument; an error of the execute half comes under the shaded call's name.
+ * Surfaces: as for meao_composite_batch. */
+typedef struct meao_target_extent {            /* 32 bytes: offsets 0, 4, 8, 16, 24 */
+    int32_t width, height;
+    uint64_t ao_pitch, color_pitch, gbuffer0_pitch;   /* bytes; 0 = tightly packed for THIS frame's width */
+} meao_target_extent;
+MEAO_API int32_t meao_composite_batch_extents(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, void *const *color,
+                                              int32_t color_format, void *const *gbuffer0_rgba8,
+                                              const meao_target_extent *extents, meao_stream stream);
+MEAO_API int32_t meao_execute_batch_extents_shaded(meao_ctx *ctx, int32_t n, const void *const *depth, void *const *ao_out,
+                                                   const meao_extent *extents, const meao_params *params, int32_t mode,
+                                                   void *const *color, int32_t color_format, const uint64_t *color_pitch,
+                                                   void *const *gbuffer0_rgba8, const uint64_t *gbuffer0_pitch, meao_stream stream);
+
 /* Per-pass device timing: when enabled, meao_execute* brackets every pass with HIP events on
  * the launch stream; meao_get_pass_times averages each pass over the executes that ran it since
  * the last reset (it waits for the stream of the last execute first); *out_samples = executes measured.
@@ -670,6 +722,15 @@ MEAO_API int32_t meao_pool_execute_batch_shaded(meao_pool *pool, int32_t n, cons
                                                 void *const *ao_out, uint64_t ao_pitch, const meao_params *params,
                                                 int32_t mode, void *const *color, int32_t color_format, uint64_t color_pitch,
                                                 void *const *gbuffer0_rgba8, uint64_t gbuffer0_pitch);
+/* meao_execute_batch_extents_shaded for the pool: frame f and all its per-frame arguments (extents[f], params[f], color_pitch[f],
+ * gbuffer0_pitch[f]) go to member f mod G.  Every member's share is validated, both halves, against that member's capacity
+ * before any member enqueues; one refused share refuses the call, and no member launches or changes.  Each member that is dealt
+ * frames runs its execute and ONE composite launch on its stream, from its worker thread, and classifies each half of its own
+ * share.  Members dealt nothing do what they do for meao_pool_execute_batch_extents. */
+MEAO_API int32_t meao_pool_execute_batch_extents_shaded(meao_pool *pool, int32_t n, const void *const *depth, void *const *ao_out,
+                                                        const meao_extent *extents, const meao_params *params, int32_t mode,
+                                                        void *const *color, int32_t color_format, const uint64_t *color_pitch,
+                                                        void *const *gbuffer0_rgba8, const uint64_t *gbuffer0_pitch);
 MEAO_API int32_t meao_pool_composite_flush(meao_pool *pool);
 MEAO_API int32_t meao_pool_composite_pending(const meao_pool *pool, int32_t *out_frames);   /* summed over the members */
 /* Copies the n DEVICE results ao_src[f] (on their owning devices) to dst[f] on dst_device with

@@ -232,6 +232,44 @@ public:
         check(meao_composite_batch(ctx_, mode, static_cast<int32_t>(deviceAo.size()), deviceAo.data(), aoPitch, deviceColor.data(),
                                    colorFormat, colorPitch, deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(), gbuffer0Pitch, stream));
     }
+    // The batch in ONE launch with one size and one set of pitches per frame (meao_composite_batch_extents): extents[f] = frame
+    // f's width, height and the row pitches of its three surfaces (bytes, 0 = packed for that width); any size, no capacity rule.
+    void CompositeBatchExtents(meao_composite_mode mode, const std::vector<const void *> &deviceAo, const std::vector<void *> &deviceColor,
+                               const std::vector<meao_target_extent> &extents, const std::vector<void *> &deviceGBuffer0 = {},
+                               meao_stream stream = nullptr)
+    {
+        if (deviceColor.size() != deviceAo.size() || extents.size() != deviceAo.size() ||
+            (!deviceGBuffer0.empty() && deviceGBuffer0.size() != deviceAo.size()))
+            throw std::invalid_argument("meao: one colour surface and one meao_target_extent per frame");
+        check(meao_composite_batch_extents(ctx_, mode, static_cast<int32_t>(deviceAo.size()), deviceAo.data(), deviceColor.data(), colorFormat,
+                                           deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(), extents.data(), stream));
+    }
+    // AO and shaded frames from one mixed-size call (meao_execute_batch_extents_shaded): RenderBatchExtents, then that composite
+    // of deviceAo[f] into deviceColor[f] on the same stream.  targets[f] = frame f's width, height and the pitches of its AO,
+    // colour and GBuffer0 surfaces; depthPitch empty = every depth frame packed, else one pitch per frame.
+    void RenderDeviceBatchExtentsShaded(const std::vector<const void *> &deviceDepth, const std::vector<void *> &deviceAo,
+                                        const std::vector<meao_target_extent> &targets, meao_composite_mode mode,
+                                        const std::vector<void *> &deviceColor, const std::vector<void *> &deviceGBuffer0 = {},
+                                        const std::vector<uint64_t> &depthPitch = {}, const std::vector<meao_params> &params = {},
+                                        meao_stream stream = nullptr)
+    {
+        const size_t n = deviceDepth.size();
+        if (deviceAo.size() != n || deviceColor.size() != n || targets.size() != n || (!deviceGBuffer0.empty() && deviceGBuffer0.size() != n))
+            throw std::invalid_argument("meao: one AO surface, one colour surface and one meao_target_extent per frame");
+        if (!depthPitch.empty() && depthPitch.size() != n) throw std::invalid_argument("meao: one depth pitch per frame");
+        if (!params.empty() && params.size() != n) throw std::invalid_argument("meao: one meao_params per frame");
+        std::vector<meao_extent> extents(n);
+        std::vector<uint64_t> colorPitch(n), gbuffer0Pitch(n);
+        for (size_t f = 0; f < n; ++f) {
+            extents[f] = meao_extent{targets[f].width, targets[f].height, depthPitch.empty() ? 0 : depthPitch[f], targets[f].ao_pitch};
+            colorPitch[f] = targets[f].color_pitch; gbuffer0Pitch[f] = targets[f].gbuffer0_pitch;
+        }
+        sync();
+        check(meao_execute_batch_extents_shaded(ctx_, static_cast<int32_t>(n), deviceDepth.data(), deviceAo.data(), extents.data(),
+                                                params.empty() ? nullptr : params.data(), mode, deviceColor.data(), colorFormat,
+                                                colorPitch.data(), deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(),
+                                                gbuffer0Pitch.data(), stream));
+    }
     // AO and shaded frames from one call (meao_execute_batch_shaded): RenderDeviceBatchPitched, then the batched composite of
     // deviceAo[f] into deviceColor[f] on the same stream.  params empty = the context's parameters.
     void RenderDeviceBatchShaded(const std::vector<const void *> &deviceDepth, uint64_t depthPitch, const std::vector<void *> &deviceAo,
@@ -409,6 +447,30 @@ public:
         check(meao_pool_execute_batch_shaded(pool_, static_cast<int32_t>(deviceDepth.size()), deviceDepth.data(), depthPitch, deviceAo.data(),
                                              aoPitch, params.empty() ? nullptr : params.data(), mode, deviceColor.data(), colorFormat,
                                              colorPitch, deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(), gbuffer0Pitch));
+    }
+    // AO and shaded frames from one mixed-size pool call (meao_pool_execute_batch_extents_shaded): targets[f] and depthPitch[f] go
+    // with frame f to member f mod G; arguments as AmbientOcclusion::RenderDeviceBatchExtentsShaded
+    void RenderDeviceBatchExtentsShaded(const std::vector<const void *> &deviceDepth, const std::vector<void *> &deviceAo,
+                                        const std::vector<meao_target_extent> &targets, meao_composite_mode mode,
+                                        const std::vector<void *> &deviceColor, meao_color_format colorFormat,
+                                        const std::vector<void *> &deviceGBuffer0 = {}, const std::vector<uint64_t> &depthPitch = {},
+                                        const std::vector<meao_params> &params = {})
+    {
+        const size_t n = deviceDepth.size();
+        if (deviceAo.size() != n || deviceColor.size() != n || targets.size() != n || (!deviceGBuffer0.empty() && deviceGBuffer0.size() != n))
+            throw std::invalid_argument("meao: one AO surface, one colour surface and one meao_target_extent per frame");
+        if (!depthPitch.empty() && depthPitch.size() != n) throw std::invalid_argument("meao: one depth pitch per frame");
+        if (!params.empty() && params.size() != n) throw std::invalid_argument("meao: one meao_params per frame");
+        std::vector<meao_extent> extents(n);
+        std::vector<uint64_t> colorPitch(n), gbuffer0Pitch(n);
+        for (size_t f = 0; f < n; ++f) {
+            extents[f] = meao_extent{targets[f].width, targets[f].height, depthPitch.empty() ? 0 : depthPitch[f], targets[f].ao_pitch};
+            colorPitch[f] = targets[f].color_pitch; gbuffer0Pitch[f] = targets[f].gbuffer0_pitch;
+        }
+        check(meao_pool_execute_batch_extents_shaded(pool_, static_cast<int32_t>(n), deviceDepth.data(), deviceAo.data(), extents.data(),
+                                                     params.empty() ? nullptr : params.data(), mode, deviceColor.data(), colorFormat,
+                                                     colorPitch.data(), deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(),
+                                                     gbuffer0Pitch.data()));
     }
     // row-pitched device surfaces (meao_pool_execute_batch_pitched); params empty = the members' own parameters
     void RenderDeviceBatchPitched(const std::vector<const void *> &deviceDepth, uint64_t depthPitch, const std::vector<void *> &deviceAo,

@@ -79,6 +79,13 @@ class Extent(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("depth_pitch", C.c_uint64), ("ao_pitch", C.c_uint64)]
 
 
+class TargetExtent(C.Structure):
+    """meao_target_extent: one frame's size and the row pitches of its AO, colour and GBuffer0 surfaces (bytes, 0 = packed for
+    its own width) in meao_composite_batch_extents."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ao_pitch", C.c_uint64), ("color_pitch", C.c_uint64),
+                ("gbuffer0_pitch", C.c_uint64)]
+
+
 class RenderConstants(C.Structure):
     _fields_ = [("inv_thickness_table", C.c_float * 12), ("sample_weight_table", C.c_float * 12),
                 ("inv_slice_dimension", C.c_float * 2), ("reject_fadeoff", C.c_float),
@@ -149,6 +156,11 @@ SIGNATURES = {
     "meao_execute_batch_shaded": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(C.c_void_p), C.c_uint64,
                                               C.POINTER(Params), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_uint64,
                                               C.POINTER(C.c_void_p), C.c_uint64, C.c_void_p]),
+    "meao_composite_batch_extents": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32,
+                                                 C.POINTER(C.c_void_p), C.POINTER(TargetExtent), C.c_void_p]),
+    "meao_execute_batch_extents_shaded": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(Extent),
+                                                      C.POINTER(Params), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_uint64),
+                                                      C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p]),
     "meao_composite_flush": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "meao_composite_pending": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
     "meao_pool_create": (C.c_int32, [C.POINTER(Config), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),
@@ -182,6 +194,9 @@ SIGNATURES = {
     "meao_pool_execute_batch_shaded": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(C.c_void_p),
                                                    C.c_uint64, C.POINTER(Params), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_uint64,
                                                    C.POINTER(C.c_void_p), C.c_uint64]),
+    "meao_pool_execute_batch_extents_shaded": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                           C.POINTER(Extent), C.POINTER(Params), C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
+                                                           C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "meao_pool_composite_flush": (C.c_int32, [C.c_void_p]),
     "meao_pool_composite_pending": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
     "meao_pool_gather_path": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -49,6 +49,29 @@ def extents_array(extents: Sequence[tuple], n: int):
     return arr
 
 
+def target_extents_array(extents: Sequence[tuple], n: int):
+    """[(width, height[, ao_pitch, color_pitch, gbuffer0_pitch]), ...] -> the meao_target_extent array of
+    meao_composite_batch_extents (pitches in bytes, 0 or absent = packed for that frame's width)."""
+    if len(extents) != n:
+        raise ValueError(f"{len(extents)} extents for {n} frames")
+    arr = (L.TargetExtent * n)()
+    for f, e in enumerate(extents):
+        if len(e) not in (2, 5):
+            raise ValueError(f"extents[{f}]: expected (width, height) or (width, height, ao_pitch, color_pitch, gbuffer0_pitch)")
+        arr[f].width, arr[f].height = int(e[0]), int(e[1])
+        arr[f].ao_pitch, arr[f].color_pitch, arr[f].gbuffer0_pitch = (int(e[2]), int(e[3]), int(e[4])) if len(e) == 5 else (0, 0, 0)
+    return arr
+
+
+def _pitch_array(pitches: Optional[Sequence[int]], n: int, what: str):
+    """One row pitch in bytes per frame -> the uint64 array of meao_execute_batch_extents_shaded; None = every frame packed."""
+    if pitches is None:
+        return None
+    if len(pitches) != n:
+        raise ValueError(f"{len(pitches)} {what} for {n} frames")
+    return (C.c_uint64 * n)(*[int(v) for v in pitches])
+
+
 class AmbientOcclusion:
     """depth in -> AO texture out, on one MI355X.  One instance per device."""
 
@@ -218,17 +241,33 @@ class AmbientOcclusion:
     def execute_shaded_device(self, depth_ptrs: Sequence[int], out_ptrs: Sequence[int], mode: int, color_ptrs: Sequence[int],
                               gbuffer0_ptrs: Optional[Sequence[int]] = None, stream: int = 0,
                               params: Optional[Sequence[Optional[FrameParams]]] = None, *, depth_pitch: int = 0, out_pitch: int = 0,
-                              color_pitch: int = 0, gbuffer0_pitch: int = 0, color_format: int = L.COLOR_RGBA16F) -> None:
+                              color_pitch: int = 0, gbuffer0_pitch: int = 0, color_format: int = L.COLOR_RGBA16F,
+                              extents: Optional[Sequence[tuple]] = None, color_pitches: Optional[Sequence[int]] = None,
+                              gbuffer0_pitches: Optional[Sequence[int]] = None) -> None:
         """execute_device() followed, on the same stream, by ONE composite launch of out_ptrs[f] into color_ptrs[f]
         (meao_execute_batch_shaded): when the call has completed the colour targets are shaded, whatever their format.  Every
-        argument of both halves is checked before anything is enqueued."""
+        argument of both halves is checked before anything is enqueued.
+        extents: a mixed-size batch as execute_device takes it (meao_execute_batch_extents_shaded); color_pitches /
+        gbuffer0_pitches then hold one row pitch in bytes per frame (None = every frame tightly packed) in place of color_pitch /
+        gbuffer0_pitch."""
         n = len(depth_ptrs)
         if len(out_ptrs) != n or len(color_ptrs) != n or (gbuffer0_ptrs and len(gbuffer0_ptrs) != n):
             raise ValueError("execute_shaded_device: one AO, one colour (and one GBuffer0) surface per depth frame")
+        if extents is None and (color_pitches is not None or gbuffer0_pitches is not None):
+            raise ValueError("execute_shaded_device: color_pitches / gbuffer0_pitches go with extents")
         self._sync_params()
         self._last_sizes = None
         prm = None if params is None else params_array(params, n, self._prm)
         g = (C.c_void_p * n)(*gbuffer0_ptrs) if gbuffer0_ptrs else None
+        if extents is not None:
+            if depth_pitch or out_pitch or color_pitch or gbuffer0_pitch:
+                raise ValueError("execute_shaded_device: with extents the pitches are given per frame (extents, color_pitches, gbuffer0_pitches)")
+            L.check(self._lib.meao_execute_batch_extents_shaded(
+                self._ctx, n, (C.c_void_p * n)(*depth_ptrs), (C.c_void_p * n)(*out_ptrs), extents_array(extents, n), prm, mode,
+                (C.c_void_p * n)(*color_ptrs), color_format, _pitch_array(color_pitches, n, "color_pitches"), g,
+                _pitch_array(gbuffer0_pitches, n, "gbuffer0_pitches"), C.c_void_p(stream) if stream else None), self._ctx)
+            self._last_sizes = [(int(e[0]), int(e[1])) for e in extents]
+            return
         L.check(self._lib.meao_execute_batch_shaded(self._ctx, n, (C.c_void_p * n)(*depth_ptrs), depth_pitch, (C.c_void_p * n)(*out_ptrs),
                                                     out_pitch, prm, mode, (C.c_void_p * n)(*color_ptrs), color_format, color_pitch, g,
                                                     gbuffer0_pitch, C.c_void_p(stream) if stream else None), self._ctx)
@@ -263,7 +302,10 @@ class AmbientOcclusion:
         frames must share one row stride, which becomes the pitch; any other layout raises ValueError (nothing is copied).
         out: the same for the AO (uint8 for R8, float16 for F16 storage), or None: allocated packed.  Returns out.
         color: colour targets as composite_tensors takes them (with gbuffer0, mode and color_format): they are shaded in place by
-        the same call (meao_execute_batch_shaded), one composite launch behind the last AO kernel."""
+        the same call (meao_execute_batch_shaded), one composite launch behind the last AO kernel.
+        A list of differently shaped (H_f, W_f) tensors is a mixed-size batch (meao_execute_batch_extents, with color
+        meao_execute_batch_extents_shaded): out, color and gbuffer0 are then lists of tensors of the frames' sizes, each tensor's own
+        row stride becomes its pitch, and the list of AO tensors is returned."""
         import torch
         from .surfaces import frame_pointers, packed_pitch
         depth_dt = getattr(torch, DEPTH_TORCH[self._cfg.depth_format])
@@ -271,9 +313,9 @@ class AmbientOcclusion:
         dev = torch.device("cuda", self._cfg.device)        # every frame of depth and out must be on the context's device
         frames = list(depth) if not hasattr(depth, "dim") else depth
         if isinstance(frames, list) and any(tuple(t.shape) != (self.height, self.width) for t in frames):
-            if color is not None or gbuffer0 is not None:
-                raise ValueError("execute_tensors: a mixed-size batch has no shaded form")
-            return self._execute_mixed_tensors(frames, out, params, depth_dt, ao_dt, dev)
+            if gbuffer0 is not None and color is None:
+                raise ValueError("execute_tensors: gbuffer0 without color")
+            return self._execute_mixed_tensors(frames, out, params, depth_dt, ao_dt, dev, color, gbuffer0, mode, color_format)
         d_ptrs, d_pitch = frame_pointers(frames, self.height, self.width, depth_dt, "depth", device=dev)
         n = len(d_ptrs)
         first = frames[0]
@@ -301,11 +343,14 @@ class AmbientOcclusion:
                             out_pitch=packed_pitch(o_pitch, self.width, o_frames[0].element_size()))
         return out
 
-    def _execute_mixed_tensors(self, frames, out, params, depth_dt, ao_dt, dev):
+    def _execute_mixed_tensors(self, frames, out, params, depth_dt, ao_dt, dev, color=None, gbuffer0=None,
+                               mode: int = L.COMPOSITE_MULTIPLY, color_format: int = L.COLOR_RGBA16F):
         """execute_tensors for a list of (H_f, W_f) tensors of different shapes (meao_execute_batch_extents): every frame's own
-        row stride becomes its pitch.  out: a list of (H_f, W_f) tensors, or None: allocated packed.  Returns the list."""
+        row stride becomes its pitch.  out: a list of (H_f, W_f) tensors, or None: allocated packed.  Returns the list.
+        color (and gbuffer0): lists of the frames' colour (GBuffer0) targets, shaded in place by the same call
+        (meao_execute_batch_extents_shaded)."""
         import torch
-        from .surfaces import frame_pointers, packed_pitch
+        from .surfaces import composite_surfaces_per_frame, frame_pointers, packed_pitch
         if out is None:
             out = [torch.empty(tuple(t.shape), dtype=ao_dt, device=dev) for t in frames]
         out = list(out)
@@ -321,7 +366,15 @@ class AmbientOcclusion:
             d_ptrs.append(dp)
             o_ptrs.append(op)
             extents.append((w, h, packed_pitch(d_pitch, w, d.element_size()), packed_pitch(o_pitch, w, o.element_size())))
-        self.execute_device(d_ptrs, o_ptrs, stream=torch.cuda.current_stream(dev).cuda_stream, params=params, extents=extents)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if color is not None:
+            a, c, g, targets = composite_surfaces_per_frame(out, color, gbuffer0, ao_dt, device=dev, color_format=color_format)
+            if len(c) != len(frames):
+                raise ValueError(f"color has {len(c)} frames, depth {len(frames)}")
+            self.execute_shaded_device(d_ptrs, a, mode, c, g, stream=stream, params=params, color_format=color_format, extents=extents,
+                                       color_pitches=[t[3] for t in targets], gbuffer0_pitches=[t[4] for t in targets] if g else None)
+            return out
+        self.execute_device(d_ptrs, o_ptrs, stream=stream, params=params, extents=extents)
         return out
 
     def synchronize(self, stream: int = 0) -> None:
@@ -393,11 +446,21 @@ class AmbientOcclusion:
 
     def composite_batch_device(self, mode: int, ao_ptrs: Sequence[int], color_ptrs: Sequence[int],
                                gbuffer0_ptrs: Optional[Sequence[int]] = None, stream: int = 0, *, ao_pitch: int = 0,
-                               color_pitch: int = 0, gbuffer0_pitch: int = 0, color_format: int = L.COLOR_RGBA16F) -> None:
+                               color_pitch: int = 0, gbuffer0_pitch: int = 0, color_format: int = L.COLOR_RGBA16F,
+                               extents: Optional[Sequence[tuple]] = None) -> None:
         """The frames (1..max_batch) composited by ONE launch on ``stream``, now (meao_composite_batch): nothing waits
-        afterwards, and a batch that waits from composite_enqueue_device() is left alone.  Arguments as composite_enqueue_device."""
+        afterwards, and a batch that waits from composite_enqueue_device() is left alone.  Arguments as composite_enqueue_device.
+        extents: one (width, height[, ao_pitch, color_pitch, gbuffer0_pitch]) per frame -- frames of their own sizes, of any size
+        (meao_composite_batch_extents); the pitches (bytes, 0 = packed for that frame's width) then come from the extents."""
         n = len(ao_ptrs)
         g = (C.c_void_p * n)(*gbuffer0_ptrs) if gbuffer0_ptrs else None
+        if extents is not None:
+            if ao_pitch or color_pitch or gbuffer0_pitch:
+                raise ValueError("composite_batch_device: with extents the pitches are given per frame, inside the extents")
+            L.check(self._lib.meao_composite_batch_extents(self._ctx, mode, n, (C.c_void_p * n)(*ao_ptrs), (C.c_void_p * n)(*color_ptrs),
+                                                           color_format, g, target_extents_array(extents, n),
+                                                           C.c_void_p(stream) if stream else None), self._ctx)
+            return
         L.check(self._lib.meao_composite_batch(self._ctx, mode, n, (C.c_void_p * n)(*ao_ptrs), ao_pitch, (C.c_void_p * n)(*color_ptrs),
                                                color_format, color_pitch, g, gbuffer0_pitch, C.c_void_p(stream) if stream else None),
                 self._ctx)
@@ -412,11 +475,17 @@ class AmbientOcclusion:
         (nothing is copied).  enqueue=False: one composite per frame now, on torch.cuda.current_stream(); enqueue=True: the
         batch waits for the next execute's render kernel (composite_enqueue_device).  color_format: another meao_color_format
         for ``color`` -- (N, H, W, 4) float32 for RGBA32F or uint8 for RGBA8, (N, H, W) int32 for R11G11B10F.  batched=True (with
-        enqueue=False): the frames in one launch now (composite_batch_device) instead of one launch each."""
+        enqueue=False): the frames in one launch now (composite_batch_device) instead of one launch each -- and then ao, color and
+        gbuffer0 may be lists of differently shaped frames, each tensor's own row stride becoming its pitch
+        (meao_composite_batch_extents)."""
         import torch
-        from .surfaces import composite_surfaces
+        from .surfaces import composite_surfaces, composite_surfaces_per_frame
         ao_dt = torch.uint8 if self._cfg.ao_format == L.AO_R8 else torch.float16
         dev = torch.device("cuda", self._cfg.device)
+        if batched and not enqueue and not hasattr(ao, "dim") and any(tuple(t.shape) != (self.height, self.width) for t in ao):
+            a, c, g, extents = composite_surfaces_per_frame(ao, color, gbuffer0, ao_dt, device=dev, color_format=color_format)
+            self.composite_batch_device(mode, a, c, g, torch.cuda.current_stream(dev).cuda_stream, color_format=color_format, extents=extents)
+            return
         a, ap, c, cp, g, gp = composite_surfaces(ao, color, gbuffer0, self.height, self.width, ao_dt, device=dev, color_format=color_format)
         if enqueue:
             if batched:
@@ -615,14 +684,28 @@ class AmbientOcclusionPool:
     def execute_shaded_device(self, depth_ptrs: Sequence[int], out_ptrs: Sequence[int], mode: int, color_ptrs: Sequence[int],
                               gbuffer0_ptrs: Optional[Sequence[int]] = None,
                               params: Optional[Sequence[Optional[FrameParams]]] = None, *, depth_pitch: int = 0, out_pitch: int = 0,
-                              color_pitch: int = 0, gbuffer0_pitch: int = 0, color_format: int = L.COLOR_RGBA16F) -> None:
+                              color_pitch: int = 0, gbuffer0_pitch: int = 0, color_format: int = L.COLOR_RGBA16F,
+                              extents: Optional[Sequence[tuple]] = None, color_pitches: Optional[Sequence[int]] = None,
+                              gbuffer0_pitches: Optional[Sequence[int]] = None) -> None:
         """AmbientOcclusion.execute_shaded_device for the pool (meao_pool_execute_batch_shaded): frame f resident on
-        device_of_frame(f); each member runs its execute and one batched composite launch.  Asynchronous (synchronize())."""
+        device_of_frame(f); each member runs its execute and one batched composite launch.  Asynchronous (synchronize()).
+        extents, color_pitches, gbuffer0_pitches: a mixed-size batch, as AmbientOcclusion.execute_shaded_device takes it
+        (meao_pool_execute_batch_extents_shaded); frame f's entries go with it to its member."""
         n = len(depth_ptrs)
         if len(out_ptrs) != n or len(color_ptrs) != n or (gbuffer0_ptrs and len(gbuffer0_ptrs) != n):
             raise ValueError("execute_shaded_device: one AO, one colour (and one GBuffer0) surface per depth frame")
+        if extents is None and (color_pitches is not None or gbuffer0_pitches is not None):
+            raise ValueError("execute_shaded_device: color_pitches / gbuffer0_pitches go with extents")
         prm = None if params is None else params_array(params, n, self._prm)
         g = (C.c_void_p * n)(*gbuffer0_ptrs) if gbuffer0_ptrs else None
+        if extents is not None:
+            if depth_pitch or out_pitch or color_pitch or gbuffer0_pitch:
+                raise ValueError("execute_shaded_device: with extents the pitches are given per frame (extents, color_pitches, gbuffer0_pitches)")
+            self._check(self._lib.meao_pool_execute_batch_extents_shaded(
+                self._pool, n, (C.c_void_p * n)(*depth_ptrs), (C.c_void_p * n)(*out_ptrs), extents_array(extents, n), prm, mode,
+                (C.c_void_p * n)(*color_ptrs), color_format, _pitch_array(color_pitches, n, "color_pitches"), g,
+                _pitch_array(gbuffer0_pitches, n, "gbuffer0_pitches")))
+            return
         self._check(self._lib.meao_pool_execute_batch_shaded(self._pool, n, (C.c_void_p * n)(*depth_ptrs), depth_pitch,
                                                              (C.c_void_p * n)(*out_ptrs), out_pitch, prm, mode,
                                                              (C.c_void_p * n)(*color_ptrs), color_format, color_pitch, g, gbuffer0_pitch))

@@ -330,6 +330,7 @@ int32_t meao_create(const meao_config *cfg, meao_ctx **out_ctx)
     }
     // the batched composite's frame tables (meao_composite_batch): the same kind of ring
     if (rc == MEAO_OK && (e = ctx->comp_ring.create(cfg->max_batch)) != hipSuccess) rc = fail_hip(ctx, e, "batched composite tables");
+    if (rc == MEAO_OK && (e = ctx->comp_sized_ring.create(cfg->max_batch)) != hipSuccess) rc = fail_hip(ctx, e, "sized composite tables");
     // cfg.pipelined: the second downsample set exists from the start, so meao_prefetch_batch never re-allocates
     if (rc == MEAO_OK) rc = reallocate(ctx, *cfg, cfg->pipelined != 0, 0, 0);
     if (rc != MEAO_OK) {
@@ -358,6 +359,7 @@ int32_t meao_destroy(meao_ctx *ctx)
     if (ctx->hostile) (void)hipFree(ctx->hostile);
     ctx->frame_ring.destroy();
     ctx->comp_ring.destroy();
+    ctx->comp_sized_ring.destroy();
     if (ctx->tracer.lib) (void)dlclose(ctx->tracer.lib);
     for (hipEvent_t ev : ctx->profiler.events) (void)hipEventDestroy(ev);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);

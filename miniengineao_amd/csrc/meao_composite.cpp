@@ -172,6 +172,109 @@ int composite_batch_launch(meao_ctx *ctx, const CompositeTargets &t, CompositePi
     return MEAO_OK;
 }
 
+// composite_pitches / composite_vec_base for one frame of its own size (meao_composite_batch_extents): e's three pitches against
+// e's width and height instead of ctx->cfg, into entry `out` (extent, strides in texels, vec; the origins are the caller's).  `at`
+// names the frame, `names` its three pitches in the errors.  A tightly packed surface is checked as rows of pitch = width: the
+// sized launch addresses it that way.  *packed_span: only that check failed -- the caller refuses unless the call is uniform.
+int composite_frame_pitches(meao_ctx *ctx, const std::string &at, const char *const names[3], const meao_target_extent &e, int32_t color_format,
+                            bool has_gbuffer0, CompositeSizedFrame *out, std::string *packed_span)
+{
+    const uint64_t elem[3] = {ao_elem(ctx->cfg), color_elem(color_format), 4};
+    const uint64_t pitch[3] = {e.ao_pitch, e.color_pitch, has_gbuffer0 ? e.gbuffer0_pitch : 0};
+    int32_t rows[3] = {e.width, e.width, e.width};
+    for (int k = 0; k < (has_gbuffer0 ? 3 : 2); ++k) {
+        if (pitch[k] != 0) {
+            const int rc = pitch_texels_of(ctx, e.width, e.height, pitch[k], elem[k], (at + names[k]).c_str(), &rows[k]);
+            if (rc != MEAO_OK) return rc;
+        } else if (static_cast<uint64_t>(e.width) * e.height * elem[k] > 0xffffffffull && packed_span->empty()) {
+            *packed_span = at + names[k] + ": a frame spans more than 2^32 - 1 bytes (tightly packed frames of a sized launch are rows like any other)";
+        }
+    }
+    out->w = e.width; out->h = e.height;
+    out->ao_stride = static_cast<uint32_t>(rows[0]); out->color_stride = static_cast<uint32_t>(rows[1]); out->gbuffer0_stride = static_cast<uint32_t>(rows[2]);
+    // this frame's own form: colour base and rows whole 16-byte accesses, AO base and rows whole lanes of AO texels
+    const uint32_t lane = color_lane_texels(color_format);
+    out->vec = aligned_to(out->color, 16) && static_cast<uint64_t>(rows[1]) * elem[1] % 16 == 0 &&
+               reinterpret_cast<uintptr_t>(out->ao) % (lane * elem[0]) == 0 && static_cast<uint32_t>(rows[0]) % lane == 0;
+    return MEAO_OK;
+}
+
+// A uniform call's targets as meao_composite_batch takes them: extents[0]'s pitches for every frame
+CompositeTargets uniform_targets(const CompositeTargets &t)
+{
+    CompositeTargets same = t;
+    same.extents = nullptr;
+    same.ao_pitch = t.extents[0].ao_pitch; same.color_pitch = t.extents[0].color_pitch; same.gbuffer0_pitch = t.extents[0].gbuffer0_pitch;
+    return same;
+}
+
+// The checks of meao_composite_batch_extents under the name `fn` (t.extents set; t's three pitches are not read).  Touches
+// nothing.  On success either *uniform -- every extent is the context's size and all frames share their strides: the call is
+// meao_composite_batch with *pitch -- or entries[0 .. n) are the frames of the sized launch.
+int composite_batch_extents_validate(meao_ctx *ctx, const char *fn, const CompositeTargets &t, CompositeSizedFrame *entries, bool *uniform,
+                                     CompositePitches *pitch)
+{
+    if (!ctx || !t.ao || !t.color || !t.extents) return MEAO_ERR_INVALID_ARGUMENT;
+    const std::string name(fn);
+    if (t.n < 1 || t.n > ctx->cfg.max_batch) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, name + ": n must be 1..max_batch");
+    if (t.mode < MEAO_COMPOSITE_MULTIPLY || t.mode > MEAO_COMPOSITE_DEBUG) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, name + ": unknown mode");
+    if (t.mode == MEAO_COMPOSITE_AMBIENT_ONLY && !t.gbuffer0)
+        return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, name + ": gbuffer0_rgba8: AMBIENT_ONLY needs the GBuffer0 targets");
+    for (int f = 0; f < t.n; ++f)
+        if (!t.ao[f] || !t.color[f] || (t.mode == MEAO_COMPOSITE_AMBIENT_ONLY && !t.gbuffer0[f]))
+            return fail(ctx, MEAO_ERR_INVALID_ARGUMENT,
+                        name + ": frame " + std::to_string(f) + ": " + (!t.ao[f] ? "ao" : !t.color[f] ? "color" : "gbuffer0_rgba8") + ": null frame pointer");
+    if (color_elem(t.color_format) == 0) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, name + ": color_format: not a meao_color_format");
+    static const char *const in_extent[3] = {".ao_pitch", ".color_pitch", ".gbuffer0_pitch"};
+    std::string packed_span;
+    *uniform = true;
+    for (int f = 0; f < t.n; ++f) {
+        const meao_target_extent &e = t.extents[f];
+        const std::string idx = "[" + std::to_string(f) + "]", at = name + ": extents" + idx;
+        if (!size_valid(e.width, e.height)) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, at + ".width/height out of range [1, 32768]");
+        entries[f] = CompositeSizedFrame{};
+        entries[f].ao = t.ao[f]; entries[f].color = t.color[f]; entries[f].gbuffer0 = t.gbuffer0 ? t.gbuffer0[f] : nullptr;
+        // (the shaded call's colour and GBuffer0 pitches are arguments of their own: color_pitch[f], gbuffer0_pitch[f])
+        const std::string color_name = name + ": color_pitch" + idx, g_name = name + ": gbuffer0_pitch" + idx;
+        int rc;
+        if (t.from_arrays) {
+            const std::string ao_name = at + ".ao_pitch";
+            const char *const names[3] = {ao_name.c_str(), color_name.c_str(), g_name.c_str()};
+            rc = composite_frame_pitches(ctx, std::string(), names, e, t.color_format, t.gbuffer0 != nullptr, &entries[f], &packed_span);
+        } else {
+            rc = composite_frame_pitches(ctx, at, in_extent, e, t.color_format, t.gbuffer0 != nullptr, &entries[f], &packed_span);
+        }
+        if (rc != MEAO_OK) return rc;
+        const CompositeSizedFrame &s = entries[f], &s0 = entries[0];
+        *uniform = *uniform && e.width == ctx->cfg.width && e.height == ctx->cfg.height && s.ao_stride == s0.ao_stride &&
+                   s.color_stride == s0.color_stride && (!t.gbuffer0 || s.gbuffer0_stride == s0.gbuffer0_stride);
+    }
+    if (*uniform) return composite_batch_validate(ctx, fn, uniform_targets(t), pitch);      // by its own rules: a packed frame there is not rows
+    if (!packed_span.empty()) return fail(ctx, MEAO_ERR_UNSUPPORTED, packed_span);
+    return MEAO_OK;
+}
+
+// The sized batched composite: the validated frames entries[0 .. n) in ONE composite_kernel launch on `stream`, through a slot
+// of the context's sized table ring (the lease, arm and copy-then-launch discipline of composite_batch_launch).
+int composite_batch_extents_launch(meao_ctx *ctx, const CompositeTargets &t, const CompositeSizedFrame *entries, hipStream_t stream)
+{
+    TableRing<CompositeSizedFrame, 8>::Lease lease;
+    const int rc = ctx->comp_sized_ring.acquire(ctx, stream, &lease);
+    if (rc != MEAO_OK) return rc;
+    CompositeSizedFrame *stage = lease.host();
+    for (int f = 0; f < t.n; ++f) stage[f] = entries[f];
+    const int blocks = composite_sized_plan(stage, t.n, t.color_format);     // each frame's lanes per row; the largest frame's workgroups
+    CompositeArgs ca{};
+    ca.mode = t.mode;
+    ca.color_format = t.color_format;
+    ca.sized = lease.device();
+    lease.arm();       // the slot is handed back guarded whatever happens from here: the copy may be in flight
+    hipError_t e = hipMemcpyAsync(lease.device(), stage, sizeof(CompositeSizedFrame) * t.n, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = launch_composite_sized(ca, ctx->cfg.ao_format, stream, t.n, blocks);
+    if (e != hipSuccess) return fail_hip(ctx, e, "composite_batch_extents_launch");
+    return MEAO_OK;
+}
+
 }  // namespace
 
 int meao::flush_pending_composite(meao_ctx *ctx, hipStream_t stream)
@@ -234,6 +337,29 @@ int meao::execute_batch_shaded_internal(meao_ctx *ctx, const char *fn, const Fra
     if (rc != MEAO_OK) return rc;
     // behind the last AO kernel on the same stream (ctx->last.stream is the one the execute just ran on)
     return composite_batch_launch(ctx, t, pitch, ctx->last.stream);
+}
+
+int meao::execute_batch_extents_shaded_internal(meao_ctx *ctx, const char *fn, const FrameSet &fs, const CompositeTargets &targets, meao_stream stream_,
+                                                bool validate_only)
+{
+    if (!ctx || !fs.depth || !fs.out || !fs.extents || !targets.color || !targets.extents) return MEAO_ERR_INVALID_ARGUMENT;
+    // both halves' checks before anything is enqueued: a refused call launches nothing
+    int32_t depth_rows[MEAO_MAX_BATCH], out_rows[MEAO_MAX_BATCH];
+    bool uniform_execute = false;
+    int rc = validate_execute_batch_extents(ctx, fs, depth_rows, out_rows, &uniform_execute);
+    if (rc != MEAO_OK) return fail(ctx, rc, std::string(fn) + ": " + ctx->err);      // the execute half's message, under this call's name
+    CompositeTargets t = targets;      // the composite reads what the execute writes
+    t.n = fs.n; t.ao = fs.out;
+    CompositeSizedFrame entries[MEAO_MAX_BATCH];
+    CompositePitches pitch{};
+    bool uniform = false;              // each half classifies itself
+    rc = composite_batch_extents_validate(ctx, fn, t, entries, &uniform, &pitch);
+    if (rc != MEAO_OK || validate_only) return rc;
+    rc = execute_batch_internal(ctx, fs, stream_, false);
+    if (rc != MEAO_OK) return rc;
+    // behind the last AO kernel on the same stream (ctx->last.stream is the one the execute just ran on)
+    if (uniform) return composite_batch_launch(ctx, uniform_targets(t), pitch, ctx->last.stream);
+    return composite_batch_extents_launch(ctx, t, entries, ctx->last.stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -318,6 +444,43 @@ int32_t meao_execute_batch_shaded(meao_ctx *ctx, int32_t n, const void *const *d
     return execute_batch_shaded_internal(ctx, "meao_execute_batch_shaded",
                                          FrameSet{n, depth, depth_pitch, MEAO_MEM_DEVICE, ao_out, ao_pitch, MEAO_MEM_DEVICE, params},
                                          CompositeTargets{mode, n, nullptr, 0, color, color_format, color_pitch, gbuffer0_rgba8, gbuffer0_pitch}, stream_, false);
+}
+
+int32_t meao_composite_batch_extents(meao_ctx *ctx, int32_t mode, int32_t n, const void *const *ao, void *const *color, int32_t color_format,
+                                     void *const *gbuffer0_rgba8, const meao_target_extent *extents, meao_stream stream_)
+{
+    static const char fn[] = "meao_composite_batch_extents";
+    if (!ctx) return MEAO_ERR_INVALID_ARGUMENT;
+    if (!ao || !color || !extents) return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": ao, color or extents is null");
+    CompositeTargets t{mode, n, ao, 0, color, color_format, 0, gbuffer0_rgba8, 0};
+    t.extents = extents;
+    CompositeSizedFrame entries[MEAO_MAX_BATCH];
+    CompositePitches pitch{};
+    bool uniform = false;
+    int rc = composite_batch_extents_validate(ctx, fn, t, entries, &uniform, &pitch);
+    if (rc != MEAO_OK) return rc;
+    rc = use_device(ctx);
+    if (rc != MEAO_OK) return rc;
+    hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->own_stream;
+    if (uniform) return composite_batch_launch(ctx, uniform_targets(t), pitch, stream);
+    return composite_batch_extents_launch(ctx, t, entries, stream);
+}
+
+int32_t meao_execute_batch_extents_shaded(meao_ctx *ctx, int32_t n, const void *const *depth, void *const *ao_out, const meao_extent *extents,
+                                          const meao_params *params, int32_t mode, void *const *color, int32_t color_format,
+                                          const uint64_t *color_pitch, void *const *gbuffer0_rgba8, const uint64_t *gbuffer0_pitch, meao_stream stream_)
+{
+    static const char fn[] = "meao_execute_batch_extents_shaded";
+    if (!ctx) return MEAO_ERR_INVALID_ARGUMENT;
+    if (!depth || !ao_out || !extents || !color)
+        return fail(ctx, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": depth, ao_out, extents or color is null");
+    FrameSet fs{n, depth, 0, MEAO_MEM_DEVICE, ao_out, 0, MEAO_MEM_DEVICE, params};
+    fs.extents = extents;
+    meao_target_extent target[MEAO_MAX_BATCH];      // (an n out of range is refused before any entry is read)
+    for (int32_t f = 0; f < n && f < MEAO_MAX_BATCH; ++f) target[f] = target_extent_of(extents[f], color_pitch, gbuffer0_pitch, f);
+    CompositeTargets t{mode, n, nullptr, 0, color, color_format, 0, gbuffer0_rgba8, 0};
+    t.extents = target; t.from_arrays = true;
+    return execute_batch_extents_shaded_internal(ctx, fn, fs, t, stream_, false);
 }
 
 }  // extern "C"

@@ -379,6 +379,9 @@ struct meao_ctx {
     // (meao_composite_batch / meao_execute_batch_shaded) go through a ring of the same kind.  Both allocated by meao_create.
     meao::TableRing<meao::FrameArgs, 8> frame_ring;
     meao::TableRing<meao::CompositeFrame, 8> comp_ring;
+    // ... and the sized composite's 64-byte CompositeSizedFrame tables (meao_composite_batch_extents /
+    // meao_execute_batch_extents_shaded) through one of their own, so that the uniform batch's entries stay 24 bytes
+    meao::TableRing<meao::CompositeSizedFrame, 8> comp_sized_ring;
     std::vector<meao::Plan> frame_plan;          // MEAO_MAX_BATCH
 
     // a composite batch waiting to ride inside the next execute's render kernel (meao_composite_enqueue),
@@ -440,8 +443,13 @@ struct CompositeTargets {
     const void *const *ao; uint64_t ao_pitch;
     void *const *color; int32_t color_format; uint64_t color_pitch;
     void *const *gbuffer0; uint64_t gbuffer0_pitch;
+    // meao_composite_batch_extents / meao_execute_batch_extents_shaded: frame f's own size and pitches (the three pitches above
+    // are then unused); null = every frame has the context's size.  from_arrays: the shaded call made them from its extents[],
+    // color_pitch[] and gbuffer0_pitch[], which is how its errors name them.
+    const meao_target_extent *extents = nullptr;
+    bool from_arrays = false;
 
-    struct Storage { const void *ao[MEAO_MAX_BATCH]; void *color[MEAO_MAX_BATCH]; void *gbuffer0[MEAO_MAX_BATCH]; };
+    struct Storage { const void *ao[MEAO_MAX_BATCH]; void *color[MEAO_MAX_BATCH]; void *gbuffer0[MEAO_MAX_BATCH]; meao_target_extent ext[MEAO_MAX_BATCH]; };
     CompositeTargets share(int32_t m, int32_t G, Storage *s) const
     {
         CompositeTargets mine = *this;
@@ -450,8 +458,10 @@ struct CompositeTargets {
             if (ao) s->ao[k] = ao[f];
             s->color[k] = color[f];
             if (gbuffer0) s->gbuffer0[k] = gbuffer0[f];
+            if (extents) s->ext[k] = extents[f];
         }
         mine.n = k; mine.ao = ao ? s->ao : nullptr; mine.color = s->color; mine.gbuffer0 = gbuffer0 ? s->gbuffer0 : nullptr;
+        mine.extents = extents ? s->ext : nullptr;
         return mine;
     }
 };
@@ -500,5 +510,14 @@ int composite_enqueue_internal(meao_ctx *ctx, const char *fn, const CompositeTar
 // = every check of both halves and nothing else (no device is touched; AO, colour, an announcement and a waiting batch stay).
 int execute_batch_shaded_internal(meao_ctx *ctx, const char *fn, const FrameSet &fs, const CompositeTargets &t, meao_stream stream,
                                   bool validate_only);
+// For meao_pool.cpp too: meao_execute_batch_extents_shaded under the name `fn`: fs.extents and t.extents set (t.extents[f]'s width,
+// height and ao_pitch are fs.extents[f]'s; t.ao / n are taken from fs.out); validate_only as above.
+int execute_batch_extents_shaded_internal(meao_ctx *ctx, const char *fn, const FrameSet &fs, const CompositeTargets &t, meao_stream stream,
+                                          bool validate_only);
+// Frame f's meao_target_extent of a shaded mixed call, from its three per-frame arguments (pitch arrays null = tightly packed).
+inline meao_target_extent target_extent_of(const meao_extent &e, const uint64_t *color_pitch, const uint64_t *gbuffer0_pitch, int32_t f)
+{
+    return meao_target_extent{e.width, e.height, e.ao_pitch, color_pitch ? color_pitch[f] : 0, gbuffer0_pitch ? gbuffer0_pitch[f] : 0};
+}
 
 }  // namespace meao

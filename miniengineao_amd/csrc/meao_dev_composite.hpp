@@ -291,6 +291,37 @@ __device__ __forceinline__ void composite_format_row(const void *ao_base, void *
         composite_format_texel<AOFMT, CFMT>(ao_base, color_base, gbuffer0_base, ao_at, color_at, g_at, mode, x);
 }
 
+// Entry `frame` of the sized form's table (meao_composite_batch_extents).  Read through the constant address space, as
+// composite_frame below reads the batched form's: 64-byte entries written by a copy ordered before the launch and never during
+// it, so every field of a frame -- its extent, strides, lanes per row and form too -- is workgroup-uniform and sits in scalar registers.
+__device__ __forceinline__ const CompositeSizedFrame &composite_sized_frame(const CompositeSizedFrame *table, uint32_t frame)
+{
+    typedef const __attribute__((address_space(4))) char *const_bytes;
+    const const_bytes p = (const_bytes)table + static_cast<uint32_t>(sizeof(CompositeSizedFrame)) * frame;
+    return *(const CompositeSizedFrame *)p;
+}
+
+// What the row forms deal: the launch's own surfaces, pitches and lanes per row, or -- kernel-uniform, the sized form -- those of
+// frame blockIdx.y from its table entry.  Read behind the packed paths, which therefore do what they did.
+struct CompositeRowFrame {
+    const void *ao;
+    void *color, *gbuffer0;
+    CompositePitches p;
+    uint32_t row_lanes_log2;
+};
+__device__ __forceinline__ CompositeRowFrame composite_row_frame(const CompositeArgs &a, const void *ao, void *color, void *gbuffer0)
+{
+    CompositeRowFrame r{ao, color, gbuffer0, a.pitch, static_cast<uint32_t>(a.row_lanes_log2)};
+    if (a.sized != nullptr) {
+        const CompositeSizedFrame &t = composite_sized_frame(a.sized, blockIdx.y);
+        r.ao = t.ao; r.color = t.color; r.gbuffer0 = t.gbuffer0;
+        r.p.ao = t.ao_stride; r.p.color = t.color_stride; r.p.gbuffer0 = t.gbuffer0_stride;
+        r.p.w = t.w; r.p.h = t.h; r.p.vec = t.vec;
+        r.row_lanes_log2 = static_cast<uint32_t>(t.row_lanes_log2);
+    }
+    return r;
+}
+
 // A frame in colour format CFMT: tightly packed = one row of `pixels` texels for the frame's workgroups, else rows as in the RGBA16F form.
 template <int AOFMT, int CFMT>
 __device__ __forceinline__ void composite_format_frame(const CompositeArgs &a, const void *ao, void *color, void *gbuffer0)
@@ -300,10 +331,11 @@ __device__ __forceinline__ void composite_format_frame(const CompositeArgs &a, c
                                           blockIdx.x * kThreads + threadIdx.x, gridDim.x * kThreads);
         return;
     }
-    const uint32_t lanes = 1u << a.row_lanes_log2, rows = static_cast<uint32_t>(kThreads) >> a.row_lanes_log2;
-    for (uint32_t row = blockIdx.x * rows + (threadIdx.x >> a.row_lanes_log2); row < static_cast<uint32_t>(a.pitch.h); row += gridDim.x * rows)
-        composite_format_row<AOFMT, CFMT>(ao, color, gbuffer0, __umul24(row, a.pitch.ao), __umul24(row, a.pitch.color),
-                                          __umul24(row, a.pitch.gbuffer0), static_cast<uint32_t>(a.pitch.w), a.pitch.vec != 0, a.mode,
+    const CompositeRowFrame r = composite_row_frame(a, ao, color, gbuffer0);
+    const uint32_t lanes = 1u << r.row_lanes_log2, rows = static_cast<uint32_t>(kThreads) >> r.row_lanes_log2;
+    for (uint32_t row = blockIdx.x * rows + (threadIdx.x >> r.row_lanes_log2); row < static_cast<uint32_t>(r.p.h); row += gridDim.x * rows)
+        composite_format_row<AOFMT, CFMT>(r.ao, r.color, r.gbuffer0, __umul24(row, r.p.ao), __umul24(row, r.p.color),
+                                          __umul24(row, r.p.gbuffer0), static_cast<uint32_t>(r.p.w), r.p.vec != 0, a.mode,
                                           threadIdx.x & (lanes - 1u), lanes);
 }
 

@@ -124,7 +124,8 @@ template <int AOFMT>
 __global__ __launch_bounds__(kThreads) void composite_kernel(const CompositeArgs a)
 {
     // The frame is the grid's y: a batched launch (meao_composite_batch) takes frame blockIdx.y's origins from the table, a
-    // single-frame launch (one y, no table) its own from the kernarg.  Within a frame the x workgroups deal it as ever.
+    // single-frame launch (one y, no table) its own from the kernarg.  Within a frame the x workgroups deal it as ever.  (The
+    // sized form's table is read where the row forms begin, behind the packed paths: composite_row_frame.)
     const void *ao = a.ao;
     void *color = a.color, *gbuffer0 = a.gbuffer0;
     if (a.frames != nullptr) {
@@ -145,10 +146,13 @@ __global__ __launch_bounds__(kThreads) void composite_kernel(const CompositeArgs
         else composite_format_frame<AOFMT, MEAO_COLOR_R11G11B10F>(a, ao, color, gbuffer0);
         return;
     }
-    // kernel-uniform: row-pitched surfaces, rows dealt to (2^row_lanes_log2 lanes x rows) workgroups
-    const uint32_t lanes = 1u << a.row_lanes_log2, rows = static_cast<uint32_t>(kThreads) >> a.row_lanes_log2;
-    for (uint32_t row = blockIdx.x * rows + (threadIdx.x >> a.row_lanes_log2); row < static_cast<uint32_t>(a.pitch.h); row += gridDim.x * rows)
-        composite_row<AOFMT>(ao, color, gbuffer0, a.pitch, a.mode, row, threadIdx.x & (lanes - 1u), lanes);
+    // kernel-uniform: row-pitched surfaces, rows dealt to (2^row_lanes_log2 lanes x rows) workgroups -- the launch's pitches, or (the
+    // sized form, meao_composite_batch_extents) frame blockIdx.y's own extent, strides, lanes per row and form from its table
+    // entry; a workgroup beyond a smaller frame's rows falls through the row loop
+    const CompositeRowFrame r = composite_row_frame(a, ao, color, gbuffer0);
+    const uint32_t lanes = 1u << r.row_lanes_log2, rows = static_cast<uint32_t>(kThreads) >> r.row_lanes_log2;
+    for (uint32_t row = blockIdx.x * rows + (threadIdx.x >> r.row_lanes_log2); row < static_cast<uint32_t>(r.p.h); row += gridDim.x * rows)
+        composite_row<AOFMT>(r.ao, r.color, r.gbuffer0, r.p, a.mode, row, threadIdx.x & (lanes - 1u), lanes);
 }
 
 // which = 4: rcp_strict, 5: div_const<3>, div_const<9>, 6: div_strict on hashed operand pairs, 8: f32_to_ufloat<6|5> (the R11G11B10F stores)
@@ -276,21 +280,57 @@ hipError_t launch_debug_view(const DebugViewArgs &a, int ao_format, hipStream_t 
     return hipGetLastError();
 }
 
+namespace {
+
+// what one lane takes at a time: a texel pair (RGBA16F), a 16-byte group of 1 or 4 texels (the other formats' vector form), a texel
+int composite_per_lane(int32_t color_format, bool vec)
+{
+    return color_format == MEAO_COLOR_RGBA16F ? 2 : !vec || color_format == MEAO_COLOR_RGBA32F ? 1 : 4;
+}
+
+// The row form for rows of w texels: the narrowest power of two of lanes that spans a row's pairs (at most the workgroup), rows
+// beside each other; returns the workgroups h rows get.
+int composite_row_blocks(int32_t w, int32_t h, int per_lane, int32_t *row_lanes_log2)
+{
+    const int row_pairs = (w + per_lane - 1) / per_lane;
+    int log2 = 0;
+    while ((1 << log2) < row_pairs && (1 << log2) < kThreads) ++log2;
+    *row_lanes_log2 = log2;
+    const int rows = kThreads >> log2;
+    return std::min((h + rows - 1) / rows, 256 * 32);
+}
+
+}  // namespace
+
 hipError_t launch_composite(const CompositeArgs &args, int ao_format, hipStream_t s, int frames)
 {
     CompositeArgs a = args;
-    // what one lane takes at a time: a texel pair (RGBA16F), a 16-byte group of 1 or 4 texels (the other formats' vector form), a texel
-    const int64_t per_lane = a.color_format == MEAO_COLOR_RGBA16F ? 2 : !a.pitch.vec || a.color_format == MEAO_COLOR_RGBA32F ? 1 : 4;
+    const int64_t per_lane = composite_per_lane(a.color_format, a.pitch.vec != 0);
     const int64_t pairs = (a.pixels + per_lane - 1) / per_lane;
     int blocks = static_cast<int>(std::min<int64_t>((pairs + kThreads - 1) / kThreads, 256 * 32));
-    if (a.pitch.on) {       // the narrowest power of two of lanes that spans a row's pairs (at most the workgroup), rows beside each other
-        const int row_pairs = static_cast<int>((a.pitch.w + per_lane - 1) / per_lane);
-        a.row_lanes_log2 = 0;
-        while ((1 << a.row_lanes_log2) < row_pairs && (1 << a.row_lanes_log2) < kThreads) ++a.row_lanes_log2;
-        const int rows = kThreads >> a.row_lanes_log2;
-        blocks = std::min((a.pitch.h + rows - 1) / rows, 256 * 32);
-    }
+    if (a.pitch.on) blocks = composite_row_blocks(a.pitch.w, a.pitch.h, static_cast<int>(per_lane), &a.row_lanes_log2);
     // every frame of a batched launch gets the workgroups a launch of its own would: grid y = the frame
+    if (ao_format == MEAO_AO_R8) composite_kernel<MEAO_AO_R8><<<dim3(blocks, frames), dim3(kThreads), 0, s>>>(a);
+    else composite_kernel<MEAO_AO_F16><<<dim3(blocks, frames), dim3(kThreads), 0, s>>>(a);
+    return hipGetLastError();
+}
+
+int composite_sized_plan(CompositeSizedFrame *stage, int frames, int32_t color_format)
+{
+    int blocks = 1;
+    for (int f = 0; f < frames; ++f)      // each frame by its own width, height and form
+        blocks = std::max(blocks, composite_row_blocks(stage[f].w, stage[f].h, composite_per_lane(color_format, stage[f].vec != 0),
+                                                       &stage[f].row_lanes_log2));
+    return blocks;
+}
+
+hipError_t launch_composite_sized(const CompositeArgs &args, int ao_format, hipStream_t s, int frames, int blocks)
+{
+    CompositeArgs a = args;
+    a.ao = nullptr; a.color = nullptr; a.gbuffer0 = nullptr; a.frames = nullptr;
+    a.pitch = CompositePitches{};
+    a.pitch.on = 1;         // never the packed RGBA16F fall-through at the kernel's entry
+    // x: the largest frame's workgroups -- the row loops are grid-stride, a workgroup beyond a smaller frame's rows touches nothing
     if (ao_format == MEAO_AO_R8) composite_kernel<MEAO_AO_R8><<<dim3(blocks, frames), dim3(kThreads), 0, s>>>(a);
     else composite_kernel<MEAO_AO_F16><<<dim3(blocks, frames), dim3(kThreads), 0, s>>>(a);
     return hipGetLastError();

@@ -221,6 +221,19 @@ struct CompositeFrame {
     void *color;
     void *gbuffer0;
 };
+// One entry of the sized form's table (meao_composite_batch_extents): a frame's origins, its own extent, row strides in texels
+// of their surfaces, the lanes a workgroup puts along one of its rows and whether ITS bases and strides take the vector form.
+// Padded to 64 bytes, a power of two, so that an entry is read with aligned scalar loads.
+struct CompositeSizedFrame {
+    const void *ao;
+    void *color;
+    void *gbuffer0;
+    int32_t w, h;
+    uint32_t ao_stride, color_stride, gbuffer0_stride;
+    int32_t row_lanes_log2, vec;
+    int32_t pad[3];
+};
+static_assert(sizeof(CompositeSizedFrame) == 64, "the sized composite table is read with aligned scalar loads");
 struct CompositeArgs {
     const void *ao;
     void *color;
@@ -234,9 +247,20 @@ struct CompositeArgs {
     // ordered before the launch; ao / color / gbuffer0 above are then unused.  nullptr = the single-frame launch, which reads
     // nothing more than it did (one more kernarg pointer, tested once per workgroup).
     const CompositeFrame *frames;
+    // The sized form (meao_composite_batch_extents), selected by this being set: frame blockIdx.y's origins, extent, strides,
+    // lanes per row and form from entry blockIdx.y of this table (written like `frames`, which is then null, as are ao / color /
+    // gbuffer0); pitch.on is set, so that no packed path is taken, pixels, the rest of pitch and row_lanes_log2 are unused, and every
+    // frame takes the row form.  nullptr = every other launch.
+    const CompositeSizedFrame *sized;
 };
 // frames: the launch's frames, a.frames[0 .. frames) (a.frames null: the single-frame launch, frames = 1).
 hipError_t launch_composite(const CompositeArgs &a, int ao_format, hipStream_t s, int frames = 1);
+// The sized form's launch rule, in two steps around the table's copy.  composite_sized_plan: stage[0 .. frames) are the entries
+// about to be copied to the device (origins, extents, strides and vec set by the caller); fills each entry's row_lanes_log2 as
+// that frame's own single-frame pitched launch would choose it and returns the grid's x: the most workgroups any of those
+// launches would get.  launch_composite_sized: the launch behind the copy, a.sized = the device table, grid (blocks, frames).
+int composite_sized_plan(CompositeSizedFrame *stage, int frames, int32_t color_format);
+hipError_t launch_composite_sized(const CompositeArgs &a, int ao_format, hipStream_t s, int frames, int blocks);
 // A batch of composites carried by a render launch (meao_composite_enqueue): frame f = ao[f] x color[f].
 struct CompositeBatchArgs {
     const void *ao[MEAO_MAX_BATCH];

@@ -596,6 +596,42 @@ int32_t meao_pool_execute_batch_shaded(meao_pool *p, int32_t n, const void *cons
     return status;
 }
 
+// The job shape of meao_pool_execute_batch_shaded with one size and one set of pitches per frame: they are dealt with the frames.
+int32_t meao_pool_execute_batch_extents_shaded(meao_pool *p, int32_t n, const void *const *depth, void *const *ao_out, const meao_extent *extents,
+                                               const meao_params *params, int32_t mode, void *const *color, int32_t color_format,
+                                               const uint64_t *color_pitch, void *const *gbuffer0_rgba8, const uint64_t *gbuffer0_pitch)
+{
+    static const char fn[] = "meao_pool_execute_batch_extents_shaded";
+    if (!p || !depth || !ao_out || !extents || !color) return MEAO_ERR_INVALID_ARGUMENT;
+    const int32_t G = static_cast<int32_t>(p->ctx.size());
+    if (n < 1 || n > p->max_batch * G) return pool_fail(p, MEAO_ERR_INVALID_ARGUMENT, std::string(fn) + ": n must be 1..max_batch * members");
+    int32_t status = pool_check_call(p, fn, n, params);
+    if (status != MEAO_OK) return status;
+    meao::FrameSet fs{n, depth, 0, MEAO_MEM_DEVICE, ao_out, 0, MEAO_MEM_DEVICE, params};
+    fs.extents = extents;
+    std::vector<meao_target_extent> target(n);
+    for (int32_t f = 0; f < n; ++f) target[f] = meao::target_extent_of(extents[f], color_pitch, gbuffer0_pitch, f);
+    meao::CompositeTargets targets{mode, n, nullptr, 0, color, color_format, 0, gbuffer0_rgba8, 0};
+    targets.extents = target.data(); targets.from_arrays = true;
+    DeviceGuard guard;
+    int32_t failed = -1;
+    for (int pass = 0; pass < 2 && status == MEAO_OK; ++pass) {
+        status = for_each_member(p, [&](int32_t m) -> int32_t {
+            meao::FrameSet::Storage frames;
+            meao::CompositeTargets::Storage surfaces;
+            const meao::FrameSet share = fs.share(m, G, &frames);
+            if (share.n == 0) return MEAO_OK;
+            return meao::execute_batch_extents_shaded_internal(p->ctx[m], fn, share, targets.share(m, G, &surfaces), p->stream[m], pass == 0);
+        }, pass == 1, &failed);
+        if (status != MEAO_OK)
+            return pool_fail(p, status, std::string(fn) + ": member " + std::to_string(failed) + " (frame k of its share is frame " +
+                                            std::to_string(failed) + " + k x " + std::to_string(G) + "): " + meao_last_error(p->ctx[failed]));
+    }
+    // members that were dealt no frame: as in meao_pool_execute_batch_extents
+    for (int32_t m = n; m < G; ++m) meao::drop_announcement(p->ctx[m], true);
+    return status;
+}
+
 // pitched: the pitches go to every member and every member's share is validated before any member enqueues.
 static int32_t pool_composite_enqueue(meao_pool *p, const char *fn, bool pitched, const meao::CompositeTargets &t)
 {

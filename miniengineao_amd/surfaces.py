@@ -117,6 +117,31 @@ def composite_surfaces(ao, color, gbuffer0, height: int, width: int, ao_dtype, d
     return a_ptrs, packed_pitch(a_pitch, width, ao_elem), c_ptrs, packed_pitch(c_pitch, width, color_elem), g_ptrs, g_pitch
 
 
+def composite_surfaces_per_frame(ao, color, gbuffer0, ao_dtype, device=None, color_format: int = 0):
+    """``composite_surfaces`` for lists of differently shaped frames (meao_composite_batch_extents): frame f is ao[f] of shape
+    (H_f, W_f), color[f] and, if given, gbuffer0[f] of that size, and each tensor's own row stride becomes its pitch.
+    -> (ao_ptrs, color_ptrs, gbuffer0_ptrs | None, [(W_f, H_f, ao_pitch, color_pitch, gbuffer0_pitch)])."""
+    ao, color = list(ao), list(color)
+    gbuffer0 = None if gbuffer0 is None else list(gbuffer0)
+    if len(color) != len(ao):
+        raise ValueError(f"color has {len(color)} frames, ao {len(ao)}")
+    if gbuffer0 is not None and len(gbuffer0) != len(ao):
+        raise ValueError(f"gbuffer0 has {len(gbuffer0)} frames, ao {len(ao)}")
+    a_ptrs, c_ptrs, g_ptrs, extents = [], [], None if gbuffer0 is None else [], []
+    for f, a in enumerate(ao):
+        if a.dim() != 2:
+            raise ValueError(f"ao[{f}]: expected an (H, W) tensor, got shape {tuple(a.shape)}")
+        h, w = a.shape
+        (ap,), a_pitch, (cp,), c_pitch, g, g_pitch = composite_surfaces([a], [color[f]], None if gbuffer0 is None else [gbuffer0[f]],
+                                                                        h, w, ao_dtype, device=device, color_format=color_format)
+        a_ptrs.append(ap)
+        c_ptrs.append(cp)
+        if g_ptrs is not None:
+            g_ptrs.append(g[0])
+        extents.append((w, h, a_pitch, c_pitch, g_pitch))
+    return a_ptrs, c_ptrs, g_ptrs, extents
+
+
 def packed_pitch(pitch: int, width: int, element_size: int) -> int:
     """The pitch the C ABI is given: 0 where the rows are tightly packed (the same kernels either way)."""
     return 0 if pitch == width * element_size else pitch
