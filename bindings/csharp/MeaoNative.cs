@@ -24,7 +24,7 @@ namespace MiniEngineAO.Native
     public enum MeaoDepthFormat { F32 = 0, Unorm16 = 1, Unorm24 = 2, F16 = 3, LinearF32 = 4, LinearF16 = 5 }   // Linear*: view-space z (meao.h)
     public enum MeaoCompositeMode { Multiply = 0, AmbientOnly = 1, Debug = 2 }
     // meao_color_format: ARGBHalf / ARGBFloat / ARGB32 (BGRA32 alike) / RGB111110Float camera targets
-    public enum MeaoColorFormat { Rgba16F = 0, Rgba32F = 1, Rgba8 = 2, R11G11B10F = 3 }
+    public enum MeaoColorFormat { Rgba16F = 0, Rgba32F = 1, Rgba8 = 2, R11G11B10F = 3, Rgba8Srgb = 5 }
     public enum MeaoFormat { F32 = 0, F16 = 1, Unorm8 = 2 }
     public enum MeaoSampleSet { Checker = 0, Exhaustive = 1 }
     public enum MeaoPoolOption { SpinUs = 0, BindNuma = 1 }

@@ -495,19 +495,28 @@ MEAO_API int32_t meao_composite_enqueue_pitched(meao_ctx *ctx, int32_t mode, int
 
 /* The composite into colour targets of other formats.  The reference blends into the camera target whatever its format
  * (AO.cs:822-839): ARGB32 on a camera without HDR, RGB111110Float where the graphics tier selects the packed HDR format, ARGBHalf
- * otherwise; torch pipelines hold float32 images. */
+ * otherwise; torch pipelines hold float32 images.  In a project in linear colour space (the reference's own setting,
+ * ProjectSettings.asset: m_ActiveColorSpace 1) the ARGB32 target of a camera without HDR is an sRGB surface: MEAO_COLOR_RGBA8_SRGB. */
 typedef enum meao_color_format {
     MEAO_COLOR_RGBA16F = 0,     /* 8 bytes per texel; what meao_composite* take today */
     MEAO_COLOR_RGBA32F = 1,     /* 16 bytes per texel */
     MEAO_COLOR_RGBA8 = 2,       /* 4 bytes per texel, UNORM, alpha in the top byte: RGBA8 and BGRA8 alike (every mode treats
                                    r, g, b the same) */
-    MEAO_COLOR_R11G11B10F = 3   /* 4 bytes per texel: R bits 0-10, G 11-21, B 22-31 (DXGI R11G11B10_FLOAT,
+    MEAO_COLOR_R11G11B10F = 3,  /* 4 bytes per texel: R bits 0-10, G 11-21, B 22-31 (DXGI R11G11B10_FLOAT,
                                    VK B10G11R11_UFLOAT_PACK32, Unity RGB111110Float); no alpha */
+    /* 4 is not assigned and never will be: it stays "not a meao_color_format" */
+    MEAO_COLOR_RGBA8_SRGB = 5   /* 4 bytes per texel: r, g, b sRGB-encoded UNORM8 in the low three bytes, blended in linear light;
+                                   alpha linear UNORM8 in the top byte.  RGBA8_SRGB and BGRA8_SRGB alike.  Libraries older than
+                                   the format refuse the value with MEAO_ERR_INVALID_ARGUMENT, which is how a host probes for
+                                   support (no ABI version change, no new entry point) */
 } meao_color_format;
 /* meao_composite_pitched / meao_composite_enqueue_pitched (and, below, meao_pool_composite_enqueue_pitched) with the format of
  * `color` as an argument; pitch 0 = tightly packed.  With MEAO_COLOR_RGBA16F they run exactly the code of the _pitched calls,
- * which are the RGBA16F forms.  (The ABI version is unchanged: hosts probe for these symbols.)  sRGB targets are out of scope:
- * blending in linear light needs a transfer function, and the reference gives no bit-level definition of one.
+ * which are the RGBA16F forms.  (The ABI version is unchanged: hosts probe for these symbols.)  With MEAO_COLOR_RGBA8,
+ * sRGB targets are out of scope: that format multiplies the stored codes as they are, and on an sRGB surface that differs from
+ * the fixed-function blend in 59 777 of the 65 536 (code, R8 AO) pairs, by up to 73 codes.  An sRGB target is named
+ * MEAO_COLOR_RGBA8_SRGB: blending in linear light needs a transfer function, the reference gives no bit-level definition of one,
+ * and that format's two tables below are one.
  * Canonical reading, as above: operands widened to f32, ONE f32 multiply per channel (f = ao in MULTIPLY, keep = 1 - (1 - ao) in
  * AMBIENT_ONLY), the result rounded to the target format:
  *                MULTIPLY                          AMBIENT_ONLY                       DEBUG
@@ -516,6 +525,8 @@ typedef enum meao_color_format {
  *   RGBA8        c = unorm8(f32(c) * ao)           rgb = unorm8(f32(c) * keep),       rgba = unorm8(ao)
  *                per channel                       a untouched
  *   R11G11B10F   rgb = enc(dec(c) * ao)            rgb = enc(dec(c) * keep)           rgb = enc(ao)
+ *   RGBA8_SRGB   rgb = senc(D[c] * ao),            rgb = senc(D[c] * keep),           rgb = senc(ao), a = unorm8(ao)
+ *                a = unorm8(f32(a) * ao)           a untouched
  * unorm8 / f32 are the conversions of the AO stores and of GBuffer0.a: saturate with NaN -> 0, x 255 and + 0.5 as two roundings,
  * truncate; code / 255 correctly rounded.  GBuffer0 is RGBA8 in every colour format and touched in AMBIENT_ONLY only.
  * R11G11B10F channels are unsigned small floats with a 5-bit exponent of bias 15 and M mantissa bits (6 for R and G, 5 for B).
@@ -525,11 +536,28 @@ typedef enum meao_color_format {
  *                value that rounds past the largest finite code (65024 for M = 6, 64512 for M = 5) becomes +inf.
  * That is the f16 output-merger rule of the RGBA16F stores restated for a format without a sign.  D3D leaves the float11 /
  * float10 rounding to the implementation: like the f16 stores, this is ONE reading of the blend, the one the tests pin.
- * Validation is that of the _pitched forms with colour element sizes of 8 / 16 / 4 / 4 bytes; an unknown color_format is
+ * RGBA8_SRGB: what the fixed-function blend does on an sRGB surface -- decode the destination to linear light, multiply,
+ * re-encode -- with the ideal conversions of the D3D functional spec written as two tables of f32 words, so that every output bit
+ * is defined.  With lin(s) = s / 12.92 for s <= 0.04045 and ((s + 0.055) / 1.055)^2.4 otherwise (IEC 61966-2-1):
+ *   D[k], k = 0..255:  the f32 nearest to the real number lin(k / 255) (D3D's sRGB -> float); D[0] = 0, D[255] = 1.
+ *   T[k], k = 1..255:  the smallest f32 that is >= lin((k - 0.5) / 255).
+ *   senc(x):           the number of k in 1..255 with x >= T[k]: the nearest code in the encoded domain (D3D's "ideal" float ->
+ *                      sRGB, inside the spec's 0.6-ULP allowance), monotone.  NaN of either sign -> 0; anything below T[1] (-0,
+ *                      negatives, -inf) -> 0; anything >= T[255] (values above 1, +inf) -> 255.
+ * Neither table has a near-tie: in 200-bit arithmetic the closest D value is 5.0e-10 (relative) from a rounding boundary and the
+ * closest T boundary 2.8e-11 from an f32, so any arithmetic of 100 bits or more reproduces both.  senc(D[k]) = k for every k: a
+ * factor of exactly 1 leaves every texel untouched.  The words of D[k] for k = 1, 10, 11, 128, 254 are 0x399f22b4, 0x3b46eb61,
+ * 0x3b5b518e, 0x3e5d0a89, 0x3f7db8de; of T[k] for k = 1, 10, 11, 128, 255: 0x391f22b4, 0x3b3cf936, 0x3b50f2d1, 0x3e5b2d9a,
+ * 0x3f7edc0e.  SHA-256 of the 256 little-endian words of D: 48a8f05136456237aae2c5349e5f0199a182daa19b7c099eb542058f794b9c5b; of
+ * the 255 words of T[1..255]: 0b408a80ff623c35aef23dc30ed2669cc9893ecc3227e21394a963f4e5bb51de; of the 256 x 256 uint8 table
+ * senc(D[c] * (a / 255)) indexed [c][a]: c7ccee49d6fa41ef4c5a950ae2d9263efd487244dee3eeef6adbc3091ffb79df.  The library carries
+ * both tables (csrc/meao_srgb_tables.inc, written by tools/gen_srgb_tables.py); meao_selftest(ctx, 9) checks its conversions
+ * against them.  Alpha is linear and moves as in RGBA8; every check, pitch rule and vector-eligibility rule is RGBA8's.
+ * Validation is that of the _pitched forms with colour element sizes of 8 / 16 / 4 / 4 / 4 bytes; an unknown color_format is
  * MEAO_ERR_INVALID_ARGUMENT (meao_last_error names the argument), and a tightly packed frame of more than 2^32 - 1 bytes of colour
  * MEAO_ERR_UNSUPPORTED.  Surfaces are aligned to their own words (RGBA32F and R11G11B10F: 4 bytes), no further.
  * Where it runs: inside the kernels that composite RGBA16F (a kernel-uniform branch).  Vector form: 16 bytes of colour per lane
- * (one RGBA32F texel, four RGBA8 / R11G11B10F texels) and their AO in one load, where colour base and pitch are multiples of 16
+ * (one RGBA32F texel, four RGBA8 / R11G11B10F / RGBA8_SRGB texels) and their AO in one load, where colour base and pitch are multiples of 16
  * bytes and AO base and pitch multiples of the AO texels a lane takes (1 / 4); the last width mod 4 texels of a row, and every
  * surface that is not eligible, run a per-texel scalar form with the same results.  An enqueued batch in a format other than
  * RGBA16F is never carried by a render kernel: the next meao_execute* runs it first, as plain launches (one per frame) on its
@@ -796,7 +824,9 @@ MEAO_API int32_t meao_set_tracing(meao_ctx *ctx, int32_t enable);
  *        (and: the uncorrected v_rcp_f32 within one ulp of it), 5 = exact 3/x and 9/x (same range), 6 = exact a/b on hashed
  *        pairs (2^-60<=|a|,|b|<=2^60), 7 = the UNORM8 bilateral result that skips the correction steps away from rounding
  *        boundaries vs the code of the exact chain, 2^32 hashed operand sets, 8 = f32->float11 and f32->float10 of the
- *        R11G11B10F stores (meao_color_format; all 2^32 inputs, both mantissa widths). */
+ *        R11G11B10F stores (meao_color_format; all 2^32 inputs, both mantissa widths), 9 = the conversions of
+ *        MEAO_COLOR_RGBA8_SRGB: f32 -> sRGB code as the composite kernels compute it vs a search over the table T (all 2^32
+ *        inputs), and code -> f32 vs the table D (256). */
 MEAO_API int32_t meao_selftest(meao_ctx *ctx, int32_t which, uint64_t *out_mismatches);
 
 #ifdef __cplusplus

@@ -209,8 +209,8 @@ public:
                                              deviceColorRgba16f.data(), colorPitch, deviceGBuffer0.empty() ? nullptr : deviceGBuffer0.data(),
                                              gbuffer0Pitch));
     }
-    // The same into colour targets in `colorFormat` (meao_composite_format / meao_composite_enqueue_format): RGBA16F, RGBA32F, RGBA8 or
-    // R11G11B10F.  A batch in another format than RGBA16F does not ride in the render kernel: the next Render* call runs it first.
+    // The same into colour targets in `colorFormat` (meao_composite_format / meao_composite_enqueue_format): RGBA16F, RGBA32F, RGBA8,
+    // R11G11B10F or -- the LDR target of a linear-colour-space project -- RGBA8_SRGB.  A batch in another format than RGBA16F does not ride in the render kernel: the next Render* call runs it first.
     void CompositeFormat(meao_composite_mode mode, const void *deviceAo, uint64_t aoPitch, void *deviceColor, uint64_t colorPitch,
                          void *deviceGBuffer0 = nullptr, uint64_t gbuffer0Pitch = 0, meao_stream stream = nullptr)
     {

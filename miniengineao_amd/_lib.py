@@ -40,7 +40,8 @@ DEPTH_LINEAR_F32, DEPTH_LINEAR_F16 = 4, 5      # linear view-space depth z (meao
 COMPOSITE_MULTIPLY, COMPOSITE_AMBIENT_ONLY, COMPOSITE_DEBUG = 0, 1, 2
 # meao_color_format: the composite's colour target (meao_composite_format); bytes per texel of each
 COLOR_RGBA16F, COLOR_RGBA32F, COLOR_RGBA8, COLOR_R11G11B10F = 0, 1, 2, 3
-COLOR_TEXEL_BYTES = {COLOR_RGBA16F: 8, COLOR_RGBA32F: 16, COLOR_RGBA8: 4, COLOR_R11G11B10F: 4}
+COLOR_RGBA8_SRGB = 5      # 4 is not a meao_color_format
+COLOR_TEXEL_BYTES = {COLOR_RGBA16F: 8, COLOR_RGBA32F: 16, COLOR_RGBA8: 4, COLOR_R11G11B10F: 4, COLOR_RGBA8_SRGB: 4}
 FMT_F32, FMT_F16, FMT_UNORM8 = 0, 1, 2
 SAMPLES_CHECKER, SAMPLES_EXHAUSTIVE = 0, 1
 DEBUG_OCCLUSION_HQ1 = 18

@@ -383,7 +383,7 @@ class AmbientOcclusion:
     # ---- composite (PushCompositeCommands, AO.cs:822-839) ------------------------------
     # color_format -> (numpy dtype, trailing shape) of a host colour array
     _HOST_COLOR = {L.COLOR_RGBA16F: (np.uint16, (4,)), L.COLOR_RGBA32F: (np.float32, (4,)), L.COLOR_RGBA8: (np.uint8, (4,)),
-                   L.COLOR_R11G11B10F: (np.uint32, ())}
+                   L.COLOR_R11G11B10F: (np.uint32, ()), L.COLOR_RGBA8_SRGB: (np.uint8, (4,))}
 
     def composite(self, ao: np.ndarray, color_rgba16f: np.ndarray, gbuffer0_rgba8: Optional[np.ndarray] = None,
                   debug: bool = False, color_format: int = L.COLOR_RGBA16F) -> None:
@@ -474,7 +474,7 @@ class AmbientOcclusion:
         and all frames of a surface must share one row stride, which becomes its pitch; any other layout raises ValueError
         (nothing is copied).  enqueue=False: one composite per frame now, on torch.cuda.current_stream(); enqueue=True: the
         batch waits for the next execute's render kernel (composite_enqueue_device).  color_format: another meao_color_format
-        for ``color`` -- (N, H, W, 4) float32 for RGBA32F or uint8 for RGBA8, (N, H, W) int32 for R11G11B10F.  batched=True (with
+        for ``color`` -- (N, H, W, 4) float32 for RGBA32F or uint8 for RGBA8 / RGBA8_SRGB, (N, H, W) int32 for R11G11B10F.  batched=True (with
         enqueue=False): the frames in one launch now (composite_batch_device) instead of one launch each -- and then ao, color and
         gbuffer0 may be lists of differently shaped frames, each tensor's own row stride becoming its pitch
         (meao_composite_batch_extents)."""

@@ -35,7 +35,7 @@ HOST_UNITS = ["meao_plan.cpp", "meao_api.cpp", "meao_execute.cpp", "meao_composi
 SOURCES = HOST_UNITS + KERNEL_UNITS
 HEADERS = ["meao_plan.hpp", "meao_kernels.hpp", "meao_ctx.hpp", "meao_dev.hpp", "meao_dev_downsample.hpp", "meao_dev_render.hpp",
            "meao_dev_upsample.hpp", "meao_dev_blend.hpp", "meao_dev_composite.hpp", "meao_dev_fused.hpp", "meao_launch.hpp",
-           "meao_kernels.hip"]
+           "meao_kernels.hip", "meao_srgb_tables.inc"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 
 # -ffp-contract=off: the only fused multiply-adds are the explicit mad()/fma2() calls, which
@@ -86,7 +86,7 @@ def _unit_stale(src: str, obj: str) -> bool:
         return True
     built = os.path.getmtime(obj)
     deps = [src, os.path.join(_INCLUDE, "meao.h"), os.path.abspath(__file__)]
-    deps += [os.path.join(_CSRC, h) for h in HEADERS if h.endswith(".hpp")]
+    deps += [os.path.join(_CSRC, h) for h in HEADERS if h.endswith((".hpp", ".inc"))]
     if os.path.basename(src) == "meao_kernels.hip":         # the unity unit #includes every kernel unit
         deps += [os.path.join(_CSRC, u) for u in KERNEL_UNITS]
     return any(os.path.getmtime(d) > built for d in deps)

@@ -605,7 +605,7 @@ __attribute__((visibility("default"))) int32_t meao_test_counters(const meao_ctx
 
 int32_t meao_selftest(meao_ctx *ctx, int32_t which, uint64_t *out_mismatches)
 {
-    if (!ctx || !out_mismatches || which < 0 || which > 8) return MEAO_ERR_INVALID_ARGUMENT;
+    if (!ctx || !out_mismatches || which < 0 || which > 9) return MEAO_ERR_INVALID_ARGUMENT;
     int rc = use_device(ctx);
     if (rc != MEAO_OK) return rc;
     if (!ctx->counter) MEAO_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->counter), sizeof(unsigned long long)));

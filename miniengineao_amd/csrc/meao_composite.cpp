@@ -16,7 +16,7 @@ uint64_t color_elem(int32_t color_format)
     switch (color_format) {
     case MEAO_COLOR_RGBA16F: return 8;
     case MEAO_COLOR_RGBA32F: return 16;
-    case MEAO_COLOR_RGBA8: case MEAO_COLOR_R11G11B10F: return 4;
+    case MEAO_COLOR_RGBA8: case MEAO_COLOR_R11G11B10F: case MEAO_COLOR_RGBA8_SRGB: return 4;
     default: return 0;
     }
 }

@@ -121,8 +121,8 @@ __device__ __forceinline__ void composite_row(const void *ao_base, void *color_b
 }
 
 // ------------------------------------------------------------------------------------------
-// The other colour formats (meao_composite_format): RGBA32F, RGBA8 and R11G11B10F targets, in composite_kernel behind one
-// kernel-uniform branch.  One lane = 16 bytes of colour = one RGBA32F texel or four RGBA8 / R11G11B10F texels, and their AO in
+// The other colour formats (meao_composite_format): RGBA32F, RGBA8, R11G11B10F and RGBA8_SRGB targets, in composite_kernel behind
+// one kernel-uniform branch.  One lane = 16 bytes of colour = one RGBA32F texel or four texels of a 4-byte format, and their AO in
 // one load; rows are dealt as in the pitched RGBA16F form, a tightly packed frame is one long row dealt to the whole grid.
 
 // Unsigned small floats (5-bit exponent of bias 15, M mantissa bits: 6 for R and G, 5 for B).  Every code is the f16 value of
@@ -174,6 +174,47 @@ __device__ __forceinline__ uint32_t composite_rgba8(uint32_t t, float ao, int32_
     const float f = composite_factor(ao, mode);
     const uint32_t a = mode == MEAO_COMPOSITE_MULTIPLY ? unorm8_times(t >> 24, f) : t >> 24;
     return unorm8_times(t & 255u, f) | (unorm8_times((t >> 8) & 255u, f) << 8) | (unorm8_times((t >> 16) & 255u, f) << 16) | (a << 24);
+}
+
+// RGBA8_SRGB: r, g, b sRGB-encoded and blended in linear light, alpha as in RGBA8.  The two f32 tables of the format's definition
+// (meao.h; meao_srgb_tables.inc) sit in the workgroup's dynamic LDS, the only LDS of the kernels that use them: 256 words of D,
+// then T[1..255].  srgb_stage_tables copies them there; a barrier follows before the first lookup.
+constexpr uint32_t kSrgbWords = 256u + 255u, kSrgbLdsBytes = 2048u;
+
+__device__ __forceinline__ float *srgb_lds()
+{
+    extern __shared__ float meao_srgb_lds[];
+    return meao_srgb_lds;
+}
+
+__device__ __forceinline__ void srgb_stage_tables(const uint32_t *words)
+{
+    float *lds = srgb_lds();
+    for (uint32_t i = threadIdx.x; i < kSrgbWords; i += blockDim.x) lds[i] = __builtin_bit_cast(float, words[i]);
+}
+
+__device__ __forceinline__ float srgb_decode(uint32_t code) { return srgb_lds()[code]; }
+
+// enc(x) = the number of k in 1..255 with x >= T[k].  The fast form: e = floor(255 s(x) + 1/4), s the inverse transfer function
+// through v_log_f32 / v_exp_f32 -- with an estimate less than a quarter of a code from the real 255 s(x), e is enc(x) or one below
+// it (enc is floor(255 s + 1/2) up to the f32 rounding of the thresholds), and ONE comparison against T[e + 1] decides.  NaN
+// takes the power arm, leaves fmaxf as 0 and fails the comparison: 0.  meao_selftest(9) checks every f32 against a search over T.
+__device__ __forceinline__ uint32_t srgb_encode(float x)
+{
+    const float lo = x * 3294.6f;                                                                    // 255 x 12.92 x
+    const float hi = 269.025f * __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(x) * (1.0f / 2.4f)) - 14.025f;    // 255 (1.055 x^(1/2.4) - 0.055)
+    const float y = (x <= 0.0031308f ? lo : hi) + 0.25f;
+    const uint32_t e = static_cast<uint32_t>(__builtin_fminf(__builtin_fmaxf(y, 0.0f), 254.0f));
+    return e + (x >= srgb_lds()[256u + e] ? 1u : 0u);                                               // [256 + e] = T[e + 1]
+}
+
+__device__ __forceinline__ uint32_t composite_rgba8_srgb(uint32_t t, float ao, int32_t mode)
+{
+    if (mode == MEAO_COMPOSITE_DEBUG) return srgb_encode(ao) * 0x00010101u | (f32_to_unorm8(ao) << 24);
+    const float f = composite_factor(ao, mode);
+    const uint32_t a = mode == MEAO_COMPOSITE_MULTIPLY ? unorm8_times(t >> 24, f) : t >> 24;
+    return srgb_encode(srgb_decode(t & 255u) * f) | (srgb_encode(srgb_decode((t >> 8) & 255u) * f) << 8) |
+           (srgb_encode(srgb_decode((t >> 16) & 255u) * f) << 16) | (a << 24);
 }
 
 __device__ __forceinline__ uint32_t composite_r11g11b10f(uint32_t t, float ao, int32_t mode)
@@ -233,6 +274,9 @@ __device__ __forceinline__ void composite_format_group(const void *ao_base, void
     } else if constexpr (CFMT == MEAO_COLOR_RGBA8) {
         raw.x = composite_rgba8(raw.x, aov[0], mode); raw.y = composite_rgba8(raw.y, aov[1], mode);
         raw.z = composite_rgba8(raw.z, aov[2], mode); raw.w = composite_rgba8(raw.w, aov[3], mode);
+    } else if constexpr (CFMT == MEAO_COLOR_RGBA8_SRGB) {
+        raw.x = composite_rgba8_srgb(raw.x, aov[0], mode); raw.y = composite_rgba8_srgb(raw.y, aov[1], mode);
+        raw.z = composite_rgba8_srgb(raw.z, aov[2], mode); raw.w = composite_rgba8_srgb(raw.w, aov[3], mode);
     } else {
         raw.x = composite_r11g11b10f(raw.x, aov[0], mode); raw.y = composite_r11g11b10f(raw.y, aov[1], mode);
         raw.z = composite_r11g11b10f(raw.z, aov[2], mode); raw.w = composite_r11g11b10f(raw.w, aov[3], mode);
@@ -245,7 +289,7 @@ __device__ __forceinline__ void composite_format_group(const void *ao_base, void
 }
 
 // Texel x of a row, scalar form: the widest accesses a surface without any alignment beyond its channel type allows (RGBA8 by
-// bytes, RGBA32F and R11G11B10F by 32-bit words), with the results of the vector form.
+// and RGBA8_SRGB by bytes, RGBA32F and R11G11B10F by 32-bit words), with the results of the vector form.
 template <int AOFMT, int CFMT>
 __device__ __forceinline__ void composite_format_texel(const void *ao_base, void *color_base, void *gbuffer0_base, uint32_t ao_at,
                                                        uint32_t color_at, uint32_t g_at, int32_t mode, uint32_t x)
@@ -258,9 +302,10 @@ __device__ __forceinline__ void composite_format_texel(const void *ao_base, void
         float *cp = at_byte_offset(static_cast<float *>(color_base), color_byte);
         const float4v t = composite_rgba32f(float4v{cp[0], cp[1], cp[2], cp[3]}, ao, mode);
         cp[0] = t.x; cp[1] = t.y; cp[2] = t.z; cp[3] = t.w;
-    } else if constexpr (CFMT == MEAO_COLOR_RGBA8) {
+    } else if constexpr (CFMT == MEAO_COLOR_RGBA8 || CFMT == MEAO_COLOR_RGBA8_SRGB) {
         uint8_t *cp = at_byte_offset(static_cast<uint8_t *>(color_base), color_byte);
-        const uint32_t t = composite_rgba8(cp[0] | (uint32_t(cp[1]) << 8) | (uint32_t(cp[2]) << 16) | (uint32_t(cp[3]) << 24), ao, mode);
+        const uint32_t in = cp[0] | (uint32_t(cp[1]) << 8) | (uint32_t(cp[2]) << 16) | (uint32_t(cp[3]) << 24);
+        const uint32_t t = CFMT == MEAO_COLOR_RGBA8 ? composite_rgba8(in, ao, mode) : composite_rgba8_srgb(in, ao, mode);
         cp[0] = static_cast<uint8_t>(t); cp[1] = static_cast<uint8_t>(t >> 8); cp[2] = static_cast<uint8_t>(t >> 16); cp[3] = static_cast<uint8_t>(t >> 24);
     } else {
         uint32_t *cp = at_byte_offset(static_cast<uint32_t *>(color_base), color_byte);

@@ -4,6 +4,12 @@
 #include "meao_dev_composite.hpp"
 #include "meao_launch.hpp"
 
+// The f32 words that define MEAO_COLOR_RGBA8_SRGB (meao.h): D[0..255], then T[1..255].  Read once per workgroup of an sRGB launch
+// (srgb_stage_tables), and by the search that meao_selftest(9) checks the kernels' encode against.
+static __device__ const uint32_t meao_srgb_table_words[meao::kSrgbWords] = {
+#include "meao_srgb_tables.inc"
+};
+
 namespace meao {
 namespace {
 
@@ -143,7 +149,12 @@ __global__ __launch_bounds__(kThreads) void composite_kernel(const CompositeArgs
     if (a.color_format != MEAO_COLOR_RGBA16F) {     // kernel-uniform: the other colour formats (meao_composite_format), packed and pitched
         if (a.color_format == MEAO_COLOR_RGBA32F) composite_format_frame<AOFMT, MEAO_COLOR_RGBA32F>(a, ao, color, gbuffer0);
         else if (a.color_format == MEAO_COLOR_RGBA8) composite_format_frame<AOFMT, MEAO_COLOR_RGBA8>(a, ao, color, gbuffer0);
-        else composite_format_frame<AOFMT, MEAO_COLOR_R11G11B10F>(a, ao, color, gbuffer0);
+        else if (a.color_format == MEAO_COLOR_R11G11B10F) composite_format_frame<AOFMT, MEAO_COLOR_R11G11B10F>(a, ao, color, gbuffer0);
+        else {      // RGBA8_SRGB: the launch brought kSrgbLdsBytes of dynamic LDS (every other format's brings none) for the two tables
+            srgb_stage_tables(meao_srgb_table_words);
+            __syncthreads();
+            composite_format_frame<AOFMT, MEAO_COLOR_RGBA8_SRGB>(a, ao, color, gbuffer0);
+        }
         return;
     }
     // kernel-uniform: row-pitched surfaces, rows dealt to (2^row_lanes_log2 lanes x rows) workgroups -- the launch's pitches, or (the
@@ -155,7 +166,8 @@ __global__ __launch_bounds__(kThreads) void composite_kernel(const CompositeArgs
         composite_row<AOFMT>(r.ao, r.color, r.gbuffer0, r.p, a.mode, row, threadIdx.x & (lanes - 1u), lanes);
 }
 
-// which = 4: rcp_strict, 5: div_const<3>, div_const<9>, 6: div_strict on hashed operand pairs, 8: f32_to_ufloat<6|5> (the R11G11B10F stores)
+// which = 4: rcp_strict, 5: div_const<3>, div_const<9>, 6: div_strict on hashed operand pairs, 8: f32_to_ufloat<6|5> (the R11G11B10F stores),
+// 9: srgb_encode / srgb_decode (the RGBA8_SRGB stores and loads)
 __device__ __forceinline__ bool in_exact_range(float x, float lo, float hi)
 {
     const float ax = __builtin_fabsf(x);
@@ -183,15 +195,34 @@ __device__ __forceinline__ uint32_t ufloat_model(uint32_t u)
     return min(code, kInf);
 }
 
+// which = 9: enc(x) by its definition, the number of k in 1..255 with x >= T[k], as a binary search over the table in memory
+// (not the LDS copy, and none of srgb_encode's arithmetic): every comparison with a NaN is false, so NaN -> 0.
+__device__ __forceinline__ uint32_t srgb_encode_model(float x)
+{
+    uint32_t lo = 0u, hi = 255u;        // T[lo] <= x < T[hi + 1], with T[0] = -inf and T[256] = +inf (NaN: lo stays 0)
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1u) / 2u;
+        if (x >= __builtin_bit_cast(float, meao_srgb_table_words[255u + mid])) lo = mid; else hi = mid - 1u;      // [255 + k] = T[k]
+    }
+    return lo;
+}
+
 __global__ __launch_bounds__(kThreads) void selftest_div_kernel(unsigned long long *count, int which)
 {
     unsigned long long bad = 0;
+    if (which == 9) {       // kernel-uniform; this launch alone brought the tables' dynamic LDS
+        srgb_stage_tables(meao_srgb_table_words);
+        __syncthreads();
+    }
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kThreads;
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x; i < (1ull << 32); i += stride) {
         const float x = __builtin_bit_cast(float, static_cast<uint32_t>(i));
         if (which == 8) {
             bad += f32_to_ufloat<6>(x) != ufloat_model<6>(static_cast<uint32_t>(i));
             bad += f32_to_ufloat<5>(x) != ufloat_model<5>(static_cast<uint32_t>(i));
+        } else if (which == 9) {
+            bad += srgb_encode(x) != srgb_encode_model(x);
+            if (i < 256u) bad += __builtin_bit_cast(uint32_t, srgb_decode(static_cast<uint32_t>(i))) != meao_srgb_table_words[i];
         } else if (which == 4) {
             if (!in_exact_range(x, 0x1p-100f, 0x1p100f)) continue;
             const float exact = 1.0f / x;
@@ -288,6 +319,9 @@ int composite_per_lane(int32_t color_format, bool vec)
     return color_format == MEAO_COLOR_RGBA16F ? 2 : !vec || color_format == MEAO_COLOR_RGBA32F ? 1 : 4;
 }
 
+// Dynamic LDS of a composite launch: the sRGB tables for RGBA8_SRGB, none for every other format (which keep "no LDS").
+uint32_t composite_lds_bytes(int32_t color_format) { return color_format == MEAO_COLOR_RGBA8_SRGB ? kSrgbLdsBytes : 0u; }
+
 // The row form for rows of w texels: the narrowest power of two of lanes that spans a row's pairs (at most the workgroup), rows
 // beside each other; returns the workgroups h rows get.
 int composite_row_blocks(int32_t w, int32_t h, int per_lane, int32_t *row_lanes_log2)
@@ -310,8 +344,9 @@ hipError_t launch_composite(const CompositeArgs &args, int ao_format, hipStream_
     int blocks = static_cast<int>(std::min<int64_t>((pairs + kThreads - 1) / kThreads, 256 * 32));
     if (a.pitch.on) blocks = composite_row_blocks(a.pitch.w, a.pitch.h, static_cast<int>(per_lane), &a.row_lanes_log2);
     // every frame of a batched launch gets the workgroups a launch of its own would: grid y = the frame
-    if (ao_format == MEAO_AO_R8) composite_kernel<MEAO_AO_R8><<<dim3(blocks, frames), dim3(kThreads), 0, s>>>(a);
-    else composite_kernel<MEAO_AO_F16><<<dim3(blocks, frames), dim3(kThreads), 0, s>>>(a);
+    const uint32_t lds = composite_lds_bytes(a.color_format);
+    if (ao_format == MEAO_AO_R8) composite_kernel<MEAO_AO_R8><<<dim3(blocks, frames), dim3(kThreads), lds, s>>>(a);
+    else composite_kernel<MEAO_AO_F16><<<dim3(blocks, frames), dim3(kThreads), lds, s>>>(a);
     return hipGetLastError();
 }
 
@@ -331,8 +366,9 @@ hipError_t launch_composite_sized(const CompositeArgs &args, int ao_format, hipS
     a.pitch = CompositePitches{};
     a.pitch.on = 1;         // never the packed RGBA16F fall-through at the kernel's entry
     // x: the largest frame's workgroups -- the row loops are grid-stride, a workgroup beyond a smaller frame's rows touches nothing
-    if (ao_format == MEAO_AO_R8) composite_kernel<MEAO_AO_R8><<<dim3(blocks, frames), dim3(kThreads), 0, s>>>(a);
-    else composite_kernel<MEAO_AO_F16><<<dim3(blocks, frames), dim3(kThreads), 0, s>>>(a);
+    const uint32_t lds = composite_lds_bytes(a.color_format);
+    if (ao_format == MEAO_AO_R8) composite_kernel<MEAO_AO_R8><<<dim3(blocks, frames), dim3(kThreads), lds, s>>>(a);
+    else composite_kernel<MEAO_AO_F16><<<dim3(blocks, frames), dim3(kThreads), lds, s>>>(a);
     return hipGetLastError();
 }
 
@@ -344,6 +380,7 @@ hipError_t launch_selftest(int which, unsigned long long *count, hipStream_t s)
     case 2: selftest_unorm8_decode_kernel<<<dim3(1), dim3(256), 0, s>>>(count); break;
     case 3: selftest_f16_decode_kernel<<<dim3(65536 / kThreads), dim3(kThreads), 0, s>>>(count); break;
     case 4: case 5: case 6: case 7: case 8: selftest_div_kernel<<<dim3(4096), dim3(kThreads), 0, s>>>(count, which); break;
+    case 9: selftest_div_kernel<<<dim3(4096), dim3(kThreads), kSrgbLdsBytes, s>>>(count, which); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -85,9 +85,10 @@ def _channel_frame_pointers(frames, height, width, dtype, what, device, channels
 
 def color_layout(color_format: int):
     """meao_color_format -> (accepted torch dtypes, channels of the tensor's last dimension or 0 for none, bytes per texel):
-    RGBA16F (N, H, W, 4) float16 / int16, RGBA32F (N, H, W, 4) float32, RGBA8 (N, H, W, 4) uint8, R11G11B10F (N, H, W) int32."""
+    RGBA16F (N, H, W, 4) float16 / int16, RGBA32F (N, H, W, 4) float32, RGBA8 and RGBA8_SRGB (N, H, W, 4) uint8, R11G11B10F (N, H, W) int32."""
     import torch
-    layouts = {0: ((torch.float16, torch.int16), 4, 8), 1: ((torch.float32,), 4, 16), 2: ((torch.uint8,), 4, 4), 3: ((torch.int32,), 0, 4)}
+    layouts = {0: ((torch.float16, torch.int16), 4, 8), 1: ((torch.float32,), 4, 16), 2: ((torch.uint8,), 4, 4), 3: ((torch.int32,), 0, 4),
+               5: ((torch.uint8,), 4, 4)}
     if color_format not in layouts:
         raise ValueError(f"color_format {color_format}: not a meao_color_format")
     return layouts[color_format]

@@ -1,13 +1,15 @@
 """The stand-alone composite per colour format: color.rgba *= ao (MULTIPLY) of 16 tightly packed 4K frames with R8 AO, once per
 meao_color_format.  HIP events around `steps` passes over the 16 frames.
 
-    python tools/composite_format_rate.py [--rounds 5] [--steps 20] [--out profiles/composite_format_rate.jsonl]
+    python tools/composite_format_rate.py [--rounds 5] [--steps 20] [--arms RGBA16F,RGBA8,...] [--out profiles/composite_format_rate.jsonl]
 
-Four arms (RGBA16F, RGBA32F, RGBA8, R11G11B10F), alternated round by round in one process.  One JSON line per arm and round, then a
-summary line: median Gpixels/s and GB/s per arm -- bytes moved, the colour counted twice (read + write) and the AO once: 17, 33, 9
-and 9 bytes per texel -- and each arm's GB/s over the RGBA16F arm's of the same run, the yardstick (all four are the same
-streaming shape).  The first frame of every arm is checked against the NumPy model of tests/color_formats.py after one pass (the
-tool runs from a checkout: it imports the model from the tests package).  Every pass multiplies the same frames in place, so over
+Five arms (RGBA16F, RGBA32F, RGBA8, R11G11B10F, RGBA8_SRGB), alternated round by round in one process; --arms runs a subset (the
+first four against a library older than RGBA8_SRGB, for an A/B).  One JSON line per arm and round, then a summary line: median
+Gpixels/s and GB/s per arm -- bytes moved, the colour counted twice (read + write) and the AO once: 17, 33, 9, 9 and 9 bytes per
+texel -- and each arm's GB/s over the RGBA16F arm's of the same run, the yardstick (all are the same streaming shape); the
+RGBA8_SRGB arm also over the RGBA8 arm's, which moves the same bytes through the same accesses.  The first frame of every arm is
+checked against the NumPy model of tests/color_formats.py (RGBA8_SRGB: tests/srgb_format.py) after one pass (the tool runs from a
+checkout: it imports the models from the tests package).  Every pass multiplies the same frames in place, so over
 the `steps` x rounds passes of an arm the colours decay towards zero (RGBA8 and R11G11B10F reach 0, RGBA32F f32 subnormals): the
 later passes move the same bytes with another operand mix.  The colours are reset before every timed round.
 """
@@ -24,8 +26,11 @@ import torch  # noqa: E402
 from miniengineao_amd import AmbientOcclusion  # noqa: E402
 from miniengineao_amd import _lib as L  # noqa: E402
 from tests import color_formats as CF  # noqa: E402
+from tests import srgb_format as SF  # noqa: E402
 
-ARMS = {"RGBA16F": L.COLOR_RGBA16F, "RGBA32F": L.COLOR_RGBA32F, "RGBA8": L.COLOR_RGBA8, "R11G11B10F": L.COLOR_R11G11B10F}
+ALL_ARMS = {"RGBA16F": L.COLOR_RGBA16F, "RGBA32F": L.COLOR_RGBA32F, "RGBA8": L.COLOR_RGBA8, "R11G11B10F": L.COLOR_R11G11B10F,
+            "RGBA8_SRGB": L.COLOR_RGBA8_SRGB}
+ARMS = dict(ALL_ARMS)
 
 
 def initial(fmt, B, h, w, dev):
@@ -34,7 +39,7 @@ def initial(fmt, B, h, w, dev):
         return (torch.rand((B, h, w, 4), device=dev, generator=g) * 4).to(torch.float16)
     if fmt == L.COLOR_RGBA32F:
         return torch.rand((B, h, w, 4), device=dev, generator=g) * 4
-    if fmt == L.COLOR_RGBA8:
+    if fmt in (L.COLOR_RGBA8, L.COLOR_RGBA8_SRGB):
         return torch.randint(0, 256, (B, h, w, 4), device=dev, generator=g, dtype=torch.uint8)
     r = torch.randint(0, 0x400, (3, B, h, w), device=dev, generator=g, dtype=torch.int32)        # finite values below 2
     return r[0] | (r[1] << 11) | ((r[2] & 0x1ff) << 22)
@@ -44,6 +49,8 @@ def model(fmt, ao, color):
     """One frame through the model; RGBA16F (not one of the model's formats) the same reading with NumPy's own f16 rounding."""
     if fmt == L.COLOR_RGBA16F:
         return (color.astype(np.float32) * CF.ao_to_f32(ao, CF.AO_R8)[..., None]).astype(np.float16).view(np.uint16)
+    if fmt == L.COLOR_RGBA8_SRGB:
+        return SF.composite(ao, SF.AO_R8, color, fmt, SF.MULTIPLY)[0]
     if fmt == L.COLOR_R11G11B10F:
         color = color.view(np.uint32)
     return CF.composite(ao, CF.AO_R8, color, fmt, CF.MULTIPLY)[0]
@@ -55,8 +62,12 @@ def main() -> int:
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
+    ap.add_argument("--arms", default=",".join(ALL_ARMS))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    for k in list(ARMS):
+        if k not in a.arms.split(","):
+            del ARMS[k]
     w, h, B = a.width, a.height, 16
     dev = torch.device("cuda", 0)
     aosurf = torch.randint(0, 256, (B, h, w), device=dev, dtype=torch.uint8)
@@ -110,7 +121,8 @@ def main() -> int:
                "median_GB_per_s": {k: round(v, 1) for k, v in med.items()},
                "median_Gpixels_per_s": {k: round(v / (2 * L.COLOR_TEXEL_BYTES[ARMS[k]] + 1), 2) for k, v in med.items()},
                "min_max_GB_per_s": {k: [round(min(v), 1), round(max(v), 1)] for k, v in res.items()},
-               "GB_per_s_over_RGBA16F": {k: round(v / med["RGBA16F"], 4) for k, v in med.items()},
+               "GB_per_s_over_RGBA16F": {k: round(v / med["RGBA16F"], 4) for k, v in med.items()} if "RGBA16F" in med else None,
+               "RGBA8_SRGB_GB_per_s_over_RGBA8": round(med["RGBA8_SRGB"] / med["RGBA8"], 4) if "RGBA8_SRGB" in med and "RGBA8" in med else None,
                "results_equal_the_model": ok, "device": torch.cuda.get_device_name(dev)}
     print(json.dumps(summary), flush=True)
     if a.out:
