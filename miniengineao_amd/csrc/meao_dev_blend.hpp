@@ -145,7 +145,7 @@ __device__ __forceinline__ void blend_window_into_lds(const UpsampleArgs &in, fl
         const uint32_t at = static_cast<uint32_t>(Y * hw + X) * static_cast<uint32_t>(sizeof(ao_t));      // byte offset in the level
         float v;
         if constexpr (!MEAO_X_UPS_EXACT_R8 && DIV == DIV_EXACT_RCP && AOFMT == MEAO_AO_R8) {
-            const ao_t q = static_cast<ao_t>(bilateral_upsample_r8<true, false, MEAO_X_BIL_PAIR_RCP != 0>(hoist_d[j], AO::decode(hoist_a[j]), dk, ak, bilateral_k));
+            const ao_t q = static_cast<ao_t>(bilateral_upsample_r8<false, MEAO_X_BIL_PAIR_RCP != 0>(hoist_d[j], AO::decode(hoist_a[j]), dk, ak, bilateral_k));
             out[i] = AO::decode(q);
             if (vx0 + wc == X && vy0 + wr == Y && X >= own_x0 && X < own_x0 + own_w && Y >= own_y0 && Y < own_y0 + own_h) *at_byte_offset(dst, at) = q;
             continue;
@@ -169,6 +169,7 @@ __device__ __forceinline__ void blend_window_into_lds(const UpsampleArgs &in, fl
 
 
 // ---- the nested blend launches (meao_k_upsample_nested.hip and its per-frame form)
+typedef BlendForm<ups_tile_h(false), Window::Nested> NestedForm;      // the outer tile: its LoResAO1 taps are in LDS already
 // Upsample.main_blendout L4 -> L3 evaluated inside the L3 -> L2 pass: the smallest pass of the chain
 // (one wave of workgroups, three barriers, two memory round trips: latency-bound, and a launch of its
 // own) disappears; each L3 -> L2 tile computes the 38 x 22 window of Combined3 it needs itself
@@ -178,14 +179,14 @@ __device__ __forceinline__ void upsample_two_level_tile(const UpsampleArgs &oute
                                                         int frame)
 {
     typedef UpsTile<ups_tile_h(false)> T;
-    typedef UpsLds<false> Lds;
+    typedef UpsLds<NestedForm> Lds;
     static_assert(kNestScratch <= Lds::kInvN + Lds::kHbN + Lds::kDepN, "the nested pass's scratch precedes s_ao");
     float *const s_ao = smem + Lds::kInvN + Lds::kHbN + Lds::kDepN;
     const int tile_x = tile % outer.tiles_x, tile_y = tile / outer.tiles_x;
     const int LX0 = (tile_x * kUpsTileW) >> 1, LY0 = (tile_y * ups_tile_h(false)) >> 1;
     blend_window_into_lds<AOFMT, RTNE, DIV>(inner, s_ao, T::kRawPitch, LX0 - 3, LY0 - 3, T::kRawW, T::kRawH, smem, frame,
                                             LX0, LY0, T::kLowW, T::kLowH);
-    upsample_tile<AOFMT, RTNE, false, DIV, true>(outer, smem, tile, frame);
+    upsample_tile<Column<AOFMT, RTNE, DIV>, NestedForm>(outer, smem, tile, frame);
 }
 
 // ---- one frame per call: L4 -> L3 and L3 -> L2 inside the L2 -> L1 launch ---------------------------------
@@ -200,7 +201,7 @@ __device__ __forceinline__ void upsample_three_level_tile(const UpsampleArgs &ou
                                                           float *smem, int tile, int frame)
 {
     typedef UpsTile<ups_tile_h(false)> T;
-    typedef UpsLds<false> Lds;
+    typedef UpsLds<NestedForm> Lds;
     float *const s_ao = smem + Lds::kInvN + Lds::kHbN + Lds::kDepN;      // raw taps of the outer tile
     float *const inner_scratch = smem + Lds::kFloats;
     const int tile_x = tile % outer.tiles_x, tile_y = tile / outer.tiles_x;
@@ -210,7 +211,7 @@ __device__ __forceinline__ void upsample_three_level_tile(const UpsampleArgs &ou
                                             inner_scratch, frame, LX0 >> 1, LY0 >> 1, T::kLowW / 2, T::kLowH / 2);
     blend_window_into_lds<AOFMT, RTNE, DIV, true>(mid, s_ao, T::kRawPitch, LX0 - 3, LY0 - 3, T::kRawW, T::kRawH, smem, frame,
                                                   LX0, LY0, T::kLowW, T::kLowH);
-    upsample_tile<AOFMT, RTNE, false, DIV, true>(outer, smem, tile, frame);
+    upsample_tile<Column<AOFMT, RTNE, DIV>, NestedForm>(outer, smem, tile, frame);
 }
 
 }  // namespace

@@ -6,6 +6,7 @@
 #define MEAO_X_NO_REDO 0
 #endif
 #include "meao_dev_downsample.hpp"      // linearize, nice_denominators, raw_depth_texel: HiResDB of the final pass
+#include "meao_launch.hpp"              // Column
 
 namespace meao {
 namespace {
@@ -175,7 +176,7 @@ __device__ __forceinline__ void bilateral_upsample_grouped(const float (&hi_dept
 // of a noisy frame, none where the AO is flat (q~ = 1 -> v~ = 255.5) -- the lane runs the exact sequence.  The agreement of
 // estimate and exact code is also checked on the running device for 2^32 hashed operand sets (meao_selftest(7)) and, with
 // adversarial 1-ulp reciprocal errors, in numpy by tests/test_r8_estimate_bound.py.
-// GROUPED: the four weight reciprocals back to back, as in bilateral_upsample_grouped.
+// The four weight reciprocals are issued back to back, as in bilateral_upsample_grouped.
 // REUSE: the exact path starts from the estimate's x and 1 / x (14 instructions fewer on that path, 5 - 8 VGPRs more live across
 // the branch); without it the whole exact sequence is run again from an opaque copy of the depth, so that nothing of the estimate
 // has to stay in registers for the rare path (the nested kernels have none to spare).
@@ -191,7 +192,7 @@ __device__ __forceinline__ void bilateral_upsample_grouped(const float (&hi_dept
 constexpr float kR8Margin = 0x1p-10f;     // (1.25 * 2^-11, still above the bound, measured the same: profiles/r04_ab_r8_margin.jsonl)
 
 // (v_cvt_pk_u8_f32, which would convert and pack in one instruction, does not truncate like v_cvt_u32_f32: tried in round 4.)
-template <bool GROUPED, bool REUSE = false, bool PAIRED = false>
+template <bool REUSE = false, bool PAIRED = false>
 __device__ __forceinline__ uint32_t bilateral_upsample_r8(float hi_depth, float hi_ao, const float (&d)[4], const float (&a)[4],
                                                           const BilateralConsts &k)
 {
@@ -202,24 +203,16 @@ __device__ __forceinline__ uint32_t bilateral_upsample_r8(float hi_depth, float 
     if constexpr (PAIRED) {
         const float p01 = x[0] * x[1], p23 = x[2] * x[3];
         float r01, r23;
-        if constexpr (GROUPED) {
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("v_rcp_f32 %0, %1" : "=v"(r01) : "v"(p01));
-            asm volatile("v_rcp_f32 %0, %1" : "=v"(r23) : "v"(p23));
-            __builtin_amdgcn_sched_barrier(0);
-        } else {
-            r01 = __builtin_amdgcn_rcpf(p01);
-            r23 = __builtin_amdgcn_rcpf(p23);
-        }
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("v_rcp_f32 %0, %1" : "=v"(r01) : "v"(p01));
+        asm volatile("v_rcp_f32 %0, %1" : "=v"(r23) : "v"(p23));
+        __builtin_amdgcn_sched_barrier(0);
         r[0] = x[1] * r01; r[1] = x[0] * r01; r[2] = x[3] * r23; r[3] = x[2] * r23;
-    } else if constexpr (GROUPED) {
+    } else {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < 4; ++i) asm volatile("v_rcp_f32 %0, %1" : "=v"(r[i]) : "v"(x[i]));
         __builtin_amdgcn_sched_barrier(0);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = __builtin_amdgcn_rcpf(x[i]);
     }
     // The estimate only has to stay inside its error bound, not to follow the reference's operation order (round 6): the constant
     // factors of the weights are folded into fused multiply-adds -- total = 9 r0 + 3 (r1 + r3) + (r2 + noise), sum = 9 a0 r0 +
@@ -456,9 +449,37 @@ __device__ __forceinline__ bool hi_depth_words(const uint4v (&raw)[QUADS], int f
 // the V-blur into the array the H-blurred values had vacated -- 17.6 KB, 57 VGPRs, one barrier more, bit-exact -- runs at 176.0 us
 // against 176.1 us: the same busy cycles, 10 % more wave-cycles, 17 % more waiting.  The pass is bound by the issue rate of its
 // instruction mix, not by the number of waves that hide latency: profiles/r04_ab_final_late_depth_8_workgroups.txt.)
-template <bool FINAL, int TILE_H = ups_tile_h(FINAL)>
+// The form of a tile: everything upsample_tile is compiled for besides its column (Column<>: AO storage, f16 rounding, division)
+// and its hook.  Call sites name it through FinalForm<> / BlendForm<>.
+//   kFinal    Upsample.main, the full-resolution pass (HiResDB from the caller's raw depth frames, HiDepthArgs); else main_blendout
+//   kTileH    rows of a tile
+//   kRawF32   (final) the caller's depth frames are f32 -- no format switch in the code (the other formats take the generic instance)
+//   kPitched  (final) the caller's surfaces are row-pitched -- raw depth rows a.pitch.depth and dst rows a.pitch.dst texels apart
+//             (meao_execute_batch_pitched).  Only the addresses of caller memory change; context-owned buffers keep hw.
+//   kLinear   (final) the caller's depth frames are linear view-space depth (MEAO_DEPTH_LINEAR_*): f32 with kRawF32, else f16;
+//             HiResDB and the from-raw window are linearize_view of them (hi->zp0 = s).
+//   kNested   (blend) the LoResAO1 taps (s_ao) were already produced in LDS by blend_window_into_lds (the previous pass of the
+//             chain evaluated inside this workgroup) instead of being read from global memory.
+template <bool FINAL, int TILE_H, bool RAW_F32, bool PITCHED, bool LINEAR, bool NESTED>
+struct UpsForm {
+    static constexpr bool kFinal = FINAL, kRawF32 = RAW_F32, kPitched = PITCHED, kLinear = LINEAR, kNested = NESTED;
+    static constexpr int kTileH = TILE_H;
+    static_assert(!LINEAR || (FINAL && !NESTED), "only the full-resolution pass reads the depth frames");
+    static_assert(!PITCHED || (FINAL && !NESTED), "only the full-resolution pass addresses caller memory");
+};
+enum class RawDepth : bool { AnyFormat, F32 };
+enum class Rows : bool { Packed, Pitched };
+enum class DepthKind : bool { Projected, Linear };
+enum class Window : bool { Loaded, Nested };
+template <int TILE_H = ups_tile_h(true), RawDepth RAW = RawDepth::F32, Rows ROWS = Rows::Packed, DepthKind DEPTH = DepthKind::Projected>
+using FinalForm = UpsForm<true, TILE_H, RAW == RawDepth::F32, ROWS == Rows::Pitched, DEPTH == DepthKind::Linear, false>;
+template <int TILE_H = ups_tile_h(false), Window WINDOW = Window::Loaded>
+using BlendForm = UpsForm<false, TILE_H, true, false, false, WINDOW == Window::Nested>;
+
+template <class Form>
 struct UpsLds {
-    typedef UpsTile<TILE_H> T;
+    static constexpr bool FINAL = Form::kFinal;
+    typedef UpsTile<Form::kTileH> T;
     static constexpr int kDep0 = FINAL ? 2 : 0;                                   // first row / column kept
     static constexpr int kDepH = FINAL ? T::kLowH + 4 : T::kRawH, kDepW = FINAL ? T::kLowW + 4 : T::kRawW;
     static constexpr int kDepPitch = FINAL ? 36 : T::kRawPitch;
@@ -471,10 +492,10 @@ struct UpsLds {
 // window as 16-byte row quads [LX0 - 4 + 4k, +4) -- depth and AO -- and the hi-res operands of the bilateral phase
 // (the RAW depth texels of the caller's frame in the full-resolution pass, f32 depth + AO in the blend passes).  Issued at the
 // top of the tile.
-template <int AOFMT, bool FINAL, int TILE_H>
+template <int AOFMT, class Form>
 struct UpsLoads {
     typedef AoTexel<AOFMT> AO;
-    static constexpr int kItems = 10 * UpsTile<TILE_H>::kRawH, kRounds = (kItems + kThreads - 1) / kThreads, kPasses = TILE_H / 32;
+    static constexpr int kItems = 10 * UpsTile<Form::kTileH>::kRawH, kRounds = (kItems + kThreads - 1) / kThreads, kPasses = Form::kTileH / 32;
     float4v wd[kRounds];
     typename AO::type4 wa[kRounds];
     uint4v hraw[kPasses][2];            // FINAL: four raw depth texels, undecoded (load_raw_quad)
@@ -488,7 +509,6 @@ struct UpsLoads {
 // i / 10 for 0 <= i < 1024 (the window items: 10 row quads per row) as one multiply and a shift
 __device__ __forceinline__ int tenth(int i) { return static_cast<int>((static_cast<uint32_t>(i) * 205u) >> 11); }
 
-template <bool FINAL, int TILE_H>
 __device__ __forceinline__ bool ups_tile_is_interior(const UpsampleArgs &a, int tile)
 {
     const int LX0 = ((tile % a.tiles_x) * kUpsTileW) >> 1;
@@ -498,9 +518,11 @@ __device__ __forceinline__ bool ups_tile_is_interior(const UpsampleArgs &a, int 
 // Hi-res operands.  CLAMPED: every lane loads (out-of-frame lanes re-read the frame's last row / quad and never use it),
 // so that the code is branch-free and the compiler's s_waitcnt counts stay exact.  PITCHED (final pass): raw depth rows are
 // a.pitch.depth texels apart.
-template <int AOFMT, bool FINAL, int TILE_H, bool CLAMPED, bool RAW_F32, bool PITCHED = false, bool LINEAR = false>
-__device__ __forceinline__ void ups_issue_hoisted(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, FINAL, TILE_H> &L)
+template <int AOFMT, class Form, bool CLAMPED>
+__device__ __forceinline__ void ups_issue_hoisted(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, Form> &L)
 {
+    constexpr bool FINAL = Form::kFinal, RAW_F32 = Form::kRawF32, PITCHED = Form::kPitched, LINEAR = Form::kLinear;
+    constexpr int TILE_H = Form::kTileH;
     const int tid = thread_index_opaque();
     typedef AoTexel<AOFMT> AO;
     typedef typename AO::type ao_t;
@@ -526,7 +548,7 @@ __device__ __forceinline__ void ups_issue_hoisted(const UpsampleArgs &a, const H
                 } else {
                     L.hd32[pass][f] = *reinterpret_cast<const float4v *>(at_byte_offset(
                         frame_ptr(static_cast<const float *>(a.hi_depth), a.frame_stride, frame), hrow * 4u));
-                    L.ha[pass][f] = *reinterpret_cast<const typename UpsLoads<AOFMT, FINAL, TILE_H>::ao_bits_t *>(at_byte_offset(
+                    L.ha[pass][f] = *reinterpret_cast<const typename UpsLoads<AOFMT, Form>::ao_bits_t *>(at_byte_offset(
                         frame_ptr(static_cast<const ao_t *>(a.hi_ao), a.frame_stride, frame), hrow * static_cast<uint32_t>(sizeof(ao_t))));
                 }
             }
@@ -535,9 +557,11 @@ __device__ __forceinline__ void ups_issue_hoisted(const UpsampleArgs &a, const H
 
 // The same for a tile that lies inside the frame: no clamps, one 24-bit multiply -- the rows of a lane are its first one plus
 // multiples of the level's width that are uniform (scalar).  PITCHED (final pass): of the raw depth's row stride instead.
-template <int AOFMT, bool FINAL, int TILE_H, bool RAW_F32, bool PITCHED = false, bool LINEAR = false>
-__device__ __forceinline__ void ups_issue_hoisted_inside(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, FINAL, TILE_H> &L)
+template <int AOFMT, class Form>
+__device__ __forceinline__ void ups_issue_hoisted_inside(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, Form> &L)
 {
+    constexpr bool FINAL = Form::kFinal, RAW_F32 = Form::kRawF32, PITCHED = Form::kPitched, LINEAR = Form::kLinear;
+    constexpr int TILE_H = Form::kTileH;
     const int tid = thread_index_opaque();
     typedef typename AoTexel<AOFMT>::type ao_t;
     const int HX0 = (tile % a.tiles_x) * kUpsTileW, HY0 = (tile / a.tiles_x) * TILE_H;
@@ -553,7 +577,7 @@ __device__ __forceinline__ void ups_issue_hoisted_inside(const UpsampleArgs &a, 
             } else {
                 L.hd32[pass][f] = *reinterpret_cast<const float4v *>(at_byte_offset(
                     frame_ptr(static_cast<const float *>(a.hi_depth), a.frame_stride, frame), hrow * 4u));
-                L.ha[pass][f] = *reinterpret_cast<const typename UpsLoads<AOFMT, FINAL, TILE_H>::ao_bits_t *>(at_byte_offset(
+                L.ha[pass][f] = *reinterpret_cast<const typename UpsLoads<AOFMT, Form>::ao_bits_t *>(at_byte_offset(
                     frame_ptr(static_cast<const ao_t *>(a.hi_ao), a.frame_stride, frame), hrow * static_cast<uint32_t>(sizeof(ao_t))));
             }
         }
@@ -562,12 +586,13 @@ __device__ __forceinline__ void ups_issue_hoisted_inside(const UpsampleArgs &a, 
 // All loads of an interior tile: window first, hi-res operands behind them.  The window comes from L2 (written by the
 // previous pass), the hi-res operands of the final pass from HBM; vmcnt retires loads in issue order, so with the hi-res
 // loads in front the window wait would last an HBM latency.
-template <int AOFMT, bool FINAL, int TILE_H, bool RAW_F32, bool PITCHED = false, bool LINEAR = false>
-__device__ __forceinline__ void ups_issue_interior_loads(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, FINAL, TILE_H> &L,
+template <int AOFMT, class Form>
+__device__ __forceinline__ void ups_issue_interior_loads(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, Form> &L,
                                                          bool inside)
 {
     const int tid = thread_index_opaque();
-    typedef UpsLoads<AOFMT, FINAL, TILE_H> Loads;
+    constexpr int TILE_H = Form::kTileH;
+    typedef UpsLoads<AOFMT, Form> Loads;
     typedef typename Loads::AO AO;
     typedef typename AO::type ao_t;
     const int LX0 = ((tile % a.tiles_x) * kUpsTileW) >> 1, LY0 = ((tile / a.tiles_x) * TILE_H) >> 1;
@@ -584,8 +609,8 @@ __device__ __forceinline__ void ups_issue_interior_loads(const UpsampleArgs &a, 
         L.wa[round] = *reinterpret_cast<const typename AO::type4 *>(at_byte_offset(lo_ao, idx * static_cast<uint32_t>(sizeof(ao_t))));
     }
     __builtin_amdgcn_sched_barrier(0);          // keep the issue order: window, then hi-res
-    if (inside) ups_issue_hoisted_inside<AOFMT, FINAL, TILE_H, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L);      // (wave-uniform; the same loads either way)
-    else ups_issue_hoisted<AOFMT, FINAL, TILE_H, true, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L);
+    if (inside) ups_issue_hoisted_inside<AOFMT, Form>(a, hi, tile, frame, L);      // (wave-uniform; the same loads either way)
+    else ups_issue_hoisted<AOFMT, Form, true>(a, hi, tile, frame, L);
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -612,21 +637,24 @@ struct UpsApron {
     }
 };
 
-template <bool FINAL, int TILE_H>
+template <class Form>
 __device__ __forceinline__ bool ups_tile_from_raw(const UpsampleArgs &a, int tile)
 {
-    if constexpr (!FINAL || !MEAO_X_LOWDEPTH_FROM_RAW) return false;
-    return MEAO_X_HOT_PATH_ONLY || (ups_tile_is_interior<FINAL, TILE_H>(a, tile) && (tile / a.tiles_x + 1) * TILE_H <= a.hh);
+    if constexpr (!Form::kFinal || !MEAO_X_LOWDEPTH_FROM_RAW) return false;
+    return MEAO_X_HOT_PATH_ONLY || (ups_tile_is_interior(a, tile) && (tile / a.tiles_x + 1) * Form::kTileH <= a.hh);
 }
 
 // Loads of a from-raw tile: the AO window (L2: the previous pass wrote it), the apron's raw texels (lines of the neighbouring
 // tiles' hi-res operands), the tile's own hi-res operands (HBM) -- in that order, vmcnt retires in issue order.
-template <int AOFMT, int TILE_H, bool RAW_F32, bool PITCHED = false, bool LINEAR = false>
-__device__ __forceinline__ void ups_issue_from_raw_loads(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, true, TILE_H> &L,
+template <int AOFMT, class Form>
+__device__ __forceinline__ void ups_issue_from_raw_loads(const UpsampleArgs &a, const HiDepthArgs *hi, int tile, int frame, UpsLoads<AOFMT, Form> &L,
                                                          int apron_r, int apron_k)
 {
+    static_assert(Form::kFinal, "the full-resolution pass");
     const int tid = thread_index_opaque();
-    typedef UpsLoads<AOFMT, true, TILE_H> Loads;
+    constexpr bool RAW_F32 = Form::kRawF32, PITCHED = Form::kPitched, LINEAR = Form::kLinear;
+    constexpr int TILE_H = Form::kTileH;
+    typedef UpsLoads<AOFMT, Form> Loads;
     typedef typename Loads::AO AO;
     typedef typename AO::type ao_t;
     const int HX0 = (tile % a.tiles_x) * kUpsTileW;
@@ -649,35 +677,27 @@ __device__ __forceinline__ void ups_issue_from_raw_loads(const UpsampleArgs &a, 
         L.araw[1] = load_raw_quad<RAW_F32, false>(hi->raw[frame], stored_format<LINEAR>(hi), at + 4u);
     }
     __builtin_amdgcn_sched_barrier(0);          // keep the issue order: window, apron, hi-res
-    ups_issue_hoisted_inside<AOFMT, true, TILE_H, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L);      // a from-raw tile lies inside the frame
+    ups_issue_hoisted_inside<AOFMT, Form>(a, hi, tile, frame, L);      // a from-raw tile lies inside the frame
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// NESTED: the LoResAO1 taps (s_ao) were already produced in LDS by blend_window_into_lds (the
-// previous pass of the chain evaluated inside this workgroup) instead of being read from global memory.
-// Places inside an upsample tile where every thread of the workgroup can put unrelated global loads in flight:
-// after_prefetch()   the tile's own low-res window is in LDS (its loads have landed); blur and bilateral follow
-// before_bilateral() the hoisted hi-res operands have landed too: nothing in the bilateral phase waits on vmcnt
+// The place inside an upsample tile where every thread of the workgroup can put unrelated global loads in flight:
+// before_bilateral() the tile's window is in LDS and blurred, the hoisted hi-res operands have landed too: nothing in the
+//                    bilateral phase waits on vmcnt
 struct NoHook {
     static constexpr bool kBeforeBilateral = false;
-    static constexpr bool kGroupReciprocals = true;      // bilateral_upsample_grouped
-    static constexpr bool kEstimateR8 = true;            // bilateral_upsample_r8
-    static constexpr bool kReuseEstimate = true;         // ... whose exact path starts from the estimate's reciprocals (five-reciprocal form only)
-    static constexpr bool kPairReciprocals = MEAO_X_BIL_PAIR_RCP != 0;    // three reciprocals per texel (bilateral_upsample_r8<PAIRED>)
-    __device__ __forceinline__ void after_prefetch() const {}
+    static constexpr bool kReuseEstimate = true;         // bilateral_upsample_r8's exact path starts from the estimate's reciprocals (five-reciprocal form only)
     __device__ __forceinline__ void before_bilateral() const {}
 };
 
-// RAW_F32 (FINAL): the caller's depth frames are f32 -- no format switch in the code (the other formats take the generic instance)
-// PITCHED (FINAL): the caller's surfaces are row-pitched -- raw depth rows a.pitch.depth and dst rows a.pitch.dst texels apart
-// (meao_execute_batch_pitched).  Only the addresses of caller memory change; context-owned buffers keep hw.
-// LINEAR (FINAL): the caller's depth frames are linear view-space depth (MEAO_DEPTH_LINEAR_*): f32 with RAW_F32, else f16;
-// HiResDB and the from-raw window are linearize_view of them (hi->zp0 = s).
-template <int AOFMT, bool RTNE, bool FINAL, int DIV, bool NESTED = false, typename Hook = NoHook, int TILE_H = ups_tile_h(FINAL), bool RAW_F32 = true,
-          bool PITCHED = false, bool LINEAR = false>
+// Col: the column (Column<>), Form: the form (UpsForm<>) of the tile.
+template <class Col, class Form, typename Hook = NoHook>
 __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem, int tile, int frame, Hook hook = Hook(),
                                               const HiDepthArgs *hi = nullptr)
 {
+    constexpr int AOFMT = Col::kAoFmt, DIV = Col::kDiv, TILE_H = Form::kTileH;
+    constexpr bool RTNE = Col::kRtne, FINAL = Form::kFinal, NESTED = Form::kNested;
+    constexpr bool RAW_F32 = Form::kRawF32, PITCHED = Form::kPitched, LINEAR = Form::kLinear;
     const int tid = thread_index_opaque();
     typedef AoTexel<AOFMT> AO;
     typedef typename AO::type ao_t;
@@ -689,7 +709,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
     // what the bilateral phase gathers (rows / columns 2 .. kLow+5): 22.3 KB per workgroup instead of
     // 24.1 KB, which lets a seventh workgroup share the CU's 160 KB (with __launch_bounds__(.., 7):
     // A/B on one box, 357 -> 343 us for the kernel that also carries the next downsample pass).
-    typedef UpsLds<FINAL, TILE_H> Lds;
+    typedef UpsLds<Form> Lds;
     constexpr int kDep0 = Lds::kDep0, kDepH = Lds::kDepH, kDepW = Lds::kDepW, kDepPitch = Lds::kDepPitch;
     constexpr int kInvN = Lds::kInvN, kHbN = Lds::kHbN, kDepN = Lds::kDepN, kAoN = Lds::kAoN;
     static_assert(kDepW <= kDepPitch && (T::kRawRows - T::kRawH) * T::kRawPitch <= kHbN &&
@@ -726,8 +746,6 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
     const float zp0 = FINAL ? hi->zp0 : 0.0f, zp1 = FINAL ? hi->zp1 : 0.0f;
     const float sky_depth = (FINAL && hi->reversed_z == 0) ? 1.0f : 0.0f;
     const int raw_format = LINEAR ? (RAW_F32 ? MEAO_DEPTH_F32 : MEAO_DEPTH_F16) : (FINAL && !RAW_F32) ? hi->depth_format : MEAO_DEPTH_F32;
-    static_assert(!LINEAR || (FINAL && !NESTED), "only the full-resolution pass reads the depth frames");
-    static_assert(!PITCHED || (FINAL && !NESTED), "only the full-resolution pass addresses caller memory");
     const int raw_pitch = PITCHED ? a.pitch.depth : hw, dst_pitch = PITCHED ? a.pitch.dst : hw;     // row strides of caller memory
 
     // White tiles (MEAO_X_WHITE_TILES): a tile of the full-resolution pass whose low-res AO window -- the kRawW x kRawH taps, clamp-
@@ -772,17 +790,14 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
     // The hi-res operands of the bilateral phase do not depend on anything computed here: their loads
     // are issued first, so that their latency hides behind the prefetch and blur phases.
     constexpr int kPasses = kTileH / 32;
-    typedef UpsLoads<AOFMT, FINAL, TILE_H> Loads;
+    typedef UpsLoads<AOFMT, Form> Loads;
     Loads L;
-    auto &hoist_hraw = L.hraw;
-    auto &hoist_hd32 = L.hd32;
-    auto &hoist_ha = L.ha;
     const bool hoist_ok = MEAO_X_HOT_PATH_ONLY || a.vec_ok != 0;
     // interior tile, 16-byte loads everywhere, no second AO input: window loads first (ups_issue_interior_loads)
     // full-resolution pass, tile inside the frame: no LowDepth1 read at all (ups_issue_from_raw_loads)
-    const bool from_raw = !NESTED && ups_tile_from_raw<FINAL, TILE_H>(a, tile);
-    const bool window_first = !NESTED && !from_raw && (MEAO_X_HOT_PATH_ONLY || ups_tile_is_interior<FINAL, TILE_H>(a, tile));
-    if (hoist_ok && !window_first && !from_raw) ups_issue_hoisted<AOFMT, FINAL, TILE_H, false, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L);
+    const bool from_raw = !NESTED && ups_tile_from_raw<Form>(a, tile);
+    const bool window_first = !NESTED && !from_raw && (MEAO_X_HOT_PATH_ONLY || ups_tile_is_interior(a, tile));
+    if (hoist_ok && !window_first && !from_raw) ups_issue_hoisted<AOFMT, Form, false>(a, hi, tile, frame, L);
 
     // ---- PrefetchData (UPS:54-72): raw window = virtual low-res texels
     // [LX0-3, LX0+34] x [LY0-3, LY0+kLowH+2], clamp addressing per texel.
@@ -794,7 +809,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
             int apron_r, apron_k;      // the lane's apron item, computed once: pinned, or the compiler derives it again where it is converted
             UpsApron<TILE_H>::item(min(tid, UpsApron<TILE_H>::kItems - 1), apron_r, apron_k);
             asm volatile("" : "+v"(apron_r), "+v"(apron_k));
-            ups_issue_from_raw_loads<AOFMT, TILE_H, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L, apron_r, apron_k);
+            ups_issue_from_raw_loads<AOFMT, Form>(a, hi, tile, frame, L, apron_r, apron_k);
             auto &wa = L.wa;
             lane_white = kWhiteTiles;
 #pragma unroll
@@ -835,7 +850,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
         }
     } else if (window_first) {
         constexpr int kItems = Loads::kItems, kRounds = Loads::kRounds;
-        if constexpr (!NESTED) ups_issue_interior_loads<AOFMT, FINAL, TILE_H, RAW_F32, PITCHED, LINEAR>(a, hi, tile, frame, L,
+        if constexpr (!NESTED) ups_issue_interior_loads<AOFMT, Form>(a, hi, tile, frame, L,
                                                                                        MEAO_X_HOT_PATH_ONLY || (HX0 + kUpsTileW <= hw && HY0 + kTileH <= hh));
         auto &wd = L.wd;
         auto &wa = L.wa;
@@ -932,7 +947,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
 #pragma unroll
                 for (int pass = 0; pass < kPasses; ++pass)
 #pragma unroll
-                    for (int f = 0; f < 2; ++f) rawq[2 * pass + f] = hoist_hraw[pass][f];
+                    for (int f = 0; f < 2; ++f) rawq[2 * pass + f] = L.hraw[pass][f];
                 float even[2 * kPasses][2];
                 lane_clean = hi_depth_words<RTNE, DIV, RAW_F32, 2 * kPasses, LINEAR>(rawq, raw_format, zp0, zp1, sky_depth, hd_words, even);
                 if (from_raw) {
@@ -960,7 +975,6 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
     __syncthreads();
     clk.mark(1);         // 1: barrier
     __builtin_amdgcn_s_setprio(0);       // (3 kept through the blur phases: +10 % on the pass; rising through the phases: +2 %, r03)
-    hook.after_prefetch();
     if constexpr (kWhiteTiles) {
         uint32_t all_white = s_white[0];
 #pragma unroll
@@ -1053,7 +1067,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
             if constexpr (FINAL) {
                 // (the raw depth quads were consumed in front of the barrier: nothing of this tile is in flight any more)
             } else {
-                asm volatile("" : : "v"(hoist_hd32[pass][0]), "v"(hoist_hd32[pass][1]), "v"(hoist_ha[pass][0]), "v"(hoist_ha[pass][1]));
+                asm volatile("" : : "v"(L.hd32[pass][0]), "v"(L.hd32[pass][1]), "v"(L.ha[pass][0]), "v"(L.ha[pass][1]));
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -1069,7 +1083,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
 #pragma unroll
         for (int pass = 0; pass < kPasses; ++pass)
 #pragma unroll
-            for (int f = 0; f < 2; ++f) asm volatile("" : "+v"(hoist_ha[pass][f]));
+            for (int f = 0; f < 2; ++f) asm volatile("" : "+v"(L.ha[pass][f]));
     }
     const bool vec_ok_frame = MEAO_X_HOT_PATH_ONLY || a.vec_ok != 0;       // hw % 4 == 0 and (final pass) 4-texel aligned caller pointers
     // Gather component order x=(c-1,c) y=(c,c) z=(c,c-1) w=(c-1,c-1) as (col,row) offsets
@@ -1126,8 +1140,8 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                     const float *p = frame_ptr(static_cast<const float *>(a.hi_depth), a.frame_stride, frame) + hrow;
                     const ao_t *q = frame_ptr(static_cast<const ao_t *>(a.hi_ao), a.frame_stride, frame) + hrow;
                     if (vec_ok) {
-                        const float4v d4 = hoist_hd32[pass][f];
-                        const typename Loads::ao_bits_t a4 = hoist_ha[pass][f];
+                        const float4v d4 = L.hd32[pass][f];
+                        const typename Loads::ao_bits_t a4 = L.ha[pass][f];
                         hd[0] = d4.x; hd[1] = d4.y; hd[2] = d4.z; hd[3] = d4.w;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) ha[e] = AO::decode(static_cast<ao_t>(a4 >> (8 * sizeof(ao_t) * e)));
@@ -1140,7 +1154,7 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                     }
                 }
                 ao_t res[4];
-                if constexpr (!MEAO_X_UPS_EXACT_R8 && Hook::kEstimateR8 && DIV == DIV_EXACT_RCP && AOFMT == MEAO_AO_R8) {
+                if constexpr (!MEAO_X_UPS_EXACT_R8 && DIV == DIV_EXACT_RCP && AOFMT == MEAO_AO_R8) {
                     // UNORM8 storage: the code from the uncorrected reciprocals wherever that provably is the reference's code
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -1153,33 +1167,27 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
                             gd[i] = dl[rr + gy[g]][cc + gx[g]];
                             ga[i] = vb[rr + gy[g]][cc + gx[g]];
                         }
-                        res[e] = static_cast<ao_t>(bilateral_upsample_r8<Hook::kGroupReciprocals, !NESTED && Hook::kReuseEstimate && !Hook::kPairReciprocals,
-                                                                          Hook::kPairReciprocals>(hd[e], ha[e], gd, ga, bilateral_k));
+                        constexpr bool kPaired = MEAO_X_BIL_PAIR_RCP != 0;      // three reciprocals per texel
+                        res[e] = static_cast<ao_t>(bilateral_upsample_r8<!NESTED && Hook::kReuseEstimate && !kPaired, kPaired>(hd[e], ha[e], gd, ga, bilateral_k));
                     }
-                } else if constexpr (DIV == DIV_EXACT_RCP && Hook::kGroupReciprocals) {
+                } else if constexpr (DIV == DIV_EXACT_RCP) {
                     // The four weight reciprocals of a texel back to back: an isolated v_rcp_f32 costs the SIMD ~3 cycles more than
                     // one that follows another (tools/ubench_issue.hip "bilateral mix": 3.81 -> 3.55 cycles per instruction).  A/B:
                     // L2->L1 65 -> 58.5 us, L1->L0 202.5 -> 199.2 us; two texels per group: the same (profiles/r03_ab_rcp_group*.jsonl).
-                    constexpr int kGroup = 1;             // texels whose reciprocals are issued together
 #pragma unroll
-                    for (int e0 = 0; e0 < 4; e0 += kGroup) {
-                        float gd[kGroup][4], ga[kGroup][4], ghd[kGroup], gha[kGroup], gout[kGroup];
+                    for (int e = 0; e < 4; ++e) {
+                        const int cc = ((e + 1) >> 1) + 1, rr = f + 1;
+                        const int comp = (e & 1) ? ((f & 1) ? 3 : 0) : ((f & 1) ? 2 : 1);
+                        float gd[1][4], ga[1][4], gout[1];
 #pragma unroll
-                        for (int t = 0; t < kGroup; ++t) {
-                            const int e = e0 + t;
-                            const int cc = ((e + 1) >> 1) + 1, rr = f + 1;
-                            const int comp = (e & 1) ? ((f & 1) ? 3 : 0) : ((f & 1) ? 2 : 1);
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int g = (comp + i) & 3;
-                                gd[t][i] = dl[rr + gy[g]][cc + gx[g]];
-                                ga[t][i] = vb[rr + gy[g]][cc + gx[g]];
-                            }
-                            ghd[t] = hd[e]; gha[t] = ha[e];
+                        for (int i = 0; i < 4; ++i) {
+                            const int g = (comp + i) & 3;
+                            gd[0][i] = dl[rr + gy[g]][cc + gx[g]];
+                            ga[0][i] = vb[rr + gy[g]][cc + gx[g]];
                         }
-                        bilateral_upsample_grouped<kGroup>(ghd, gha, gd, ga, bilateral_k, gout);
-#pragma unroll
-                        for (int t = 0; t < kGroup; ++t) res[e0 + t] = AO::template encode<RTNE>(gout[t]);
+                        const float ghd[1] = {hd[e]}, gha[1] = {ha[e]};
+                        bilateral_upsample_grouped<1>(ghd, gha, gd, ga, bilateral_k, gout);
+                        res[e] = AO::template encode<RTNE>(gout[0]);
                     }
                 } else
 #pragma unroll
@@ -1254,18 +1262,18 @@ __device__ __forceinline__ void upsample_tile(const UpsampleArgs &a, float *smem
 }
 
 // The (rare) hostile-frame variant of a tile: the same code with IEEE division.
-template <int AOFMT, bool RTNE, bool FINAL, int DIV, typename Hook = NoHook, int TILE_H = ups_tile_h(FINAL), bool RAW_F32 = true,
-          bool PITCHED = false, bool LINEAR = false>
+template <class Col, class Form, typename Hook = NoHook>
 __device__ __forceinline__ void upsample_tile_checked(const UpsampleArgs &a, float *smem, int tile, int frame, Hook hook = Hook(),
                                                       const HiDepthArgs *hi = nullptr)
 {
-    if constexpr (DIV == DIV_EXACT_RCP) {
+    static_assert(!Form::kNested, "a nested tile runs with the division its window was made with");
+    if constexpr (Col::kDiv == DIV_EXACT_RCP) {
         if (frame_is_hostile(a.hostile, a.generation, frame)) {       // wave-uniform, decided per frame
-            upsample_tile<AOFMT, RTNE, FINAL, DIV_IEEE, false, Hook, TILE_H, RAW_F32, PITCHED, LINEAR>(a, smem, tile, frame, hook, hi);
+            upsample_tile<Column<Col::kAoFmt, Col::kRtne, DIV_IEEE>, Form, Hook>(a, smem, tile, frame, hook, hi);
             return;
         }
     }
-    upsample_tile<AOFMT, RTNE, FINAL, DIV, false, Hook, TILE_H, RAW_F32, PITCHED, LINEAR>(a, smem, tile, frame, hook, hi);
+    upsample_tile<Col, Form, Hook>(a, smem, tile, frame, hook, hi);
 }
 
 

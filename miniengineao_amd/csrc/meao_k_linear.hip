@@ -21,17 +21,17 @@ __global__ __launch_bounds__(kThreads) void downsample_linear_kernel(const Downs
 template <int AOFMT, bool RTNE, int DIV, bool F32>
 __global__ __launch_bounds__(kThreads, 7) void upsample_final_linear_kernel(const UpsampleArgs a, const HiDepthArgs hi)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true>::kFloats];
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, ups_tile_h(true), F32, true, true>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x),
-                                                                                          blockIdx.z, NoHook(), &hi);
+    typedef FinalForm<ups_tile_h(true), RawDepth(F32), Rows::Pitched, DepthKind::Linear> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z, NoHook(), &hi);
 }
 
 template <int AOFMT, bool RTNE, int DIV, bool F32>
 __global__ __launch_bounds__(kThreads) void upsample_final_small_linear_kernel(const UpsampleArgs a, const HiDepthArgs hi)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true, kUpsTileHSmall>::kFloats];
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, kUpsTileHSmall, F32, true, true>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x),
-                                                                                        blockIdx.z, NoHook(), &hi);
+    typedef FinalForm<kUpsTileHSmall, RawDepth(F32), Rows::Pitched, DepthKind::Linear> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z, NoHook(), &hi);
 }
 
 // LinearDepth (debug id 1) of a linear frame: f16(linearize_view(z)), packed frame

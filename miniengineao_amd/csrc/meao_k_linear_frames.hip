@@ -18,23 +18,23 @@ __global__ __launch_bounds__(kThreads) void downsample_linear_frames_kernel(cons
 template <int AOFMT, bool RTNE, int DIV, bool F32>
 __global__ __launch_bounds__(kThreads, 7) void upsample_final_linear_frames_kernel(const UpsampleArgs *t, const HiDepthArgs *th)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true>::kFloats];
+    typedef FinalForm<ups_tile_h(true), RawDepth(F32), Rows::Pitched, DepthKind::Linear> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
     const UpsampleArgs &a = frame_block(t, blockIdx.z);
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x);
     if (beyond_frame(tile, a.tiles_x * a.tiles_y)) return;
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, ups_tile_h(true), F32, true, true>(a, smem, tile, blockIdx.z, NoHook(),
-                                                                                          &frame_block(th, blockIdx.z));
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, tile, blockIdx.z, NoHook(), &frame_block(th, blockIdx.z));
 }
 
 template <int AOFMT, bool RTNE, int DIV, bool F32>
 __global__ __launch_bounds__(kThreads) void upsample_final_small_linear_frames_kernel(const UpsampleArgs *t, const HiDepthArgs *th)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true, kUpsTileHSmall>::kFloats];
+    typedef FinalForm<kUpsTileHSmall, RawDepth(F32), Rows::Pitched, DepthKind::Linear> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
     const UpsampleArgs &a = frame_block(t, blockIdx.z);
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x);
     if (beyond_frame(tile, a.tiles_x * a.tiles_y)) return;
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, kUpsTileHSmall, F32, true, true>(a, smem, tile, blockIdx.z, NoHook(),
-                                                                                        &frame_block(th, blockIdx.z));
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, tile, blockIdx.z, NoHook(), &frame_block(th, blockIdx.z));
 }
 
 }  // namespace

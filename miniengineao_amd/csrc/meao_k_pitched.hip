@@ -19,17 +19,17 @@ __global__ __launch_bounds__(kThreads) void downsample_pitched_kernel(const Down
 template <int AOFMT, bool RTNE, int DIV, bool RAW_F32>
 __global__ __launch_bounds__(kThreads, RAW_F32 ? 7 : 6) void upsample_final_pitched_kernel(const UpsampleArgs a, const HiDepthArgs hi)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true>::kFloats];
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, ups_tile_h(true), RAW_F32, true>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x),
-                                                                                        blockIdx.z, NoHook(), &hi);
+    typedef FinalForm<ups_tile_h(true), RawDepth(RAW_F32), Rows::Pitched> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z, NoHook(), &hi);
 }
 
 template <int AOFMT, bool RTNE, int DIV, bool RAW_F32>
 __global__ __launch_bounds__(kThreads) void upsample_final_small_pitched_kernel(const UpsampleArgs a, const HiDepthArgs hi)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true, kUpsTileHSmall>::kFloats];
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, kUpsTileHSmall, RAW_F32, true>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x),
-                                                                                      blockIdx.z, NoHook(), &hi);
+    typedef FinalForm<kUpsTileHSmall, RawDepth(RAW_F32), Rows::Pitched> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z, NoHook(), &hi);
 }
 
 }  // namespace

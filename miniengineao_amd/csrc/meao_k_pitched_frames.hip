@@ -18,23 +18,23 @@ __global__ __launch_bounds__(kThreads) void downsample_pitched_frames_kernel(con
 template <int AOFMT, bool RTNE, int DIV, bool RAW_F32>
 __global__ __launch_bounds__(kThreads, RAW_F32 ? 7 : 6) void upsample_final_pitched_frames_kernel(const UpsampleArgs *t, const HiDepthArgs *th)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true>::kFloats];
+    typedef FinalForm<ups_tile_h(true), RawDepth(RAW_F32), Rows::Pitched> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
     const UpsampleArgs &a = frame_block(t, blockIdx.z);
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x);
     if (beyond_frame(tile, a.tiles_x * a.tiles_y)) return;
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, ups_tile_h(true), RAW_F32, true>(a, smem, tile, blockIdx.z, NoHook(),
-                                                                                        &frame_block(th, blockIdx.z));
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, tile, blockIdx.z, NoHook(), &frame_block(th, blockIdx.z));
 }
 
 template <int AOFMT, bool RTNE, int DIV, bool RAW_F32>
 __global__ __launch_bounds__(kThreads) void upsample_final_small_pitched_frames_kernel(const UpsampleArgs *t, const HiDepthArgs *th)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true, kUpsTileHSmall>::kFloats];
+    typedef FinalForm<kUpsTileHSmall, RawDepth(RAW_F32), Rows::Pitched> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
     const UpsampleArgs &a = frame_block(t, blockIdx.z);
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x);
     if (beyond_frame(tile, a.tiles_x * a.tiles_y)) return;
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, kUpsTileHSmall, RAW_F32, true>(a, smem, tile, blockIdx.z, NoHook(),
-                                                                                      &frame_block(th, blockIdx.z));
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, tile, blockIdx.z, NoHook(), &frame_block(th, blockIdx.z));
 }
 
 }  // namespace

@@ -8,8 +8,9 @@ namespace {
 template <int AOFMT, bool RTNE, int DIV>
 __global__ __launch_bounds__(kThreads, 1) void upsample_kernel(const UpsampleArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<false>::kFloats];
-    upsample_tile_checked<AOFMT, RTNE, false, DIV>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z);
+    typedef BlendForm<> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z);
 }
 
 // Upsample.main: the full-resolution pass.  HiResDB comes from the caller's raw depth frames (HiDepthArgs); RAW_F32 = they are f32
@@ -17,9 +18,9 @@ __global__ __launch_bounds__(kThreads, 1) void upsample_kernel(const UpsampleArg
 template <int AOFMT, bool RTNE, int DIV, bool RAW_F32>
 __global__ __launch_bounds__(kThreads, RAW_F32 ? 7 : 6) void upsample_final_kernel(const UpsampleArgs a, const HiDepthArgs hi)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true>::kFloats];
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, ups_tile_h(true), RAW_F32>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z,
-                                                                                  NoHook(), &hi);
+    typedef FinalForm<ups_tile_h(true), RawDepth(RAW_F32)> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z, NoHook(), &hi);
 }
 
 // Upsample.main for calls with few tiles (one 1080p frame: 510 tiles of 64 x 64 on 256 CUs): 64 x 32 tiles, twice
@@ -27,9 +28,9 @@ __global__ __launch_bounds__(kThreads, RAW_F32 ? 7 : 6) void upsample_final_kern
 template <int AOFMT, bool RTNE, int DIV, bool RAW_F32>
 __global__ __launch_bounds__(kThreads) void upsample_final_small_kernel(const UpsampleArgs a, const HiDepthArgs hi)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true, kUpsTileHSmall>::kFloats];
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, kUpsTileHSmall, RAW_F32>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z,
-                                                                                NoHook(), &hi);
+    typedef FinalForm<kUpsTileHSmall, RawDepth(RAW_F32)> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z, NoHook(), &hi);
 }
 
 // Upsample.main_blendout with the full-resolution pass's 64 x 64 tiles, for launches of many tiles (L2 -> L1 of a batch: 16 320 tiles
@@ -38,8 +39,9 @@ __global__ __launch_bounds__(kThreads) void upsample_final_small_kernel(const Up
 template <int AOFMT, bool RTNE, int DIV>
 __global__ __launch_bounds__(kThreads, 6) void upsample_blend_tall_kernel(const UpsampleArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<false, kUpsTileHTall>::kFloats];
-    upsample_tile_checked<AOFMT, RTNE, false, DIV, NoHook, kUpsTileHTall>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z);
+    typedef BlendForm<kUpsTileHTall> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z);
 }
 
 }  // namespace

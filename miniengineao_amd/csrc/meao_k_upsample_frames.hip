@@ -10,43 +10,45 @@ namespace {
 template <int AOFMT, bool RTNE, int DIV>
 __global__ __launch_bounds__(kThreads, 1) void upsample_frames_kernel(const UpsampleArgs *t)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<false>::kFloats];
+    typedef BlendForm<> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
     const UpsampleArgs &a = frame_block(t, blockIdx.z);
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x);
     if (beyond_frame(tile, a.tiles_x * a.tiles_y)) return;
-    upsample_tile_checked<AOFMT, RTNE, false, DIV>(a, smem, tile, blockIdx.z);
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, tile, blockIdx.z);
 }
 
 template <int AOFMT, bool RTNE, int DIV, bool RAW_F32>
 __global__ __launch_bounds__(kThreads, RAW_F32 ? 7 : 6) void upsample_final_frames_kernel(const UpsampleArgs *t, const HiDepthArgs *th)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true>::kFloats];
+    typedef FinalForm<ups_tile_h(true), RawDepth(RAW_F32)> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
     const UpsampleArgs &a = frame_block(t, blockIdx.z);
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x);
     if (beyond_frame(tile, a.tiles_x * a.tiles_y)) return;
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, ups_tile_h(true), RAW_F32>(a, smem, tile, blockIdx.z, NoHook(),
-                                                                                  &frame_block(th, blockIdx.z));
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, tile, blockIdx.z, NoHook(), &frame_block(th, blockIdx.z));
 }
 
 template <int AOFMT, bool RTNE, int DIV, bool RAW_F32>
 __global__ __launch_bounds__(kThreads) void upsample_final_small_frames_kernel(const UpsampleArgs *t, const HiDepthArgs *th)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true, kUpsTileHSmall>::kFloats];
+    typedef FinalForm<kUpsTileHSmall, RawDepth(RAW_F32)> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
     const UpsampleArgs &a = frame_block(t, blockIdx.z);
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x);
     if (beyond_frame(tile, a.tiles_x * a.tiles_y)) return;
-    upsample_tile_checked<AOFMT, RTNE, true, DIV, NoHook, kUpsTileHSmall, RAW_F32>(a, smem, tile, blockIdx.z, NoHook(),
-                                                                                &frame_block(th, blockIdx.z));
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, tile, blockIdx.z, NoHook(), &frame_block(th, blockIdx.z));
 }
 
 template <int AOFMT, bool RTNE, int DIV>
 __global__ __launch_bounds__(kThreads, 6) void upsample_blend_tall_frames_kernel(const UpsampleArgs *t)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<false, kUpsTileHTall>::kFloats];
+    typedef BlendForm<kUpsTileHTall> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
     const UpsampleArgs &a = frame_block(t, blockIdx.z);
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x);
     if (beyond_frame(tile, a.tiles_x * a.tiles_y)) return;
-    upsample_tile_checked<AOFMT, RTNE, false, DIV, NoHook, kUpsTileHTall>(a, smem, tile, blockIdx.z);
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, tile, blockIdx.z);
 }
 
 }  // namespace

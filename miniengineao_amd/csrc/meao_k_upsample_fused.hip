@@ -16,12 +16,13 @@ template <int AOFMT, bool RTNE, int DIV>
 __global__ __launch_bounds__(kThreads, 7) void upsample_final_with_next_downsample_kernel(const UpsampleArgs a, const HiDepthArgs hi,
                                                                                        const DownsampleArgs d)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<true>::kFloats];
+    typedef FinalForm<> Form;
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<Form>::kFloats];
     const bool mine = blockIdx.x < static_cast<unsigned>(d.tiles_x * d.tiles_y) && blockIdx.z < static_cast<unsigned>(d.frames);
     float4v q[2];
     const bool full = (static_cast<int>(blockIdx.x) / d.tiles_x + 1) * kLeanRows <= d.h[1];
     const IssueCarriedLoadsLean issue = {d, q, mine, full, static_cast<int>(blockIdx.x), static_cast<int>(blockIdx.z)};
-    upsample_tile_checked<AOFMT, RTNE, true, DIV>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z, issue, &hi);
+    upsample_tile_checked<Column<AOFMT, RTNE, DIV>, Form>(a, smem, xcd_contiguous(blockIdx.x, gridDim.x), blockIdx.z, issue, &hi);
     if (mine) {
         if (full) downsample_lean_finish<DIV, true>(d, blockIdx.x, blockIdx.z, q);
         else downsample_lean_finish<DIV, false>(d, blockIdx.x, blockIdx.z, q);

@@ -9,7 +9,7 @@ namespace {
 template <int AOFMT, bool RTNE, int DIV>
 __global__ __launch_bounds__(kThreads, 8) void upsample_two_level_kernel(const UpsampleArgs outer, const UpsampleArgs inner)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<false>::kFloats];
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<NestedForm>::kFloats];
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x), frame = blockIdx.z;
     if constexpr (DIV == DIV_EXACT_RCP) {
         if (frame_is_hostile(outer.hostile, outer.generation, frame)) {
@@ -25,7 +25,7 @@ template <int AOFMT, bool RTNE, int DIV>
 __global__ __launch_bounds__(kThreads) void upsample_three_level_kernel(const UpsampleArgs outer, const UpsampleArgs mid,
                                                                         const UpsampleArgs inner)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<false>::kFloats + kNestScratch];
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<NestedForm>::kFloats + kNestScratch];
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x), frame = blockIdx.z;
     if constexpr (DIV == DIV_EXACT_RCP) {
         if (frame_is_hostile(outer.hostile, outer.generation, frame)) {

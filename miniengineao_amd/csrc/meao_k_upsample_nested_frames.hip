@@ -9,7 +9,7 @@ namespace {
 template <int AOFMT, bool RTNE, int DIV>
 __global__ __launch_bounds__(kThreads, 8) void upsample_two_level_frames_kernel(const UpsampleArgs *t_outer, const UpsampleArgs *t_inner)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<false>::kFloats];
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<NestedForm>::kFloats];
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x), frame = blockIdx.z;
     const UpsampleArgs &outer = frame_block(t_outer, frame), &inner = frame_block(t_inner, frame);
     if (beyond_frame(tile, outer.tiles_x * outer.tiles_y)) return;
@@ -26,7 +26,7 @@ template <int AOFMT, bool RTNE, int DIV>
 __global__ __launch_bounds__(kThreads) void upsample_three_level_frames_kernel(const UpsampleArgs *t_outer, const UpsampleArgs *t_mid,
                                                                                const UpsampleArgs *t_inner)
 {
-    __shared__ __attribute__((aligned(16))) float smem[UpsLds<false>::kFloats + kNestScratch];
+    __shared__ __attribute__((aligned(16))) float smem[UpsLds<NestedForm>::kFloats + kNestScratch];
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x), frame = blockIdx.z;
     const UpsampleArgs &outer = frame_block(t_outer, frame), &mid = frame_block(t_mid, frame), &inner = frame_block(t_inner, frame);
     if (beyond_frame(tile, outer.tiles_x * outer.tiles_y)) return;

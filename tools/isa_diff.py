@@ -3,6 +3,8 @@
 kernel source is codegen-neutral, or lists the kernels it touched.
 
     python tools/isa_diff.py <git-rev | path/to/meao_kernels.hip> [-DFLAG ...]     # against the working tree
+
+Exit status 1 when a kernel changed, appeared or disappeared.
 """
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,9 +41,8 @@ def main():
             listing = subprocess.run(["git", "ls-tree", "--name-only", f"{ref}:miniengineao_amd/csrc/"], cwd=ROOT, check=True,
                                      capture_output=True, text=True).stdout.split()
             for f in listing:
-                if f.endswith((".hip", ".hpp")):
-                    open(os.path.join(tmp, f), "w").write(subprocess.run(
-                        ["git", "show", f"{ref}:miniengineao_amd/csrc/{f}"], cwd=ROOT, check=True, capture_output=True, text=True).stdout)
+                open(os.path.join(tmp, f), "w").write(subprocess.run(
+                    ["git", "show", f"{ref}:miniengineao_amd/csrc/{f}"], cwd=ROOT, check=True, capture_output=True, text=True).stdout)
             src = open(os.path.join(tmp, "meao_kernels.hpp")).read().replace('"../../include/meao.h"', '"meao.h"')
             open(os.path.join(tmp, "meao_kernels.hpp"), "w").write(src)
         old_units = [u for u in build.KERNEL_UNITS if os.path.exists(os.path.join(old_dir, u))] or ["meao_kernels.hip"]
@@ -53,7 +54,7 @@ def main():
     strip = re.compile(r"^void |meao::\(anonymous namespace\)::")
     for k, n in zip(changed, names):
         print("  %6d -> %6d instructions  %s" % (len(a[k]), len(b[k]), strip.sub("", n)[:110]))
-    return 0
+    return 1 if changed or set(a) ^ set(b) else 0
 
 if __name__ == "__main__":
     sys.exit(main())
