@@ -1,8 +1,8 @@
-// MeaoNative.cs -- P/Invoke declarations for libmeao_hip.so (include/meao.h, ABI version 6).
+// MeaoNative.cs -- P/Invoke declarations for libmeao_hip.so (include/meao.h, ABI version 7).
 //
 // NOT COMPILED IN THIS REPOSITORY'S ENVIRONMENT: the build image has no dotnet/mono/csc
-// (SURVEY.md, "Environment facts").  tests/test_host_mirror.py cross-checks every
-// [DllImport] below against the C header (names, arity, struct field order) instead.
+// (SURVEY.md, "Environment facts").  tests/test_abi_mirrors.py checks every
+// [DllImport], struct, enum and constant below against the C header (names, types, order, values) instead.
 //
 // One extern per C entry point; struct layouts are sequential and mirror the C structs
 // field by field (all members are 4-byte scalars except meao_desc.bytes).
@@ -119,7 +119,7 @@ namespace MiniEngineAO.Native
     public static class Meao
     {
         const string Lib = "meao_hip";   // libmeao_hip.so
-        public const int AbiVersion = 6;
+        public const int AbiVersion = 7;
         public const int MaxBatch = 64;
         public const int NumPasses = 7;
         public const int DebugOcclusionHq1 = 18;
@@ -216,7 +216,7 @@ namespace MiniEngineAO.Native
         [DllImport(Lib)] public static extern int meao_pool_member_placement(IntPtr pool, int member, out int numa_node, out int worker_bound);
         [DllImport(Lib)] public static extern int meao_hostile_frames(IntPtr ctx, out ulong mask);
         [DllImport(Lib)] public static extern int meao_debug_set(IntPtr ctx, int key, int value);   // launch-structure overrides (tests, A/B runs)
-        [DllImport(Lib)] public static extern int meao_debug_view(IntPtr ctx, int frame, int debug_id, IntPtr dst, int out_loc, IntPtr stream);
+        [DllImport(Lib)] public static extern int meao_debug_view(IntPtr ctx, int frame, int debug_id, IntPtr @out, int out_loc, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_composite(IntPtr ctx, int mode, IntPtr ao, IntPtr color_rgba16f, IntPtr gbuffer0_rgba8, int loc, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_composite_pitched(IntPtr ctx, int mode, IntPtr ao, ulong ao_pitch, IntPtr color_rgba16f, ulong color_pitch, IntPtr gbuffer0_rgba8, ulong gbuffer0_pitch, int loc, IntPtr stream);
         [DllImport(Lib)] public static extern int meao_composite_format(IntPtr ctx, int mode, IntPtr ao, ulong ao_pitch, IntPtr color, int color_format, ulong color_pitch, IntPtr gbuffer0_rgba8, ulong gbuffer0_pitch, int loc, IntPtr stream);

@@ -1,5 +1,6 @@
-"""C-ABI library: loads, exports every symbol include/meao.h declares, host-side plan functions
-agree with the oracle, error behaviour.  No compute calls here (CPU suite, no GPU needed)."""
+"""C-ABI library: host-side plan functions agree with the oracle, error behaviour, what the product links and imports.  No compute
+calls here (CPU suite, no GPU needed).  That the library exports what the header declares, and that the mirrors match it, is
+tests/test_abi_mirrors.py."""
 import ctypes as C
 import os
 import re
@@ -13,26 +14,6 @@ from miniengineao_amd import synth
 from tests import helpers as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-with open(os.path.join(ROOT, "include", "meao.h")) as _f:
-    HEADER = _f.read()
-
-
-def header_functions():
-    return re.findall(r"MEAO_API\s+[\w\s\*]+?\b(meao_\w+)\s*\(", HEADER)
-
-
-def test_header_declares_what_the_binding_binds():
-    declared = set(header_functions())
-    assert len(declared) >= 24
-    assert declared == set(L.SIGNATURES), declared ^ set(L.SIGNATURES)
-
-
-def test_library_exports_every_declared_symbol(meao_lib):
-    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (meao_\w+)", out))
-    assert set(header_functions()) <= exported
-    assert all(not s.startswith("meao_oracle") for s in exported), "oracle code must not be in the product library"
-    assert meao_lib.meao_abi_version() == L.ABI_VERSION
 
 
 def test_product_library_does_not_link_the_oracle():
@@ -40,22 +21,6 @@ def test_product_library_does_not_link_the_oracle():
     needed = re.findall(r"NEEDED\s+(\S+)", out)
     assert any("amdhip64" in n for n in needed)
     assert not any("oracle" in n or "torch" in n or "python" in n for n in needed), needed
-
-
-def test_struct_layouts_match_header():
-    # every member is a 4-byte scalar except meao_desc.bytes (u64, naturally aligned)
-    assert C.sizeof(L.Config) == 12 * 4 and C.sizeof(L.Params) == 11 * 4
-    assert C.sizeof(L.Desc) == 32 and L.Desc.bytes.offset == 24
-    assert C.sizeof(L.RenderConstants) == 28 * 4 and C.sizeof(L.UpsampleConstants) == 8 * 4
-    for struct, cname in ((L.Config, "meao_config"), (L.Params, "meao_params"), (L.Desc, "meao_desc")):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), HEADER, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if decl:
-                names += [n.strip() for n in decl.split(None, 1)[1].split(",")]
-        assert names == [f[0] for f in struct._fields_], cname
 
 
 def test_defaults_are_the_reference_defaults(meao_lib):

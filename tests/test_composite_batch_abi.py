@@ -1,10 +1,9 @@
-"""meao_composite_batch, meao_execute_batch_shaded and meao_pool_execute_batch_shaded: the ABI surface in every binding, what
-needs no device of their argument checks, and the rule that the batched form lives inside composite_kernel<0|1>: no new
-instantiation, the resources of the two kernels as they were."""
+"""meao_composite_batch, meao_execute_batch_shaded and meao_pool_execute_batch_shaded: the contracts the header states, the C#
+wrapper and the Python signatures, what needs no device of their argument checks, and the rule that the batched form lives
+inside composite_kernel<0|1>: no new instantiation, the resources of the two kernels as they were."""
 import ctypes as C
 import json
 import os
-import re
 import shutil
 import subprocess
 import sys
@@ -12,22 +11,18 @@ import sys
 import pytest
 
 from miniengineao_amd import _lib as L
+from tests import abi_model as A
 from tests import kernel_inventory as K
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "meao.h")).read()
-
-NEW = {"meao_composite_batch": 11, "meao_execute_batch_shaded": 14, "meao_pool_execute_batch_shaded": 13}
 
 
-@pytest.mark.parametrize("name", sorted(NEW))
+@pytest.mark.parametrize("name", ["meao_composite_batch", "meao_execute_batch_shaded", "meao_pool_execute_batch_shaded"])
 def test_entry_point_in_the_header(name):
-    m = re.search(r"MEAO_API\s+int32_t\s+%s\s*\((.*?)\);" % name, HEADER, re.S)
-    assert m, name
-    args = [" ".join(a.split()) for a in m.group(1).split(",")]
-    assert len(args) == NEW[name], args
+    """Where the feature's arguments sit (the whole prototype, with its types and count, is pinned by tests/abi_snapshot.json)."""
+    args = A.prototype(name)
     at = args.index("int32_t color_format")
-    assert args[at - 1].endswith("color") and args[at + 1] == "uint64_t color_pitch"
+    assert args[at - 1].endswith("color") and args[at + 1] == "uint64_t color_pitch"         # inserted after `color`
     for pitch in ("uint64_t ao_pitch", "uint64_t color_pitch", "uint64_t gbuffer0_pitch"):
         assert pitch in args, (name, pitch)
     assert ("meao_stream stream" in args) == (not name.startswith("meao_pool")), args
@@ -36,29 +31,16 @@ def test_entry_point_in_the_header(name):
 
 
 def test_the_contracts_are_in_the_header():
-    text = " ".join(HEADER.split())
+    text = A.header_prose()
     for phrase in ("ONE composite_kernel launch", "before anything is enqueued", "must not overlap", "neither run nor disturbed",
                    "meao_composite_pending is unchanged"):
         assert phrase in text, phrase
 
 
-@pytest.mark.parametrize("name", sorted(NEW))
+@pytest.mark.parametrize("name", ["meao_composite_batch", "meao_execute_batch_shaded"])
 def test_entry_point_in_every_binding(name):
-    assert len(L.SIGNATURES[name][1]) == NEW[name]
-    cs = open(os.path.join(ROOT, "bindings", "csharp", "MeaoNative.cs")).read()
-    m = re.search(r"public static extern int %s\((.*?)\);" % name, cs)
-    assert m and len(m.group(1).split(",")) == NEW[name] and "int color_format" in m.group(1), name
-    assert "%s(" % name in open(os.path.join(ROOT, "include", "meao.hpp")).read()
-    if not name.startswith("meao_pool"):
-        assert "Meao.%s(" % name in open(os.path.join(ROOT, "bindings", "csharp", "AmbientOcclusionOverMeao.cs")).read()
-
-
-def test_abi_version_sizes_and_exports(meao_lib):
-    assert re.search(r"#define MEAO_ABI_VERSION 7\b", HEADER) and L.ABI_VERSION == 7
-    assert meao_lib.meao_abi_version() == 7
-    assert C.sizeof(L.Config) == 12 * 4 and C.sizeof(L.Params) == 11 * 4 and C.sizeof(L.Desc) == 32
-    for name in NEW:
-        assert hasattr(meao_lib, name), name
+    """(The imports, signatures and the C++ wrapper's calls are tests/test_abi_mirrors.py.)  The C# wrapper calls it."""
+    assert "Meao.%s(" % name in open(os.path.join(ROOT, "bindings", "csharp", "AmbientOcclusionOverMeao.cs")).read()
 
 
 def test_entry_points_reject_null_handles(meao_lib):

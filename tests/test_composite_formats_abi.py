@@ -1,63 +1,40 @@
 """The composite into RGBA32F, RGBA8 and R11G11B10F colour targets (meao_composite_format, meao_composite_enqueue_format,
-meao_pool_composite_enqueue_format): the ABI surface in every binding, argument checks that need no device, the tensor layouts
-composite_surfaces accepts under its color_format keyword, and the rule that the formats live in the kernels that already
-composite: no new instantiation."""
+meao_pool_composite_enqueue_format): what the header leaves open, the C# wrapper, argument checks that need no device, the
+tensor layouts composite_surfaces accepts under its color_format keyword, and the rule that the formats live in the kernels that
+already composite: no new instantiation."""
 import ctypes as C
 import os
-import re
 
 import pytest
 import torch
 
 from miniengineao_amd import _lib as L
 from miniengineao_amd.surfaces import composite_surfaces
+from tests import abi_model as A
 from tests import kernel_inventory as K
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "meao.h")).read()
-
-NEW = {"meao_composite_format": 11, "meao_composite_enqueue_format": 10, "meao_pool_composite_enqueue_format": 10}
-
 COMPOSITE_KERNELS = {"composite_kernel<0>", "composite_kernel<1>"} | {
     "render_with_composite_kernel<%d, %s, %d>" % (fmt, rtne, div)
     for fmt in (0, 1) for rtne, div in (("false", 0), ("false", 1), ("true", 1))}
 
 
-@pytest.mark.parametrize("name", sorted(NEW))
+@pytest.mark.parametrize("name", ["meao_composite_format", "meao_composite_enqueue_format", "meao_pool_composite_enqueue_format"])
 def test_entry_point_in_the_header(name):
-    m = re.search(r"MEAO_API\s+int32_t\s+%s\s*\((.*?)\);" % name, HEADER, re.S)
-    assert m, name
-    args = [a.strip() for a in m.group(1).split(",")]
-    assert len(args) == NEW[name]
+    """Where the format sits (the whole prototype, with its types and count, is pinned by tests/abi_snapshot.json)."""
+    args = A.prototype(name)
     at = args.index("int32_t color_format")
     assert args[at - 1].endswith("color") and args[at + 1] == "uint64_t color_pitch"         # inserted after `color`
     for pitch in ("uint64_t ao_pitch", "uint64_t color_pitch", "uint64_t gbuffer0_pitch"):
         assert pitch in args, (name, pitch)
 
 
-def test_the_enum_in_the_header_and_in_python():
-    for name, value in (("RGBA16F", 0), ("RGBA32F", 1), ("RGBA8", 2), ("R11G11B10F", 3)):
-        assert re.search(r"MEAO_COLOR_%s = %d\b" % (name, value), HEADER), name
-        assert getattr(L, "COLOR_" + name) == value
-    assert "one reading" in HEADER.lower() and "sRGB targets are out of scope" in HEADER
+def test_the_header_says_what_the_formats_leave_open():
+    assert "one reading" in A.header_prose().lower() and "sRGB targets are out of scope" in A.header_prose()
 
 
-@pytest.mark.parametrize("name", sorted(NEW))
-def test_entry_point_in_every_binding(name):
-    assert len(L.SIGNATURES[name][1]) == NEW[name]
-    assert L.SIGNATURES[name][1].count(C.c_uint64) == 3
-    cs = open(os.path.join(ROOT, "bindings", "csharp", "MeaoNative.cs")).read()
-    m = re.search(r"public static extern int %s\((.*?)\);" % name, cs)
-    assert m and len(m.group(1).split(",")) == NEW[name] and m.group(1).count("ulong ") == 3 and "int color_format" in m.group(1)
-    assert "%s(" % name in open(os.path.join(ROOT, "include", "meao.hpp")).read()
+def test_csharp_wrapper_takes_a_colour_format():
     assert "colorFormat" in open(os.path.join(ROOT, "bindings", "csharp", "AmbientOcclusionOverMeao.cs")).read()
-
-
-def test_abi_version_still_7_and_exports(meao_lib):
-    assert re.search(r"#define MEAO_ABI_VERSION 7\b", HEADER) and L.ABI_VERSION == 7
-    assert meao_lib.meao_abi_version() == 7
-    for name in NEW:
-        assert hasattr(meao_lib, name), name
 
 
 def test_entry_points_reject_a_null_context(meao_lib):

@@ -1,11 +1,10 @@
-"""The composite into row-pitched surfaces (meao_composite_pitched, meao_composite_enqueue_pitched, meao_pool_composite_enqueue_pitched):
-the ABI surface in every binding, argument checks that need no device, the tensor -> (pointer, pitch) helper behind
+"""The composite into row-pitched surfaces (meao_composite_pitched, meao_composite_enqueue_pitched,
+meao_pool_composite_enqueue_pitched): argument checks that need no device, the tensor -> (pointer, pitch) helper behind
 composite_tensors, and the rule that the feature lives in the kernels that already composite: no new instantiation, and the six
 carrying kernels inside the budget of tests/test_kernel_resources.py."""
 import ctypes as C
 import json
 import os
-import re
 import shutil
 import subprocess
 import sys
@@ -15,48 +14,18 @@ import torch
 
 from miniengineao_amd import _lib as L
 from miniengineao_amd.surfaces import composite_surfaces, frame_pointers
+from tests import abi_model as A
 from tests import kernel_inventory as K
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "meao.h")).read()
-
-NEW = {"meao_composite_pitched": 10, "meao_composite_enqueue_pitched": 9, "meao_pool_composite_enqueue_pitched": 9}
-
 COMPOSITE_KERNELS = {"composite_kernel<0>", "composite_kernel<1>"} | {
     "render_with_composite_kernel<%d, %s, %d>" % (fmt, rtne, div)
     for fmt in (0, 1) for rtne, div in (("false", 0), ("false", 1), ("true", 1))}
 
 
-@pytest.mark.parametrize("name", sorted(NEW))
-def test_entry_point_in_the_header(name):
-    m = re.search(r"MEAO_API\s+int32_t\s+%s\s*\((.*?)\);" % name, HEADER, re.S)
-    assert m, name
-    args = m.group(1)
-    assert len(args.split(",")) == NEW[name]
-    for pitch in ("uint64_t ao_pitch", "uint64_t color_pitch", "uint64_t gbuffer0_pitch"):
-        assert pitch in args, (name, pitch)
-
-
-@pytest.mark.parametrize("name", sorted(NEW))
-def test_entry_point_in_every_binding(name):
-    assert len(L.SIGNATURES[name][1]) == NEW[name]
-    assert L.SIGNATURES[name][1].count(C.c_uint64) == 3
-    cs = open(os.path.join(ROOT, "bindings", "csharp", "MeaoNative.cs")).read()
-    m = re.search(r"public static extern int %s\((.*?)\);" % name, cs)
-    assert m and len(m.group(1).split(",")) == NEW[name] and m.group(1).count("ulong ") == 3
-    assert "%s(" % name in open(os.path.join(ROOT, "include", "meao.hpp")).read()
-
-
 def test_the_header_no_longer_says_the_composite_is_packed_only():
-    assert "meao_composite* and meao_pool_gather_to_device take" not in HEADER
-    assert re.search(r"meao_pool_gather_to_device takes\s+\*?\s*tightly packed surfaces only", HEADER)
-
-
-def test_abi_version_still_7_and_exports(meao_lib):
-    assert re.search(r"#define MEAO_ABI_VERSION 7\b", HEADER) and L.ABI_VERSION == 7
-    assert meao_lib.meao_abi_version() == 7
-    for name in NEW:
-        assert hasattr(meao_lib, name), name
+    assert "meao_composite* and meao_pool_gather_to_device take" not in A.header_prose()
+    assert "meao_pool_gather_to_device takes tightly packed surfaces only" in A.header_prose()
 
 
 def test_entry_points_reject_a_null_context(meao_lib):

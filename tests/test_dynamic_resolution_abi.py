@@ -1,19 +1,15 @@
-"""Dynamic resolution, the part that needs no GPU: the prototypes in include/meao.h, the host-plan function meao_reserve_bytes, and
-the Python, C++ and C# mirrors of the new calls (meao_reserve, meao_get_capacity, meao_reserve_bytes, meao_prefetch_batch_sized,
-meao_pool_reserve, meao_pool_resize, meao_pool_prefetch_batch_sized)."""
+"""Dynamic resolution, the part that needs no GPU: the host-plan function meao_reserve_bytes, the null-argument checks, and what
+the Python and C++ wrappers offer for meao_reserve, meao_get_capacity, meao_reserve_bytes, meao_prefetch_batch_sized,
+meao_pool_reserve, meao_pool_resize and meao_pool_prefetch_batch_sized (their prototypes in every mirror are
+tests/test_abi_mirrors.py)."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import pytest
 
 from miniengineao_amd import _lib as L
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "meao.h")).read()
-NEW_CALLS = {"meao_reserve": 3, "meao_get_capacity": 3, "meao_reserve_bytes": 4, "meao_prefetch_batch_sized": 7,
-             "meao_pool_reserve": 3, "meao_pool_resize": 3, "meao_pool_prefetch_batch_sized": 7}
+from tests import abi_model as A
 
 
 def config(meao_lib, **fields):
@@ -34,23 +30,6 @@ def level_px(meao_lib, w, h, k):
     lw, lh = C.c_int32(), C.c_int32()
     assert meao_lib.meao_level_dims(w, h, k, C.byref(lw), C.byref(lh)) == L.OK
     return lw.value * lh.value
-
-
-def test_header_carries_the_prototypes_and_the_abi_version_stays():
-    for name, nargs in NEW_CALLS.items():
-        m = re.search(r"MEAO_API\s+int32_t\s+%s\s*\((.*?)\);" % name, HEADER, re.S)
-        assert m, name
-        assert len(m.group(1).split(",")) == nargs, name
-    assert re.search(r"#define\s+MEAO_ABI_VERSION\s+7\b", HEADER)
-    assert L.ABI_VERSION == 7
-    assert "meao_test_counters" not in HEADER          # the test hook is no part of the product's interface
-
-
-def test_library_exports_the_calls(meao_lib):
-    for name in NEW_CALLS:
-        assert name in L.SIGNATURES and getattr(meao_lib, name)
-    assert meao_lib.meao_abi_version() == 7
-    assert not hasattr(meao_lib, "meao_test_counters")
 
 
 @pytest.mark.parametrize("fields", [dict(), dict(ao_format=L.AO_F16, hq_levels=2, max_batch=3), dict(num_levels=2, pipelined=1)])
@@ -122,10 +101,6 @@ def test_python_signatures():
 
 
 def test_cpp_and_csharp_mirrors_carry_the_calls():
-    hpp = open(os.path.join(ROOT, "include", "meao.hpp")).read()
-    cs = open(os.path.join(ROOT, "bindings", "csharp", "MeaoNative.cs")).read()
-    for name in NEW_CALLS:
-        assert re.search(r"\b%s\(" % name, hpp), name
-        assert re.search(r"\[DllImport\(Lib\)\] public static extern int %s\(" % name, cs), name
+    hpp = A.read(A.HPP_PATH)
     for method in ("Reserve", "Capacity", "ReserveBytes", "PrefetchBatchSized", "Resize"):
         assert re.search(r"\b%s\(" % method, hpp), method

@@ -1,9 +1,8 @@
-"""Per-frame parameters (meao_execute_batch_params and friends): the ABI surface in every binding, the per-frame kernels'
-compile-time resources against their shared forms, and FrameParams -> meao_params (no device needed)."""
+"""Per-frame parameters (meao_execute_batch_params and friends): the null-argument checks, the per-frame kernels' compile-time
+resources against their shared forms, and FrameParams -> meao_params (no device needed)."""
 import ctypes as C
 import json
 import os
-import re
 import shutil
 import subprocess
 import sys
@@ -13,36 +12,20 @@ import pytest
 from miniengineao_amd import FrameParams
 from miniengineao_amd import _lib as L
 from miniengineao_amd.frame_params import params_array, to_params
+from tests import abi_model as A
 from tests.kernel_inventory import HOT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "meao.h")).read()
-
-NEW = {"meao_execute_batch_params": 8, "meao_prefetch_batch_params": 4,
-       "meao_pool_execute_batch_params": 7, "meao_pool_prefetch_batch_params": 4}
 
 
-def test_abi_version_is_7():
-    assert re.search(r"#define MEAO_ABI_VERSION 7\b", HEADER)
-    assert L.ABI_VERSION == 7
-
-
-@pytest.mark.parametrize("name", sorted(NEW))
+@pytest.mark.parametrize("name", ["meao_execute_batch_params", "meao_prefetch_batch_params",
+                                  "meao_pool_execute_batch_params", "meao_pool_prefetch_batch_params"])
 def test_entry_point_everywhere(name):
-    m = re.search(r"MEAO_API\s+int32_t\s+%s\s*\((.*?)\);" % name, HEADER, re.S)
-    assert m and len(m.group(1).split(",")) == NEW[name]
-    assert "const meao_params *params" in m.group(1)
-    assert len(L.SIGNATURES[name][1]) == NEW[name]
-    cs = open(os.path.join(ROOT, "bindings", "csharp", "MeaoNative.cs")).read()
-    m = re.search(r"public static extern int %s\((.*?)\);" % name, cs)
-    assert m and len(m.group(1).split(",")) == NEW[name]
-    assert "%s(" % name in open(os.path.join(ROOT, "include", "meao.hpp")).read()
-
-
-def test_library_exports_and_reports_abi_7(meao_lib):
-    assert meao_lib.meao_abi_version() == 7
-    for name in NEW:
-        assert hasattr(meao_lib, name), name
+    """Every per-frame form takes one meao_params per frame, as its last argument before the stream (types, counts and the three
+    mirrors of the whole prototype are tests/test_abi_mirrors.py)."""
+    args = A.prototype(name)
+    assert "const meao_params *params" in args
+    assert [a for a in args if a != "meao_stream stream"][-1] == "const meao_params *params"
 
 
 def test_entry_points_reject_null_params(meao_lib):

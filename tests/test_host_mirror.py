@@ -1,48 +1,19 @@
 """Host-side mirrors of the reference component: the Python class, the C++ header-only class
-and the (uncompilable here) C# P/Invoke source all expose AmbientOcclusion.cs's surface and
-bind exactly the C ABI."""
+and the (uncompilable here) C# wrapper all expose AmbientOcclusion.cs's surface.  (That the mirrors bind exactly the C ABI is
+tests/test_abi_mirrors.py.)"""
 import os
 import re
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-with open(os.path.join(ROOT, "include", "meao.h")) as _f:
-    HEADER = _f.read()
 REFERENCE_PROPERTIES = ["noiseFilterTolerance", "blurTolerance", "upsampleTolerance",
                         "thicknessModifier", "intensity", "ambientOnly"]     # AmbientOcclusion.cs:22-66
-
-
-def c_prototypes():
-    protos = {}
-    for m in re.finditer(r"MEAO_API\s+[\w\s\*]+?\b(meao_\w+)\s*\((.*?)\);", HEADER, re.S):
-        args = m.group(2).strip()
-        protos[m.group(1)] = 0 if args == "void" else len(args.split(","))
-    return protos
 
 
 def test_python_mirror_has_the_reference_properties():
     from miniengineao_amd.ambient_occlusion import AmbientOcclusion
     for name in REFERENCE_PROPERTIES:
         assert isinstance(getattr(AmbientOcclusion, name), property), name
-
-
-def test_csharp_dllimports_match_the_header():
-    src = open(os.path.join(ROOT, "bindings", "csharp", "MeaoNative.cs")).read()
-    imports = {}
-    for m in re.finditer(r"\[DllImport\(Lib\)\]\s*public static extern \w+ (meao_\w+)\((.*?)\);", src):
-        args = m.group(2).strip()
-        imports[m.group(1)] = 0 if not args else len(args.split(","))
-    assert imports == c_prototypes()
-    assert 'const string Lib = "meao_hip"' in src
-    # struct field order mirrors the C structs
-    for cname, csname in (("meao_config", "MeaoConfig"), ("meao_params", "MeaoParams"), ("meao_desc", "MeaoDesc")):
-        cbody = re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct %s \{(.*?)\}" % cname, HEADER, re.S).group(1), flags=re.S)
-        cnames = []
-        for decl in cbody.split(";"):
-            if decl.strip():
-                cnames += [n.strip() for n in decl.strip().split(None, 1)[1].split(",")]
-        csbody = re.search(r"public struct %s\s*\{(.*?)\}" % csname, src, re.S).group(1)
-        assert re.findall(r"public \w+ (\w+);", csbody) == cnames, cname
 
 
 def test_csharp_wrapper_keeps_the_reference_surface():

@@ -1,9 +1,8 @@
-"""Linear view-space depth input (MEAO_DEPTH_LINEAR_F32 / _F16): the enum in every binding, the config checks and byte counts that
-need no device, the Python dtype maps, and the linear kernels' compile-time resources against their raw-F32 twins."""
+"""Linear view-space depth input (MEAO_DEPTH_LINEAR_F32 / _F16): the config checks and byte counts that need no device, the
+Python dtype maps, and the linear kernels' compile-time resources against their raw-F32 twins."""
 import ctypes as C
 import json
 import os
-import re
 import shutil
 import subprocess
 import sys
@@ -16,16 +15,6 @@ from miniengineao_amd.ambient_occlusion import DEPTH_NUMPY, DEPTH_TORCH
 from tests.kernel_inventory import HOT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "meao.h")).read()
-CSHARP = open(os.path.join(ROOT, "bindings", "csharp", "MeaoNative.cs")).read()
-
-
-def test_enum_values_in_every_binding():
-    assert re.search(r"MEAO_DEPTH_LINEAR_F32\s*=\s*4\b", HEADER) and re.search(r"MEAO_DEPTH_LINEAR_F16\s*=\s*5\b", HEADER)
-    assert (L.DEPTH_LINEAR_F32, L.DEPTH_LINEAR_F16) == (4, 5)
-    m = re.search(r"enum MeaoDepthFormat\s*\{(.*?)\}", CSHARP)
-    assert m and re.search(r"LinearF32\s*=\s*4\b", m.group(1)) and re.search(r"LinearF16\s*=\s*5\b", m.group(1))
-    assert re.search(r"#define MEAO_ABI_VERSION 7\b", HEADER) and L.ABI_VERSION == 7
 
 
 def config(fmt, w=640, h=360):

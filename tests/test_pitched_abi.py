@@ -1,10 +1,9 @@
-"""Row-pitched surfaces (meao_execute_batch_pitched and friends): the ABI surface in every binding, argument checks that need no
-device, the tensor -> (pointer, pitch) helper behind AmbientOcclusion.execute_tensors, and the pitched kernels' compile-time
-resources against their packed forms."""
+"""Row-pitched surfaces (meao_execute_batch_pitched and friends): argument checks that need no device, the tensor -> (pointer,
+pitch) helper behind AmbientOcclusion.execute_tensors, and the pitched kernels' compile-time resources against their packed
+forms."""
 import ctypes as C
 import json
 import os
-import re
 import shutil
 import subprocess
 import sys
@@ -14,37 +13,20 @@ import torch
 
 from miniengineao_amd import _lib as L
 from miniengineao_amd.surfaces import frame_pointers, packed_pitch
+from tests import abi_model as A
 from tests.kernel_inventory import HOT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "meao.h")).read()
-
-NEW = {"meao_execute_batch_pitched": 10, "meao_prefetch_batch_pitched": 5,
-       "meao_pool_execute_batch_pitched": 9, "meao_pool_prefetch_batch_pitched": 5}
 
 
-def test_abi_version_still_7():
-    assert re.search(r"#define MEAO_ABI_VERSION 7\b", HEADER)
-    assert L.ABI_VERSION == 7
-
-
-@pytest.mark.parametrize("name", sorted(NEW))
+@pytest.mark.parametrize("name", ["meao_execute_batch_pitched", "meao_prefetch_batch_pitched",
+                                  "meao_pool_execute_batch_pitched", "meao_pool_prefetch_batch_pitched"])
 def test_entry_point_everywhere(name):
-    m = re.search(r"MEAO_API\s+int32_t\s+%s\s*\((.*?)\);" % name, HEADER, re.S)
-    assert m and len(m.group(1).split(",")) == NEW[name]
-    assert "uint64_t depth_pitch" in m.group(1) and "const meao_params *params" in m.group(1)
-    assert len(L.SIGNATURES[name][1]) == NEW[name]
-    assert C.c_uint64 in L.SIGNATURES[name][1]
-    cs = open(os.path.join(ROOT, "bindings", "csharp", "MeaoNative.cs")).read()
-    m = re.search(r"public static extern int %s\((.*?)\);" % name, cs)
-    assert m and len(m.group(1).split(",")) == NEW[name] and "ulong depth_pitch" in m.group(1)
-    assert "%s(" % name in open(os.path.join(ROOT, "include", "meao.hpp")).read()
-
-
-def test_library_exports_and_reports_abi_7(meao_lib):
-    assert meao_lib.meao_abi_version() == 7
-    for name in NEW:
-        assert hasattr(meao_lib, name), name
+    """Every pitched form takes the depth pitch in bytes and optional per-frame parameters (types, counts and the three mirrors of
+    the whole prototype are tests/test_abi_mirrors.py)."""
+    args = A.prototype(name)
+    assert "uint64_t depth_pitch" in args and "const meao_params *params" in args
+    assert ("uint64_t ao_pitch" in args) == ("execute" in name)
 
 
 def test_entry_points_reject_null_arguments(meao_lib):
