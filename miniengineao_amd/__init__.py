@@ -10,11 +10,14 @@ from . import synth  # noqa: F401
 from .sharding import frames_for_rank  # noqa: F401
 from .frame_params import FrameParams  # noqa: F401
 
-__all__ = ["AmbientOcclusion", "AmbientOcclusionPool", "FrameParams", "synth", "frames_for_rank"]
+__all__ = ["AmbientOcclusion", "AmbientOcclusionPool", "FrameParams", "FrameStream", "synth", "frames_for_rank"]
 
 
 def __getattr__(name):
     if name in ("AmbientOcclusion", "AmbientOcclusionPool"):
         from . import ambient_occlusion
         return getattr(ambient_occlusion, name)
+    if name == "FrameStream":
+        from .stream import FrameStream
+        return FrameStream
     raise AttributeError(name)
